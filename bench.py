@@ -12,12 +12,16 @@ auto-reset), action tape and all outputs resident in HBM, every tick's obs/rewar
     python bench.py --gpus 8             # spawns 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # what the driver does
+    python bench.py --full               # + cpu_baseline and the other configurations under `extra`
+    python bench.py --dump-outputs DIR   # + the last timed launch's outputs as DIR/<name>.npy
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM: the algorithmic
 bytes of SURVEY.md §8d over the kernel time measured with HIP events; plus the FP64-issue fraction, which
-is the bound this kernel actually sits on) and `cpu_baseline` (the CPU oracle = a C port of the reference
-path timed live on this box's host cores, plus the reference's own Python rate measured in the build
-container and committed under profiles/).
+is the bound this kernel actually sits on).  With --full the line also carries `cpu_baseline` (the CPU
+oracle = a C port of the reference path timed live on this box's host cores, plus the reference's own
+Python rate measured in the build container and committed under profiles/) and `extra` (short runs of
+BASELINE.json's other configurations).  The warm-up and timed launches start from the state right after
+reset in every run (the clock spin-up before them is undone), so the same arguments give the same outputs.
 """
 import argparse
 import json
@@ -82,8 +86,13 @@ def parse_args():
     ap.add_argument("--streams", type=int, default=0, help="rollout / hier --pilot net: split the arenas into this many sub-worlds (disjoint global arena ids, "
                                                                  "bit-identical to one world) stepped on as many HIP streams inside the one graph, so that one sub-world's world "
                                                                  "launches run under another's policy kernel (0 = the workload's default)")
-    ap.add_argument("--no-extra", action="store_true", help="default workload at 1 GPU: skip the short runs of the other single-GPU configurations "
-                                                             "(BASELINE configs[2], configs[3] tape / networks) that fill line['extra']")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the short runs of the other configurations "
+                                                             "(BASELINE configs[2], configs[3] tape / networks; configs[4] with N ranks) that fill line['extra']")
+    ap.add_argument("--full", action="store_true", help="default workload: also measure what the headline does not need — the CPU baseline (cpu_baseline) "
+                                                         "and the short runs of the other configurations (extra).  Off: set up, warm up, time --steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: after the timed steps write what the last timed launch returned (obs, reward, reward_valid, done) as float32 "
+                         "DIR/<name>.npy: the last tick of every arena (<name>_last.npy) and every tick of a fixed, seeded sample of arenas (<name>.npy)")
     return ap.parse_args()
 
 
@@ -369,6 +378,37 @@ def make_tape(args, R, T, N, n_units, step0=0):
     return (torch.rand((T, N, n_units, 4), device=R.dev, generator=gen) * hi).to(torch.int8).contiguous()
 
 
+DUMP_BYTES_LAST, DUMP_BYTES_SERIES = 20_000_000, 40_000_000   # --dump-outputs: at most 60 MB of arrays (+ .npy headers)
+DUMP_SEED = 20250101                                           # the fixed sample of arenas whose every tick is written
+
+
+def dump_outputs(d, out, N, R):
+    """--dump-outputs: what the last timed hh_rollout launch returned — obs [T, N, 2, 26] f32, reward [T, N, 2] f32, reward_valid
+    [T, N, 2] u8, done [T, N] u8 — as float32 .npy files.  <name>_last.npy: the last tick of every arena (a seeded sample of arenas when
+    that exceeds DUMP_BYTES_LAST); <name>.npy: the last ticks (all of them when they fit DUMP_BYTES_SERIES) of min(N, 256) arenas drawn
+    with DUMP_SEED.  Rank r > 0 of a multi-rank job writes <name>_rank<r>.npy (its own arenas)."""
+    import numpy as np
+    names = ("obs", "reward", "reward_valid", "done")
+    T = out[0].shape[0]
+    per_tick = sum(x[0, 0].numel() for x in out) * 4   # float32 bytes of one arena-tick of all four outputs
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def arenas(m):
+        return np.arange(N) if m >= N else np.sort(rng.choice(N, m, replace=False))
+    last = arenas(max(1, DUMP_BYTES_LAST // per_tick))
+    series = arenas(min(N, 256))
+    t_keep = max(1, min(T, DUMP_BYTES_SERIES // (per_tick * len(series))))
+    sfx = "" if R.world == 1 else f"_rank{R.rank}"
+    os.makedirs(d, exist_ok=True)
+    last_t, ser_t = [R.torch.from_numpy(a).to(out[0].device) for a in (last, series)]
+    for name, x in zip(names, out):
+        np.save(os.path.join(d, f"{name}_last{sfx}.npy"), x[T - 1].index_select(0, last_t).float().cpu().numpy())
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), x[T - t_keep:].index_select(1, ser_t).float().cpu().numpy())
+    return {"dir": d, "files": [f"{n}{s}{sfx}.npy" for n in names for s in ("_last", "")], "dtype": "float32",
+            "last_tick_arenas": len(last), "series_arenas": len(series), "series_ticks": t_keep, "sample_seed": DUMP_SEED,
+            "of": f"the last timed launch: {T} ticks x {N} arenas (arena indices local to this rank)"}
+
+
 TAPE_DESC = {"keyed": "actions i.i.d. uniform over MultiDiscrete([13,9,2,2]) from the keyed RNG, key = (seed, global arena, step, agent)",
              "torch": "actions i.i.d. uniform over MultiDiscrete([13,9,2,2]) from torch.rand (per-rank seed)"}
 
@@ -387,10 +427,12 @@ def main_low(args, R=None):
     w.reset()
     tape, out, side = None, w.alloc_outputs(chunk), None
     n_tape = 4 if N * chunk <= (1 << 26) else 2  # distinct chunks of actions, cycled (8 B per arena-tick: 1 GB per chunk at 262144 arenas x 500 ticks)
+    snap = None
     if not R.dry:
         # action tape resident in HBM before the timed region: i.i.d. uniform MultiDiscrete([13,9,2,2])
         tape = make_tape(args, R, n_tape * chunk, N, w.n_ctrl).view(n_tape, chunk, N, w.n_ctrl, 4)
         side = torch.cuda.Stream()
+        snap = w.get_state()   # the state after reset: restored after the spin-up, whose launch count depends on the clock
     state = {"k": 0}
 
     def launch(timed_events=None):
@@ -410,6 +452,9 @@ def main_low(args, R=None):
     while time.perf_counter() - t_spin < args.spinup and not R.dry:   # clocks ramp up from idle: not part of W or K
         launch()
         torch.cuda.synchronize()
+    if snap is not None:   # warm-up and timed launches start from the same state and tape position in every run: same inputs, same outputs
+        w.set_state(snap)
+        state["k"] = 0
     for _ in range(args.warmup):
         launch()
     R.barrier()
@@ -463,7 +508,9 @@ def main_low(args, R=None):
                                     "slots that carry an instruction, `fp64` the share of the vector-FP64 pipe; HBM traffic is far below the algorithmic "
                                     "bytes because state stays in registers across the ticks of a launch.  `achieved` / `frac` are measured by this run "
                                     "(HIP events); `traffic`, `issue` and `fp64` are quoted from the committed counter passes"}
-        if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, out, N, R)
+        if R.rank == 0 and R.world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, args.level, args.seed)
     if not own:
         return line
@@ -1005,6 +1052,8 @@ def main():
         args.chunk = 64     # T of a collect unless given
     if args.dry_run and args.workload != "low":
         sys.exit("--dry-run exercises the rank plumbing of the default workload on a CPU box (gloo); the other workloads need the GPU")
+    if args.dump_outputs and (args.workload != "low" or args.dry_run):
+        sys.exit("--dump-outputs writes the outputs of the default workload's launches (--workload low, not --dry-run)")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
     if args.workload == "hier":
@@ -1014,6 +1063,8 @@ def main():
     if args.workload == "collect":
         return main_collect(args)
     single = args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    if not args.full:   # the plain run: the headline line alone
+        return main_low(args)
     if not single and not args.no_extra:
         # N ranks: configs[1] per rank stays the headline `value`; BASELINE configs[4] (8192 arenas x 3-vs-3 HighLevelEnv per rank, the episode
         # statistics all-gathered over RCCL on a side stream) rides along, measured by the same ranks right after it
@@ -1027,7 +1078,7 @@ def main():
         return
     if args.dry_run or args.no_extra:
         return main_low(args)
-    # the driver's line: configs[1] is the headline; the other single-GPU configurations of BASELINE.json ride along as short runs
+    # --full: configs[1] is the headline; the other single-GPU configurations of BASELINE.json ride along as short runs
     R = Ranks(args)
     line = main_low(args, R)
     line["extra"] = extra_configs(args, R)

@@ -17,7 +17,7 @@ Run:  PYTHONDONTWRITEBYTECODE=1 python oracle/gen_env_golden.py [--out DIR] [nam
       PYTHONDONTWRITEBYTECODE=1 python oracle/gen_env_golden.py --check                      regenerate to a temp dir and
                                                                                             compare with tests/golden
 Everything is deterministic (keyed tape, crc32-seeded action policies), so --check must report no difference;
-tests/test_golden_provenance.py runs it whenever /root/reference is present.
+run it by hand wherever the reference tree is available (the suite cannot: the reference is not part of the repository).
 """
 import json
 import math

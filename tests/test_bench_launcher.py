@@ -31,9 +31,9 @@ def test_gpus_2_self_spawns_two_ranks():
 
 
 def test_two_rank_line_carries_configs4():
-    """with more than one rank the line keeps configs[1] as its value and adds extra.configs4 (8192 arenas x 3-vs-3 per rank): here the dry
+    """with more than one rank and --full the line keeps configs[1] as its value and adds extra.configs4 (8192 arenas x 3-vs-3 per rank): here the dry
     run of that branch — both ranks' [8192, 3] blocks arrive in the all-gather, in global arena order"""
-    line = _run(["--gpus", "2"])
+    line = _run(["--gpus", "2", "--full"])
     c4 = line["extra"]["configs4"]
     assert c4["dry_run"] is True and c4["n_gpus"] == 2 and c4["arenas_per_gpu"] == 8192
     assert c4["gathered_rows"] == 2 * 8192
@@ -41,11 +41,19 @@ def test_two_rank_line_carries_configs4():
     assert line["metric"].startswith("env-steps/sec") and line["n_gpus"] == 2   # the headline is still configs[1]
 
 
+def test_plain_run_is_the_headline_alone():
+    """without --full the line carries no riders: no extra (configs[4] with N ranks) and no cpu_baseline"""
+    for extra in ([], ["--gpus", "2"]):
+        line = _run(extra)
+        assert "extra" not in line and "cpu_baseline" not in line
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+
+
 def test_gpus_8_dry_run_is_the_scale_table_the_driver_will_fill():
     """8-rank readiness without hardware: `bench.py --gpus 8` self-spawns eight ranks (gloo here, RCCL on the
     node), weak scaling, per-rank rates, the configs[4] branch with 8 x 8192 rows gathered in global arena order — and, given the 1-GPU line's
     value, the line carries scaling_efficiency = value_8 / (8 x value_1) so that the first real SCALE run yields the table with no edits"""
-    line = _run(["--gpus", "8", "--one-gpu-value", "1000.0"])
+    line = _run(["--gpus", "8", "--one-gpu-value", "1000.0", "--full"])
     assert line["n_gpus"] == 8 and line["dry_run"] is True and line["scaling"] == "weak"
     assert len(line["per_rank_env_steps_per_s"]) == 8 and all(v > 0 for v in line["per_rank_env_steps_per_s"])
     assert line["gathered_rows"] == 8 * 8
