@@ -59,6 +59,17 @@ class HHCriticWeights(C.Structure):
                 ("shared_w", C.c_void_p), ("shared_b", C.c_void_p), ("val_w", C.c_void_p), ("val_b", C.c_void_p)]
 
 
+class HHEpisodeBufs(C.Structure):
+    """hh_episode_bufs (include/hh_abi.h): sizes, then device pointers (collect, carry, batch); field order is ABI"""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32), ("carry_cap", C.c_int32),
+                ("reserved0", C.c_int32), ("row_cap", C.c_int64), ("ep_cap", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double)] + [
+        (name, C.c_void_p) for name in (
+            "obs", "actions", "logp", "vf", "reward", "valid", "done",
+            "c_obs", "c_actions", "c_logp", "c_vf", "c_reward", "c_valid", "carried", "episode", "scratch",
+            "o_obs", "o_actions", "o_logp", "o_vf", "o_reward", "o_valid", "o_adv", "o_target", "o_done", "o_arena", "o_episode", "o_t",
+            "ep_start", "ep_len", "ep_arena", "counts")]
+
+
 EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim", "hh_n_ctrl", "hh_reset", "hh_step",
            "hh_rollout", "hh_episode_stats", "hh_get_state", "hh_set_state", "hh_get_event_masks", "hh_observe",
            "hh_hl_begin", "hh_hl_agents_act", "hh_hl_tick", "hh_hl_end", "hh_step_begin", "hh_step_finish", "hh_gae", "hh_hl_commands",
@@ -66,7 +77,7 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_create", "hh_policy_destroy", "hh_policy_set_net", "hh_policy_set_lut", "hh_policy_set_tile_rows", "hh_policy_act",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
-           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live"]
+           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit"]
 
 _lib = None
 
@@ -114,6 +125,7 @@ def lib():
         L.hh_arena_status.argtypes = [vp, vp, vp]
         L.hh_gae.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
         L.hh_gae_rllib.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
+        L.hh_episodes_emit.argtypes = [C.POINTER(HHEpisodeBufs), vp]
         L.hh_math_eval.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
         L.hh_policy_destroy.argtypes = [vp]

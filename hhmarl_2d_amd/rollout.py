@@ -93,6 +93,84 @@ def episode_segments(done):
     return seg, seg < n_done
 
 
+class EpisodeBatch:
+    """The whole-episode batch of a `PPORollout(..., batch_mode="complete_episodes")` (train_hetero.py:212): after every collect, the rows
+    of every episode that ENDED in it, from its reset row to its done row, in one flat batch — the episode's earlier rows come from a
+    per-arena carry that holds the running episode on the device across collects — with advantages / value targets computed over the
+    whole episode (hh_gae_rllib's float64 recursion with last_r = 0.0 after the done row: oracle/gae_ref.compute_advantages on each
+    episode).  Written by hh_episodes_emit (include/hh_abi.h) inside the collect's graph; no host synchronisation until `rows()`.
+
+    Device buffers of fixed capacity, overwritten by every collect (the first n_rows rows / n_episodes episodes are valid), in the order
+    arena-major, then episode, then time:
+      obs f32 [R, 2, D], actions i8 [R, 2, 4], logp / vf / reward f32 [R, 2], valid u8 [R, 2], adv / target f32 [R, 2],
+      done u8 [R] (1 on an episode's last row only), arena / episode / t i32 [R] (`episode` counts per arena from `start()`, `t` is the
+      step within the episode from 0); episode table ep_start / ep_len / ep_arena i32 [E]; n_rows / n_episodes (0-d i32 views of the
+      device counts); carried i32 [N] (rows of each arena's running episode held for a later collect).
+    Capacity, with H = world.cfg.horizon (an episode has at most H rows): the carry holds N (H - 1) rows, the batch R = N (H - 1 + T)
+    rows and E = N T episodes — for two agents about (H - 1) (8 D + 26) + (H - 1 + T) (8 D + 47) + 12 T bytes per arena (N = 16384,
+    H = 300, T = 64, fight D = 26: 1.17 GB of carry, 1.60 GB of batch).  Nothing overflows under that rule; if something did anyway, a
+    sticky device flag is set and `rows()` raises."""
+
+    COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
+
+    def __init__(self, N, T, horizon, n_agents, D, device, gamma, lam, collect):
+        """collect: the rollout's [T(+1), N, ...] buffers (obs, actions, logp, vf, reward, valid, done) that every emission reads"""
+        self.N, self.T, self.n_agents, self.D = int(N), int(T), int(n_agents), int(D)
+        self.carry_cap = max(int(horizon) - 1, 0)
+        R, E, cap, nA = self.N * (self.carry_cap + self.T), self.N * self.T, max(self.carry_cap, 1), self.n_agents
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        f32, i8, u8, i32 = torch.float32, torch.int8, torch.uint8, torch.int32
+        self.obs, self.actions = z((R, nA, D), f32), z((R, nA, 4), i8)
+        self.logp, self.vf, self.reward, self.valid = z((R, nA), f32), z((R, nA), f32), z((R, nA), f32), z((R, nA), u8)
+        self.adv, self.target = z((R, nA), f32), z((R, nA), f32)
+        self.done, self.arena, self.episode, self.t = z((R,), u8), z((R,), i32), z((R,), i32), z((R,), i32)
+        self.ep_start, self.ep_len, self.ep_arena = z((E,), i32), z((E,), i32), z((E,), i32)
+        self.carried = z((N,), i32)
+        self._carry = {"obs": z((N, cap, nA, D), f32), "actions": z((N, cap, nA, 4), i8), "logp": z((N, cap, nA), f32),
+                       "vf": z((N, cap, nA), f32), "reward": z((N, cap, nA), f32), "valid": z((N, cap, nA), u8)}
+        self._finished = z((N,), i32)            # episodes finished per arena since start()
+        self._scratch = z((5, N), i32)
+        self._counts = z((3,), i32)              # rows, episodes of the last collect; overflow flag (sticky)
+        self.n_rows, self.n_episodes = self._counts[0], self._counts[1]
+        b = L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=nA, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R, ep_cap=E,
+                            gamma=float(gamma), lam=float(lam))
+        for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done"):
+            assert collect[k].is_contiguous() and collect[k].shape[1] == N
+            setattr(b, k, collect[k].data_ptr())
+        for k, v in self._carry.items():
+            setattr(b, "c_" + k, v.data_ptr())
+        b.carried, b.episode, b.scratch = self.carried.data_ptr(), self._finished.data_ptr(), self._scratch.data_ptr()
+        for k in self.COLUMNS:
+            setattr(b, "o_" + k, getattr(self, k).data_ptr())
+        b.ep_start, b.ep_len, b.ep_arena, b.counts = (x.data_ptr() for x in (self.ep_start, self.ep_len, self.ep_arena, self._counts))
+        self._bufs, self._collect, self._device = b, collect, device   # the struct holds raw pointers: keep the tensors alive
+
+    def reset(self):
+        """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
+        self.carried.zero_()
+        self._finished.zero_()
+        self._counts[:2].zero_()
+
+    def emit(self, stream):
+        L.check(L.lib().hh_episodes_emit(C.byref(self._bufs), stream))
+
+    def rows(self):
+        """synchronises; -> dict of views cut to the rows (COLUMNS) and the episode table (ep_start, ep_len, ep_arena) of the last collect"""
+        torch.cuda.synchronize(self._device)
+        R, E, overflow = self._counts.tolist()
+        if overflow:
+            raise RuntimeError("EpisodeBatch: an episode outgrew the carry or the batch capacity (more rows than the horizon?): the batches "
+                               "since that collect are incomplete")
+        out = {k: getattr(self, k)[:R] for k in self.COLUMNS}
+        out.update({k: getattr(self, k)[:E] for k in ("ep_start", "ep_len", "ep_arena")})
+        return out
+
+    def critic_rows(self, agent):
+        """the CUR_OBS rows of `agent` (1 | 2) for the emitted rows (central_critic_rows)"""
+        r = self.rows()
+        return central_critic_rows(r["obs"], r["actions"], agent)
+
+
 class PPORollout:
     """What RLlib's rollout workers produce for train_hetero.py's PPO (train_hetero.py:206-243), for every arena of a `World` at once and
     without leaving the device: per tick the two trainable policies are sampled by `hh_policy_sample` (actor forward, Categorical draw
@@ -110,21 +188,32 @@ class PPORollout:
       * last_r = 0.0 at every episode end (terminateds["__all__"] also at the horizon, env_base.py:108): the recursion is cut there and
         no value is bootstrapped across it; float64 delta and discounted sum, float32 results;
       * train_hetero.py:212 batch_mode = "complete_episodes": RLlib trains on whole episodes only.  `complete` (bool [T, N]) marks the
-        rows of episodes that END inside this collect — the rows of that batch; the trailing fragment of every arena (its episode is still
-        running after tick T - 1) gets RLlib's truncated-trajectory bootstrap from one more value evaluation and is flagged
-        complete = False, so that a learner either drops it or keeps it for the next batch (`segments` numbers the episodes per arena).
+        rows of episodes that END inside this collect; the trailing fragment of every arena (its episode is still running after
+        tick T - 1) gets RLlib's truncated-trajectory bootstrap from one more value evaluation and is flagged complete = False
+        (`segments` numbers the episodes per arena).  The head of an episode that began in an earlier collect is not in this window,
+        so these rows are not RLlib's batch: batch_mode = "complete_episodes" (below) builds that one.
     semantics = "masked": the pre-round-5 convention (`hh_gae`): rows without a reward key have advantage = target = 0 and do not
     propagate, float32 throughout — for learners that cut dead agents' rows out.
 
     Buffers (device, overwritten by every `collect`):  obs f32 [T+1, N, 2, D] (row t = what the policy saw at tick t), actions i8
     [T, N, 2, 4], logp f32 [T, N, 2], vf f32 [T+1, N, 2], reward f32 [T, N, 2] (0.0 where valid = 0), valid u8 [T, N, 2], done u8
     [T, N], adv / target f32 [T, N, 2]; `complete` / `segments` are derived from `done` on demand.  `critic_rows(agent)` gives the
-    flattened CUR_OBS rows the reference's critic is trained on (actions filled in the way on_postprocess_trajectory does)."""
+    flattened CUR_OBS rows the reference's critic is trained on (actions filled in the way on_postprocess_trajectory does).
 
-    def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib"):
+    batch_mode = "truncate_episodes" (default): the buffers above are the result.  batch_mode = "complete_episodes" (train_hetero.py:212;
+    semantics = "rllib" only): every collect still fills the buffers above exactly the same way, and then also `episodes`, an
+    `EpisodeBatch` of every episode that ended in it — whole, its earlier rows carried on the device from the collects before — with
+    advantages / value targets over the whole episode (last_r = 0): the batch RLlib hands its learner.  Its 4 launches are part of the
+    collect's graph."""
+
+    def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes"):
         """opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
         a `pilots.OpponentNets(world, skip_first=False)` (its bank bound, so that hh_step_begin lists the opponents' rows itself) or any
         callable(opp_obs f32 [N, 2, 30] on the device, None) -> int8 [N, 2, 4] that only enqueues work on the current stream"""
+        if batch_mode not in ("truncate_episodes", "complete_episodes"):
+            raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes: EpisodeBatch)")
+        if batch_mode == "complete_episodes" and semantics == "masked":
+            raise ValueError("batch_mode='complete_episodes' is defined for RLlib's trajectory view only (semantics='rllib')")
         from . import pilots
         assert world.cfg.env_kind == L.ENV_LOWLEVEL and world.n_agents == 2 and world.cfg.auto_reset, "PPORollout drives an auto-resetting LowLevelEnv world"
         if semantics not in ("rllib", "masked"):
@@ -159,6 +248,11 @@ class PPORollout:
         self._opp_obs = z((N, world.A - 2, 30), torch.float32) if self.split else None
         # level 5 in fight mode: every arena observes in the mode of its own episode's draw (HH_OPP_MODE_EPISODE); otherwise fight mode
         self._opp_mode = L.OPP_MODE_EPISODE if (world.cfg.level == 5 and world.cfg.agent_mode == L.MODE_FIGHT) else 0
+        self.batch_mode = batch_mode
+        self.episodes = None
+        if batch_mode == "complete_episodes":
+            self.episodes = EpisodeBatch(N, self.T, world.cfg.horizon, 2, D, dev, self.gamma, self.lam,
+                                         {k: getattr(self, k) for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done")})
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -167,6 +261,8 @@ class PPORollout:
         """reset every arena; the first observation becomes row 0 of the next collect.  Also builds the row lists of the fixed agent ->
         network mapping (a greedy evaluation whose results are discarded), so that every later call re-uses them (sel = NULL)."""
         self.w.reset(obs=self.obs[self.T])
+        if self.episodes is not None:
+            self.episodes.reset()
         self.bank.sample(self.obs[self.T], self.sel, greedy=True, actions=self._tmp_act, logp=self._tmp_logp, vf=self.vf[self.T])
         self._started = True
 
@@ -192,6 +288,8 @@ class PPORollout:
         else:
             L.check(L.lib().hh_gae(T, self.w.N, 2, _p(self.reward), _p(self.vf), _p(self.valid), _p(self.done), self.gamma, self.lam,
                                    _p(self.adv), _p(self.target), st))
+        if self.episodes is not None:
+            self.episodes.emit(st)
 
     def collect(self):
         """T ticks of every arena -> self (the buffers above): 2 T + 2 launches, replayed from ONE HIP graph; no host synchronisation."""

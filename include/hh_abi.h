@@ -258,6 +258,69 @@ int hh_gae(int32_t T, int32_t N, int32_t n_agents, const float *reward, const fl
 int hh_gae_rllib(int32_t T, int32_t N, int32_t n_agents, const float *reward, const float *value, const uint8_t *done, double gamma,
                  double lam, float *adv, float *ret, void *stream);
 
+/* Whole-episode batches (batch_mode = "complete_episodes", train_hetero.py:212 / train_hier.py:182): RLlib gives its learner only
+ * whole episodes, from the reset row to the done row, with GAE over each episode and last_r = 0 at its end.  hh_episodes_emit takes
+ * one collect's [T, N, ...] buffers (auto-resetting arenas: the row after a done is the next episode's reset row), keeps every arena's
+ * running episode in a device-side carry across calls, and writes the rows of every episode that ended in this window — the carried
+ * rows first, then the window's — into one flat batch, arena-major, then episode, then time (fixed by a scan, not by scheduling).
+ * advantages / value targets are hh_gae_rllib's recursion (float64 delta and discounted sum, float32 results) run over each whole
+ * episode with last_r = 0.0.  Not tied to a world: generic in n_agents and the observation width; launches on the calling thread's
+ * current device, which must own every buffer; no host synchronisation and no allocation (graph-capturable).  All pointers [dev].
+ * Capacities: an episode has at most `horizon` rows, so carry_cap = horizon - 1 rows per arena and row_cap = N (carry_cap + T) rows
+ * per call never overflow, ep_cap = N T episodes per call; if they did anyway, counts[2] is set (sticky) and nothing is written out of
+ * bounds.  The caller zeroes carried / episode (and counts) before the first call and whenever its arenas are reset. */
+typedef struct hh_episode_bufs {
+    int32_t T;                /* ticks per call */
+    int32_t N;                /* arenas */
+    int32_t n_agents;         /* agents per arena row */
+    int32_t obs_dim;          /* D: floats per agent in an observation row */
+    int32_t carry_cap;        /* rows per arena the carry holds (horizon - 1) */
+    int32_t reserved0;        /* must be 0 */
+    int64_t row_cap;          /* rows of every output column (N (carry_cap + T); < 2^31) */
+    int64_t ep_cap;           /* entries of the episode table (N T) */
+    double gamma;
+    double lam;
+    /* one collect (read): obs f32 [T(+1), N, n_agents, D], actions i8 [T, N, n_agents, 4], logp / vf (T(+1)) / reward f32 [T, N, n_agents],
+       valid u8 [T, N, n_agents], done u8 [T, N] */
+    const float *obs;
+    const int8_t *actions;
+    const float *logp;
+    const float *vf;
+    const float *reward;
+    const uint8_t *valid;
+    const uint8_t *done;
+    /* carry (read and written): the same columns [N, carry_cap, ...] */
+    float *c_obs;
+    int8_t *c_actions;
+    float *c_logp;
+    float *c_vf;
+    float *c_reward;
+    uint8_t *c_valid;
+    int32_t *carried;         /* [N] rows held per arena */
+    int32_t *episode;         /* [N] episodes finished per arena (the `episode` column of the next one) */
+    int32_t *scratch;         /* [5, N] */
+    /* batch (written): the collect's columns [row_cap, ...], then adv / target f32 [row_cap, n_agents], done u8 [row_cap] (1 on an
+       episode's last row only), arena / episode / t i32 [row_cap] (t = step within the episode, from 0) */
+    float *o_obs;
+    int8_t *o_actions;
+    float *o_logp;
+    float *o_vf;
+    float *o_reward;
+    uint8_t *o_valid;
+    float *o_adv;
+    float *o_target;
+    uint8_t *o_done;
+    int32_t *o_arena;
+    int32_t *o_episode;
+    int32_t *o_t;
+    int32_t *ep_start;        /* [ep_cap] first row of each episode in the batch */
+    int32_t *ep_len;          /* [ep_cap] */
+    int32_t *ep_arena;        /* [ep_cap] */
+    int32_t *counts;          /* [3]: rows, episodes written by this call; overflow flag (sticky) */
+} hh_episode_bufs;
+
+int hh_episodes_emit(const hh_episode_bufs *b, void *stream);
+
 /* Test probe: the shared math of include/hh_math.h / hh_geodesic.h evaluated ON THE DEVICE over arrays of operands, so that a
  * -m gpu test can compare the kernels' arithmetic with the CPU oracle's bit for bit (tests/test_gpu_math.py), not only through
  * trajectories.  fn: 0 sincos(a) -> o0, o1 | 1 atan2(a, b) | 2 acos(a) | 3 sincosd(a) -> o0, o1 | 4 atan2d(a, b) | 5 pymod(a, b) |
