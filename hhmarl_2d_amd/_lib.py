@@ -59,6 +59,16 @@ class HHCriticWeights(C.Structure):
                 ("shared_w", C.c_void_p), ("shared_b", C.c_void_p), ("val_w", C.c_void_p), ("val_b", C.c_void_p)]
 
 
+class HHCommanderWeights(C.Structure):
+    """hh_commander_weights (include/hh_commander.h): host pointers to CommanderGru's tensors, nn.Linear / nn.GRU layout; field order is ABI"""
+    _fields_ = [("inp_w", C.c_void_p * 4), ("inp_b", C.c_void_p * 4),
+                ("act_w_ih", C.c_void_p), ("act_w_hh", C.c_void_p), ("act_b_ih", C.c_void_p), ("act_b_hh", C.c_void_p),
+                ("shared_w", C.c_void_p), ("shared_b", C.c_void_p), ("act_out_w", C.c_void_p), ("act_out_b", C.c_void_p),
+                ("v_w", C.c_void_p * 4), ("v_b", C.c_void_p * 4),
+                ("val_w_ih", C.c_void_p), ("val_w_hh", C.c_void_p), ("val_b_ih", C.c_void_p), ("val_b_hh", C.c_void_p),
+                ("val_out_w", C.c_void_p), ("val_out_b", C.c_void_p)]
+
+
 class HHEpisodeBufs(C.Structure):
     """hh_episode_bufs (include/hh_abi.h): sizes, then device pointers (collect, carry, batch); field order is ABI"""
     _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32), ("carry_cap", C.c_int32),
@@ -78,6 +88,8 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit"]
+COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
+                     "hh_commander_kernel_name"]  # include/hh_commander.h
 
 _lib = None
 
@@ -143,6 +155,11 @@ def lib():
         L.hh_policy_kernel_name.argtypes = [vp, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
         L.hh_action_faults.argtypes = [vp, vp, C.c_int32, vp]
         L.hh_action_tape_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+        L.hh_commander_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
+        L.hh_commander_destroy.argtypes = [vp]
+        L.hh_commander_set_weights.argtypes = [vp, C.POINTER(HHCommanderWeights)]
+        L.hh_commander_sample.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.hh_commander_kernel_name.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32]
         _lib = L
     return _lib
 

@@ -1,0 +1,246 @@
+"""The trainable commander of train_hier.py (commander side) on the device: `CommanderNet` evaluates
+models/ac_models_hier.py:CommanderGru the way RLlib's sampler does (actor, value branch, both GRU cells, Categorical draw and
+log-probability) for every agent row of every arena in one fused gfx950 kernel (include/hh_commander.h), and `CommanderRollout`
+does for train_hier.py what `rollout.PPORollout` does for train_hetero.py."""
+import ctypes as C
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .rollout import central_critic_rows_hl
+
+OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
+
+
+def state_keys():
+    """the reference's CommanderGru state_dict keys -> shapes (nn.Linear [out, in]; nn.GRU gate rows r | z | n)"""
+    k = OrderedDict()
+    k["shared_layer._model.0.weight"], k["shared_layer._model.0.bias"] = (500, 500), (500,)
+    for rnn in ("rnn_act", "rnn_val"):
+        k[f"{rnn}.weight_ih_l0"], k[f"{rnn}.weight_hh_l0"] = (600, 200), (600, 200)
+        k[f"{rnn}.bias_ih_l0"], k[f"{rnn}.bias_hh_l0"] = (600,), (600,)
+    for name, shp in (("inp1", (50, 4)), ("inp2", (200, 20)), ("inp3", (50, 10)), ("inp4", (200, 34)), ("act_out", (3, 500)),
+                      ("v1", (100, 35)), ("v2", (100, 35)), ("v3", (100, 35)), ("v4", (200, 105)), ("val_out", (1, 500))):
+        k[f"{name}._model.0.weight"], k[f"{name}._model.0.bias"] = shp, shp[:1]
+    return k
+
+
+def random_weights(seed):
+    """Deterministic synthetic CommanderGru weights (policy_nets.random_weights' convention): numpy PCG64, N(0, 1/fan_in) weights,
+    N(0, 0.1^2) biases — fixtures store the seed, not the matrices."""
+    rng = np.random.default_rng([int(seed), 0xC0])
+    sd = OrderedDict()
+    for k, shp in state_keys().items():
+        if len(shp) == 2:
+            sd[k] = (rng.standard_normal(shp) / np.sqrt(shp[-1])).astype(np.float32)
+        else:
+            sd[k] = (0.1 * rng.standard_normal(shp)).astype(np.float32)
+    return sd
+
+
+def from_torch_module(module):
+    """weights of a real CommanderGru (e.g. restored from a train_hier.py checkpoint) -> dict of numpy arrays"""
+    sd = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in module.state_dict().items()}
+    return OrderedDict((k, sd[k]) for k in state_keys())
+
+
+class CommanderNet:
+    """CommanderGru on one GPU: `set_weights(sd)` (the reference's state_dict, numpy or torch), `sample(...)` = one sampler step of
+    [N, 3] agent rows (hh_commander_sample)."""
+
+    def __init__(self, device, max_rows):
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.max_rows = int(max_rows)
+        self.h = C.c_void_p()
+        L.check(L.lib().hh_commander_create(self.device.index or 0, self.max_rows, C.byref(self.h)))
+        self._w = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().hh_commander_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, sd):
+        """load (or replace) the weights; synchronous.  The device copy keeps its addresses, so a captured rollout graph sees the new weights."""
+        keys = state_keys()
+        arr = {}
+        for k, shp in keys.items():
+            v = sd[k]
+            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            v = np.ascontiguousarray(v, dtype=np.float32)
+            if v.shape != shp:
+                raise ValueError(f"{k}: shape {v.shape}, CommanderGru has {shp}")
+            arr[k] = v
+        p = lambda k: arr[k].ctypes.data
+        w = L.HHCommanderWeights()
+        for i in range(4):
+            w.inp_w[i], w.inp_b[i] = p(f"inp{i + 1}._model.0.weight"), p(f"inp{i + 1}._model.0.bias")
+            w.v_w[i], w.v_b[i] = p(f"v{i + 1}._model.0.weight"), p(f"v{i + 1}._model.0.bias")
+        w.act_w_ih, w.act_w_hh, w.act_b_ih, w.act_b_hh = (p(f"rnn_act.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+        w.val_w_ih, w.val_w_hh, w.val_b_ih, w.val_b_hh = (p(f"rnn_val.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+        w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
+        w.act_out_w, w.act_out_b = p("act_out._model.0.weight"), p("act_out._model.0.bias")
+        w.val_out_w, w.val_out_b = p("val_out._model.0.weight"), p("val_out._model.0.bias")
+        L.check(L.lib().hh_commander_set_weights(self.h, C.byref(w)))
+        self._w = arr
+        return self
+
+    def sample(self, obs, h_in, h_out, fresh=None, world=None, uniforms=None, crit_act=None, greedy=False, actions=None, logp=None,
+               vf=None, logits=None, want_vf=True):
+        """obs f32 [N, 3, 34]; h_in / h_out f32 [N, 3, 2, 200] (state_in / state_out: 0 = rnn_act, 1 = rnn_val; rows of `fresh` arenas of
+        h_in are overwritten with zeros); fresh u8 [N] or None; world (keyed draws) or uniforms f64 [N, 3]; crit_act f32 [N, 3] = the value
+        branch's act inputs (None = zeros, as while sampling) -> (actions i8 [N, 3], logp f32 [N, 3], vf f32 [N, 3] or None)"""
+        N = obs.shape[0]
+        dev = obs.device
+        assert obs.dtype == torch.float32 and obs.is_contiguous() and tuple(obs.shape) == (N, N_AGENTS, OBS)
+        for t in (h_in, h_out):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * N_AGENTS * 2 * HIDDEN
+        if actions is None:
+            actions = torch.empty((N, N_AGENTS), dtype=torch.int8, device=dev)
+        if logp is None:
+            logp = torch.empty((N, N_AGENTS), dtype=torch.float32, device=dev)
+        if vf is None and want_vf:
+            vf = torch.empty((N, N_AGENTS), dtype=torch.float32, device=dev)
+        assert actions.dtype == torch.int8 and actions.is_contiguous() and actions.numel() == N * N_AGENTS
+        assert logp.dtype == torch.float32 and logp.is_contiguous() and logp.numel() == N * N_AGENTS
+        assert vf is None or (vf.dtype == torch.float32 and vf.is_contiguous() and vf.numel() == N * N_AGENTS)
+        if fresh is not None:
+            assert fresh.dtype == torch.uint8 and fresh.is_contiguous() and fresh.numel() == N
+        if uniforms is not None:
+            assert uniforms.dtype == torch.float64 and uniforms.is_contiguous() and uniforms.numel() == N * N_AGENTS
+        if crit_act is not None:
+            assert crit_act.dtype == torch.float32 and crit_act.is_contiguous() and crit_act.numel() == N * N_AGENTS
+        if logits is not None:
+            assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == N * N_AGENTS * 4
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().hh_commander_sample(self.h, ptr(obs), N, ptr(h_in), ptr(h_out), ptr(fresh), None if world is None else world.h,
+                                            ptr(uniforms), ptr(crit_act), 1 if greedy else 0, ptr(actions), ptr(logp), ptr(vf), ptr(logits), st))
+        return actions, logp, vf
+
+    def kernel_name(self, n_arenas):
+        buf = C.create_string_buffer(64)
+        L.check(L.lib().hh_commander_kernel_name(self.h, int(n_arenas), buf, 64))
+        return buf.value.decode()
+
+
+class CommanderRollout:
+    """What RLlib's rollout workers produce for train_hier.py's commander PPO (train_hier.py:100-199), for every arena of a 3-vs-3
+    HighLevelEnv `World` at once and without leaving the device: per commander step `CommanderNet.sample` (actor + value branch of
+    CommanderGru on central_critic_observer's rows with zero action inputs, both GRU states carried per agent and zeroed at every
+    episode start, the Categorical draw from the keyed RNG: HH_SITE_COMMANDER_SAMPLE) and one `env_hier.macro_step` with the frozen
+    pilots; after T commander steps a greedy bootstrap evaluation of obs[T] and hh_gae_rllib (gamma 0.99, RLlib's default lambda 1.0:
+    train_hier.py:186).  With the library's own NetPilot / VariantNetPilot a collect is ONE HIP graph; any other pilot runs eagerly.
+
+    Buffers (device, overwritten by every collect): obs f32 [T+1, N, 3, 34], actions i8 [T, N, 3], logp f32 [T, N, 3], vf f32
+    [T+1, N, 3], reward f32 [T, N, 3], valid u8 [T, N, 3], done u8 [T, N], adv / target f32 [T, N, 3], state_in f32 [T+1, N, 3, 2, 200]
+    (row t = the state step t's forward used — zero at an episode's first step; row T carries into the next collect).
+    Rewards: HighLevelEnv gives every agent id a reward key every step, dead agents included (env_hier.py:154,188); hh_hl_end writes
+    0.0 wherever it reports valid = 0, and in an auto-resetting world valid is 1 on every row — RLlib's rewards.get(agent_id, 0.0) is the
+    world's reward as it stands, nothing is masked."""
+
+    def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True):
+        assert world.cfg.env_kind == L.ENV_HIGHLEVEL and world.n_agents == N_AGENTS and world.cfg.auto_reset, \
+            "CommanderRollout drives an auto-resetting 3-agent HighLevelEnv world (central_critic_observer hard-codes three agents)"
+        assert commander.max_rows >= N_AGENTS * world.N, "the commander's max_rows must cover 3 x n_arenas rows"
+        self.w, self.net, self.pilot, self.T, self.gamma, self.lam = world, commander, pilot, int(T), float(gamma), float(lam)
+        N, dev, T = world.N, world.device, self.T
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.obs = z((T + 1, N, N_AGENTS, OBS), torch.float32)
+        self.actions = z((T, N, N_AGENTS), torch.int8)
+        self.logp = z((T, N, N_AGENTS), torch.float32)
+        self.vf = z((T + 1, N, N_AGENTS), torch.float32)
+        self.reward = z((T, N, N_AGENTS), torch.float32)
+        self.valid = z((T, N, N_AGENTS), torch.uint8)
+        self.done = z((T, N), torch.uint8)
+        self.adv = z((T, N, N_AGENTS), torch.float32)
+        self.target = z((T, N, N_AGENTS), torch.float32)
+        self.state_in = z((T + 1, N, N_AGENTS, 2, HIDDEN), torch.float32)
+        self._fresh = z((N,), torch.uint8)                     # episode starts at the next collect's first step
+        self._h_scratch = z((N, N_AGENTS, 2, HIDDEN), torch.float32)
+        self._tmp_act, self._tmp_logp = z((N, N_AGENTS), torch.int8), z((N, N_AGENTS), torch.float32)
+        self._pbuf = world.alloc_pilot_variants() if getattr(pilot, "variants", False) else world.alloc_pilot()
+        self.use_graph = use_graph
+        self._graph = None
+        self._started = False
+
+    def _own_pilot(self):
+        from .pilots import NetPilot, VariantNetPilot
+        return isinstance(self.pilot, (NetPilot, VariantNetPilot))
+
+    def start(self):
+        """reset every arena (the first observation becomes row 0 of the next collect) and mark every arena fresh"""
+        self.w.reset(obs=self.obs[self.T])
+        self._fresh.fill_(1)
+        self.state_in[self.T].zero_()
+        self._started = True
+
+    def _run(self):
+        from .env_hier import macro_step
+        T, w = self.T, self.w
+        self.obs[0].copy_(self.obs[T])           # where the previous collect (or start) left every arena
+        self.state_in[0].copy_(self.state_in[T])
+        for t in range(T):
+            fresh = self._fresh if t == 0 else self.done[t - 1]
+            self.net.sample(self.obs[t], self.state_in[t], self.state_in[t + 1], fresh=fresh, world=w, actions=self.actions[t],
+                            logp=self.logp[t], vf=self.vf[t])
+            macro_step(w, self.actions[t], self.pilot, out=(self.obs[t + 1], self.reward[t], self.valid[t], self.done[t]),
+                       pilot_buf=self._pbuf, early_exit=False)
+        # the bootstrap value of every arena's unfinished tail; its state_out goes to scratch (the carried state does not advance), arenas
+        # that just finished are evaluated from zero state (their value is cut by the recursion and never read)
+        self.net.sample(self.obs[T], self.state_in[T], self._h_scratch, fresh=self.done[T - 1], greedy=True, actions=self._tmp_act,
+                        logp=self._tmp_logp, vf=self.vf[T])
+        self._fresh.copy_(self.done[T - 1])
+        st = C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+        L.check(L.lib().hh_gae_rllib(T, w.N, N_AGENTS, C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.vf.data_ptr()),
+                                     C.c_void_p(self.done.data_ptr()), self.gamma, self.lam, C.c_void_p(self.adv.data_ptr()),
+                                     C.c_void_p(self.target.data_ptr()), st))
+
+    def _warm(self):
+        """first launches of every kernel outside a capture"""
+        dev = self.w.device
+        nw = min(64, self.pilot.bank.max_rows)
+        self.pilot.bank.act(torch.zeros((nw, 30), device=dev), torch.zeros((nw,), dtype=torch.uint8, device=dev))
+        h = torch.zeros_like(self._h_scratch)
+        self.net.sample(self.obs[self.T], h, self._h_scratch, greedy=True, actions=self._tmp_act, logp=self._tmp_logp)
+
+    def collect(self):
+        """T commander steps of every arena -> self (the buffers above); no host synchronisation"""
+        if not self._started:
+            self.start()
+        if not (self.use_graph and self._own_pilot()):
+            self._run()
+            return self
+        # the captured graph holds device pointers by value: the world's (trace ring, bound bank's row lists), the pilot bank's (weight blobs,
+        # selector table, the kernel instance its tile width picks) and the commander's — re-capture whenever World.trace_enable / bind_policy or
+        # PolicyBank.set_net / set_critic / set_lut / set_tile_rows / close changed them since (CommanderNet.set_weights rewrites its weights
+        # in place: the same addresses)
+        gen = (getattr(self.w, "ptr_generation", 0), id(self.pilot.bank), getattr(self.pilot.bank, "generation", 0), id(self.net), self.net.h.value)
+        if self._graph is not None and self._graph_gen != gen:
+            self._graph = None
+        if self._graph is None:
+            dev = self.w.device
+            self._warm()
+            torch.cuda.synchronize(dev)
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=side):
+                    self._run()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            self._graph, self._graph_gen = graph, gen
+        self._graph.replay()
+        return self
+
+    def critic_rows(self, agent):
+        """the flattened CUR_OBS rows of `agent` (1..3) for the T collected steps with the actions filled in (central_critic_rows_hl)"""
+        return central_critic_rows_hl(self.obs[: self.T], self.actions, agent)

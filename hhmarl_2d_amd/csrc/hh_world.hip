@@ -880,3 +880,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- frozen pilot / opponent networks (C ABI in include/hh_policy.h) ---- */
 #include "hh_policy_kernel.h"
+
+/* ---- the trainable commander of train_hier.py (C ABI in include/hh_commander.h) ---- */
+#include "hh_commander_kernel.h"

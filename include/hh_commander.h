@@ -1,0 +1,81 @@
+/*
+ * hh_commander.h — C ABI of the TRAINABLE commander policy of train_hier.py (part of libhh_world.so).
+ *
+ * What RLlib's sampler evaluates per commander step for every agent of a 3-vs-3 HighLevelEnv arena (train_hier.py:100-165 with
+ * models/ac_models_hier.py:70-112 CommanderGru): the actor (three input FCs on column ranges of the own 34-wide observation, a
+ * fourth FC on all of it, one step of a 200-wide GRU, normalize(x_full + y), the module-level shared layer, 3 logits), the
+ * Categorical draw and its log-probability, and the value branch (v1..v3 on [obs_k | act_k] of the own and the two other agents
+ * in ascending id, v4 on all three, its own GRU, the same shared layer, val_out).  Both GRU states are per agent row and are
+ * carried by the caller: h_in / h_out [rows, 2, 200], state 0 = rnn_act, state 1 = rnn_val (get_initial_state order).
+ * One fused gfx950 kernel over rows = 3 x n_arenas agent rows (hh_commander_kernel.h).
+ *
+ * Conventions as in hh_abi.h: 0 on success or a negative HH_E_* code, never throws; [dev] = caller-owned device memory,
+ * [host] = host memory; `stream` is a hipStream_t passed as void*.
+ */
+#ifndef HH_COMMANDER_H
+#define HH_COMMANDER_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define HH_CMD_OBS 34     /* commander observation width (env_hier.py: 14 + 10 N_OPP_HL) */
+#define HH_CMD_AGENTS 3   /* agent rows per arena (central_critic_observer hard-codes three) */
+#define HH_CMD_HIDDEN 200 /* GRU width of both branches */
+#define HH_CMD_ACTIONS 3  /* Discrete(N_OPP_HL + 1) */
+#define HH_CMD_LOGITS 4   /* row width of the optional logits output (zero padded) */
+
+typedef struct hh_commander hh_commander;
+
+/* [host] fp32, row-major [out, in] as the reference's state_dict() holds them */
+typedef struct hh_commander_weights {
+    const float *inp_w[4], *inp_b[4];                       /* inp1 [50,4]  inp2 [200,20]  inp3 [50,10]  inp4 [200,34] */
+    const float *act_w_ih, *act_w_hh, *act_b_ih, *act_b_hh; /* rnn_act.{weight,bias}_{ih,hh}_l0  [600,200] [600], gate rows r|z|n */
+    const float *shared_w, *shared_b;                       /* shared_layer._model.0  [500,500] [500]  (one tensor, both branches) */
+    const float *act_out_w, *act_out_b;                     /* [3,500] [3] */
+    const float *v_w[4], *v_b[4];                           /* v1..v3 [100,35]  v4 [200,105] */
+    const float *val_w_ih, *val_w_hh, *val_b_ih, *val_b_hh; /* rnn_val.* */
+    const float *val_out_w, *val_out_b;                     /* [1,500] [1] */
+} hh_commander_weights;
+
+/* a commander network on `device`; max_rows = the largest 3 x n_arenas hh_commander_sample will be given */
+int hh_commander_create(int device, int32_t max_rows, hh_commander **out);
+int hh_commander_destroy(hh_commander *c);
+
+/* load (or replace) the weights: repacked on the host into the kernel's split-fp16 fragment layout and copied.  Synchronous. */
+int hh_commander_set_weights(hh_commander *c, const hh_commander_weights *w);
+
+/* One sampler step of every agent row (row r = agent slot r % 3 of arena r / 3):
+ *   obs       [dev] f32 [N, 3, 34]      the commander observations hh_hl_end / hh_reset write (dead agents: zero rows)
+ *   h_in      [dev] f32 [3N, 2, 200]    the GRU states the forward uses; rows of arenas flagged fresh are OVERWRITTEN with zeros (the
+ *                                       stored state_in is then exactly what the forward used)
+ *   h_out     [dev] f32 [3N, 2, 200]    the new states (state_out); must not overlap h_in (HH_E_ARG)
+ *   fresh     [dev] u8  [N] or NULL     non-zero: the arena starts an episode at this step (get_initial_state: zero states)
+ *   w         the world whose agents these are (n_arenas == its arena count), or NULL.  With a world, agent slot i of arena n draws
+ *             u = U(seed, arena_offset + n, episode, steps, i + 1, HH_SITE_COMMANDER_SAMPLE, 0)  (hh_rng.h) with the arena's CURRENT
+ *             counters, as hh_policy_sample does.
+ *   uniforms  [dev] f64 [3N] or NULL    overrides the keyed draw.  Exactly one of w / uniforms unless greedy.
+ *   crit_act  [dev] f32 [N, 3] or NULL  the value branch's act_k inputs per agent slot (on_postprocess_trajectory's action / 2); NULL =
+ *                                       zeros, which is what the sampler sees
+ *   greedy    != 0: arg-max instead of a draw (logp is then the log-probability of the arg-max)
+ *   actions   [dev] i8  [N, 3]          the layout hh_hl_begin / hh_hl_begin_variants read
+ *   logp      [dev] f32 [N, 3]
+ *   vf        [dev] f32 [N, 3]          value_function(); nullable (the value GRU state still advances)
+ *   logits    [dev] f32 [3N, 4]         nullable (4-byte alignment suffices)
+ * Inverse CDF as hh_policy_sample: m = max l, S = sum exp(l_i - m) in index order, t = (float)u * S, the action is the first i whose
+ * running sum exceeds t (the last if none does); logp = (l_a - m) - log S.  Everything is ordered on `stream`; no host synchronisation
+ * and no allocation (HIP-graph capturable). */
+struct hh_world;
+int hh_commander_sample(hh_commander *c, const float *obs, int32_t n_arenas, float *h_in, float *h_out, const uint8_t *fresh,
+                        struct hh_world *w, const double *uniforms, const float *crit_act, int32_t greedy, int8_t *actions, float *logp,
+                        float *vf, float *logits, void *stream);
+
+/* name of the kernel a call of n_arenas arenas launches, as a profiler prints it */
+int hh_commander_kernel_name(hh_commander *c, int32_t n_arenas, char *buf, int32_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HH_COMMANDER_H */

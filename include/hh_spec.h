@@ -123,7 +123,8 @@ enum {
                                    (TorchMultiCategorical.sample -> torch.multinomial, unseeded in the reference); sub = component */
     HH_SITE_ACTION_TAPE = 26,   /* hh_action_tape_uniform (hh_abi.h): the synthetic "random actions" of the benchmark workloads (SURVEY.md 8d:
                                    i.i.d. uniform over MultiDiscrete([13,9,2,2]) keyed by (arena, step, agent)); sub = component; episode key 0 */
-    HH_SITE_COUNT = 27
+    HH_SITE_COMMANDER_SAMPLE = 27, /* hh_commander_sample (hh_commander.h): the commander's Categorical draw (Discrete(3)) per agent; sub = 0 */
+    HH_SITE_COUNT = 28
 };
 
 #endif /* HH_SPEC_H */
