@@ -80,6 +80,17 @@ class HHEpisodeBufs(C.Structure):
             "ep_start", "ep_len", "ep_arena", "counts")]
 
 
+class HHCommanderEpisodeBufs(C.Structure):
+    """hh_commander_episode_bufs (include/hh_commander.h): sizes, then device pointers (collect, carry, batch); field order is ABI"""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("max_seq_len", C.c_int32), ("carry_cap", C.c_int32), ("row_cap", C.c_int64),
+                ("ep_cap", C.c_int64), ("seq_cap", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double)] + [
+        (name, C.c_void_p) for name in (
+            "obs", "actions", "logp", "vf", "reward", "valid", "done", "state_in",
+            "c_obs", "c_actions", "c_logp", "c_vf", "c_reward", "c_valid", "c_state", "carried", "episode", "scratch",
+            "o_obs", "o_actions", "o_logp", "o_vf", "o_reward", "o_valid", "o_adv", "o_target", "o_done", "o_arena", "o_episode", "o_t",
+            "ep_start", "ep_len", "ep_arena", "seq_start", "seq_len", "seq_ep", "o_state_in", "counts")]
+
+
 EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim", "hh_n_ctrl", "hh_reset", "hh_step",
            "hh_rollout", "hh_episode_stats", "hh_get_state", "hh_set_state", "hh_get_event_masks", "hh_observe",
            "hh_hl_begin", "hh_hl_agents_act", "hh_hl_tick", "hh_hl_end", "hh_step_begin", "hh_step_finish", "hh_gae", "hh_hl_commands",
@@ -89,7 +100,7 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
-                     "hh_commander_kernel_name"]  # include/hh_commander.h
+                     "hh_commander_kernel_name", "hh_commander_episodes_emit"]  # include/hh_commander.h
 
 _lib = None
 
@@ -160,6 +171,7 @@ def lib():
         L.hh_commander_set_weights.argtypes = [vp, C.POINTER(HHCommanderWeights)]
         L.hh_commander_sample.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_commander_kernel_name.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32]
+        L.hh_commander_episodes_emit.argtypes = [C.POINTER(HHCommanderEpisodeBufs), vp]
         _lib = L
     return _lib
 

@@ -132,6 +132,137 @@ class CommanderNet:
         return buf.value.decode()
 
 
+def default_carry_cap(horizon, n_agents=N_AGENTS, n_opps=3):
+    """rows an unfinished commander episode can hold, with `horizon` H ticks (the carry of CommanderEpisodeBatch): ceil(H / 12) + n_agents
+    + n_opps - 1 (47 at H = 500, 3 vs 3).
+
+    The world's sub-step loop (env_hier.py:114-140; hh_kernels_hier.h / hh_kernels_oct.h, hl_run after every tick): a commander step
+    runs ticks until hl_s > 15 (16 ticks), a kill event (an aircraft removed in the tick) or the surrounding event, which is looked for
+    only while hl_s > 10 before the tick's increment, i.e. from the 12th tick on.  So a step without a kill event lasts at least 12 ticks,
+    a step with one at least 1.  The episode ends (done) after the step in which `steps` reaches H or one side has no aircraft left.
+    An episode still running after r steps therefore has fewer than H ticks behind it and both sides alive: at most
+    (n_agents - 1) + (n_opps - 1) deaths, so at most that many kill-event steps, and the others fit 12 ticks each into H - 1:
+    r <= floor((H - 1) / 12) + n_agents + n_opps - 2.  The rounder ceil(H / 12) + n_agents + n_opps - 1 is at least one more than that
+    for every H.  (horizon - 1 rows, one per tick, would be 10 times as much carry: 1.7 GB of observations at N = 8192.)"""
+    return -(-int(horizon) // 12) + int(n_agents) + int(n_opps) - 1
+
+
+class CommanderEpisodeBatch:
+    """The whole-episode GRU-sequence batch of a `CommanderRollout(..., batch_mode="complete_episodes")` (train_hier.py:182 with the
+    recurrent CommanderGru, RLlib's max_seq_len = 20): after every collect, the rows of every episode that ENDED in it, from its reset
+    row to its done row, in one flat batch; GAE over each whole episode (hh_gae_rllib's float64 recursion, last_r = 0.0:
+    oracle/gae_ref.compute_advantages per episode and agent); every episode cut into sequences of at most L = max_seq_len steps
+    (ceil(E / L) per episode of E rows: L, ..., L, then the remainder; a sequence never crosses a done), and the GRU states of each
+    sequence's first step, bit-identical to the state_in the sampler's forward used there — also when that step lies in an earlier
+    collect: the device carry keeps, besides the running episode's rows, the states at its sequence starts.  Written by
+    hh_commander_episodes_emit (include/hh_commander.h) inside the collect's graph; no host synchronisation until `rows()`.
+
+    Device buffers of fixed capacity, overwritten by every collect, in the order arena-major, then episode, then time:
+      obs f32 [R, 3, 34], actions i8 [R, 3], logp / vf / reward f32 [R, 3], valid u8 [R, 3], adv / target f32 [R, 3], done u8 [R] (1 on
+      an episode's last row only), arena / episode / t i32 [R] (`episode` counts per arena from `start()`, `t` the step within the
+      episode from 0); episode table ep_start / ep_len / ep_arena i32 [E]; sequence table seq_start (row in the batch) / seq_len /
+      seq_ep (episode entry) i32 [S]; state_in f32 [S, 3, 2, 200] ([:, :, 0] = state_in_0 = rnn_act, [:, :, 1] = state_in_1 = rnn_val);
+      carried i32 [N] (rows of each arena's running episode held for a later collect).
+    vf stays VF_PREDS as sampled (zero action inputs); `critic_rows` gives the learner's action-filled CUR_OBS rows.
+
+    Capacity, with C = carry_cap (default_carry_cap: the rows an unfinished episode can have) and L: the carry holds N C rows and
+    N ceil(C / L) states; the batch R = N (C + T) rows, E = N T episodes and S = N (T + C // L) sequences (an arena emits at most
+    C + T rows in at most T episodes, and sum ceil(E_k / L) <= n_eps + (rows - n_eps) / L).  Bytes per arena:
+      450 C + 4800 ceil(C / L) (carry) + 487 (C + T) (rows) + 12 T (episode table) + 4812 (T + C // L) (sequences and their states).
+    N = 8192, T = 16, H = 500 (C = 47), L = 20: 173 MB of row carry, 118 MB of state carry, 251 MB of rows, 2 MB of episode table
+    and 710 MB of sequences: 1.25 GB in all.  Nothing overflows under that rule; if something did anyway (a carry_cap below it), a
+    sticky device flag is set and `rows()` raises."""
+
+    COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
+    TABLES = ("ep_start", "ep_len", "ep_arena")
+    SEQ_TABLE = ("seq_start", "seq_len", "seq_ep")
+
+    def __init__(self, N, T, max_seq_len, carry_cap, device, gamma, lam, collect):
+        """collect: the rollout's [T(+1), N, ...] buffers (obs, actions, logp, vf, reward, valid, done, state_in) that every emission reads"""
+        self.N, self.T, self.L, self.carry_cap = int(N), int(T), int(max_seq_len), int(carry_cap)
+        N, T, sl, cap, nA = self.N, self.T, self.L, self.carry_cap, N_AGENTS
+        R, E, S = N * (cap + T), N * T, N * (T + cap // sl)
+        sc = max(-(-cap // sl), 1)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        f32, i8, u8, i32 = torch.float32, torch.int8, torch.uint8, torch.int32
+        self.obs, self.actions = z((R, nA, OBS), f32), z((R, nA), i8)
+        self.logp, self.vf, self.reward, self.valid = z((R, nA), f32), z((R, nA), f32), z((R, nA), f32), z((R, nA), u8)
+        self.adv, self.target = z((R, nA), f32), z((R, nA), f32)
+        self.done, self.arena, self.episode, self.t = z((R,), u8), z((R,), i32), z((R,), i32), z((R,), i32)
+        self.ep_start, self.ep_len, self.ep_arena = z((E,), i32), z((E,), i32), z((E,), i32)
+        self.seq_start, self.seq_len, self.seq_ep = z((S,), i32), z((S,), i32), z((S,), i32)
+        self.state_in = z((S, nA, 2, HIDDEN), f32)
+        self.carried = z((N,), i32)
+        c = max(cap, 1)
+        self._carry = {"obs": z((N, c, nA, OBS), f32), "actions": z((N, c, nA), i8), "logp": z((N, c, nA), f32),
+                       "vf": z((N, c, nA), f32), "reward": z((N, c, nA), f32), "valid": z((N, c, nA), u8),
+                       "state": z((N, sc, nA, 2, HIDDEN), f32)}
+        self._finished = z((N,), i32)            # episodes finished per arena since start()
+        self._scratch = z((10 * N + 4,), i32)
+        self._counts = z((4,), i32)              # rows, episodes of the last collect; overflow flag (sticky); sequences of the last collect
+        self.n_rows, self.n_episodes, self.n_sequences = self._counts[0], self._counts[1], self._counts[3]
+        b = L.HHCommanderEpisodeBufs(T=T, N=N, max_seq_len=sl, carry_cap=cap, row_cap=R, ep_cap=E, seq_cap=S, gamma=float(gamma), lam=float(lam))
+        for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done", "state_in"):
+            assert collect[k].is_contiguous() and collect[k].shape[1] == N
+            setattr(b, k, collect[k].data_ptr())
+        for k, v in self._carry.items():
+            setattr(b, "c_" + k, v.data_ptr())
+        b.carried, b.episode, b.scratch = self.carried.data_ptr(), self._finished.data_ptr(), self._scratch.data_ptr()
+        for k in self.COLUMNS:
+            setattr(b, "o_" + k, getattr(self, k).data_ptr())
+        for k in self.TABLES + self.SEQ_TABLE:
+            setattr(b, k, getattr(self, k).data_ptr())
+        b.o_state_in, b.counts = self.state_in.data_ptr(), self._counts.data_ptr()
+        self._bufs, self._collect, self._device = b, collect, device   # the struct holds raw pointers: keep the tensors alive
+
+    def reset(self):
+        """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
+        self.carried.zero_()
+        self._finished.zero_()
+        self._counts[:2].zero_()
+        self._counts[3:].zero_()
+
+    def emit(self, stream):
+        L.check(L.lib().hh_commander_episodes_emit(C.byref(self._bufs), stream))
+
+    def rows(self):
+        """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES), the sequence table
+        (SEQ_TABLE) and state_in [S, 3, 2, 200]"""
+        torch.cuda.synchronize(self._device)
+        R, E, overflow, S = self._counts.tolist()
+        if overflow:
+            raise RuntimeError("CommanderEpisodeBatch: an episode outgrew the carry or a batch capacity (carry_cap below the episode "
+                               "bound?): the batches since that collect are incomplete")
+        out = {k: getattr(self, k)[:R] for k in self.COLUMNS}
+        out.update({k: getattr(self, k)[:E] for k in self.TABLES})
+        out.update({k: getattr(self, k)[:S] for k in self.SEQ_TABLE})
+        out["state_in"] = self.state_in[:S]
+        return out
+
+    def sequences(self):
+        """the learner's padded form (RLlib's chop_into_sequences, all three agents of an arena row side by side; per agent it is the slice
+        [..., a, ...]), gathered on the device through the sequence table: obs f32 [S, L, 3, 34], actions i8 / logp / vf / adv / target
+        [S, L, 3] (zero past seq_len), seq_lens i32 [S], mask bool [S, L], state_in f32 [S, 3, 2, 200]"""
+        r = self.rows()
+        S, sl = r["seq_start"].shape[0], self.L
+        steps = torch.arange(sl, dtype=torch.int64, device=self._device)
+        mask = steps[None, :] < r["seq_len"].long()[:, None]
+        idx = torch.where(mask, r["seq_start"].long()[:, None] + steps[None, :], torch.zeros((), dtype=torch.int64, device=self._device))
+        out = {}
+        for k in ("obs", "actions", "logp", "vf", "adv", "target"):
+            col = r[k]
+            g = col[idx] if col.shape[0] > 0 else torch.zeros((S, sl) + tuple(col.shape[1:]), dtype=col.dtype, device=self._device)
+            m = mask.view(S, sl, *([1] * (g.dim() - 2)))
+            out[k] = torch.where(m, g, torch.zeros((), dtype=g.dtype, device=self._device))
+        out["seq_lens"], out["mask"], out["state_in"] = r["seq_len"], mask, r["state_in"]
+        return out
+
+    def critic_rows(self, agent):
+        """the CUR_OBS rows of `agent` (1..3) for the emitted rows with the actions filled in (central_critic_rows_hl)"""
+        r = self.rows()
+        return central_critic_rows_hl(r["obs"], r["actions"], agent)
+
+
 class CommanderRollout:
     """What RLlib's rollout workers produce for train_hier.py's commander PPO (train_hier.py:100-199), for every arena of a 3-vs-3
     HighLevelEnv `World` at once and without leaving the device: per commander step `CommanderNet.sample` (actor + value branch of
@@ -145,9 +276,22 @@ class CommanderRollout:
     (row t = the state step t's forward used — zero at an episode's first step; row T carries into the next collect).
     Rewards: HighLevelEnv gives every agent id a reward key every step, dead agents included (env_hier.py:154,188); hh_hl_end writes
     0.0 wherever it reports valid = 0, and in an auto-resetting world valid is 1 on every row — RLlib's rewards.get(agent_id, 0.0) is the
-    world's reward as it stands, nothing is masked."""
+    world's reward as it stands, nothing is masked.
 
-    def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True):
+    batch_mode = "truncate_episodes" (default): the buffers above are the result.  batch_mode = "complete_episodes" (train_hier.py:182):
+    every collect still fills them exactly the same way, and then also `episodes`, a `CommanderEpisodeBatch` of every episode that ended
+    in it, whole and cut into GRU sequences of at most `max_seq_len` steps; its launches join the collect's graph after the GAE."""
+
+    def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
+                 carry_cap=None):
+        """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world)"""
+        if batch_mode not in ("truncate_episodes", "complete_episodes"):
+            raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes cut into GRU "
+                             "sequences: CommanderEpisodeBatch)")
+        if int(max_seq_len) < 1:
+            raise ValueError("max_seq_len must be at least 1")
+        if carry_cap is not None and int(carry_cap) < 0:
+            raise ValueError("carry_cap must not be negative")
         assert world.cfg.env_kind == L.ENV_HIGHLEVEL and world.n_agents == N_AGENTS and world.cfg.auto_reset, \
             "CommanderRollout drives an auto-resetting 3-agent HighLevelEnv world (central_critic_observer hard-codes three agents)"
         assert commander.max_rows >= N_AGENTS * world.N, "the commander's max_rows must cover 3 x n_arenas rows"
@@ -168,6 +312,13 @@ class CommanderRollout:
         self._h_scratch = z((N, N_AGENTS, 2, HIDDEN), torch.float32)
         self._tmp_act, self._tmp_logp = z((N, N_AGENTS), torch.int8), z((N, N_AGENTS), torch.float32)
         self._pbuf = world.alloc_pilot_variants() if getattr(pilot, "variants", False) else world.alloc_pilot()
+        self.batch_mode, self.max_seq_len = batch_mode, int(max_seq_len)
+        self.episodes = None
+        if batch_mode == "complete_episodes":
+            cap = default_carry_cap(world.cfg.horizon, world.cfg.n_agents, world.cfg.n_opps) if carry_cap is None else int(carry_cap)
+            self.episodes = CommanderEpisodeBatch(N, T, self.max_seq_len, cap, dev, self.gamma, self.lam,
+                                                  {k: getattr(self, k) for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done",
+                                                                                 "state_in")})
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -181,6 +332,8 @@ class CommanderRollout:
         self.w.reset(obs=self.obs[self.T])
         self._fresh.fill_(1)
         self.state_in[self.T].zero_()
+        if self.episodes is not None:
+            self.episodes.reset()
         self._started = True
 
     def _run(self):
@@ -203,6 +356,8 @@ class CommanderRollout:
         L.check(L.lib().hh_gae_rllib(T, w.N, N_AGENTS, C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.vf.data_ptr()),
                                      C.c_void_p(self.done.data_ptr()), self.gamma, self.lam, C.c_void_p(self.adv.data_ptr()),
                                      C.c_void_p(self.target.data_ptr()), st))
+        if self.episodes is not None:
+            self.episodes.emit(st)
 
     def _warm(self):
         """first launches of every kernel outside a capture"""

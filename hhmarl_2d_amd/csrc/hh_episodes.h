@@ -87,6 +87,25 @@ __global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_episode_bufs b) {
     }
 }
 
+/* wave 0 of an arena's workgroup (lane = tid < 64): per tick t of the window, the episodes that ended strictly before t (l_seg), the last
+ * done tick strictly before t (l_prev, -1: none) and the done flag (l_done) */
+__device__ __forceinline__ void hh_ep_tick_tables(const uint8_t *done, int T, int N, int n, int lane, int *l_seg, int *l_prev, int *l_done) {
+    int cnt = 0, prev = -1;
+    for (int base = 0; base < T; base += 64) {
+        const int t = base + lane;
+        const bool d = t < T && done[(size_t)t * N + n] != 0;
+        const unsigned long long m = __ballot(d);
+        const unsigned long long below = m & ((1ull << lane) - 1ull);
+        if (t < T) {
+            l_seg[t] = cnt + __popcll(below);
+            l_prev[t] = below ? base + 63 - __clzll((long long)below) : prev;
+            l_done[t] = d;
+        }
+        cnt += __popcll(m);
+        if (m) prev = base + 63 - __clzll((long long)m);
+    }
+}
+
 /* rows [0, rows) of one arena's emission: row i < cl is carry slot i, row i >= cl is tick i - cl of the window */
 template <typename U>
 __device__ __forceinline__ void hh_ep_gather(U *out, const U *carry, const U *coll, int upr, int rows, int cl, size_t crow0, int N, int n, size_t orow0) {
@@ -118,22 +137,7 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_episode_bufs b) {
     const int last = s[HH_EP_S_LAST * N + n], nd = s[HH_EP_S_EPS * N + n];
     const int ro = s[HH_EP_S_ROW_OFF * N + n], eo = s[HH_EP_S_EP_OFF * N + n];
     const int ep0 = b.episode[n];
-    if (tid < 64) {
-        int cnt = 0, prev = -1;
-        for (int base = 0; base < b.T; base += 64) {
-            const int t = base + tid;
-            const bool d = t < b.T && b.done[(size_t)t * N + n] != 0;
-            const unsigned long long m = __ballot(d);
-            const unsigned long long below = m & ((1ull << tid) - 1ull);
-            if (t < b.T) {
-                l_seg[t] = cnt + __popcll(below);
-                l_prev[t] = below ? base + 63 - __clzll((long long)below) : prev;
-                l_done[t] = d;
-            }
-            cnt += __popcll(m);
-            if (m) prev = base + 63 - __clzll((long long)m);
-        }
-    }
+    if (tid < 64) hh_ep_tick_tables(b.done, b.T, N, n, tid, l_seg, l_prev, l_done);
     __syncthreads();
 
     // 1. the finished episodes: carry slots [0, cl), then ticks [0, last]

@@ -883,3 +883,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- the trainable commander of train_hier.py (C ABI in include/hh_commander.h) ---- */
 #include "hh_commander_kernel.h"
+
+/* ---- whole-episode GRU-sequence batches of the commander (C ABI in include/hh_commander.h) ---- */
+#include "hh_commander_episodes.h"

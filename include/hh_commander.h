@@ -75,6 +75,80 @@ int hh_commander_sample(hh_commander *c, const float *obs, int32_t n_arenas, flo
 /* name of the kernel a call of n_arenas arenas launches, as a profiler prints it */
 int hh_commander_kernel_name(hh_commander *c, int32_t n_arenas, char *buf, int32_t len);
 
+/* Whole-episode GRU-sequence batches of the commander (batch_mode = "complete_episodes" with a recurrent model, train_hier.py:182):
+ * what hh_episodes_emit (hh_abi.h) does for PPORollout, plus RLlib's cut of every agent's trajectory into sequences of at most
+ * max_seq_len (L) steps, each with the GRU states of its first step.  hh_commander_episodes_emit takes one collect's [T, N, ...]
+ * buffers (auto-resetting arenas: the row after a done is the next episode's row 0), keeps every arena's running episode in a
+ * device-side carry across calls — its rows, and the GRU states at its sequence starts (within-episode steps 0, L, 2L, ...) only —
+ * and writes every episode that ended in this window into one flat batch, arena-major, then episode, then time; its sequences
+ * (ceil(E / L) per episode of E rows: L, ..., L, then the remainder) in the same order; and o_state_in[s] = state_in of the
+ * sequence's first step, bit for bit.  adv / target: hh_gae_rllib's recursion over each whole episode with last_r = 0.0.
+ * Launches on the calling thread's current device, which must own every buffer; no host synchronisation and no allocation
+ * (graph-capturable).  All pointers [dev].
+ * Capacities (checked): carry_cap >= the rows an unfinished episode can have; row_cap >= N (carry_cap + T); ep_cap >= N T;
+ * seq_cap >= N (T + carry_cap / L) (an arena emits at most carry_cap + T rows in at most T episodes, and sum ceil(E_k / L) <=
+ * n_eps + (rows - n_eps) / L).  If an episode outgrows the carry anyway, counts[2] is set (sticky) and nothing is written out of
+ * bounds.  The caller zeroes carried / episode (and counts) before the first call and whenever its arenas are reset. */
+typedef struct hh_commander_episode_bufs {
+    int32_t T;                /* commander steps per call */
+    int32_t N;                /* arenas */
+    int32_t max_seq_len;      /* L >= 1 */
+    int32_t carry_cap;        /* rows per arena the carry holds */
+    int64_t row_cap;          /* rows of every output column (>= N (carry_cap + T); < 2^31) */
+    int64_t ep_cap;           /* entries of the episode table (>= N T) */
+    int64_t seq_cap;          /* entries of the sequence table and of o_state_in (>= N (T + carry_cap / L)) */
+    double gamma;
+    double lam;
+    /* one collect (read): obs f32 [T+1, N, 3, 34], actions i8 [T, N, 3], logp f32 [T, N, 3], vf f32 [T+1, N, 3], reward f32 [T, N, 3],
+       valid u8 [T, N, 3], done u8 [T, N], state_in f32 [T+1, N, 3, 2, 200] (16-byte aligned) */
+    const float *obs;
+    const int8_t *actions;
+    const float *logp;
+    const float *vf;
+    const float *reward;
+    const uint8_t *valid;
+    const uint8_t *done;
+    const float *state_in;
+    /* carry (read and written): the same row columns [N, carry_cap, ...], c_state f32 [N, ceil(carry_cap / L), 3, 2, 200] (16-byte
+       aligned: the states at the running episode's sequence starts), carried / episode i32 [N] (rows held; episodes finished since the
+       reset), scratch i32 [10 N + 4] */
+    float *c_obs;
+    int8_t *c_actions;
+    float *c_logp;
+    float *c_vf;
+    float *c_reward;
+    uint8_t *c_valid;
+    float *c_state;
+    int32_t *carried;
+    int32_t *episode;
+    int32_t *scratch;
+    /* batch (written): the collect's row columns [row_cap, ...], adv / target f32 [row_cap, 3], done u8 [row_cap] (1 on an episode's
+       last row only), arena / episode / t i32 [row_cap]; episode table [ep_cap]; sequence table [seq_cap]: first row in the batch,
+       length, episode entry; o_state_in f32 [seq_cap, 3, 2, 200] (16-byte aligned) */
+    float *o_obs;
+    int8_t *o_actions;
+    float *o_logp;
+    float *o_vf;
+    float *o_reward;
+    uint8_t *o_valid;
+    float *o_adv;
+    float *o_target;
+    uint8_t *o_done;
+    int32_t *o_arena;
+    int32_t *o_episode;
+    int32_t *o_t;
+    int32_t *ep_start;
+    int32_t *ep_len;
+    int32_t *ep_arena;
+    int32_t *seq_start;
+    int32_t *seq_len;
+    int32_t *seq_ep;
+    float *o_state_in;
+    int32_t *counts;          /* [4]: rows, episodes written by this call; overflow flag (sticky); sequences written by this call */
+} hh_commander_episode_bufs;
+
+int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
