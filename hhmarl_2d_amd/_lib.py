@@ -46,14 +46,14 @@ class HHStateView(C.Structure):
 
 
 class HHNetWeights(C.Structure):
-    """hh_net_weights (include/hh_policy.h): host pointers to one network's tensors, nn.Linear layout"""
+    """hh_net_weights (include/hh_policy.h): pointers to one network's tensors, nn.Linear layout (host; device for hh_policy_refresh)"""
     _fields_ = [("kind", C.c_int32), ("inp_w", C.c_void_p * 3), ("inp_b", C.c_void_p * 3),
                 ("att_in_proj_w", C.c_void_p), ("att_in_proj_b", C.c_void_p), ("att_out_w", C.c_void_p), ("att_out_b", C.c_void_p),
                 ("shared_w", C.c_void_p), ("shared_b", C.c_void_p), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
 
 
 class HHCriticWeights(C.Structure):
-    """hh_critic_weights (include/hh_policy.h): host pointers to one network's value branch, nn.Linear layout"""
+    """hh_critic_weights (include/hh_policy.h): pointers to one network's value branch, nn.Linear layout (host; device for hh_policy_refresh)"""
     _fields_ = [("kind", C.c_int32), ("v_w", C.c_void_p * 3), ("v_b", C.c_void_p * 3),
                 ("att_in_proj_w", C.c_void_p), ("att_in_proj_b", C.c_void_p), ("att_out_w", C.c_void_p), ("att_out_b", C.c_void_p),
                 ("shared_w", C.c_void_p), ("shared_b", C.c_void_p), ("val_w", C.c_void_p), ("val_b", C.c_void_p)]
@@ -98,9 +98,10 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_create", "hh_policy_destroy", "hh_policy_set_net", "hh_policy_set_lut", "hh_policy_set_tile_rows", "hh_policy_act",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
-           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit"]
+           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
-                     "hh_commander_kernel_name", "hh_commander_episodes_emit"]  # include/hh_commander.h
+                     "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
+                     "hh_commander_copy_packed"]  # include/hh_commander.h
 
 _lib = None
 
@@ -164,6 +165,8 @@ def lib():
         L.hh_policy_set_critic.argtypes = [vp, C.c_int32, C.POINTER(HHCriticWeights)]
         L.hh_policy_sample.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_kernel_name.argtypes = [vp, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
+        L.hh_policy_refresh.argtypes = [vp, C.c_int32, C.POINTER(HHNetWeights), C.POINTER(HHCriticWeights), vp]
+        L.hh_policy_copy_packed.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
         L.hh_action_faults.argtypes = [vp, vp, C.c_int32, vp]
         L.hh_action_tape_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
         L.hh_commander_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
@@ -172,6 +175,8 @@ def lib():
         L.hh_commander_sample.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_commander_kernel_name.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32]
         L.hh_commander_episodes_emit.argtypes = [C.POINTER(HHCommanderEpisodeBufs), vp]
+        L.hh_commander_refresh_weights.argtypes = [vp, C.POINTER(HHCommanderWeights), vp]
+        L.hh_commander_copy_packed.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
         _lib = L
     return _lib
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import policy_nets as PN
 from .rollout import central_critic_rows_hl
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
@@ -46,9 +47,23 @@ def from_torch_module(module):
     return OrderedDict((k, sd[k]) for k in state_keys())
 
 
+def _weights_struct(p):
+    """hh_commander_weights; p(state_dict key) -> pointer"""
+    w = L.HHCommanderWeights()
+    for i in range(4):
+        w.inp_w[i], w.inp_b[i] = p(f"inp{i + 1}._model.0.weight"), p(f"inp{i + 1}._model.0.bias")
+        w.v_w[i], w.v_b[i] = p(f"v{i + 1}._model.0.weight"), p(f"v{i + 1}._model.0.bias")
+    w.act_w_ih, w.act_w_hh, w.act_b_ih, w.act_b_hh = (p(f"rnn_act.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+    w.val_w_ih, w.val_w_hh, w.val_b_ih, w.val_b_hh = (p(f"rnn_val.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+    w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
+    w.act_out_w, w.act_out_b = p("act_out._model.0.weight"), p("act_out._model.0.bias")
+    w.val_out_w, w.val_out_b = p("val_out._model.0.weight"), p("val_out._model.0.bias")
+    return w
+
+
 class CommanderNet:
-    """CommanderGru on one GPU: `set_weights(sd)` (the reference's state_dict, numpy or torch), `sample(...)` = one sampler step of
-    [N, 3] agent rows (hh_commander_sample)."""
+    """CommanderGru on one GPU: `set_weights(sd)` (the reference's state_dict, numpy or torch), `refresh_weights(sd)` (the same from CUDA
+    tensors, on the device), `sample(...)` = one sampler step of [N, 3] agent rows (hh_commander_sample)."""
 
     def __init__(self, device, max_rows):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -79,19 +94,31 @@ class CommanderNet:
             if v.shape != shp:
                 raise ValueError(f"{k}: shape {v.shape}, CommanderGru has {shp}")
             arr[k] = v
-        p = lambda k: arr[k].ctypes.data
-        w = L.HHCommanderWeights()
-        for i in range(4):
-            w.inp_w[i], w.inp_b[i] = p(f"inp{i + 1}._model.0.weight"), p(f"inp{i + 1}._model.0.bias")
-            w.v_w[i], w.v_b[i] = p(f"v{i + 1}._model.0.weight"), p(f"v{i + 1}._model.0.bias")
-        w.act_w_ih, w.act_w_hh, w.act_b_ih, w.act_b_hh = (p(f"rnn_act.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
-        w.val_w_ih, w.val_w_hh, w.val_b_ih, w.val_b_hh = (p(f"rnn_val.{n}_l0") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
-        w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
-        w.act_out_w, w.act_out_b = p("act_out._model.0.weight"), p("act_out._model.0.bias")
-        w.val_out_w, w.val_out_b = p("val_out._model.0.weight"), p("val_out._model.0.bias")
+        w = _weights_struct(lambda k: arr[k].ctypes.data)
         L.check(L.lib().hh_commander_set_weights(self.h, C.byref(w)))
         self._w = arr
         return self
+
+    def refresh_weights(self, sd):
+        """The learner's new weights from float32 CUDA tensors keyed like the reference's state_dict() (state_keys), repacked on the device
+        into the same bytes set_weights writes, in place, ordered on the current torch stream (hh_commander_refresh_weights): no host
+        synchronisation, capturable into a CUDA graph, and a captured CommanderRollout keeps replaying (same addresses, no re-capture).
+        The commander must have been loaded once with set_weights."""
+        arr = PN.device_weights(state_keys(), sd, self.device, "CommanderNet.refresh_weights")
+        w = _weights_struct(lambda k: arr[k].data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hh_commander_refresh_weights(self.h, C.byref(w), st))
+        self._w = None   # the host copy of set_weights is stale now
+        return self
+
+    def packed(self, part):
+        """test hook: one packed part as the kernel reads it (hh_commander_copy_packed; 0 fp16 planes, 1 fp32 section) -> uint8 CUDA tensor"""
+        n = C.c_int64()
+        L.check(L.lib().hh_commander_copy_packed(self.h, int(part), None, 0, C.byref(n), None))
+        out = torch.empty((n.value,), dtype=torch.uint8, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hh_commander_copy_packed(self.h, int(part), C.c_void_p(out.data_ptr()), n.value, C.byref(n), st))
+        return out
 
     def sample(self, obs, h_in, h_out, fresh=None, world=None, uniforms=None, crit_act=None, greedy=False, actions=None, logp=None,
                vf=None, logits=None, want_vf=True):

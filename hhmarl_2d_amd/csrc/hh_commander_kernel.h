@@ -286,6 +286,12 @@ extern "C" int hh_commander_destroy(hh_commander *c) {
     return HH_OK;
 }
 
+/* the first layer's blocks (hhc_set_weights and the device refresh, hh_weight_refresh.h): first input column, last + 1 | width, output
+ * width and first output column in S order [e (300) | 0 | f (200) | 0] — actor inp1..inp4 on the observation, critic v1..v4 on
+ * [obs_own|act_own|obs_o1|act_o1|obs_o2|act_o2] */
+static const int HHC_L1A_C0[4] = {0, 4, 24, 0}, HHC_L1A_C1[4] = {4, 24, 34, 34}, HHC_L1A_WD[4] = {50, 200, 50, 200}, HHC_L1A_OUT0[4] = {0, 50, 250, HHC_FOFF};
+static const int HHC_L1V_C0[4] = {0, 35, 70, 0}, HHC_L1V_IN[4] = {35, 35, 35, 105}, HHC_L1V_WD[4] = {100, 100, 100, 200}, HHC_L1V_OUT0[4] = {0, 100, 200, HHC_FOFF};
+
 /* host repack: every matrix as (hi, lo) fp16 fragment planes in hhp_hidx order, biases and the output layers in fp32 */
 static int hhc_set_weights(hh_commander *c, const hh_commander_weights *w) {
     const float *need[] = {w->act_w_ih, w->act_w_hh, w->act_b_ih, w->act_b_hh, w->shared_w, w->shared_b, w->act_out_w, w->act_out_b,
@@ -302,13 +308,13 @@ static int hhc_set_weights(hh_commander *c, const hh_commander_weights *w) {
     std::vector<uint16_t> Hh(h_total, 0), Hl(h_total, 0);
     std::vector<float> F(f_total, 0.0f);
     /* L1: output column of hidden unit o of input block k; S order [e (300) | 0 | f (200) | 0] */
-    const int a_c0[4] = {0, 4, 24, 0}, a_c1[4] = {4, 24, 34, 34}, a_wd[4] = {50, 200, 50, 200}, out0[4] = {0, 50, 250, HHC_FOFF};
+    const int *a_c0 = HHC_L1A_C0, *a_c1 = HHC_L1A_C1, *a_wd = HHC_L1A_WD, *out0 = HHC_L1A_OUT0;
     for (int k = 0; k < 4; k++)
         for (int o = 0; o < a_wd[k]; o++) {
             for (int ci = a_c0[k]; ci < a_c1[k]; ci++) hhp_split_put(Hh, Hl, h_w1a, ci, out0[k] + o, 512, w->inp_w[k][(size_t)o * (a_c1[k] - a_c0[k]) + ci - a_c0[k]]);
             F[f_b1a + out0[k] + o] = w->inp_b[k][o];
         }
-    const int v_c0[4] = {0, 35, 70, 0}, v_in[4] = {35, 35, 35, 105}, v_wd[4] = {100, 100, 100, 200}, vout0[4] = {0, 100, 200, HHC_FOFF};
+    const int *v_c0 = HHC_L1V_C0, *v_in = HHC_L1V_IN, *v_wd = HHC_L1V_WD, *vout0 = HHC_L1V_OUT0;
     for (int k = 0; k < 4; k++)
         for (int o = 0; o < v_wd[k]; o++) {
             for (int ci = 0; ci < v_in[k]; ci++) hhp_split_put(Hh, Hl, h_w1c, v_c0[k] + ci, vout0[k] + o, 512, w->v_w[k][(size_t)o * v_in[k] + ci]);

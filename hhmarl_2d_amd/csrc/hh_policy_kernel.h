@@ -527,6 +527,9 @@ static const int HHC_DIMS[4][4] = {
     /* own obs, own act, other obs, other act: train_hetero.py:183-198 observer spaces */
     {26, 4, 24, 3}, {24, 3, 26, 4}, {30, 4, 29, 3}, {29, 3, 30, 4},
 };
+/* hidden column of the reference's concatenation cat(v1, v2, y3) (ac_models_hetero.py:274-281) in the kernel's order y3 | pad | v1 | v2
+ * (escape nets: the identity) */
+__host__ __device__ inline int hhc_hcol(bool att, int c) { return att ? (c < 350 ? HHC_V12_OFF + c : HHC_V3_OFF + (c - 350)) : c; }
 static int hhp_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w);
 extern "C" int hh_policy_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w) {
     try {
@@ -553,8 +556,7 @@ static int hhp_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w
     std::vector<uint16_t> Hh(h_total, 0), Hl(h_total, 0);
     const size_t o_b1 = 0, o_bs = 512, o_bov = 1024, o_ba = 1024 + HHC_ATT_W, n_bias = o_ba + HHP_OUT;
     std::vector<float> Bf(n_bias, 0.0f);
-    /* hidden column of the reference's concatenation cat(v1, v2, y3) (ac_models_hetero.py:274-281) in the kernel's order y3 | pad | v1 | v2 */
-    auto hcol = [att](int c) { return att ? (c < 350 ? HHC_V12_OFF + c : HHC_V3_OFF + (c - 350)) : c; };
+    auto hcol = [att](int c) { return hhc_hcol(att, c); };
     if (att) {
         const int in0[3] = {0, d1 + a1, 0}, in1[3] = {d1 + a1, n_in, n_in}, wd[3] = {175, 175, 150}, out0[3] = {0, 175, 350};
         for (int b = 0; b < 3; b++)

@@ -520,8 +520,9 @@ __global__ __launch_bounds__(256 * RH, RH == 1 ? 2 : 1) void hh_k_policy_h(HhpBa
     hhp_consume_counts(counts, consume);
 }
 
-/* ---- host side: fp32 -> (hi, lo) fp16, round to nearest even, subnormals kept ---- */
-static inline uint16_t hhp_f2h(float f) {
+/* ---- fp32 -> (hi, lo) fp16, round to nearest even, subnormals kept.  Software rounding on both sides: the host repack (hhp_set_net ...)
+ * and the device refresh (hh_weight_refresh.h) produce the same halves by construction ---- */
+__host__ __device__ static inline uint16_t hhp_f2h(float f) {
     uint32_t x;
     memcpy(&x, &f, 4);
     const uint32_t sign = (x >> 16) & 0x8000u;
@@ -540,7 +541,7 @@ static inline uint16_t hhp_f2h(float f) {
     if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h++; /* may carry into the exponent: still the right encoding */
     return (uint16_t)(sign | h);
 }
-static inline float hhp_h2f(uint16_t h) {
+__host__ __device__ static inline float hhp_h2f(uint16_t h) {
     const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
     float v;
     if (e == 0) v = (float)m * (1.0f / 16777216.0f);

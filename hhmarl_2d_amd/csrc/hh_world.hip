@@ -886,3 +886,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- whole-episode GRU-sequence batches of the commander (C ABI in include/hh_commander.h) ---- */
 #include "hh_commander_episodes.h"
+
+/* ---- the learner's weights into the policy bank and the commander on the device (C ABI in include/hh_policy.h, include/hh_commander.h) ---- */
+#include "hh_weight_refresh.h"

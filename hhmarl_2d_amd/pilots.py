@@ -32,6 +32,35 @@ def tie_shared_layer(sds):
     return sds
 
 
+def _net_struct(kind, p):
+    """hh_net_weights of `kind`; p(state_dict key) -> pointer (None for the keys the kind does not have)"""
+    w = L.HHNetWeights()
+    w.kind = kind
+    for i in range(3):
+        w.inp_w[i] = p(f"inp{i + 1}._model.0.weight")
+        w.inp_b[i] = p(f"inp{i + 1}._model.0.bias")
+    w.att_in_proj_w, w.att_in_proj_b = p("att_act.in_proj_weight"), p("att_act.in_proj_bias")
+    w.att_out_w, w.att_out_b = p("att_act.out_proj.weight"), p("att_act.out_proj.bias")
+    w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
+    w.out_w, w.out_b = p("act_out._model.0.weight"), p("act_out._model.0.bias")
+    return w
+
+
+def _critic_struct(kind, p):
+    """hh_critic_weights of `kind`; p(key) -> pointer, the shared layer under the actor's keys"""
+    w = L.HHCriticWeights()
+    w.kind = kind
+    names = ("v1", "v2", "v3") if PN.HAS_ATT[kind] else ("inp1_val",)
+    for i, n in enumerate(names):
+        w.v_w[i] = p(f"{n}._model.0.weight")
+        w.v_b[i] = p(f"{n}._model.0.bias")
+    w.att_in_proj_w, w.att_in_proj_b = p("att_val.in_proj_weight"), p("att_val.in_proj_bias")
+    w.att_out_w, w.att_out_b = p("att_val.out_proj.weight"), p("att_val.out_proj.bias")
+    w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
+    w.val_w, w.val_b = p("val_out._model.0.weight"), p("val_out._model.0.bias")
+    return w
+
+
 class PolicyBank:
     """Up to 8 frozen actor networks resident on one GPU (hh_policy_* of include/hh_policy.h)."""
     FIGHT1, FIGHT2, ESC1, ESC2 = PN.FIGHT1, PN.FIGHT2, PN.ESC1, PN.ESC2
@@ -44,6 +73,7 @@ class PolicyBank:
         self.h = C.c_void_p()
         L.check(L.lib().hh_policy_create(self.device.index or 0, self.max_rows, C.byref(self.h)))
         self.kinds = {}
+        self._critics = set()   # slots whose value branch is loaded (set_critic since the last set_net)
         self._lut = np.zeros(256, dtype=np.uint8)
         self.generation = 0   # bumped by every call that (re)allocates or rewrites what a captured HIP graph holds by value: weight blobs, the selector table
 
@@ -64,18 +94,10 @@ class PolicyBank:
         a = {k: np.ascontiguousarray(sd[k], dtype=np.float32) for k in PN.actor_keys(kind)}
         for k, shp in PN.actor_keys(kind).items():
             assert a[k].shape == shp, (k, a[k].shape, shp)
-        p = lambda k: a[k].ctypes.data_as(C.c_void_p) if k in a else None
-        w = L.HHNetWeights()
-        w.kind = kind
-        for i in range(3):
-            w.inp_w[i] = p(f"inp{i + 1}._model.0.weight")
-            w.inp_b[i] = p(f"inp{i + 1}._model.0.bias")
-        w.att_in_proj_w, w.att_in_proj_b = p("att_act.in_proj_weight"), p("att_act.in_proj_bias")
-        w.att_out_w, w.att_out_b = p("att_act.out_proj.weight"), p("att_act.out_proj.bias")
-        w.shared_w, w.shared_b = p("shared_layer._model.0.weight"), p("shared_layer._model.0.bias")
-        w.out_w, w.out_b = p("act_out._model.0.weight"), p("act_out._model.0.bias")
+        w = _net_struct(kind, lambda k: a[k].ctypes.data_as(C.c_void_p) if k in a else None)
         L.check(L.lib().hh_policy_set_net(self.h, int(slot), C.byref(w)))
         self.kinds[int(slot)] = kind
+        self._critics.discard(int(slot))   # hh_policy_set_net invalidates the slot's value branch
         self.generation += 1
 
     def set_critic(self, slot, kind, sd, csd):
@@ -84,20 +106,11 @@ class PolicyBank:
         a = {k: np.ascontiguousarray(csd[k], dtype=np.float32) for k in PN.critic_keys(kind)}
         for k, shp in PN.critic_keys(kind).items():
             assert a[k].shape == shp, (k, a[k].shape, shp)
-        a["sw"] = np.ascontiguousarray(sd["shared_layer._model.0.weight"], dtype=np.float32)
-        a["sb"] = np.ascontiguousarray(sd["shared_layer._model.0.bias"], dtype=np.float32)
-        p = lambda k: a[k].ctypes.data_as(C.c_void_p) if k in a else None
-        w = L.HHCriticWeights()
-        w.kind = kind
-        names = ("v1", "v2", "v3") if PN.HAS_ATT[kind] else ("inp1_val",)
-        for i, n in enumerate(names):
-            w.v_w[i] = p(f"{n}._model.0.weight")
-            w.v_b[i] = p(f"{n}._model.0.bias")
-        w.att_in_proj_w, w.att_in_proj_b = p("att_val.in_proj_weight"), p("att_val.in_proj_bias")
-        w.att_out_w, w.att_out_b = p("att_val.out_proj.weight"), p("att_val.out_proj.bias")
-        w.shared_w, w.shared_b = p("sw"), p("sb")
-        w.val_w, w.val_b = p("val_out._model.0.weight"), p("val_out._model.0.bias")
+        for k in ("shared_layer._model.0.weight", "shared_layer._model.0.bias"):
+            a[k] = np.ascontiguousarray(sd[k], dtype=np.float32)
+        w = _critic_struct(kind, lambda k: a[k].ctypes.data_as(C.c_void_p) if k in a else None)
         L.check(L.lib().hh_policy_set_critic(self.h, int(slot), C.byref(w)))
+        self._critics.add(int(slot))
         self.generation += 1
 
     def sample(self, obs, sel, world=None, uniforms=None, crit_act=None, greedy=False, actions=None, logp=None, vf=None, logits=None,
@@ -153,6 +166,45 @@ class PolicyBank:
         shared_layer tensors for every slot (tie_shared_layer): the reference has one SHARED_LAYER for all four architectures."""
         self.set_net(slot, kind, sd)
         self.set_critic(slot, kind, sd, csd)
+
+    def refresh(self, slot, sd, csd=None):
+        """The learner's new weights for a LOADED slot, from float32 CUDA tensors keyed like the reference's state_dict()
+        (policy_nets.actor_keys; csd: critic_keys, required exactly when the slot's value branch is loaded, its shared layer taken from
+        sd): repacked on the device into the same bytes set_net + set_critic write, in place, ordered on the current torch stream
+        (hh_policy_refresh).  No host synchronisation; capturable into a CUDA graph.  The device addresses stay, so `generation` is not
+        bumped and graphs captured before keep replaying, with the new weights.  A sampler on another stream must wait for an event
+        recorded after this call; the tensors must stay unchanged until the stream has run it.  Tied shared layers
+        (tie_shared_layer): pass the same tensor to both slots."""
+        slot = int(slot)
+        if slot not in self.kinds:
+            raise ValueError(f"PolicyBank.refresh: slot {slot} is empty (load it once with set_net / load_trainable)")
+        kind = self.kinds[slot]
+        a = PN.device_weights(PN.actor_keys(kind), sd, self.device, "PolicyBank.refresh actor")
+        w = _net_struct(kind, lambda k: a[k].data_ptr() if k in a else None)
+        cw = None
+        if csd is not None:
+            c = PN.device_weights(PN.critic_keys(kind), csd, self.device, "PolicyBank.refresh critic")
+            c.update({k: a[k] for k in ("shared_layer._model.0.weight", "shared_layer._model.0.bias")})
+            cw = _critic_struct(kind, lambda k: c[k].data_ptr() if k in c else None)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hh_policy_refresh(self.h, slot, C.byref(w), None if cw is None else C.byref(cw), st))
+
+    def refresh_trainable(self, modules_or_dicts):
+        """refresh() for the slots of trainable_init (0: ac1_policy, 1: ac2_policy) from the learner's modules or their state dicts (actor
+        and value-branch keys in one dict, as the reference's state_dict() holds them); the value branch goes along wherever it is loaded"""
+        for slot, m in enumerate(modules_or_dicts):
+            sd = m.state_dict() if hasattr(m, "state_dict") else m
+            self.refresh(slot, sd, sd if slot in self._critics else None)
+
+    def packed(self, slot, part):
+        """test hook: one packed part of a slot as the forward kernels read it (hh_policy_copy_packed; 0 fp32 blob, 1 fp16 planes, 2 fragment
+        stream, 3 value-branch planes + biases, 4 value-branch stream) -> uint8 CUDA tensor, copied on the current stream"""
+        n = C.c_int64()
+        L.check(L.lib().hh_policy_copy_packed(self.h, int(slot), int(part), None, 0, C.byref(n), None))
+        out = torch.empty((n.value,), dtype=torch.uint8, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(L.lib().hh_policy_copy_packed(self.h, int(slot), int(part), C.c_void_p(out.data_ptr()), n.value, C.byref(n), st))
+        return out
 
     def kernel_name(self, n_rows, sampler=False):
         """the forward kernel instance a call of n_rows rows launches (hh_policy_kernel_name)"""

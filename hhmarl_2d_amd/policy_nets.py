@@ -114,6 +114,30 @@ def critic_from_torch_module(module, kind):
     return {k: sd[k] for k in critic_keys(kind)}
 
 
+def device_weights(keys, sd, device, what):
+    """the learner's tensors for a device refresh (PolicyBank.refresh, CommanderNet.refresh_weights): every key of `keys` (-> shape) of
+    `sd` as a float32 CUDA tensor on `device`, made contiguous where it is not.  ValueError (nothing enqueued) on a missing key, a
+    non-tensor, a wrong shape, dtype or device."""
+    import torch
+    want_index = device.index or 0
+    out = {}
+    for k, shp in keys.items():
+        if k not in sd:
+            raise ValueError(f"{what}: {k} is missing")
+        v = sd[k]
+        if not isinstance(v, torch.Tensor):
+            raise ValueError(f"{what}: {k} is a {type(v).__name__}, not a torch tensor (host arrays go through set_net / set_weights)")
+        if tuple(v.shape) != tuple(shp):
+            raise ValueError(f"{what}: {k} has shape {tuple(v.shape)}, the network has {tuple(shp)}")
+        if v.dtype != torch.float32:
+            raise ValueError(f"{what}: {k} is {v.dtype}, not torch.float32")
+        if v.device.type != "cuda" or v.device.index != want_index:
+            raise ValueError(f"{what}: {k} lives on {v.device}, not on cuda:{want_index}")
+        v = v.detach()
+        out[k] = v if v.is_contiguous() else v.contiguous()
+    return out
+
+
 def scale_actions(act):
     """on_postprocess_trajectory's scaling of an action into the critic's act inputs (train_hetero.py:138-160): a0 / 12, a1 / 8, a2, a3"""
     a = np.asarray(act, dtype=np.float32).copy()

@@ -47,6 +47,16 @@ int hh_commander_destroy(hh_commander *c);
 /* load (or replace) the weights: repacked on the host into the kernel's split-fp16 fragment layout and copied.  Synchronous. */
 int hh_commander_set_weights(hh_commander *c, const hh_commander_weights *w);
 
+/* The learner's new weights without a host round trip (csrc/hh_weight_refresh.h): the same struct with [dev] fp32 pointers in the same
+ * layout; what hh_commander_set_weights writes is rewritten in place with the same bytes (fp16 planes, fp32 section; the GRU bias sums
+ * b_ih + b_hh are fp32 adds as on the host) by one kernel ordered on `stream`: no host synchronisation, no allocation, graph-capturable,
+ * device addresses unchanged.  HH_E_ARG, nothing enqueued: no weights loaded yet, or a missing pointer. */
+int hh_commander_refresh_weights(hh_commander *c, const hh_commander_weights *w, void *stream);
+/* Test hook: one packed part (HH_COMMANDER_PART_*) to dst [dev] (cap bytes) on `stream`; *bytes = its size (dst == NULL: the size only) */
+#define HH_COMMANDER_PART_PLANES 0 /* (hi, lo) fp16 fragment planes */
+#define HH_COMMANDER_PART_F32 1    /* biases, GRU bias sums, output layers (fp32) */
+int hh_commander_copy_packed(hh_commander *c, int32_t part, void *dst, int64_t cap, int64_t *bytes, void *stream);
+
 /* One sampler step of every agent row (row r = agent slot r % 3 of arena r / 3):
  *   obs       [dev] f32 [N, 3, 34]      the commander observations hh_hl_end / hh_reset write (dead agents: zero rows)
  *   h_in      [dev] f32 [3N, 2, 200]    the GRU states the forward uses; rows of arenas flagged fresh are OVERWRITTEN with zeros (the

@@ -151,6 +151,28 @@ int hh_policy_sample(hh_policy *p, const float *obs, int32_t n_rows, int32_t obs
                      const double *uniforms, const float *crit_act, int32_t greedy, int8_t *actions, float *logp, float *vf, float *logits,
                      void *stream);
 
+/* ---- The learner's new weights into a loaded slot without a host round trip (csrc/hh_weight_refresh.h).  What hh_policy_set_net followed
+ * by hh_policy_set_critic write, but from DEVICE pointers: `actor` / `critic` hold [dev] fp32 tensors in the reference layout described
+ * above (row-major, contiguous).  Every packed form is rewritten in place with the same bytes the host path writes (fp32 blob, fp16
+ * fragment planes, fragment streams of the actor and of the value branch, the attention folded in fp64 in the host's summation order),
+ * by kernels ordered on `stream`: no host synchronisation, no allocation, graph-capturable.  Nothing the host keeps changes (kinds, loaded
+ * flags, device addresses), so a HIP graph captured before a refresh replays with the new weights.
+ *   critic  non-NULL exactly when the slot's value branch is loaded: the branch's private copy of the shared layer is refreshed together
+ *           with the actor (the set_net + set_critic pair rule); critic->shared_w / shared_b are the actor's tensors.
+ * HH_E_ARG, with nothing enqueued: an empty slot, actor->kind or critic->kind other than the loaded kind, a missing pointer, a critic
+ * missing for a slot with a value branch or given for one without.  The sources must stay unchanged until the stream has run the refresh;
+ * a sampler on ANOTHER stream sees the new weights only behind an event recorded after the refresh. */
+int hh_policy_refresh(hh_policy *p, int32_t slot, const hh_net_weights *actor, const hh_critic_weights *critic, void *stream);
+
+/* Test hook: copy one packed part of a slot, as the forward kernels read it, to dst [dev] (cap bytes), ordered on `stream`; *bytes = the
+ * part's size (dst == NULL: the size only).  The value-branch parts need a slot whose value branch was loaded once. */
+#define HH_POLICY_PART_BLOB 0          /* fp32 blob: w1 | b1 | wov | bov | ws | bs | wa | ba */
+#define HH_POLICY_PART_PLANES 1        /* (hi, lo) fp16 fragment planes of the tile forms */
+#define HH_POLICY_PART_STREAM 2        /* the 1 KB-fragment stream of the weights-through-LDS forms */
+#define HH_POLICY_PART_CRITIC 3        /* the value branch's fp16 planes + fp32 biases */
+#define HH_POLICY_PART_CRITIC_STREAM 4 /* the value branch's fragment stream + its biases */
+int hh_policy_copy_packed(hh_policy *p, int32_t slot, int32_t part, void *dst, int64_t cap, int64_t *bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
