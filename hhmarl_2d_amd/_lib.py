@@ -101,7 +101,7 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
-                     "hh_commander_copy_packed"]  # include/hh_commander.h
+                     "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name"]  # include/hh_commander.h
 
 _lib = None
 
@@ -177,6 +177,8 @@ def lib():
         L.hh_commander_episodes_emit.argtypes = [C.POINTER(HHCommanderEpisodeBufs), vp]
         L.hh_commander_refresh_weights.argtypes = [vp, C.POINTER(HHCommanderWeights), vp]
         L.hh_commander_copy_packed.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
+        L.hh_commander_act_chain.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.hh_commander_chain_kernel_name.argtypes = [vp, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
         _lib = L
     return _lib
 

@@ -63,7 +63,8 @@ def _weights_struct(p):
 
 class CommanderNet:
     """CommanderGru on one GPU: `set_weights(sd)` (the reference's state_dict, numpy or torch), `refresh_weights(sd)` (the same from CUDA
-    tensors, on the device), `sample(...)` = one sampler step of [N, 3] agent rows (hh_commander_sample)."""
+    tensors, on the device), `sample(...)` = one sampler step of [N, 3] agent rows (hh_commander_sample), `act_chain(obs)` = one greedy
+    commander step as evaluation.py takes it, the actor's state chained through the agent slots (hh_commander_act_chain)."""
 
     def __init__(self, device, max_rows):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -156,6 +157,35 @@ class CommanderNet:
     def kernel_name(self, n_arenas):
         buf = C.create_string_buffer(64)
         L.check(L.lib().hh_commander_kernel_name(self.h, int(n_arenas), buf, 64))
+        return buf.value.decode()
+
+    def act_chain(self, obs, actions=None, h_out=None, logits=None):
+        """The commander as evaluation.py:40-48 runs it (hh_commander_act_chain): per arena the actor over agent slots 0..n-1 in order,
+        slot 0 from zero rnn_act state, slot k from slot k-1's state_out, greedy first arg-max; no value branch.
+        obs f32 [N, n, 34] (1 <= n <= 5); h_out f32 [N, n, 200] / logits f32 [N, n, 4] optional outputs -> actions i8 [N, n].
+        Ordered on the current torch stream; no host synchronisation (graph-capturable)."""
+        if obs.dim() != 3 or tuple(obs.shape[2:]) != (OBS,):
+            raise ValueError(f"act_chain: obs must be [N, n_agents, {OBS}], got {tuple(obs.shape)}")
+        N, nA = int(obs.shape[0]), int(obs.shape[1])
+        if not 1 <= nA <= 5:
+            raise ValueError(f"act_chain: n_agents must be 1..5, got {nA}")
+        if N < 1:
+            raise ValueError("act_chain: no arenas")
+        dev = obs.device
+        if actions is None:
+            actions = torch.empty((N, nA), dtype=torch.int8, device=dev)
+        for name, t, dt, n in (("obs", obs, torch.float32, N * nA * OBS), ("actions", actions, torch.int8, N * nA),
+                               ("h_out", h_out, torch.float32, N * nA * HIDDEN), ("logits", logits, torch.float32, N * nA * 4)):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() != n or t.device != dev):
+                raise ValueError(f"act_chain: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().hh_commander_act_chain(self.h, ptr(obs), N, nA, ptr(actions), ptr(h_out), ptr(logits), st))
+        return actions
+
+    def chain_kernel_name(self, n_arenas, n_agents):
+        buf = C.create_string_buffer(64)
+        L.check(L.lib().hh_commander_chain_kernel_name(self.h, int(n_arenas), int(n_agents), buf, 64))
         return buf.value.decode()
 
 

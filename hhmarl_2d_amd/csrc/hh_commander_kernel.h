@@ -16,7 +16,8 @@
  *   shared  S = [e | 0 | normalize(f + h') | 0] (K 512, the shared layer's input rows permuted to this order on the host) -> 512, tanh
  *   out     act_out (3) / val_out (1) contracted in fp32 straight from the shared layer's C tiles in registers, partials in LDS
  * The activation tile lives in one LDS buffer of 720 k-columns (hi and lo planes, 90 KB): S at 0..511, h at 512..719, the input X
- * aliases the h region before h is loaded.  One workgroup per CU.
+ * aliases the h region before h is loaded.  One workgroup per CU.  The stages are device functions (hhc_l1, hhc_gru, hhc_normalize,
+ * hhc_shared_out, hhc_out_sum, hhc_first_max) that hh_k_commander_chain (hh_commander_chain.h) runs too.
  */
 #ifndef HH_COMMANDER_KERNEL_H
 #define HH_COMMANDER_KERNEL_H
@@ -66,13 +67,142 @@ struct HhcArgs {
 
 __device__ __forceinline__ float hhc_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+/* ---- the stages of one 32-row tile of one branch, shared by hh_k_commander and hh_k_commander_chain (hh_commander_chain.h): the same
+ * contractions in the same order, so both kernels give the same bits for the same row and state */
+struct HhcLds {
+    _Float16 *Sh, *Sl;
+    const float4 *Sh4, *Sl4;
+    float *npart, *opart;
+};
+__device__ __forceinline__ HhcLds hhc_lds(unsigned char *ldsb) {
+    HhcLds s;
+    s.Sh = reinterpret_cast<_Float16 *>(ldsb);
+    s.Sl = reinterpret_cast<_Float16 *>(ldsb + HHC_PLANE_BYTES);
+    s.Sh4 = reinterpret_cast<const float4 *>(s.Sh); s.Sl4 = reinterpret_cast<const float4 *>(s.Sl);
+    s.npart = reinterpret_cast<float *>(ldsb + HHC_OFF_NP);
+    s.opart = reinterpret_cast<float *>(ldsb + HHC_OFF_OP);
+    return s;
+}
+
+/* L1 on the input X at columns HHC_HOFF ..: 16 column tiles, two per wave: tanh -> S */
+__device__ __forceinline__ void hhc_l1(const HhcLds &s, const HhcBranch &B, int K1, int wave, int lane, int ci, int g) {
+    hh_f32x16 acc[1][2];
+#pragma unroll
+    for (int t = 0; t < 2; t++) acc[0][t] = (hh_f32x16)(0.0f);
+    hhp_gemm_h<2, 1>(s.Sh4, s.Sl4, HHC_HOFF / 16, K1 / 16, B.w1h, B.w1l, 0, HHC_KS, 64 * wave, lane, acc);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+        hhp_store_tile_t<HHC_R>(s.Sh, s.Sl, 64 * wave + 32 * t, ci, g, acc[0][t], B.b1, [](hh_f2 x) { return hhp_tanh2(x); });
+}
+
+/* GRU on [f | 0 | h | 0] (h split into columns HHC_HOFF ..): wave w < 7 owns hidden units 32 w .. 32 w + 31 of row ci.  h_of(u) = the
+ * fp32 state the forward used, put(u, h') stores the new one; vsum <- f + h' and the wave's sum of squares -> npart */
+template <class HOf, class Put>
+__device__ __forceinline__ void hhc_gru(const HhcLds &s, const HhcBranch &B, int wave, int lane, int ci, int g, HOf h_of, Put put,
+                                        float (&vsum)[16]) {
+    float ss = 0.0f;
+    if (wave < HHC_HT) {
+        hh_f32x16 rz[1][2], an[1][1], ah[1][1];
+        rz[0][0] = (hh_f32x16)(0.0f); rz[0][1] = (hh_f32x16)(0.0f); an[0][0] = (hh_f32x16)(0.0f); ah[0][0] = (hh_f32x16)(0.0f);
+        const int j0 = 128 * wave;
+        hhp_gemm_h<2, 1>(s.Sh4, s.Sl4, HHC_FOFF / 16, HHC_KG / 16, B.wgh, B.wgl, 0, HHC_JG, j0, lane, rz);
+        hhp_gemm_h<1, 1>(s.Sh4, s.Sl4, HHC_FOFF / 16, HHC_KG / 32, B.wgh, B.wgl, 0, HHC_JG, j0 + 64, lane, an);
+        hhp_gemm_h<1, 1>(s.Sh4, s.Sl4, HHC_HOFF / 16, HHC_KG / 32, B.wgh, B.wgl, HHC_KG / 32, HHC_JG, j0 + 96, lane, ah);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int reg = 4 * q + e, u = 32 * wave + 8 * q + 4 * g + e;
+                float v = 0.0f;
+                if (u < HH_CMD_HIDDEN) {
+                    const float rr = hhc_sigmoid(rz[0][0][reg] + B.bg[u]);
+                    const float zz = hhc_sigmoid(rz[0][1][reg] + B.bg[224 + u]);
+                    const float nn = tanhf(an[0][0][reg] + B.bg[448 + u] + rr * (ah[0][0][reg] + B.bg[672 + u]));
+                    const float h = h_of(u);
+                    const float hn = (1.0f - zz) * nn + zz * h;
+                    put(u, hn);
+                    const int fi = hhp_haidx<HHC_R>(HHC_FOFF + u, ci);
+                    const float f = (float)s.Sh[fi] + (float)s.Sl[fi];
+                    v = f + hn;
+                }
+                vsum[reg] = v;
+                ss += v * v;
+            }
+        }
+        ss += __shfl_xor(ss, 32);
+        if (g == 0) s.npart[wave * HHC_R + ci] = ss;
+    }
+}
+
+/* normalize(f + h') over the row (the waves' partial sums in npart) -> S columns HHC_FOFF .. */
+__device__ __forceinline__ void hhc_normalize(const HhcLds &s, int wave, int ci, int g, const float (&vsum)[16]) {
+    if (wave < HHC_HT) {
+        float nn = 0.0f;
+#pragma unroll
+        for (int w = 0; w < HHC_HT; w++) nn += s.npart[w * HHC_R + ci];
+        const float den = fmaxf(sqrtf(nn), 1e-12f);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int u = 32 * wave + 8 * q + 4 * g + e;
+                if (u < 208) hhp_split_store<HHC_R>(s.Sh, s.Sl, hhp_haidx<HHC_R>(HHC_FOFF + u, ci), u < HH_CMD_HIDDEN ? vsum[4 * q + e] / den : 0.0f);
+            }
+        }
+    }
+}
+
+/* shared layer (16 column tiles, two per wave), tanh, and the output layer (3 columns for the actor, kind 0; 1 for the value branch)
+ * from registers: the waves' partials -> opart */
+__device__ __forceinline__ void hhc_shared_out(const HhcLds &s, const HhcNet &net, const HhcBranch &B, int kind, int wave, int lane, int ci,
+                                               int g) {
+    hh_f32x16 acc[1][2];
+#pragma unroll
+    for (int t = 0; t < 2; t++) acc[0][t] = (hh_f32x16)(0.0f);
+    hhp_gemm_h<2, 1>(s.Sh4, s.Sl4, 0, HHC_KS / 16, net.wsh, net.wsl, 0, HHC_KS, 64 * wave, lane, acc);
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int col = 64 * wave + 32 * t + 8 * q + 4 * g + e;
+                const float y = tanhf(acc[0][t][4 * q + e] + net.bs[col]);
+                p0 += y * B.wo[col];
+                if (kind == 0) { p1 += y * B.wo[512 + col]; p2 += y * B.wo[1024 + col]; }
+            }
+        }
+    }
+    p0 += __shfl_xor(p0, 32); p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
+    if (g == 0) {
+        float *op = s.opart + (wave * HHC_R + ci) * 3;
+        op[0] = p0; op[1] = p1; op[2] = p2;
+    }
+}
+
+/* row `row`'s three output sums over the eight waves' partials, in wave order */
+__device__ __forceinline__ void hhc_out_sum(const float *opart, int row, float (&l)[3]) {
+    l[0] = 0.0f; l[1] = 0.0f; l[2] = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        const float *op = opart + (w * HHC_R + row) * 3;
+        l[0] += op[0]; l[1] += op[1]; l[2] += op[2];
+    }
+}
+
+/* the first arg-max of the three logits (explore = False); m <- its logit */
+__device__ __forceinline__ int hhc_first_max(const float (&l)[3], float &m) {
+    m = l[0];
+    int best = 0;
+    if (l[1] > m) { m = l[1]; best = 1; }
+    if (l[2] > m) { m = l[2]; best = 2; }
+    return best;
+}
+
 __global__ __launch_bounds__(HHC_THREADS, 1) void hh_k_commander(HhcNet net, HhcArgs a) {
     extern __shared__ __align__(16) unsigned char ldsb[];
-    _Float16 *Sh = reinterpret_cast<_Float16 *>(ldsb);
-    _Float16 *Sl = reinterpret_cast<_Float16 *>(ldsb + HHC_PLANE_BYTES);
-    const float4 *Sh4 = reinterpret_cast<const float4 *>(Sh), *Sl4 = reinterpret_cast<const float4 *>(Sl);
-    float *npart = reinterpret_cast<float *>(ldsb + HHC_OFF_NP);
-    float *opart = reinterpret_cast<float *>(ldsb + HHC_OFF_OP);
+    const HhcLds s = hhc_lds(ldsb);
     const int kind = (int)blockIdx.x & 1, row0 = ((int)blockIdx.x >> 1) * HHC_R;
     const HhcBranch B = kind ? net.br[1] : net.br[0];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -94,20 +224,12 @@ __global__ __launch_bounds__(HHC_THREADS, 1) void hh_k_commander(HhcNet net, Hhc
                 else if (a.crit_act) v = a.crit_act[(size_t)n * 3 + slot];
             }
         }
-        hhp_split_store<HHC_R>(Sh, Sl, hhp_haidx<HHC_R>(HHC_HOFF + c, i), v);
+        hhp_split_store<HHC_R>(s.Sh, s.Sl, hhp_haidx<HHC_R>(HHC_HOFF + c, i), v);
     }
     __syncthreads();
 
-    /* ---- L1: 16 column tiles, two per wave: tanh -> S */
-    {
-        hh_f32x16 acc[1][2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) acc[0][t] = (hh_f32x16)(0.0f);
-        hhp_gemm_h<2, 1>(Sh4, Sl4, HHC_HOFF / 16, K1 / 16, B.w1h, B.w1l, 0, HHC_KS, 64 * wave, lane, acc);
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-            hhp_store_tile_t<HHC_R>(Sh, Sl, 64 * wave + 32 * t, ci, g, acc[0][t], B.b1, [](hh_f2 x) { return hhp_tanh2(x); });
-    }
+    /* ---- L1 */
+    hhc_l1(s, B, K1, wave, lane, ci, g);
     __syncthreads();
 
     /* ---- h (zeros for fresh arenas, which are also written back into h_in) into columns 512 .. 719 */
@@ -119,111 +241,37 @@ __global__ __launch_bounds__(HHC_THREADS, 1) void hh_k_commander(HhcNet net, Hhc
             if (a.fresh && a.fresh[r / 3]) *hp = 0.0f;
             else v = *hp;
         }
-        hhp_split_store<HHC_R>(Sh, Sl, hhp_haidx<HHC_R>(HHC_HOFF + c, i), v);
+        hhp_split_store<HHC_R>(s.Sh, s.Sl, hhp_haidx<HHC_R>(HHC_HOFF + c, i), v);
     }
     __syncthreads();
 
-    /* ---- GRU: wave w < 7 owns hidden units 32 w .. 32 w + 31 */
+    /* ---- GRU: h from h_in (zero for fresh rows), h' to h_out */
     const int r_me = row0 + ci;
     const bool row_ok = r_me < a.rows;
     const bool row_fresh = row_ok && a.fresh && a.fresh[r_me / 3];
     float vsum[16];
-    {
-        float ss = 0.0f;
-        if (wave < HHC_HT) {
-            hh_f32x16 rz[1][2], an[1][1], ah[1][1];
-            rz[0][0] = (hh_f32x16)(0.0f); rz[0][1] = (hh_f32x16)(0.0f); an[0][0] = (hh_f32x16)(0.0f); ah[0][0] = (hh_f32x16)(0.0f);
-            const int j0 = 128 * wave;
-            hhp_gemm_h<2, 1>(Sh4, Sl4, HHC_FOFF / 16, HHC_KG / 16, B.wgh, B.wgl, 0, HHC_JG, j0, lane, rz);
-            hhp_gemm_h<1, 1>(Sh4, Sl4, HHC_FOFF / 16, HHC_KG / 32, B.wgh, B.wgl, 0, HHC_JG, j0 + 64, lane, an);
-            hhp_gemm_h<1, 1>(Sh4, Sl4, HHC_HOFF / 16, HHC_KG / 32, B.wgh, B.wgl, HHC_KG / 32, HHC_JG, j0 + 96, lane, ah);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const int reg = 4 * q + e, u = 32 * wave + 8 * q + 4 * g + e;
-                    float v = 0.0f;
-                    if (u < HH_CMD_HIDDEN) {
-                        const float rr = hhc_sigmoid(rz[0][0][reg] + B.bg[u]);
-                        const float zz = hhc_sigmoid(rz[0][1][reg] + B.bg[224 + u]);
-                        const float nn = tanhf(an[0][0][reg] + B.bg[448 + u] + rr * (ah[0][0][reg] + B.bg[672 + u]));
-                        const float h = (row_ok && !row_fresh) ? a.h_in[((size_t)r_me * 2 + kind) * HH_CMD_HIDDEN + u] : 0.0f;
-                        const float hn = (1.0f - zz) * nn + zz * h;
-                        if (row_ok) a.h_out[((size_t)r_me * 2 + kind) * HH_CMD_HIDDEN + u] = hn;
-                        const int fi = hhp_haidx<HHC_R>(HHC_FOFF + u, ci);
-                        const float f = (float)Sh[fi] + (float)Sl[fi];
-                        v = f + hn;
-                    }
-                    vsum[reg] = v;
-                    ss += v * v;
-                }
-            }
-            ss += __shfl_xor(ss, 32);
-            if (g == 0) npart[wave * HHC_R + ci] = ss;
-        }
-    }
+    hhc_gru(s, B, wave, lane, ci, g,
+            [&](int u) { return (row_ok && !row_fresh) ? a.h_in[((size_t)r_me * 2 + kind) * HH_CMD_HIDDEN + u] : 0.0f; },
+            [&](int u, float hn) { if (row_ok) a.h_out[((size_t)r_me * 2 + kind) * HH_CMD_HIDDEN + u] = hn; }, vsum);
     __syncthreads();
-    if (wave < HHC_HT) {
-        float nn = 0.0f;
-#pragma unroll
-        for (int w = 0; w < HHC_HT; w++) nn += npart[w * HHC_R + ci];
-        const float den = fmaxf(sqrtf(nn), 1e-12f);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int u = 32 * wave + 8 * q + 4 * g + e;
-                if (u < 208) hhp_split_store<HHC_R>(Sh, Sl, hhp_haidx<HHC_R>(HHC_FOFF + u, ci), u < HH_CMD_HIDDEN ? vsum[4 * q + e] / den : 0.0f);
-            }
-        }
-    }
+    hhc_normalize(s, wave, ci, g, vsum);
     __syncthreads();
 
-    /* ---- shared layer (16 column tiles, two per wave), tanh, and the output layer from registers */
-    {
-        hh_f32x16 acc[1][2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) acc[0][t] = (hh_f32x16)(0.0f);
-        hhp_gemm_h<2, 1>(Sh4, Sl4, 0, HHC_KS / 16, net.wsh, net.wsl, 0, HHC_KS, 64 * wave, lane, acc);
-        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const int col = 64 * wave + 32 * t + 8 * q + 4 * g + e;
-                    const float y = tanhf(acc[0][t][4 * q + e] + net.bs[col]);
-                    p0 += y * B.wo[col];
-                    if (kind == 0) { p1 += y * B.wo[512 + col]; p2 += y * B.wo[1024 + col]; }
-                }
-            }
-        }
-        p0 += __shfl_xor(p0, 32); p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
-        if (g == 0) {
-            float *op = opart + (wave * HHC_R + ci) * 3;
-            op[0] = p0; op[1] = p1; op[2] = p2;
-        }
-    }
+    /* ---- shared layer and the output layer */
+    hhc_shared_out(s, net, B, kind, wave, lane, ci, g);
     __syncthreads();
 
     /* ---- per row: logits -> draw, or the value */
     if (tid < HHC_R && row0 + tid < a.rows) {
         const int r = row0 + tid;
-        float l[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            const float *op = opart + (w * HHC_R + tid) * 3;
-            l[0] += op[0]; l[1] += op[1]; l[2] += op[2];
-        }
+        float l[3];
+        hhc_out_sum(s.opart, tid, l);
         if (kind == 1) {
             if (a.vf) a.vf[r] = l[0] + B.bo[0];
         } else {
             l[0] += B.bo[0]; l[1] += B.bo[1]; l[2] += B.bo[2];
-            float m = l[0];
-            int best = 0;
-            if (l[1] > m) { m = l[1]; best = 1; }
-            if (l[2] > m) { m = l[2]; best = 2; }
+            float m;
+            const int best = hhc_first_max(l, m);
             const float e0 = expf(l[0] - m), e1 = expf(l[1] - m), e2 = expf(l[2] - m);
             const float S = e0 + e1 + e2;
             int act = best;
@@ -262,6 +310,8 @@ struct hh_commander {
     char *blob;
 };
 
+static hipError_t hhc_chain_set_lds(); /* hh_commander_chain.h: the chain kernel's LDS attribute */
+
 extern "C" int hh_commander_create(int device, int32_t max_rows, hh_commander **out) {
     if (!out || max_rows <= 0) { g_err = "hh_commander_create: bad argument"; return HH_E_ARG; }
     int ndev = 0;
@@ -270,6 +320,7 @@ extern "C" int hh_commander_create(int device, int32_t max_rows, hh_commander **
     DeviceGuard guard_(device);
     if (!guard_.ok) { g_err = "hipSetDevice failed"; return HH_E_HIP; }
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(hh_k_commander), hipFuncAttributeMaxDynamicSharedMemorySize, HHC_LDS_BYTES));
+    HIPCHK(hhc_chain_set_lds());
     hh_commander *c = new (std::nothrow) hh_commander();
     if (!c) { g_err = "hh_commander_create: out of host memory"; return HH_E_HIP; }
     c->device = device; c->max_rows = max_rows; c->loaded = 0; c->blob = nullptr;

@@ -884,6 +884,9 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 /* ---- the trainable commander of train_hier.py (C ABI in include/hh_commander.h) ---- */
 #include "hh_commander_kernel.h"
 
+/* ---- the commander as evaluation.py runs it: greedy, the actor's state chained through the agent slots (C ABI in include/hh_commander.h) ---- */
+#include "hh_commander_chain.h"
+
 /* ---- whole-episode GRU-sequence batches of the commander (C ABI in include/hh_commander.h) ---- */
 #include "hh_commander_episodes.h"
 

@@ -85,6 +85,21 @@ int hh_commander_sample(hh_commander *c, const float *obs, int32_t n_arenas, flo
 /* name of the kernel a call of n_arenas arenas launches, as a profiler prints it */
 int hh_commander_kernel_name(hh_commander *c, int32_t n_arenas, char *buf, int32_t len);
 
+/* evaluation.py:40-48 for every arena: per commander step the actor of CommanderGru over agent slots 0..n_agents-1 in order, slot 0
+ * from zero rnn_act state, slot k from slot k-1's state_out (the reference resets states = [zeros(200), zeros(200)] at the start of
+ * every step and threads each agent's state_out into the next agent's state_in); greedy first arg-max (explore = False).  No value
+ * branch: evaluation never reads it.  Every link's logits equal, bit for bit, what hh_commander_sample gives for the same row and h_in.
+ *   obs     [dev] f32 [N, n_agents, 34]   dead agents: the zero rows hh_hl_end writes
+ *   actions [dev] i8  [N, n_agents]       the layout hh_hl_begin / hh_hl_begin_variants read
+ *   h_out   [dev] f32 [N, n_agents, 200]  nullable: rnn_act state after each link (test hook)
+ *   logits  [dev] f32 [N, n_agents, 4]    nullable (zero padded like hh_commander_sample's)
+ * 1 <= n_agents <= 5 and n_arenas x n_agents <= max_rows of hh_commander_create; stream-ordered, no host sync, no allocation,
+ * graph-capturable. */
+int hh_commander_act_chain(hh_commander *c, const float *obs, int32_t n_arenas, int32_t n_agents, int8_t *actions, float *h_out,
+                           float *logits, void *stream);
+/* name of the kernel hh_commander_act_chain launches, as a profiler prints it */
+int hh_commander_chain_kernel_name(hh_commander *c, int32_t n_arenas, int32_t n_agents, char *buf, int32_t len);
+
 /* Whole-episode GRU-sequence batches of the commander (batch_mode = "complete_episodes" with a recurrent model, train_hier.py:182):
  * what hh_episodes_emit (hh_abi.h) does for PPORollout, plus RLlib's cut of every agent's trajectory into sequences of at most
  * max_seq_len (L) steps, each with the GRU states of its first step.  hh_commander_episodes_emit takes one collect's [T, N, ...]
