@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from . import policy_nets as PN
-from .rollout import central_critic_rows_hl
+from .rollout import EpisodeBatch, central_critic_rows_hl
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
 
@@ -204,7 +204,7 @@ def default_carry_cap(horizon, n_agents=N_AGENTS, n_opps=3):
     return -(-int(horizon) // 12) + int(n_agents) + int(n_opps) - 1
 
 
-class CommanderEpisodeBatch:
+class CommanderEpisodeBatch(EpisodeBatch):
     """The whole-episode GRU-sequence batch of a `CommanderRollout(..., batch_mode="complete_episodes")` (train_hier.py:182 with the
     recurrent CommanderGru, RLlib's max_seq_len = 20): after every collect, the rows of every episode that ENDED in it, from its reset
     row to its done row, in one flat batch; GAE over each whole episode (hh_gae_rllib's float64 recursion, last_r = 0.0:
@@ -230,71 +230,29 @@ class CommanderEpisodeBatch:
     and 710 MB of sequences: 1.25 GB in all.  Nothing overflows under that rule; if something did anyway (a carry_cap below it), a
     sticky device flag is set and `rows()` raises."""
 
-    COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
-    TABLES = ("ep_start", "ep_len", "ep_arena")
     SEQ_TABLE = ("seq_start", "seq_len", "seq_ep")
+    _EMIT, _SCRATCH, _N_COUNTS = "hh_commander_episodes_emit", (10, 4), 4
+    _critic_rows = staticmethod(central_critic_rows_hl)
 
-    def __init__(self, N, T, max_seq_len, carry_cap, device, gamma, lam, collect):
-        """collect: the rollout's [T(+1), N, ...] buffers (obs, actions, logp, vf, reward, valid, done, state_in) that every emission reads"""
-        self.N, self.T, self.L, self.carry_cap = int(N), int(T), int(max_seq_len), int(carry_cap)
-        N, T, sl, cap, nA = self.N, self.T, self.L, self.carry_cap, N_AGENTS
-        R, E, S = N * (cap + T), N * T, N * (T + cap // sl)
-        sc = max(-(-cap // sl), 1)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        f32, i8, u8, i32 = torch.float32, torch.int8, torch.uint8, torch.int32
-        self.obs, self.actions = z((R, nA, OBS), f32), z((R, nA), i8)
-        self.logp, self.vf, self.reward, self.valid = z((R, nA), f32), z((R, nA), f32), z((R, nA), f32), z((R, nA), u8)
-        self.adv, self.target = z((R, nA), f32), z((R, nA), f32)
-        self.done, self.arena, self.episode, self.t = z((R,), u8), z((R,), i32), z((R,), i32), z((R,), i32)
-        self.ep_start, self.ep_len, self.ep_arena = z((E,), i32), z((E,), i32), z((E,), i32)
-        self.seq_start, self.seq_len, self.seq_ep = z((S,), i32), z((S,), i32), z((S,), i32)
-        self.state_in = z((S, nA, 2, HIDDEN), f32)
-        self.carried = z((N,), i32)
-        c = max(cap, 1)
-        self._carry = {"obs": z((N, c, nA, OBS), f32), "actions": z((N, c, nA), i8), "logp": z((N, c, nA), f32),
-                       "vf": z((N, c, nA), f32), "reward": z((N, c, nA), f32), "valid": z((N, c, nA), u8),
-                       "state": z((N, sc, nA, 2, HIDDEN), f32)}
-        self._finished = z((N,), i32)            # episodes finished per arena since start()
-        self._scratch = z((10 * N + 4,), i32)
-        self._counts = z((4,), i32)              # rows, episodes of the last collect; overflow flag (sticky); sequences of the last collect
-        self.n_rows, self.n_episodes, self.n_sequences = self._counts[0], self._counts[1], self._counts[3]
-        b = L.HHCommanderEpisodeBufs(T=T, N=N, max_seq_len=sl, carry_cap=cap, row_cap=R, ep_cap=E, seq_cap=S, gamma=float(gamma), lam=float(lam))
-        for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done", "state_in"):
-            assert collect[k].is_contiguous() and collect[k].shape[1] == N
-            setattr(b, k, collect[k].data_ptr())
-        for k, v in self._carry.items():
-            setattr(b, "c_" + k, v.data_ptr())
-        b.carried, b.episode, b.scratch = self.carried.data_ptr(), self._finished.data_ptr(), self._scratch.data_ptr()
-        for k in self.COLUMNS:
-            setattr(b, "o_" + k, getattr(self, k).data_ptr())
-        for k in self.TABLES + self.SEQ_TABLE:
-            setattr(b, k, getattr(self, k).data_ptr())
-        b.o_state_in, b.counts = self.state_in.data_ptr(), self._counts.data_ptr()
-        self._bufs, self._collect, self._device = b, collect, device   # the struct holds raw pointers: keep the tensors alive
+    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam):
+        """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS, done and state_in) that every emission reads"""
+        self.L = int(max_seq_len)
+        super().__init__(collect, carry_cap, gamma, lam)
+        S, sc = self._bufs.seq_cap, max(-(-self.carry_cap // self.L), 1)
+        z = lambda shape: torch.zeros(shape, dtype=torch.int32, device=self._device)
+        self.seq_start, self.seq_len, self.seq_ep = z((S,)), z((S,)), z((S,))
+        state = tuple(collect["state_in"].shape[2:])
+        self.state_in = torch.zeros((S,) + state, dtype=torch.float32, device=self._device)
+        self._carry["state"] = torch.zeros((self.N, sc) + state, dtype=torch.float32, device=self._device)
+        self.n_sequences = self._counts[3]
+        self._bind(collect, {"state": self._carry["state"]}, ("state_in",), ("state_in",), self.SEQ_TABLE)
 
-    def reset(self):
-        """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
-        self.carried.zero_()
-        self._finished.zero_()
-        self._counts[:2].zero_()
-        self._counts[3:].zero_()
+    def _struct(self, R, E, gamma, lam):
+        return L.HHCommanderEpisodeBufs(T=self.T, N=self.N, max_seq_len=self.L, carry_cap=self.carry_cap, row_cap=R, ep_cap=E,
+                                        seq_cap=self.N * (self.T + self.carry_cap // self.L), gamma=gamma, lam=lam)
 
-    def emit(self, stream):
-        L.check(L.lib().hh_commander_episodes_emit(C.byref(self._bufs), stream))
-
-    def rows(self):
-        """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES), the sequence table
-        (SEQ_TABLE) and state_in [S, 3, 2, 200]"""
-        torch.cuda.synchronize(self._device)
-        R, E, overflow, S = self._counts.tolist()
-        if overflow:
-            raise RuntimeError("CommanderEpisodeBatch: an episode outgrew the carry or a batch capacity (carry_cap below the episode "
-                               "bound?): the batches since that collect are incomplete")
-        out = {k: getattr(self, k)[:R] for k in self.COLUMNS}
-        out.update({k: getattr(self, k)[:E] for k in self.TABLES})
-        out.update({k: getattr(self, k)[:S] for k in self.SEQ_TABLE})
-        out["state_in"] = self.state_in[:S]
-        return out
+    def _parts(self):
+        return super()._parts() + ((self.SEQ_TABLE + ("state_in",), 3),)   # rows() also holds the sequence table and state_in [S, 3, 2, 200]
 
     def sequences(self):
         """the learner's padded form (RLlib's chop_into_sequences, all three agents of an arena row side by side; per agent it is the slice
@@ -313,11 +271,6 @@ class CommanderEpisodeBatch:
             out[k] = torch.where(m, g, torch.zeros((), dtype=g.dtype, device=self._device))
         out["seq_lens"], out["mask"], out["state_in"] = r["seq_len"], mask, r["state_in"]
         return out
-
-    def critic_rows(self, agent):
-        """the CUR_OBS rows of `agent` (1..3) for the emitted rows with the actions filled in (central_critic_rows_hl)"""
-        r = self.rows()
-        return central_critic_rows_hl(r["obs"], r["actions"], agent)
 
 
 class CommanderRollout:
@@ -373,9 +326,8 @@ class CommanderRollout:
         self.episodes = None
         if batch_mode == "complete_episodes":
             cap = default_carry_cap(world.cfg.horizon, world.cfg.n_agents, world.cfg.n_opps) if carry_cap is None else int(carry_cap)
-            self.episodes = CommanderEpisodeBatch(N, T, self.max_seq_len, cap, dev, self.gamma, self.lam,
-                                                  {k: getattr(self, k) for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done",
-                                                                                 "state_in")})
+            self.episodes = CommanderEpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done", "state_in")},
+                                                  self.max_seq_len, cap, self.gamma, self.lam)
         self.use_graph = use_graph
         self._graph = None
         self._started = False

@@ -4,16 +4,27 @@
  * GAE over each episode and last_r = 0 at its end.  A collect fills [T, N, ...] windows; an episode that spans collects is held in a
  * per-arena carry on the device until its done row arrives, then all its rows go out together in one flat batch.
  *
- * Not tied to a world (like hh_gae.h): generic in n_agents and in the observation width D.  One call (hh_episodes_emit) = four
- * launches on one stream, no host synchronisation, no allocation, so it can be captured into the collect's graph:
+ * Two entry points share one path: hh_episodes_emit (include/hh_abi.h: PPORollout, generic in n_agents and the observation width D)
+ * and hh_commander_episodes_emit (include/hh_commander.h: CommanderRollout's 3 x 34 rows), which adds one stage — RLlib's cut of every
+ * episode into sequences of at most L = max_seq_len steps, each carrying the GRU states (state_in_0 / state_in_1) of its first step.
+ * Its carry holds, besides the running episode's rows, only the states at its sequence starts (ceil(carry_cap / L) per arena).
+ * Each entry point fills the internal descriptor hh_ep_desc from its own struct; the kernels below take only that.
+ *
+ * One call = four launches on one stream, no host synchronisation, no allocation, so it can be captured into the collect's graph:
  *   1. hh_k_ep_count  one lane per arena: last done tick, episodes ending in the window, rows to emit (carry + last_done + 1, or 0)
- *   2. hh_k_ep_scan   one 1024-thread workgroup: exclusive scan of those counts over the arenas -> output offsets (no atomics: the
- *                     order is arena-major, then episode, then time, whatever the scheduling)
- *   3. hh_k_ep_emit   one workgroup per arena: gather the finished episodes' rows (carry first, then the window) into the batch, then
- *                     (after a barrier, so the carry is read before it is rewritten in the same launch) move the trailing fragment
- *                     into the carry
+ *                     and, when sequences are cut, their sequences (sum of ceil(E / L))
+ *   2. hh_k_ep_scan   one 1024-thread workgroup: exclusive scans of those counts over the arenas -> output offsets (no atomics: the
+ *                     order is arena-major, then episode, then time, whatever the scheduling), counts[0..3]
+ *   3. hh_k_ep_emit   one workgroup per arena: (sequences) the sequence table and the states at the sequence starts (window state_in
+ *                     or state carry); gather the finished episodes' rows (carry first, then the window) into the batch with their
+ *                     metadata and episode table; then (after a barrier, so the carry is read before it is rewritten in the same
+ *                     launch) move the trailing fragment, (sequences) with its sequence-start states, into the carry
  *   4. hh_k_ep_gae    one wave per episode, one lane per agent: the recursion of hh_k_gae_rllib over the whole episode with
  *                     last_r = 0, float64 delta and discounted sum in its operation order, float32 results
+ * Every order (rows, episodes, sequences) is fixed by the scans and the arrangement, never by scheduling: graph and eager runs give
+ * identical batches.
+ *
+ * Host part: needs g_err / HIPCHK of the including translation unit (hh_world.hip).
  */
 #ifndef HH_EPISODES_H
 #define HH_EPISODES_H
@@ -22,68 +33,134 @@
 #include <stdint.h>
 
 #include "hh_abi.h"
+#include "hh_commander.h"
 
-#define HH_EP_MAX_T 4096   /* the emit kernel keeps three ints per tick of the window in LDS */
+#define HH_EP_MAX_T 4096   /* the emit kernel keeps three ints per tick of the window in LDS (five or six with sequences) */
 
-/* scratch rows ([5, N] i32) */
+/* scratch rows ([5, N] i32; [7, N] with sequences) */
 #define HH_EP_S_ROWS 0
 #define HH_EP_S_EPS 1
 #define HH_EP_S_LAST 2
 #define HH_EP_S_ROW_OFF 3
 #define HH_EP_S_EP_OFF 4
+#define HH_EP_S_SEQ 5
+#define HH_EP_S_SEQ_OFF 6
 
-__global__ __launch_bounds__(256) void hh_k_ep_count(hh_episode_bufs b) {
+#define HH_EP_STATE4 (HH_CMD_AGENTS * 2 * HH_CMD_HIDDEN / 4) /* float4 per arena row of GRU states (4800 B) */
+
+/* dynamic LDS of the sequence instance of hh_k_ep_emit, in ints: l_seg / l_prev / l_done / l_end [T], l_sq [T + 1], l_src [T + carry_cap / L] */
+static inline int64_t hh_cep_lds_ints(int T, int carry_cap, int L) { return 5 * (int64_t)T + 1 + T + carry_cap / L; }
+
+/* the buffers of one emission; max_seq_len, seq_cap, the state columns and the sequence table are the sequence instance's only */
+struct hh_ep_desc {
+    int32_t T, N, n_agents, obs_dim, carry_cap, max_seq_len;
+    int64_t row_cap, ep_cap, seq_cap;
+    double gamma, lam;
+    const float *obs;
+    const int8_t *actions;
+    const float *logp, *vf, *reward;
+    const uint8_t *valid, *done;
+    const float *state_in;
+    float *c_obs;
+    int8_t *c_actions;
+    float *c_logp, *c_vf, *c_reward;
+    uint8_t *c_valid;
+    float *c_state;
+    int32_t *carried, *episode, *scratch;
+    float *o_obs;
+    int8_t *o_actions;
+    float *o_logp, *o_vf, *o_reward;
+    uint8_t *o_valid;
+    float *o_adv, *o_target;
+    uint8_t *o_done;
+    int32_t *o_arena, *o_episode, *o_t, *ep_start, *ep_len, *ep_arena, *seq_start, *seq_len, *seq_ep;
+    float *o_state_in;
+    int32_t *counts;
+};
+
+template <bool SEQ>
+__global__ __launch_bounds__(256) void hh_k_ep_count(hh_ep_desc b) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= b.N) return;
-    int nd = 0, last = -1;
+    const int cl = b.carried[n], L = b.max_seq_len;
+    int nd = 0, last = -1, ns = 0;
     for (int t0 = 0; t0 < b.T; t0 += 16) {   // lanes = consecutive arenas: every tick's read is one coalesced row of done; 16 in flight
         uint8_t d[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) d[k] = t0 + k < b.T ? b.done[(size_t)(t0 + k) * b.N + n] : 0;
 #pragma unroll
         for (int k = 0; k < 16; k++)
-            if (d[k]) { nd++; last = t0 + k; }
+            if (d[k]) {
+                // the episode ending here began after the previous done, or carried[n] rows before tick 0
+                if constexpr (SEQ) ns += (t0 + k - (last >= 0 ? last : -1 - cl) + L - 1) / L;
+                nd++;
+                last = t0 + k;
+            }
     }
     int32_t *s = b.scratch;
-    s[HH_EP_S_ROWS * b.N + n] = last >= 0 ? b.carried[n] + last + 1 : 0;
+    s[HH_EP_S_ROWS * b.N + n] = last >= 0 ? cl + last + 1 : 0;
     s[HH_EP_S_EPS * b.N + n] = nd;
     s[HH_EP_S_LAST * b.N + n] = last;
+    if constexpr (SEQ) s[HH_EP_S_SEQ * b.N + n] = ns;
 }
 
 /* one workgroup: thread i sums a contiguous run of arenas, the 1024 sums are scanned (wave shuffles, then the 16 wave totals), and
- * every thread writes the exclusive offsets of its run.  Totals fit in int: N (carry_cap + T) < 2^31 is checked at the entry point */
-__global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_episode_bufs b) {
-    __shared__ int w_rows[16], w_eps[16];
+ * every thread writes the exclusive offsets of its run; rows, episodes and (SEQ) sequences side by side.  Totals fit in int:
+ * N (carry_cap + T) < 2^31 is checked at the entry points (and bounds the sequences) */
+template <bool SEQ>
+__global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_ep_desc b) {
+    constexpr int Q = SEQ ? 3 : 2;
+    constexpr int in[3] = {HH_EP_S_ROWS, HH_EP_S_EPS, HH_EP_S_SEQ}, out[3] = {HH_EP_S_ROW_OFF, HH_EP_S_EP_OFF, HH_EP_S_SEQ_OFF};
+    __shared__ int w_tot[Q][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = b.N;
     int32_t *s = b.scratch;
     const int per = (N + 1023) / 1024, n0 = tid * per < N ? tid * per : N, n1 = n0 + per < N ? n0 + per : N;
-    int sr = 0, se = 0;
+    int sum[Q], x[Q], pre[Q], tot[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) sum[q] = 0;
 #pragma unroll 8
-    for (int n = n0; n < n1; n++) { sr += s[HH_EP_S_ROWS * N + n]; se += s[HH_EP_S_EPS * N + n]; }
-    int r = sr, e = se;
+    for (int n = n0; n < n1; n++)
+#pragma unroll
+        for (int q = 0; q < Q; q++) sum[q] += s[in[q] * N + n];
+#pragma unroll
+    for (int q = 0; q < Q; q++) x[q] = sum[q];
     for (int off = 1; off < 64; off <<= 1) {   // inclusive scan inside the wave
-        const int r2 = __shfl_up(r, off), e2 = __shfl_up(e, off);
-        if (lane >= off) { r += r2; e += e2; }
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int y = __shfl_up(x[q], off);
+            if (lane >= off) x[q] += y;
+        }
     }
-    if (lane == 63) { w_rows[wave] = r; w_eps[wave] = e; }
+    if (lane == 63)
+#pragma unroll
+        for (int q = 0; q < Q; q++) w_tot[q][wave] = x[q];
     __syncthreads();
-    int pre_r = r - sr, pre_e = e - se, tot_r = 0, tot_e = 0;
-    for (int w = 0; w < 16; w++) {
-        if (w < wave) { pre_r += w_rows[w]; pre_e += w_eps[w]; }
-        tot_r += w_rows[w];
-        tot_e += w_eps[w];
-    }
+#pragma unroll
+    for (int q = 0; q < Q; q++) { pre[q] = x[q] - sum[q]; tot[q] = 0; }
+#pragma unroll SEQ ? 4 : 16   // fully unrolled, the 48 totals of three scans would cost the sequence instance occupancy
+    for (int w = 0; w < 16; w++)
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            if (w < wave) pre[q] += w_tot[q][w];
+            tot[q] += w_tot[q][w];
+        }
 #pragma unroll 8
-    for (int n = n0; n < n1; n++) {
-        s[HH_EP_S_ROW_OFF * N + n] = pre_r;
-        s[HH_EP_S_EP_OFF * N + n] = pre_e;
-        pre_r += s[HH_EP_S_ROWS * N + n];
-        pre_e += s[HH_EP_S_EPS * N + n];
-    }
+    for (int n = n0; n < n1; n++)
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            s[out[q] * N + n] = pre[q];
+            pre[q] += s[in[q] * N + n];
+        }
     if (tid == 0) {
-        b.counts[0] = tot_r < b.row_cap ? tot_r : (int)b.row_cap;
-        b.counts[1] = tot_e < b.ep_cap ? tot_e : (int)b.ep_cap;
-        if (tot_r > b.row_cap || tot_e > b.ep_cap) b.counts[2] = 1;   // sticky: never cleared by a kernel
+        const int64_t cap[3] = {b.row_cap, b.ep_cap, b.seq_cap};
+        constexpr int slot[3] = {0, 1, 3};
+        bool over = false;
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            b.counts[slot[q]] = tot[q] < cap[q] ? tot[q] : (int)cap[q];
+            over |= tot[q] > cap[q];
+        }
+        if (over) b.counts[2] = 1;   // sticky: never cleared by a kernel
     }
 }
 
@@ -126,31 +203,91 @@ __device__ __forceinline__ void hh_ep_stash(U *carry, const U *coll, int upr, in
     }
 }
 
-__global__ __launch_bounds__(256) void hh_k_ep_emit(hh_episode_bufs b) {
+/* OBS / ACT: the access units of the observation and action columns (an action row holds one ACT per agent); SEQ: cut sequences —
+ * the commander's instance, whose row geometry (3 x 34) and states (3 x 2 x 200) are compile-time constants */
+template <typename OBS, typename ACT, bool SEQ>
+__global__ __launch_bounds__(256) void hh_k_ep_emit(hh_ep_desc b) {
     extern __shared__ int ep_lds[];
-    int *l_seg = ep_lds;              // episodes of the window that ended strictly before tick t
-    int *l_prev = ep_lds + b.T;       // last done tick strictly before t (-1: none)
-    int *l_done = ep_lds + 2 * b.T;
-    const int n = blockIdx.x, tid = threadIdx.x, N = b.N, nA = b.n_agents, cap = b.carry_cap;
+    const int T = b.T, N = b.N, nA = SEQ ? HH_CMD_AGENTS : b.n_agents, D = SEQ ? HH_CMD_OBS : b.obs_dim, cap = b.carry_cap, L = b.max_seq_len;
+    int *l_seg = ep_lds;           // episodes of the window that ended strictly before tick t
+    int *l_prev = l_seg + T;       // last done tick strictly before t (-1: none)
+    int *l_done = l_prev + T;
+    int *l_end = l_done + T;       // (SEQ) [k]: the window tick episode k of the window ends on
+    int *l_sq = l_end + T;         // (SEQ) [k]: sequences of the episodes before k; [nd]: all of them
+    int *l_src = l_sq + T + 1;     // (SEQ) [q]: where sequence q's first state is: window tick (>= 0) or carry slot -1 - src
+    const int n = blockIdx.x, tid = threadIdx.x;
     const int32_t *s = b.scratch;
     const int cl = b.carried[n];
     const int last = s[HH_EP_S_LAST * N + n], nd = s[HH_EP_S_EPS * N + n];
     const int ro = s[HH_EP_S_ROW_OFF * N + n], eo = s[HH_EP_S_EP_OFF * N + n];
     const int ep0 = b.episode[n];
-    if (tid < 64) hh_ep_tick_tables(b.done, b.T, N, n, tid, l_seg, l_prev, l_done);
+    if (tid < 64) hh_ep_tick_tables(b.done, T, N, n, tid, l_seg, l_prev, l_done);
     __syncthreads();
 
-    // 1. the finished episodes: carry slots [0, cl), then ticks [0, last]
+    // 1. (SEQ) the sequence table, and the states at the sequence starts: 4800 B per sequence, dwordx4 (ahead of the rows: in this
+    //    order the commander's instance needs fewer registers)
+    const int SC = SEQ ? (cap + L - 1) / L : 0;   // state carry slots per arena
+    const float4 *__restrict__ sin4 = (const float4 *)b.state_in;
+    float4 *__restrict__ cs4 = (float4 *)b.c_state;
+    if constexpr (SEQ) {
+        for (int t = tid; t < T; t += blockDim.x)
+            if (l_done[t]) l_end[l_seg[t]] = t;
+        __syncthreads();
+        if (tid < 64) {   // sequences per finished episode -> exclusive prefix (wave scan, 64 episodes at a time)
+            int run = 0;
+            for (int k0 = 0; k0 < nd; k0 += 64) {
+                const int k = k0 + tid;
+                int c = 0;
+                if (k < nd) c = ((k == 0 ? cl + l_end[0] + 1 : l_end[k] - l_end[k - 1]) + L - 1) / L;
+                int x = c;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int y = __shfl_up(x, off);
+                    if (tid >= off) x += y;
+                }
+                if (k < nd) l_sq[k] = run + x - c;
+                run += __shfl(x, 63);
+            }
+            if (tid == 0) l_sq[nd] = run;
+        }
+        __syncthreads();
+        const int so = s[HH_EP_S_SEQ_OFF * N + n], Q = T + cap / L;
+        int ns = l_sq[nd];
+        if (ns > Q) ns = Q;   // cannot happen while carried <= carry_cap (sum ceil(E_k / L) <= nd + (rows - nd) / L); keeps l_src in bounds
+        for (int q = tid; q < ns; q += blockDim.x) {
+            int lo = 0, hi = nd - 1;   // the episode of sequence q: the last k with l_sq[k] <= q
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (l_sq[mid] <= q) lo = mid; else hi = mid - 1;
+            }
+            const int k = lo, j = q - l_sq[k];
+            const int i0 = k == 0 ? 0 : cl + l_end[k - 1] + 1, len = k == 0 ? cl + l_end[0] + 1 : l_end[k] - l_end[k - 1];
+            const int i = i0 + j * L, rem = len - j * L;
+            l_src[q] = i < cl ? -1 - j : i - cl;   // only the first episode reaches into the carry, whose slot j holds its step j L
+            const long long e = (long long)so + q;
+            if (e < b.seq_cap) {
+                b.seq_start[e] = ro + i;
+                b.seq_len[e] = rem < L ? rem : L;
+                b.seq_ep[e] = eo + k;
+            }
+        }
+        __syncthreads();
+        const int nsw = (long long)so + ns <= b.seq_cap ? ns : (so < b.seq_cap ? (int)(b.seq_cap - so) : 0);   // flagged by the scan
+        float4 *__restrict__ os4 = (float4 *)b.o_state_in + (size_t)so * HH_EP_STATE4;
+        const int units = nsw * HH_EP_STATE4;
+        for (int u = tid; u < units; u += blockDim.x) {
+            const int q = u / HH_EP_STATE4, w = u - q * HH_EP_STATE4, src = l_src[q];
+            os4[u] = src >= 0 ? sin4[((size_t)src * N + n) * HH_EP_STATE4 + w] : cs4[((size_t)n * SC + (-1 - src)) * HH_EP_STATE4 + w];
+        }
+    }
+
+    // 2. the finished episodes: carry slots [0, cl), then ticks [0, last]
     int emit = last >= 0 ? cl + last + 1 : 0;
     if (emit > 0 && (long long)ro + emit > b.row_cap) emit = ro < b.row_cap ? (int)(b.row_cap - ro) : 0;   // flagged by the scan
     const size_t crow0 = (size_t)n * cap, orow0 = (size_t)ro;
+    const int obs_units = nA * D / (int)(sizeof(OBS) / sizeof(float));
     if (emit > 0) {
-        const int D = b.obs_dim;
-        if ((nA * D) % 4 == 0)   // an obs row is 2 D floats = 16 B aligned for D = 26 | 30: dwordx4
-            hh_ep_gather((float4 *)b.o_obs, (const float4 *)b.c_obs, (const float4 *)b.obs, nA * D / 4, emit, cl, crow0, N, n, orow0);
-        else
-            hh_ep_gather(b.o_obs, b.c_obs, b.obs, nA * D, emit, cl, crow0, N, n, orow0);
-        hh_ep_gather((uint32_t *)b.o_actions, (const uint32_t *)b.c_actions, (const uint32_t *)b.actions, nA, emit, cl, crow0, N, n, orow0);
+        hh_ep_gather((OBS *)b.o_obs, (const OBS *)b.c_obs, (const OBS *)b.obs, obs_units, emit, cl, crow0, N, n, orow0);
+        hh_ep_gather((ACT *)b.o_actions, (const ACT *)b.c_actions, (const ACT *)b.actions, nA, emit, cl, crow0, N, n, orow0);
         hh_ep_gather(b.o_logp, b.c_logp, b.logp, nA, emit, cl, crow0, N, n, orow0);
         hh_ep_gather(b.o_vf, b.c_vf, b.vf, nA, emit, cl, crow0, N, n, orow0);
         hh_ep_gather(b.o_reward, b.c_reward, b.reward, nA, emit, cl, crow0, N, n, orow0);
@@ -175,27 +312,32 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_episode_bufs b) {
             }
         }
     }
-    __syncthreads();   // every read of the carry above happens before it is rewritten below
+    __syncthreads();   // every read of the carry above (rows and states) happens before it is rewritten below
 
-    // 2. the trailing fragment: ticks (last, T) replace the carry, or, with no done in the window, all T ticks extend it
+    // 3. the trailing fragment: ticks (last, T) replace the carry, or, with no done in the window, all T ticks extend it
     const int c0 = last >= 0 ? 0 : cl, t0 = last + 1;
-    int keep = b.T - t0;
-    if (c0 + keep > cap) keep = cap - c0 > 0 ? cap - c0 : 0;   // cannot happen under the horizon rule (an episode has <= horizon rows)
+    int keep = T - t0;
+    if (c0 + keep > cap) keep = cap - c0 > 0 ? cap - c0 : 0;   // only if an episode outgrew carry_cap (flagged below)
     if (keep > 0) {
         const size_t c = crow0 + c0;
-        const int D = b.obs_dim;
-        if ((nA * D) % 4 == 0)
-            hh_ep_stash((float4 *)b.c_obs, (const float4 *)b.obs, nA * D / 4, keep, t0, c, N, n);
-        else
-            hh_ep_stash(b.c_obs, b.obs, nA * D, keep, t0, c, N, n);
-        hh_ep_stash((uint32_t *)b.c_actions, (const uint32_t *)b.actions, nA, keep, t0, c, N, n);
+        hh_ep_stash((OBS *)b.c_obs, (const OBS *)b.obs, obs_units, keep, t0, c, N, n);
+        hh_ep_stash((ACT *)b.c_actions, (const ACT *)b.actions, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_logp, b.logp, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_vf, b.vf, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_reward, b.reward, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_valid, b.valid, nA, keep, t0, c, N, n);
+        if constexpr (SEQ) {
+            // the running episode's sequence starts among the new carry slots: steps j L in [c0, c0 + keep), window tick t0 + j L - c0
+            const int j0 = (c0 + L - 1) / L, j1 = (c0 + keep + L - 1) / L;   // j1 <= SC: c0 + keep <= cap
+            const int units = (j1 - j0) * HH_EP_STATE4;
+            for (int u = tid; u < units; u += blockDim.x) {
+                const int q = u / HH_EP_STATE4, w = u - q * HH_EP_STATE4, j = j0 + q, t = t0 + j * L - c0;
+                cs4[((size_t)n * SC + j) * HH_EP_STATE4 + w] = sin4[((size_t)t * N + n) * HH_EP_STATE4 + w];
+            }
+        }
     }
     if (tid == 0) {
-        if (keep < b.T - t0) b.counts[2] = 1;
+        if (keep < T - t0 || (SEQ && l_sq[nd] > T + cap / L)) b.counts[2] = 1;
         b.carried[n] = c0 + keep;
         b.episode[n] = ep0 + nd;
     }
@@ -206,7 +348,7 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_episode_bufs b) {
  * a < n_agents walks agent a backwards on the LDS copy (the chain is sequential: bit-exactness fixes its order), and the results leave
  * with coalesced stores.  Episodes longer than a chunk are walked chunk by chunk from the end, the recursion carried in registers. */
 #define HH_EP_GAE_LDS 512   /* floats per staged column */
-__global__ __launch_bounds__(64) void hh_k_ep_gae(hh_episode_bufs b) {
+__global__ __launch_bounds__(64) void hh_k_ep_gae(hh_ep_desc b) {
     __shared__ float l_r[HH_EP_GAE_LDS], l_v[HH_EP_GAE_LDS];
     const int nA = b.n_agents, tid = threadIdx.x, chunk = HH_EP_GAE_LDS / nA;
     const int n_eps = b.counts[1];
@@ -240,6 +382,100 @@ __global__ __launch_bounds__(64) void hh_k_ep_gae(hh_episode_bufs b) {
             __syncthreads();   // before the next chunk overwrites the staging
         }
     }
+}
+
+/* ---- host side ---- */
+
+/* the fields both public structs name alike */
+template <typename B>
+static hh_ep_desc hh_ep_common(const B *b) {
+    hh_ep_desc d = {};
+    d.T = b->T; d.N = b->N; d.carry_cap = b->carry_cap; d.row_cap = b->row_cap; d.ep_cap = b->ep_cap; d.gamma = b->gamma; d.lam = b->lam;
+    d.obs = b->obs; d.actions = b->actions; d.logp = b->logp; d.vf = b->vf; d.reward = b->reward; d.valid = b->valid; d.done = b->done;
+    d.c_obs = b->c_obs; d.c_actions = b->c_actions; d.c_logp = b->c_logp; d.c_vf = b->c_vf; d.c_reward = b->c_reward; d.c_valid = b->c_valid;
+    d.carried = b->carried; d.episode = b->episode; d.scratch = b->scratch;
+    d.o_obs = b->o_obs; d.o_actions = b->o_actions; d.o_logp = b->o_logp; d.o_vf = b->o_vf; d.o_reward = b->o_reward; d.o_valid = b->o_valid;
+    d.o_adv = b->o_adv; d.o_target = b->o_target; d.o_done = b->o_done; d.o_arena = b->o_arena; d.o_episode = b->o_episode; d.o_t = b->o_t;
+    d.ep_start = b->ep_start; d.ep_len = b->ep_len; d.ep_arena = b->ep_arena; d.counts = b->counts;
+    return d;
+}
+
+static int hh_ep_fail(const char *fn, const char *what) {
+    g_err = std::string(fn) + ": " + what;
+    return HH_E_ARG;
+}
+
+/* The checks both entry points make, in this order: sizes, T, capacities below 2^31.  own_* is the entry point's own condition of the
+ * same step, reported with it (t_msg: the T step's message). */
+static int hh_ep_check_sizes(const char *fn, const hh_ep_desc &d, bool own_sizes, bool own_t, const char *t_msg, bool own_caps) {
+    if (d.T <= 0 || d.N <= 0 || d.carry_cap < 0 || own_sizes) return hh_ep_fail(fn, "bad sizes");
+    if (d.T > HH_EP_MAX_T || own_t) return hh_ep_fail(fn, t_msg);
+    if ((int64_t)d.N * ((int64_t)d.carry_cap + d.T) > INT32_MAX || d.row_cap > INT32_MAX || d.ep_cap > INT32_MAX || own_caps)
+        return hh_ep_fail(fn, "capacities must stay below 2^31");
+    return HH_OK;
+}
+
+/* the null-pointer sweep: every buffer of the descriptor (with sequences: the state columns and the sequence table as well) */
+static int hh_ep_check_ptrs(const char *fn, const hh_ep_desc &d) {
+    const void *ptrs[] = {d.obs, d.actions, d.logp, d.vf, d.reward, d.valid, d.done, d.c_obs, d.c_actions, d.c_logp, d.c_vf, d.c_reward,
+                          d.c_valid, d.carried, d.episode, d.scratch, d.o_obs, d.o_actions, d.o_logp, d.o_vf, d.o_reward, d.o_valid,
+                          d.o_adv, d.o_target, d.o_done, d.o_arena, d.o_episode, d.o_t, d.ep_start, d.ep_len, d.ep_arena, d.counts};
+    const void *seq[] = {d.state_in, d.c_state, d.seq_start, d.seq_len, d.seq_ep, d.o_state_in};
+    for (const void *p : ptrs)
+        if (!p) return hh_ep_fail(fn, "null buffer");
+    if (d.max_seq_len > 0)
+        for (const void *p : seq)
+            if (!p) return hh_ep_fail(fn, "null buffer");
+    return HH_OK;
+}
+
+template <typename OBS, typename ACT, bool SEQ>
+static int hh_ep_launch(const hh_ep_desc &d, size_t lds, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(hh_k_ep_count<SEQ>, dim3((d.N + 255) / 256), dim3(256), 0, st, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hh_k_ep_scan<SEQ>, dim3(1), dim3(1024), 0, st, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((hh_k_ep_emit<OBS, ACT, SEQ>), dim3(d.N), dim3(256), lds, st, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hh_k_ep_gae, dim3(d.ep_cap < 8192 ? (int)d.ep_cap : 8192), dim3(64), 0, st, d);
+    HIPCHK(hipGetLastError());
+    return HH_OK;
+}
+
+extern "C" int hh_episodes_emit(const hh_episode_bufs *b, void *stream) {
+    const char *fn = "hh_episodes_emit";
+    if (!b) return hh_ep_fail(fn, "bad sizes");
+    hh_ep_desc d = hh_ep_common(b);
+    d.n_agents = b->n_agents; d.obs_dim = b->obs_dim;
+    int rc = hh_ep_check_sizes(fn, d, b->n_agents <= 0 || b->obs_dim <= 0 || b->reserved0 != 0, b->n_agents > 64,
+                               "T > HH_EP_MAX_T or n_agents > 64", b->row_cap < 1 || b->ep_cap < 1);
+    if (rc != HH_OK || (rc = hh_ep_check_ptrs(fn, d)) != HH_OK) return rc;
+    const bool obs4 = (b->n_agents * b->obs_dim) % 4 == 0;   // an obs row is 2 D floats = 16 B aligned for D = 26 | 30: dwordx4
+    if (obs4 && (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 15)) return hh_ep_fail(fn, "obs buffers must be 16-byte aligned");
+    if ((((uintptr_t)b->actions | (uintptr_t)b->c_actions | (uintptr_t)b->o_actions) & 3)) return hh_ep_fail(fn, "action buffers must be 4-byte aligned");
+    const size_t lds = 3 * (size_t)b->T * sizeof(int);
+    return obs4 ? hh_ep_launch<float4, uint32_t, false>(d, lds, stream) : hh_ep_launch<float, uint32_t, false>(d, lds, stream);
+}
+
+extern "C" int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream) {
+    const char *fn = "hh_commander_episodes_emit";
+    if (!b) return hh_ep_fail(fn, "bad sizes");
+    hh_ep_desc d = hh_ep_common(b);
+    d.n_agents = HH_CMD_AGENTS; d.obs_dim = HH_CMD_OBS; d.max_seq_len = b->max_seq_len; d.seq_cap = b->seq_cap;
+    d.state_in = b->state_in; d.c_state = b->c_state; d.o_state_in = b->o_state_in;
+    d.seq_start = b->seq_start; d.seq_len = b->seq_len; d.seq_ep = b->seq_ep;
+    int rc = hh_ep_check_sizes(fn, d, b->max_seq_len < 1, false, "T > HH_EP_MAX_T", b->seq_cap > INT32_MAX);
+    if (rc != HH_OK) return rc;
+    const int64_t N = b->N, T = b->T, cap = b->carry_cap, L = b->max_seq_len;
+    if (b->row_cap < N * (cap + T) || b->ep_cap < N * T || b->seq_cap < N * (T + cap / L))
+        return hh_ep_fail(fn, "row_cap >= N (carry_cap + T), ep_cap >= N T and seq_cap >= N (T + carry_cap / max_seq_len) are required");
+    const int64_t lds = hh_cep_lds_ints((int)T, (int)cap, (int)L) * (int64_t)sizeof(int);
+    if (lds > 65536) return hh_ep_fail(fn, "T and carry_cap / max_seq_len too large for the emit kernel's LDS");
+    if ((rc = hh_ep_check_ptrs(fn, d)) != HH_OK) return rc;
+    if (((uintptr_t)b->state_in | (uintptr_t)b->c_state | (uintptr_t)b->o_state_in) & 15) return hh_ep_fail(fn, "state buffers must be 16-byte aligned");
+    if (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 7) return hh_ep_fail(fn, "obs buffers must be 8-byte aligned");
+    return hh_ep_launch<float2, uint8_t, true>(d, (size_t)lds, stream);
 }
 
 #endif /* HH_EPISODES_H */

@@ -14,7 +14,6 @@
 #include "hh_kernels_quad.h"
 #include "hh_kernels_oct.h"
 #include "hh_gae.h"
-#include "hh_episodes.h"
 
 /* ===================================================================== host side */
 static thread_local std::string g_err;
@@ -804,32 +803,9 @@ extern "C" int hh_gae_rllib(int32_t T, int32_t N, int32_t n_agents, const float 
     return HH_OK;
 }
 
-/* ---- whole-episode batches (batch_mode = "complete_episodes"): hh_episodes.h ---- */
-extern "C" int hh_episodes_emit(const hh_episode_bufs *b, void *stream) {
-    if (!b || b->T <= 0 || b->N <= 0 || b->n_agents <= 0 || b->obs_dim <= 0 || b->carry_cap < 0 || b->reserved0 != 0) { g_err = "hh_episodes_emit: bad sizes"; return HH_E_ARG; }
-    if (b->T > HH_EP_MAX_T || b->n_agents > 64) { g_err = "hh_episodes_emit: T > HH_EP_MAX_T or n_agents > 64"; return HH_E_ARG; }
-    if (b->row_cap < 1 || b->row_cap > INT32_MAX || b->ep_cap < 1 || b->ep_cap > INT32_MAX ||
-        (int64_t)b->N * ((int64_t)b->carry_cap + b->T) > INT32_MAX) { g_err = "hh_episodes_emit: capacities must stay below 2^31"; return HH_E_ARG; }
-    const void *ptrs[] = {b->obs, b->actions, b->logp, b->vf, b->reward, b->valid, b->done, b->c_obs, b->c_actions, b->c_logp, b->c_vf, b->c_reward,
-                          b->c_valid, b->carried, b->episode, b->scratch, b->o_obs, b->o_actions, b->o_logp, b->o_vf, b->o_reward, b->o_valid,
-                          b->o_adv, b->o_target, b->o_done, b->o_arena, b->o_episode, b->o_t, b->ep_start, b->ep_len, b->ep_arena, b->counts};
-    for (const void *p : ptrs)
-        if (!p) { g_err = "hh_episodes_emit: null buffer"; return HH_E_ARG; }
-    if ((b->n_agents * b->obs_dim) % 4 == 0 && (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 15)) {
-        g_err = "hh_episodes_emit: obs buffers must be 16-byte aligned"; return HH_E_ARG;
-    }
-    if ((((uintptr_t)b->actions | (uintptr_t)b->c_actions | (uintptr_t)b->o_actions) & 3)) { g_err = "hh_episodes_emit: action buffers must be 4-byte aligned"; return HH_E_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(hh_k_ep_count, dim3((b->N + 255) / 256), dim3(256), 0, st, *b);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hh_k_ep_scan, dim3(1), dim3(1024), 0, st, *b);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hh_k_ep_emit, dim3(b->N), dim3(256), 3 * b->T * sizeof(int), st, *b);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hh_k_ep_gae, dim3(b->ep_cap < 8192 ? (int)b->ep_cap : 8192), dim3(64), 0, st, *b);
-    HIPCHK(hipGetLastError());
-    return HH_OK;
-}
+/* ---- whole-episode batches (batch_mode = "complete_episodes"; C ABI in include/hh_abi.h, and for the commander's GRU sequences in
+ * include/hh_commander.h) ---- */
+#include "hh_episodes.h"
 
 /* hh_math_eval: the shared math headers on the device (test probe, include/hh_abi.h) */
 __global__ void hh_k_math_eval(int fn, int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ o0, double *__restrict__ o1) {
@@ -886,9 +862,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- the commander as evaluation.py runs it: greedy, the actor's state chained through the agent slots (C ABI in include/hh_commander.h) ---- */
 #include "hh_commander_chain.h"
-
-/* ---- whole-episode GRU-sequence batches of the commander (C ABI in include/hh_commander.h) ---- */
-#include "hh_commander_episodes.h"
 
 /* ---- the learner's weights into the policy bank and the commander on the device (C ABI in include/hh_policy.h, include/hh_commander.h) ---- */
 #include "hh_weight_refresh.h"

@@ -112,63 +112,86 @@ class EpisodeBatch:
     sticky device flag is set and `rows()` raises."""
 
     COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
+    TABLES = ("ep_start", "ep_len", "ep_arena")
+    ROW_INPUTS = ("obs", "actions", "logp", "vf", "reward", "valid")   # the collect's columns the rows carry (and the carry holds)
+    _EMIT, _SCRATCH, _N_COUNTS = "hh_episodes_emit", (5, 0), 3       # entry point; scratch i32 [5 N + 0]; counts
+    _critic_rows = staticmethod(central_critic_rows)
 
-    def __init__(self, N, T, horizon, n_agents, D, device, gamma, lam, collect):
-        """collect: the rollout's [T(+1), N, ...] buffers (obs, actions, logp, vf, reward, valid, done) that every emission reads"""
-        self.N, self.T, self.n_agents, self.D = int(N), int(T), int(n_agents), int(D)
-        self.carry_cap = max(int(horizon) - 1, 0)
-        R, E, cap, nA = self.N * (self.carry_cap + self.T), self.N * self.T, max(self.carry_cap, 1), self.n_agents
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        f32, i8, u8, i32 = torch.float32, torch.int8, torch.uint8, torch.int32
-        self.obs, self.actions = z((R, nA, D), f32), z((R, nA, 4), i8)
-        self.logp, self.vf, self.reward, self.valid = z((R, nA), f32), z((R, nA), f32), z((R, nA), f32), z((R, nA), u8)
-        self.adv, self.target = z((R, nA), f32), z((R, nA), f32)
-        self.done, self.arena, self.episode, self.t = z((R,), u8), z((R,), i32), z((R,), i32), z((R,), i32)
-        self.ep_start, self.ep_len, self.ep_arena = z((E,), i32), z((E,), i32), z((E,), i32)
+    def __init__(self, collect, carry_cap, gamma, lam):
+        """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS and done) that every emission reads; every row column of the batch and
+        of the carry takes its per-row shape and dtype from the collect's.  carry_cap: rows the carry holds per arena (horizon - 1)."""
+        T, N = collect["done"].shape
+        self.N, self.T, self.carry_cap = int(N), int(T), int(carry_cap)
+        self.n_agents, self.D = int(collect["obs"].shape[2]), int(collect["obs"].shape[-1])
+        self._device = collect["done"].device
+        N, T, cap = self.N, self.T, max(self.carry_cap, 1)
+        R, E = N * (self.carry_cap + T), N * T
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self._device)
+        i32 = torch.int32
+        self._carry = {}
+        for k in self.ROW_INPUTS:
+            row, dt = tuple(collect[k].shape[2:]), collect[k].dtype
+            setattr(self, k, z((R,) + row, dt))
+            self._carry[k] = z((N, cap) + row, dt)
+        self.adv, self.target = z(self.reward.shape, torch.float32), z(self.reward.shape, torch.float32)
+        self.done, self.arena, self.episode, self.t = z((R,), torch.uint8), z((R,), i32), z((R,), i32), z((R,), i32)
+        for k in self.TABLES:
+            setattr(self, k, z((E,), i32))
         self.carried = z((N,), i32)
-        self._carry = {"obs": z((N, cap, nA, D), f32), "actions": z((N, cap, nA, 4), i8), "logp": z((N, cap, nA), f32),
-                       "vf": z((N, cap, nA), f32), "reward": z((N, cap, nA), f32), "valid": z((N, cap, nA), u8)}
         self._finished = z((N,), i32)            # episodes finished per arena since start()
-        self._scratch = z((5, N), i32)
-        self._counts = z((3,), i32)              # rows, episodes of the last collect; overflow flag (sticky)
+        self._scratch = z((self._SCRATCH[0] * N + self._SCRATCH[1],), i32)
+        self._counts = z((self._N_COUNTS,), i32)  # rows, episodes of the last collect; overflow flag (sticky)[; sequences of the last collect]
         self.n_rows, self.n_episodes = self._counts[0], self._counts[1]
-        b = L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=nA, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R, ep_cap=E,
-                            gamma=float(gamma), lam=float(lam))
-        for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done"):
-            assert collect[k].is_contiguous() and collect[k].shape[1] == N
+        b = self._struct(R, E, float(gamma), float(lam))
+        self._bufs, self._collect = b, collect   # the struct holds raw pointers: keep the tensors alive
+        self._bind(collect, self._carry, ("done",) + self.ROW_INPUTS, self.COLUMNS, self.TABLES)
+        b.carried, b.episode, b.scratch, b.counts = (x.data_ptr() for x in (self.carried, self._finished, self._scratch, self._counts))
+
+    def _struct(self, R, E, gamma, lam):
+        return L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=self.n_agents, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R,
+                               ep_cap=E, gamma=gamma, lam=lam)
+
+    def _bind(self, collect, carry, inputs, columns, tables):
+        """the device pointers of the struct: collect inputs, carry columns (c_), batch columns (o_), tables"""
+        b = self._bufs
+        for k in inputs:
+            assert collect[k].is_contiguous() and collect[k].shape[1] == self.N
             setattr(b, k, collect[k].data_ptr())
-        for k, v in self._carry.items():
+        for k, v in carry.items():
             setattr(b, "c_" + k, v.data_ptr())
-        b.carried, b.episode, b.scratch = self.carried.data_ptr(), self._finished.data_ptr(), self._scratch.data_ptr()
-        for k in self.COLUMNS:
+        for k in columns:
             setattr(b, "o_" + k, getattr(self, k).data_ptr())
-        b.ep_start, b.ep_len, b.ep_arena, b.counts = (x.data_ptr() for x in (self.ep_start, self.ep_len, self.ep_arena, self._counts))
-        self._bufs, self._collect, self._device = b, collect, device   # the struct holds raw pointers: keep the tensors alive
+        for k in tables:
+            setattr(b, k, getattr(self, k).data_ptr())
+
+    def _parts(self):
+        """(names, index in the counts of the length they are cut to) for rows()"""
+        return ((self.COLUMNS, 0), (self.TABLES, 1))
 
     def reset(self):
         """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
         self.carried.zero_()
         self._finished.zero_()
         self._counts[:2].zero_()
+        self._counts[3:].zero_()
 
     def emit(self, stream):
-        L.check(L.lib().hh_episodes_emit(C.byref(self._bufs), stream))
+        L.check(getattr(L.lib(), self._EMIT)(C.byref(self._bufs), stream))
 
     def rows(self):
-        """synchronises; -> dict of views cut to the rows (COLUMNS) and the episode table (ep_start, ep_len, ep_arena) of the last collect"""
+        """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES) and a subclass's own
+        parts (_parts)"""
         torch.cuda.synchronize(self._device)
-        R, E, overflow = self._counts.tolist()
-        if overflow:
-            raise RuntimeError("EpisodeBatch: an episode outgrew the carry or the batch capacity (more rows than the horizon?): the batches "
-                               "since that collect are incomplete")
-        out = {k: getattr(self, k)[:R] for k in self.COLUMNS}
-        out.update({k: getattr(self, k)[:E] for k in ("ep_start", "ep_len", "ep_arena")})
-        return out
+        counts = self._counts.tolist()
+        if counts[2]:
+            raise RuntimeError(f"{type(self).__name__}: an episode outgrew the carry or a batch capacity (more rows than carry_cap + 1?): "
+                               "the batches since that collect are incomplete")
+        return {k: getattr(self, k)[:counts[i]] for names, i in self._parts() for k in names}
 
     def critic_rows(self, agent):
-        """the CUR_OBS rows of `agent` (1 | 2) for the emitted rows (central_critic_rows)"""
+        """the CUR_OBS rows of `agent` for the emitted rows with the actions filled in (central_critic_rows: agent 1 | 2)"""
         r = self.rows()
-        return central_critic_rows(r["obs"], r["actions"], agent)
+        return self._critic_rows(r["obs"], r["actions"], agent)
 
 
 class PPORollout:
@@ -251,8 +274,8 @@ class PPORollout:
         self.batch_mode = batch_mode
         self.episodes = None
         if batch_mode == "complete_episodes":
-            self.episodes = EpisodeBatch(N, self.T, world.cfg.horizon, 2, D, dev, self.gamma, self.lam,
-                                         {k: getattr(self, k) for k in ("obs", "actions", "logp", "vf", "reward", "valid", "done")})
+            self.episodes = EpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done",)}, max(world.cfg.horizon - 1, 0),
+                                         self.gamma, self.lam)
         self.use_graph = use_graph
         self._graph = None
         self._started = False

@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-from commander_episodes_ref import pad_sequences, restate
+from episodes_ref import pad_sequences, restate
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -114,7 +114,7 @@ def test_restatement_on_hand_built_streams():
     r2 = np.zeros((T, N, 3), np.float32)
     r2[1, 0] = 1.0
     c = _stream([_collect(T, N, {0: [0]}, r0, v0), _collect(T, N, {}), _collect(T, N, {0: [1], 1: [1]}, r2)])
-    (b0, b1, b2), carried = restate(c, L, 0.5, 0.5)
+    (b0, b1, b2), carried = restate(c, L, gamma=0.5, lam=0.5)
     assert np.array_equal(carried, [0, 0, 6])
     # collect 0: the one-row episode of arena 0, one sequence of one row, zero state
     assert np.array_equal(b0["t"], [0]) and np.array_equal(b0["done"], [1]) and np.array_equal(b0["arena"], [0])

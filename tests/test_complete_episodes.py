@@ -1,5 +1,5 @@
 """batch_mode = "complete_episodes" (train_hetero.py:212) without a GPU: argument validation of PPORollout, the C ABI of
-hh_episodes_emit (export, binding, layout of hh_episode_bufs), and the host restatement of the whole-episode batch that
+hh_episodes_emit (export, binding, layout of hh_episode_bufs), and the host restatement of the whole-episode batch (tests/episodes_ref.py) that
 tests/test_gpu_complete_episodes.py compares the device's batches with, pinned on hand-built streams of exactly representable numbers."""
 import ctypes as C
 import os
@@ -8,49 +8,11 @@ import re
 import numpy as np
 import pytest
 
+from episodes_ref import restate
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IN_COLS = ("obs", "actions", "logp", "vf", "reward", "valid", "done")
 OUT_COLS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
-
-
-def restate_episodes(collects, gamma=0.99, lam=0.95):
-    """What RLlib's complete_episodes batches are for a sequence of collects after one start(): the [T, N, ...] windows (obs / vf
-    cut to their first T rows) concatenated per arena, cut after every done row (the next row is the reset row of the arena's
-    next episode), every episode that has ended computed with oracle/gae_ref.compute_advantages(last_r = 0) per agent.
-    -> (one dict per collect: the columns of the episodes that end in it, arena-major, then episode, then time;
-        carried [N]: rows of every arena's running episode after the last collect)"""
-    import gae_ref
-    T, N = collects[0]["done"].shape
-    cat = {k: np.concatenate([c[k] for c in collects], axis=0) for k in IN_COLS}
-    nA = cat["reward"].shape[2]
-    start, ep = np.zeros(N, dtype=np.int64), np.zeros(N, dtype=np.int64)
-    batches = []
-    for ci in range(len(collects)):
-        parts = {k: [] for k in OUT_COLS}
-        for n in range(N):
-            for g in np.nonzero(cat["done"][ci * T:(ci + 1) * T, n])[0] + ci * T:
-                sl, L = slice(int(start[n]), int(g) + 1), int(g) + 1 - int(start[n])
-                adv, tgt = np.zeros((L, nA), dtype=np.float32), np.zeros((L, nA), dtype=np.float32)
-                for a in range(nA):
-                    adv[:, a], tgt[:, a] = gae_ref.compute_advantages(cat["reward"][sl, n, a], cat["vf"][sl, n, a], 0.0, gamma, lam)
-                for k in ("obs", "actions", "logp", "vf", "reward", "valid"):
-                    parts[k].append(cat[k][sl, n])
-                done = np.zeros(L, dtype=np.uint8)
-                done[-1] = 1
-                parts["adv"].append(adv)
-                parts["target"].append(tgt)
-                parts["done"].append(done)
-                parts["arena"].append(np.full(L, n, dtype=np.int32))
-                parts["episode"].append(np.full(L, ep[n], dtype=np.int32))
-                parts["t"].append(np.arange(L, dtype=np.int32))
-                ep[n] += 1
-                start[n] = g + 1
-        empty = {"obs": cat["obs"][:0, 0], "actions": cat["actions"][:0, 0], "logp": cat["logp"][:0, 0], "vf": cat["vf"][:0, 0],
-                 "reward": cat["reward"][:0, 0], "valid": cat["valid"][:0, 0], "adv": np.zeros((0, nA), np.float32),
-                 "target": np.zeros((0, nA), np.float32), "done": np.zeros(0, np.uint8), "arena": np.zeros(0, np.int32),
-                 "episode": np.zeros(0, np.int32), "t": np.zeros(0, np.int32)}
-        batches.append({k: np.concatenate(v, axis=0) if v else empty[k] for k, v in parts.items()})
-    return batches, (len(collects) * T - start).astype(np.int32)
 
 
 def _stream(T, N, nA, done_rows, reward, vf, D=2):
@@ -109,7 +71,7 @@ def test_restatement_on_hand_built_streams():
     v1 = np.array([[-1, 0], [7, 0], [7, 0]], dtype=np.float32)[..., None]
     c0 = _stream(3, 2, 1, {0: [0]}, r0, v0)
     c1 = _stream(3, 2, 1, {0: [0], 1: [2]}, r1, v1)
-    (b0, b1), carried = restate_episodes([c0, c1], 0.5, 0.5)
+    (b0, b1), carried = restate([c0, c1], gamma=0.5, lam=0.5)
     assert np.array_equal(carried, [2, 0])
     # collect 0: only the one-row episode of arena 0
     assert np.array_equal(b0["arena"], [0]) and np.array_equal(b0["episode"], [0]) and np.array_equal(b0["t"], [0])
@@ -127,6 +89,6 @@ def test_restatement_on_hand_built_streams():
 
 def test_restatement_without_any_finished_episode_is_empty():
     c = _stream(4, 3, 2, {}, np.zeros((4, 3, 2)), np.zeros((4, 3, 2)), D=5)
-    (b,), carried = restate_episodes([c])
+    (b,), carried = restate([c])
     assert np.array_equal(carried, [4, 4, 4])
     assert all(len(v) == 0 for v in b.values()) and b["obs"].shape == (0, 2, 5) and b["adv"].shape == (0, 2)

@@ -1,12 +1,12 @@
 """CommanderRollout(batch_mode="complete_episodes") on the MI355X: the whole-episode GRU-sequence batch of hh_commander_episodes_emit
-against the host restatement of tests/commander_episodes_ref.py (the rollout's own [T, N] buffers, cloned after every collect), bit for
+against the host restatement of tests/episodes_ref.py (the rollout's own [T, N] buffers, cloned after every collect), bit for
 bit in every column, table and sequence-start state; its bookkeeping; a replay of the learner's forward from the emitted states; graph
 against eager; the default mode unchanged; the overflow flag; and the default carry at 8192 arenas."""
 import numpy as np
 import pytest
 import torch
 
-from commander_episodes_ref import IN_COLS, OUT_COLS, SEQ_TABLE, TABLE, pad_sequences, restate
+from episodes_ref import IN_COLS, OUT_COLS, SEQ_TABLE, TABLE, pad_sequences, restate
 
 pytestmark = pytest.mark.gpu
 ALL = OUT_COLS + TABLE + SEQ_TABLE + ("state_in",)
@@ -47,7 +47,7 @@ def _assert_equal(got, want, what):
 
 def _check_against_restatement(ro, K):
     collects, emitted, carried = _collect(ro, K)
-    want, want_carried = restate(collects, ro.max_seq_len, ro.gamma, ro.lam)
+    want, want_carried = restate(collects, ro.max_seq_len, gamma=ro.gamma, lam=ro.lam)
     for i, (g, w) in enumerate(zip(emitted, want)):
         _assert_equal(g, w, f"collect {i}")
     assert np.array_equal(carried[-1], want_carried)

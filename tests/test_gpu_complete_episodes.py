@@ -1,12 +1,13 @@
 """batch_mode = "complete_episodes" on the MI355X (train_hetero.py:212): PPORollout's EpisodeBatch after every collect against the
-host restatement of tests/test_complete_episodes.py (the collects' own [T, N] buffers concatenated per arena, cut at the done
+host restatement of tests/episodes_ref.py (the collects' own [T, N] buffers concatenated per arena, cut at the done
 rows, oracle/gae_ref.compute_advantages with last_r = 0 per agent and whole episode) — bit for bit, every column, in emission
 order — and its bookkeeping: every episode whole, from a reset row to its only done row, emitted exactly once."""
 import numpy as np
 import pytest
 import torch
 
-from test_complete_episodes import IN_COLS, OUT_COLS, restate_episodes
+from episodes_ref import restate
+from test_complete_episodes import IN_COLS, OUT_COLS
 
 pytestmark = pytest.mark.gpu
 TABLE = ("ep_start", "ep_len", "ep_arena")
@@ -57,7 +58,7 @@ def _check_table(b):
 
 def _check_against_restatement(ro, K):
     collects, emitted, carried = _collect(ro, K)
-    want, want_carried = restate_episodes(collects, ro.gamma, ro.lam)
+    want, want_carried = restate(collects, gamma=ro.gamma, lam=ro.lam)
     for i, (g, w) in enumerate(zip(emitted, want)):
         _assert_equal_batches(g, w, f"collect {i}")
         _check_table(g)

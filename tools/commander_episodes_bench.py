@@ -42,8 +42,8 @@ def ms_per_collect(ro, n):
 
 
 def emission_bytes(ep, done, carried_before, carried_after, rows, seqs):
-    """bytes hh_k_cep_emit reads and writes in one collect (row gather, sequence-start states, carry rewrite); the small count / scan / GAE
-    traffic is left out"""
+    """bytes the commander's hh_k_ep_emit instance reads and writes in one collect (row gather, sequence-start states, carry rewrite);
+    the small count / scan / GAE traffic is left out"""
     Lq = ep.L
     fin = done.bool().any(dim=0).cpu()                                      # arenas with an episode ending in the window
     cb, ca = carried_before.cpu().long(), carried_after.cpu().long()
@@ -105,8 +105,8 @@ def main():
         f"{a.collects * N * T} = {rows / (a.collects * N * T):.4f}; {eps} episodes (mean length {rows / max(eps, 1):.1f} steps, longest "
         f"{longest}), {seqs} sequences; carried after the last: mean {ep.carried.float().mean().item():.1f} max {int(ep.carried.max())}")
     mb = statistics.mean(nbytes) / 1e6
-    say(f"hh_k_cep_emit moves {mb:.1f} MB per collect (row gather, sequence-start states, carry rewrite): at 6.3 TB/s that is "
-        f"{mb / 6.3e3 * 1e3:.1f} us; at the measured emission above {mb / max(ce - tr, 1e-9):.0f} GB/s over the whole emission")
+    say(f"hh_k_ep_emit (the commander's instance) moves {mb:.1f} MB per collect (row gather, sequence-start states, carry rewrite): at "
+        f"6.3 TB/s that is {mb / 6.3e3 * 1e3:.1f} us; at the measured emission above {mb / max(ce - tr, 1e-9):.0f} GB/s over the whole emission")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
