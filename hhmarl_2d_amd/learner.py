@@ -1,0 +1,432 @@
+"""The learner half of train_hetero.py's PPO on the device (train_hetero.py:206-243 with RLlib 2.4's PPO): the fused loss kernel
+`hh_ppo_loss` (include/hh_learner.h) behind a torch.autograd.Function, the four trainable networks as torch modules in TRAINING form, and
+`PPOLearner`, which turns the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")` into one PPO update of ac1_policy and
+ac2_policy and hands the new weights back to the sampler's `PolicyBank` — collect -> update -> publish -> collect on one GPU, the
+batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss and its gradient are one HIP pass.
+
+The reference's learner does not compute what its sampler computes, and this module keeps the difference:
+  * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
+    out_proj(v_proj(x)), what hh_policy_sample folds).  The learner sees each agent trajectory cut into chunks of max_seq_len = 20 rows,
+    the last one zero-padded (rnn_sequencing.pad_batch_to_sequences_of_same_size), and `add_time_dimension` makes att_act / att_val
+    attend over the 20 steps of a chunk, padded rows included as keys (no key padding mask).  ModelV2.__call__ hands the dummy state_in
+    back as the state, so PPOTorchPolicy.loss takes its RNN branch: the loss is averaged over the unpadded rows only.
+    Esc1 / Esc2 are plain TorchModelV2s: no chunks, no mask.
+  * The critic is trained on rows with the actions filled in (rollout.central_critic_rows), while the batch's `vf` was predicted with
+    zero action inputs.
+  * ac1_policy and ac2_policy hold the same 500 x 500 shared_layer tensor (models/ac_models_hetero.py:22) and each has its own optimizer.
+A learner for `commander.CommanderRollout` (train_hier.py) is out of scope here."""
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib as L
+from . import pilots
+from . import policy_nets as PN
+from .rollout import central_critic_rows
+
+OLD_LD = 32   # HH_POLICY_LOGITS: row width of the sampler's logits
+
+
+def n_comp_of(kind):
+    """action components of the kind's MultiDiscrete: 4 ([13, 9, 2, 2], 26 logits) for type-1 aircraft, 3 ([13, 9, 2], 24) for type-2"""
+    return 4 if PN.N_OUT[kind] == 26 else 3
+
+
+# ------------------------------------------------------------------------------------------------------------------ the loss
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class _PPOLoss(torch.autograd.Function):
+    """forward: hh_ppo_loss (loss, stats and the gradients in one pass); backward: the kept gradients times the incoming one"""
+
+    @staticmethod
+    def forward(ctx, logits, vf, old_logits, actions, old_logp, adv, target, mask, n_valid, prm):
+        R, ld = logits.shape
+        dev = logits.device
+        stats = torch.empty((len(L.PPO_STATS),), dtype=torch.float64, device=dev)
+        d_logits, d_vf = torch.empty_like(logits), torch.empty_like(vf)
+        nbytes = C.c_int64()
+        lib = L.lib()
+        L.check(lib.hh_ppo_loss_scratch_bytes(R, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(lib.hh_ppo_loss(R, ld, _p(logits), _p(old_logits), _p(actions), _p(old_logp), _p(adv), _p(vf), _p(target), _p(mask), _p(n_valid),
+                                C.byref(prm), _p(stats), _p(d_logits), _p(d_vf), _p(scratch), nbytes.value, st))
+        ctx.save_for_backward(d_logits, d_vf)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].float(), stats
+
+    @staticmethod
+    def backward(ctx, g_total, g_stats):
+        d_logits, d_vf = ctx.saved_tensors
+        return (d_logits * g_total, d_vf * g_total) + (None,) * 8
+
+
+def _flat_batch(logits, vf, batch):
+    """the learner's outputs and the batch columns as contiguous [R, ...] rows; n_valid made on the device where the batch has none"""
+    ld = logits.shape[-1]
+    logits = logits.reshape(-1, ld)
+    R = logits.shape[0]
+    col = lambda k, dt, w=None: batch[k].reshape((R,) if w is None else (R, w)).to(dt).contiguous()
+    mask = batch.get("mask")
+    mask = None if mask is None else col("mask", torch.uint8)
+    n_valid = batch.get("n_valid")
+    if n_valid is None:
+        n_valid = (torch.full((1,), R, dtype=torch.int32, device=logits.device) if mask is None
+                   else mask.ne(0).sum(dtype=torch.int32).reshape(1))
+    return (logits, vf.reshape(R), col("old_logits", torch.float32, OLD_LD), col("actions", torch.int8, 4), col("old_logp", torch.float32),
+            col("adv", torch.float32), col("target", torch.float32), mask, n_valid.reshape(1))
+
+
+def ppo_loss(logits, vf, batch, *, n_comp, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2):
+    """RLlib 2.4's PPOTorchPolicy.loss for a TorchMultiCategorical, fused (hh_ppo_loss: include/hh_learner.h has the formulas).
+    logits f32 [..., ld] (ld >= 26 | 24, at most 32) and vf f32 [...]: the learner's outputs, CUDA, with autograd history.
+    batch: dict of CUDA tensors over the same leading shape — old_logits f32 [..., 32] (the sampler's logits rows), actions i8 [..., 4],
+    old_logp / adv / target f32 [...]; optional mask (u8 | bool [...], rows that count; absent = all) and n_valid (i32 [1] on the
+    device: the number of rows that count, computed here when absent).
+    -> (total loss: float32 0-d tensor on the device, differentiable with respect to logits and vf;
+        stats f64 [6] on the device: total_loss, mean_policy_loss, mean_vf_loss, mean_kl, mean_entropy, n_valid  (_lib.PPO_STATS))
+    No host synchronisation.  A missing library or GPU is an error, there is no fallback."""
+    if not (logits.is_cuda and logits.dtype == torch.float32 and vf.dtype == torch.float32):
+        raise ValueError("ppo_loss: logits and vf are float32 CUDA tensors (the torch-op form for other dtypes is ppo_loss_torch)")
+    flat = _flat_batch(logits.contiguous(), vf.contiguous(), batch)
+    prm = L.HHPpoLossParams(n_comp=int(n_comp), reserved0=0, clip_param=clip_param, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff,
+                            entropy_coeff=entropy_coeff, kl_coeff=kl_coeff, reserved1=0.0)
+    return _PPOLoss.apply(*flat, prm)
+
+
+def ppo_loss_torch(logits, vf, batch, *, n_comp, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2):
+    """the same loss with torch ops in the dtype of `logits` (PPOLearner(fused=False): the A/B and timing partner of ppo_loss; same
+    arguments, same results up to rounding)"""
+    logits, vf, old_logits, actions, old_logp, adv, target, mask, n_valid = _flat_batch(logits, vf, batch)
+    dt = logits.dtype
+    splits = PN.ACTION_SPLIT[:n_comp]
+    n_out = sum(splits)
+    logp, ent, kl = 0.0, 0.0, 0.0
+    a = actions.long()
+    for c, (new, old) in enumerate(zip(logits[:, :n_out].split(splits, dim=1), old_logits[:, :n_out].to(dt).split(splits, dim=1))):
+        lp, lq = F.log_softmax(new, dim=1), F.log_softmax(old, dim=1)
+        logp = logp + lp.gather(1, a[:, c:c + 1]).squeeze(1)
+        ent = ent - (lp.exp() * lp).sum(dim=1)
+        kl = kl + (lq.exp() * (lq - lp)).sum(dim=1)
+    ratio = torch.exp(logp - old_logp.to(dt))
+    A = adv.to(dt)
+    surrogate = torch.min(A * ratio, A * torch.clamp(ratio, 1 - clip_param, 1 + clip_param))
+    vf_loss = torch.clamp(torch.pow(vf - target.to(dt), 2.0), 0, vf_clip_param)
+    w = torch.ones_like(ratio) if mask is None else mask.ne(0).to(dt)
+    n = n_valid.to(dt)[0]
+    mean = lambda t: (t * w).sum() / n
+    total = mean(-surrogate + vf_loss_coeff * vf_loss - entropy_coeff * ent)
+    mean_kl = mean(kl) if kl_coeff > 0.0 else torch.zeros((), dtype=dt, device=logits.device)
+    if kl_coeff > 0.0:
+        total = total + kl_coeff * mean_kl
+    stats = torch.stack([total, mean(-surrogate), mean(vf_loss), mean_kl, mean(ent), n]).detach().double()
+    return total, stats
+
+
+# ------------------------------------------------------------------------------------------------------------------ the networks
+class _FC(nn.Module):
+    """a linear layer under the reference's parameter names (RLlib's SlimFC keeps its nn.Linear in `_model.0`)"""
+
+    def __init__(self, n_in, n_out):
+        super().__init__()
+        self._model = nn.Sequential(nn.Linear(n_in, n_out))
+
+    def forward(self, x):
+        return self._model(x)
+
+
+class TrainableNet(nn.Module):
+    """One of the four trainable architectures (policy_nets: Fight1 / Fight2 / Esc1 / Esc2) in training form, written from the architecture
+    tables of policy_nets.py; parameters named and shaped exactly as actor_keys(kind) + critic_keys(kind), so `state_dict()` goes
+    straight into `PolicyBank.refresh`.
+
+    forward(obs_own, critic_row) -> (logits, value):
+      fight kinds:  obs_own [S, L, >= OBS_DIM] and critic_row [S, L, 57] are chunks of L consecutive steps of one agent; att_act / att_val
+                    attend over the L steps of a chunk with no padding mask (a zero-padded row is a key like any other), then
+                    normalize(x + att) per row.  2-D inputs [R, ...] are R chunks of length 1 — the sampler's forward.
+                    -> logits [S, L, 26 | 24], value [S, L]
+      escape kinds: rows [..., >= OBS_DIM], [..., 66] -> logits [..., 26 | 24], value [...]
+    critic_row is rollout.central_critic_rows' layout: [own act | friend's act | own obs | friend's obs]."""
+
+    def __init__(self, kind):
+        super().__init__()
+        self.kind = int(kind)
+        for i, (c0, c1, w) in enumerate(PN.INPUTS[kind]):
+            setattr(self, f"inp{i + 1}", _FC(c1 - c0, w))
+        self.shared_layer = _FC(500, 500)
+        self.act_out = _FC(500, PN.N_OUT[kind])
+        d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
+        if PN.HAS_ATT[kind]:
+            self.att_act = nn.MultiheadAttention(100, 2, batch_first=True)
+            self.v1, self.v2, self.v3 = _FC(d1 + a1, 175), _FC(d2 + a2, 175), _FC(d1 + a1 + d2 + a2, 150)
+            self.att_val = nn.MultiheadAttention(150, 2, batch_first=True)
+        else:
+            self.inp1_val = _FC(d1 + a1 + d2 + a2, 500)
+        self.val_out = _FC(500, 1)
+
+    def forward(self, obs_own, critic_row):
+        kind = self.kind
+        d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
+        flat = PN.HAS_ATT[kind] and obs_own.dim() == 2
+        if flat:
+            obs_own, critic_row = obs_own[:, None], critic_row[:, None]
+        x = obs_own[..., :PN.OBS_DIM[kind]]
+        h = [torch.tanh(getattr(self, f"inp{i + 1}")(x[..., c0:c1])) for i, (c0, c1, _) in enumerate(PN.INPUTS[kind])]
+        act_own, act_2 = critic_row[..., :a1], critic_row[..., a1:a1 + a2]
+        o_own, o_2 = critic_row[..., a1 + a2:a1 + a2 + d1], critic_row[..., a1 + a2 + d1:]
+        v1, v2 = torch.cat((o_own, act_own), dim=-1), torch.cat((o_2, act_2), dim=-1)
+        v3 = torch.cat((v1, v2), dim=-1)
+        if PN.HAS_ATT[kind]:
+            att, _ = self.att_act(h[2], h[2], h[2], need_weights=False)
+            h[2] = F.normalize(h[2] + att, dim=-1)
+            y = torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1)
+            yf = torch.tanh(self.v3(v3))
+            att, _ = self.att_val(yf, yf, yf, need_weights=False)
+            y = torch.cat((y, F.normalize(yf + att, dim=-1)), dim=-1)
+        else:
+            y = torch.tanh(self.inp1_val(v3))
+        logits = self.act_out(torch.tanh(self.shared_layer(torch.cat(h, dim=-1))))
+        value = self.val_out(torch.tanh(self.shared_layer(y))).squeeze(-1)
+        if flat:
+            logits, value = logits[:, 0], value[:, 0]
+        return logits, value
+
+    def load_numpy(self, sd):
+        """the weights of a dict of numpy arrays keyed like state_dict() (policy_nets.random_weights + random_critic_weights)"""
+        own = self.state_dict()
+        with torch.no_grad():
+            for k, v in sd.items():
+                own[k].copy_(torch.as_tensor(np.asarray(v)))
+        return self
+
+
+def tie(modules):
+    """make every module hold the FIRST one's shared_layer: ONE parameter object for all (models/ac_models_hetero.py:22: one
+    module-level SHARED_LAYER serves Fight1, Fight2, Esc1 and Esc2)"""
+    for m in modules[1:]:
+        m.shared_layer = modules[0].shared_layer
+    return modules
+
+
+# ------------------------------------------------------------------------------------------------------------------ batch geometry
+def cut_chunks(ep_start, ep_len, max_seq_len):
+    """chop_into_sequences (rllib/policy/rnn_sequencing.py) on an episode table: every episode's rows cut into chunks of max_seq_len
+    (L, ..., L, remainder).  ep_start / ep_len integer tensors [E] (any device) -> (seq_start, seq_len) int64 [S], episodes in order"""
+    Lm = int(max_seq_len)
+    ep_start, ep_len = ep_start.long(), ep_len.long()
+    n_ch = (ep_len + (Lm - 1)) // Lm
+    seq_ep = torch.repeat_interleave(torch.arange(ep_len.numel(), device=ep_len.device), n_ch)
+    first = torch.cumsum(n_ch, dim=0) - n_ch
+    j = torch.arange(seq_ep.numel(), device=ep_len.device) - first[seq_ep]
+    return ep_start[seq_ep] + j * Lm, torch.clamp(ep_len[seq_ep] - j * Lm, max=Lm)
+
+
+def pad_chunks(col, seq_start, seq_len, max_seq_len):
+    """pad_batch_to_sequences_of_same_size on one column [R, ...]: -> [S, L, ...], zero beyond each chunk's seq_len"""
+    Lm = int(max_seq_len)
+    t = torch.arange(Lm, device=col.device)
+    mask = t[None, :] < seq_len[:, None]
+    idx = torch.where(mask, seq_start[:, None] + t[None, :], torch.zeros_like(seq_start[:, None]))
+    out = col[idx.reshape(-1)].reshape((idx.shape[0], Lm) + tuple(col.shape[1:]))
+    return out * mask.reshape(mask.shape + (1,) * (col.dim() - 1)).to(col.dtype)
+
+
+def chunk_mask(seq_len, max_seq_len):
+    """sequence_mask: bool [S, L], the unpadded rows"""
+    return torch.arange(int(max_seq_len), device=seq_len.device)[None, :] < seq_len[:, None]
+
+
+def minibatch_partition(seq_len, sgd_minibatch_size):
+    """the chunks (escape: rows, seq_len all 1) in order, split into consecutive minibatches of at least sgd_minibatch_size unpadded rows
+    (the last one holds what is left).  seq_len: host integers [S] -> list of (first chunk, last chunk + 1)"""
+    csum = np.cumsum(np.asarray(seq_len, dtype=np.int64))
+    out, s0, base = [], 0, 0
+    S = len(csum)
+    while s0 < S:
+        s1 = int(np.searchsorted(csum, base + int(sgd_minibatch_size), side="left")) + 1
+        s1 = min(s1, S)
+        out.append((s0, s1))
+        base, s0 = int(csum[s1 - 1]), s1
+    return out
+
+
+def minibatch_order(n, seed, update, policy, sgd_pass):
+    """the order in which one pass visits its n minibatches: keyed by (seed, update count, policy, pass), so two learners with the same
+    seed visit the same order.  (RLlib shuffles with the unseeded global numpy generator: its order is not reproducible at all.)"""
+    return np.random.default_rng([int(seed), int(update), int(policy), int(sgd_pass)]).permutation(int(n))
+
+
+def kl_coeff_update(kl_coeff, sampled_kl, kl_target):
+    """KLCoeffMixin.update_kl (ray/rllib/policy/torch_mixins.py): above 2 x target the coefficient grows by 1.5, below 0.5 x target it halves"""
+    if sampled_kl > 2.0 * kl_target:
+        return kl_coeff * 1.5
+    if sampled_kl < 0.5 * kl_target:
+        return kl_coeff * 0.5
+    return kl_coeff
+
+
+def standardize(adv):
+    """standardized (ray/rllib/utils/sgd.py) over a policy's whole batch: (x - mean) / max(1e-4, std), population std"""
+    return (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the learner
+class PPOLearner:
+    """One PPO update of train_hetero.py's two policies from the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")`:
+
+        learner = PPOLearner.trainable_init(device, mode="fight", seed=0)     # the weights of PolicyBank.trainable_init(seed)
+        stats = learner.update(ro.episodes, bank)
+        learner.publish(bank)
+
+    Defaults: train_hetero.py:216 (lr, clip_param, kl_target), config.py:36-37 (sgd_minibatch_size) and RLlib 2.4's PPO defaults for the
+    rest.  Per policy (agent 1, then agent 2; each with its own Adam over its module's parameters, the tied shared layer in both):
+      * rows: the agent's column of every emitted row — nothing is masked by `valid` (semantics = "rllib"); own observation cut to the
+        kind's width, critic rows from central_critic_rows (actions filled in);
+      * old_logits: recomputed once per update from `bank`, which still holds the pre-update weights — the sampler's sequence-length-1
+        forward, which is what RLlib's ACTION_DIST_INPUTS column holds.  Every bank call has the rollout's own shape ([N, 2] rows, the
+        same selectors), so the row lists a captured collect re-uses stay what they were.  Rows that a collect carried over from before
+        the last publish (the head of an episode that was still running) were sampled by older weights: their stored logp, and so the
+        ratio, is exact, but their recomputed old_logits are the newer weights', so the KL term sees them as on-policy.  RLlib never
+        mixes weight versions inside an episode; `rollout.start()` after `publish` gives the same (fresh episodes, nothing carried);
+      * advantages standardised over the policy's whole batch;
+      * fight kinds: each episode cut into chunks of max_seq_len, zero-padded, mask = the unpadded rows;
+      * num_sgd_iter passes; in each the chunks (escape: rows), in batch order, are split into consecutive minibatches of at least
+        sgd_minibatch_size unpadded rows, visited in the order of minibatch_order(seed, update count, policy, pass).  RLlib's own
+        order is drawn from an unseeded generator and shuffles the chunks themselves; this one is reproducible by construction;
+      * after the passes KLCoeffMixin.update_kl on the mean of the minibatches' mean_kl.
+    fused = False computes the loss with torch ops (ppo_loss_torch) instead of hh_ppo_loss; nothing else differs.
+    Inside a minibatch step nothing synchronises with the host (beyond what torch.optim.Adam does by itself); `update` itself synchronises
+    when it reads the batch's row count, cuts the minibatches and reads the statistics.  CommanderRollout's batches are out of scope."""
+
+    def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True):
+        """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
+        torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
+        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.kinds = tuple(int(k) for k in kinds)
+        assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
+        self.modules = tie([TrainableNet(k).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+                            for k, sd in zip(self.kinds, state_dicts)])
+        for m in self.modules:
+            m.to(self.device)
+        tie(self.modules)
+        self.optimizers = [torch.optim.Adam(m.parameters(), lr=lr) for m in self.modules]
+        self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
+        self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
+        self.use_kl = kl_coeff > 0.0            # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
+        self.kl_coeff = [float(kl_coeff), float(kl_coeff)]
+        self.num_sgd_iter, self.sgd_minibatch_size, self.max_seq_len = int(num_sgd_iter), int(sgd_minibatch_size), int(max_seq_len)
+        self.seed, self.fused, self.updates = int(seed), bool(fused), 0
+        self.recurrent = PN.HAS_ATT[self.kinds[0]]
+        esc = not self.recurrent
+        self._sel = (pilots.SEL_ESC1 if esc else pilots.SEL_FIGHT1, pilots.SEL_ESC2 if esc else pilots.SEL_FIGHT2)
+        self._tmp = None
+
+    @classmethod
+    def trainable_init(cls, device, mode="fight", seed=0, **kw):
+        """the learner whose weights equal PolicyBank.trainable_init(device, mode, seed)'s (tied shared layer)"""
+        kinds = (PN.FIGHT1, PN.FIGHT2) if mode == "fight" else (PN.ESC1, PN.ESC2)
+        sds = [dict(PN.random_weights(k, seed), **PN.random_critic_weights(k, seed)) for k in kinds]
+        return cls(kinds, sds, device, seed=seed, **kw)
+
+    # ---- the batch
+    def old_logits(self, obs, bank, n_arenas):
+        """the sampler's logits of every row of obs f32 [R, 2, D] from `bank` -> f32 [R, 2, 32]; calls of [n_arenas, 2] rows each"""
+        R, _, D = obs.shape
+        N = int(n_arenas)
+        assert 2 * N <= bank.max_rows, "the bank serves the rollout's [N, 2] rows"
+        n_calls = (R + N - 1) // N
+        out = torch.zeros((max(n_calls, 1) * N, 2, OLD_LD), dtype=torch.float32, device=obs.device)
+        if self._tmp is None or self._tmp[0].shape[0] != N or self._tmp[0].shape[2] != D:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=obs.device)
+            self._tmp = (z((N, 2, D), torch.float32), z((N, 2, 4), torch.int8), z((N, 2), torch.float32),
+                         torch.tensor(self._sel, dtype=torch.uint8, device=obs.device).repeat(N, 1).contiguous())
+        stage, act, logp, sel = self._tmp
+        for i in range(n_calls):
+            src = obs[i * N:(i + 1) * N]
+            if src.shape[0] < N:
+                stage.zero_()
+                stage[:src.shape[0]].copy_(src)
+                src = stage
+            bank.sample(src, sel, greedy=True, actions=act, logp=logp, logits=out[i * N:(i + 1) * N], want_vf=False)
+        return out[:R]
+
+    def policy_batch(self, rows, old_logits, agent):
+        """the training batch of policy `agent` (0 | 1) from the emitted rows: dict of [S, L, ...] chunks (fight) or [R, ...] rows (escape)
+        and, for chunks, seq_len [S] and mask [S, L]"""
+        kind = self.kinds[agent]
+        b = {"obs": rows["obs"][:, agent, :PN.OBS_DIM[kind]].contiguous(),
+             "critic": central_critic_rows(rows["obs"], rows["actions"], agent + 1),
+             "actions": rows["actions"][:, agent].contiguous(), "old_logp": rows["logp"][:, agent].contiguous(),
+             "adv": standardize(rows["adv"][:, agent]), "target": rows["target"][:, agent].contiguous(),
+             "old_logits": old_logits[:, agent].contiguous()}
+        if not self.recurrent:
+            return b
+        seq_start, seq_len = cut_chunks(rows["ep_start"], rows["ep_len"], self.max_seq_len)
+        b = {k: pad_chunks(v, seq_start, seq_len, self.max_seq_len) for k, v in b.items()}
+        b["seq_len"] = seq_len
+        b["mask"] = chunk_mask(seq_len, self.max_seq_len).to(torch.uint8)
+        return b
+
+    # ---- one minibatch step
+    def loss(self, agent, logits, vf, mb):
+        kw = dict(n_comp=n_comp_of(self.kinds[agent]), clip_param=self.clip_param, vf_clip_param=self.vf_clip_param,
+                  vf_loss_coeff=self.vf_loss_coeff, entropy_coeff=self.entropy_coeff, kl_coeff=self.kl_coeff[agent] if self.use_kl else 0.0)
+        return (ppo_loss if self.fused else ppo_loss_torch)(logits, vf, mb, **kw)
+
+    def minibatch_step(self, agent, mb):
+        """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with n_valid) -> stats f64 [6] (device)"""
+        opt = self.optimizers[agent]
+        logits, vf = self.modules[agent](mb["obs"], mb["critic"])
+        total, stats = self.loss(agent, logits, vf, mb)
+        opt.zero_grad(set_to_none=True)
+        total.backward()
+        opt.step()
+        return stats
+
+    # ---- one update
+    def update(self, episodes, bank):
+        """one PPO update of both policies from episodes (an EpisodeBatch after a collect) -> per policy a dict: total_loss, policy_loss,
+        vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows"""
+        rows = episodes.rows()
+        out = []
+        if rows["obs"].shape[0] == 0:
+            return [dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
+                         kl_coeff=self.kl_coeff[a], steps=0, rows=0) for a in range(2)]
+        with torch.no_grad():
+            old = self.old_logits(rows["obs"], bank, episodes.N)
+            batches = [self.policy_batch(rows, old, a) for a in range(2)]
+        for agent, b in enumerate(batches):
+            if self.recurrent:
+                seq_len = b["seq_len"].cpu().numpy()
+            else:
+                seq_len = np.ones(b["obs"].shape[0], dtype=np.int64)
+            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+            csum = np.concatenate([[0], np.cumsum(seq_len)])
+            n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
+            cols = [k for k in b if k != "seq_len"]
+            all_stats = []
+            for sgd_pass in range(self.num_sgd_iter):
+                for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
+                    s0, s1 = parts[i]
+                    mb = {k: b[k][s0:s1] for k in cols}
+                    mb["n_valid"] = n_valid[i:i + 1]
+                    all_stats.append(self.minibatch_step(agent, mb))
+            m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
+            if self.use_kl and all_stats:
+                self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
+            out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
+                            steps=len(all_stats), rows=int(seq_len.sum())))
+        self.updates += 1
+        return out
+
+    def publish(self, bank):
+        """the new weights into the sampler's bank on the current stream (PolicyBank.refresh_trainable): captured collects replay with them"""
+        bank.refresh_trainable(self.modules)

@@ -1,0 +1,65 @@
+/*
+ * hh_learner.h — C ABI of the learner side of train_hetero.py's PPO (part of libhh_world.so): the fused PPO loss, forward and
+ * backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies.
+ *
+ * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
+ * predictions, per row that the mask keeps (n = number of such rows):
+ *     logp      = sum_c log_softmax(logits_c)[a_c]                          TorchMultiCategorical.logp
+ *     ratio     = exp(logp - old_logp)                                      logp_ratio
+ *     surrogate = min(adv * ratio, adv * clamp(ratio, 1 - clip, 1 + clip))  surrogate_loss
+ *     kl        = sum_c KL(old_c || new_c)                                  prev_action_dist.kl(curr_action_dist)
+ *     entropy   = sum_c H(new_c)                                            curr_action_dist.entropy()
+ *     vf_loss   = clamp((vf - target)^2, 0, vf_clip_param)                  vf_loss_clipped
+ *     total     = sum(-surrogate + vf_loss_coeff * vf_loss - entropy_coeff * entropy) / n  [+ kl_coeff * sum(kl) / n  when kl_coeff > 0]
+ * with c over the components of MultiDiscrete([13, 9, 2, 2]) (n_comp = 4, 26 logits) or ([13, 9, 2]) (n_comp = 3, 24 logits).  With
+ * kl_coeff <= 0 the KL term is left out and mean_kl is reported as 0.0, as ray does.
+ *
+ * Conventions as in hh_abi.h: 0 on success or a negative HH_E_* code, never throws; [dev] = caller-owned device memory; `stream` is a
+ * hipStream_t passed as void*.
+ */
+#ifndef HH_LEARNER_H
+#define HH_LEARNER_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define HH_PPO_STATS 6 /* stats f64: total_loss, mean_policy_loss, mean_vf_loss, mean_kl, mean_entropy, n_valid */
+
+typedef struct hh_ppo_loss_params {
+    int32_t n_comp; /* 4: splits [13, 9, 2, 2], 26 logits; 3: splits [13, 9, 2], 24 logits */
+    int32_t reserved0; /* must be 0 */
+    float clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff;
+    float reserved1; /* must be 0 */
+} hh_ppo_loss_params;
+
+/* bytes of `scratch` a call of n_rows rows needs (the per-workgroup float64 partial sums) */
+int hh_ppo_loss_scratch_bytes(int64_t n_rows, int64_t *bytes);
+
+/* Loss and gradients in one pass over the rows (two launches: the row pass, which also writes every gradient, and the final sum of the
+ * per-workgroup partials), ordered on `stream`; no host synchronisation, no allocation, HIP-graph capturable.
+ *   logits      [dev] f32 [n_rows, ld]   the learner's logits, ld >= 26 | 24 (the columns from there on are ignored)
+ *   old_logits  [dev] f32 [n_rows, 32]   the sampler's logits (HH_POLICY_LOGITS rows: hh_policy_act / hh_policy_sample)
+ *   actions     [dev] i8  [n_rows, 4]    the sampled action (components outside their range are clamped into it)
+ *   old_logp, adv, vf, target [dev] f32 [n_rows]    ACTION_LOGP, standardised advantages, the learner's value predictions, VALUE_TARGETS
+ *   mask        [dev] u8  [n_rows]       rows with mask != 0 count (the unpadded rows of RLlib's sequence chunks); NULL = all rows
+ *   n_valid     [dev] i32 [1]            the number of rows with mask != 0 (n_rows with mask == NULL): the divisor, known before the pass, which
+ *                                        is what makes every row's gradient local
+ *   stats       [dev] f64 [HH_PPO_STATS]
+ *   d_logits    [dev] f32 [n_rows, ld]   d total / d logits; exactly 0.0f in masked rows and in the columns beyond the policy's logits
+ *   d_vf        [dev] f32 [n_rows]       d total / d vf; exactly 0.0f in masked rows
+ *   scratch     [dev] scratch_bytes >= hh_ppo_loss_scratch_bytes(n_rows)
+ * logits, old_logits, d_logits and actions must be 16-byte / 4-byte aligned at row 0 (whole tensors are).  Per-row arithmetic is float32;
+ * the five sums are float64 in a fixed order (no floating-point atomics): the same inputs give the same bytes on every run.
+ * The gradient of min / clamp at their kinks follows PyTorch's autograd (clamp passes the gradient on its closed interval; where
+ * the two arguments of min are equal their gradients add up). */
+int hh_ppo_loss(int64_t n_rows, int32_t ld, const float *logits, const float *old_logits, const int8_t *actions, const float *old_logp,
+                const float *adv, const float *vf, const float *target, const uint8_t *mask, const int32_t *n_valid,
+                const hh_ppo_loss_params *prm, double *stats, float *d_logits, float *d_vf, void *scratch, int64_t scratch_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HH_LEARNER_H */

@@ -1,0 +1,216 @@
+"""hh_ppo_loss on the MI355X (include/hh_learner.h) against the float64 restatement of RLlib 2.4's PPO loss (tests/ppo_loss_ref.py):
+statistics and every gradient element, masked rows and padding columns exactly zero, the same bytes on every run and from a replayed
+graph, and through autograd into a TrainableNet's parameters (fused against the torch-op loss, both against float64).
+
+The error bound is relative to the format, not to the kernel: e32 = the largest error of the float32 torch restatement against the
+float64 one on the same inputs, per compared quantity (the five statistics together; d_logits; d_vf), and the kernel may be at most
+4 x e32 away from float64 (other exp / log implementations and another summation order; its float64 reductions should make it smaller).
+Rows within 1e-4 of a clip boundary of the ratio or within 1e-3 of vf_clip_param in the squared value error are left out of the gradient
+comparison (min and clamp make it discontinuous there): at most 1 % of a case's rows, which tests/test_learner_host.py checks on the
+generator without a GPU."""
+import ctypes as C
+
+import pytest
+import torch
+
+import ppo_loss_ref as REF
+
+pytestmark = pytest.mark.gpu
+CLIP, VCLIP = 0.25, 10.0
+CASES = [(R, n_comp, masked, klc, ec) for R in (1, 63, 4096, 100003) for n_comp in (4, 3) for masked in (False, True)
+         for klc in (0.0, 0.2) for ec in (0.0, 0.01)]
+
+
+def _ld(R, n_comp):
+    return {4: 26, 3: 24}[n_comp] if R % 2 else 32
+
+
+def _kw(n_comp, klc, ec):
+    return dict(n_comp=n_comp, clip_param=CLIP, vf_clip_param=VCLIP, vf_loss_coeff=1.0, entropy_coeff=ec, kl_coeff=klc)
+
+
+class Raw:
+    """hh_ppo_loss called directly on preallocated device buffers (what a graph capture needs)"""
+
+    def __init__(self, inp, kw):
+        from hhmarl_2d_amd import _lib as L
+        dev = torch.device("cuda", 0)
+        self.L = L
+        self.t = {k: (None if v is None else v.to(dev).contiguous()) for k, v in inp.items()}
+        if self.t["mask"] is not None:
+            self.t["mask"] = self.t["mask"].to(torch.uint8)
+        R, self.ld = inp["logits"].shape
+        self.R = R
+        n = R if inp["mask"] is None else int(inp["mask"].sum())
+        self.n_valid = torch.tensor([n], dtype=torch.int32, device=dev)
+        self.prm = L.HHPpoLossParams(n_comp=kw["n_comp"], reserved0=0, clip_param=kw["clip_param"], vf_clip_param=kw["vf_clip_param"],
+                                     vf_loss_coeff=kw["vf_loss_coeff"], entropy_coeff=kw["entropy_coeff"], kl_coeff=kw["kl_coeff"], reserved1=0.0)
+        nb = C.c_int64()
+        L.check(L.lib().hh_ppo_loss_scratch_bytes(R, C.byref(nb)))
+        self.nb = nb.value
+        # outputs start as junk: whatever the kernel must write is written
+        self.stats = torch.full((6,), float("nan"), dtype=torch.float64, device=dev)
+        self.d_logits = torch.full((R, self.ld), float("nan"), dtype=torch.float32, device=dev)
+        self.d_vf = torch.full((R,), float("nan"), dtype=torch.float32, device=dev)
+        self.scratch = torch.full((self.nb // 8,), float("nan"), dtype=torch.float64, device=dev)
+
+    def run(self):
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        t = self.t
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.L.check(self.L.lib().hh_ppo_loss(self.R, self.ld, p(t["logits"]), p(t["old_logits"]), p(t["actions"]), p(t["old_logp"]), p(t["adv"]),
+                                              p(t["vf"]), p(t["target"]), p(t["mask"]), p(self.n_valid), C.byref(self.prm), p(self.stats),
+                                              p(self.d_logits), p(self.d_vf), p(self.scratch), self.nb, st))
+
+    def outputs(self):
+        torch.cuda.synchronize()
+        return self.stats.cpu().clone(), self.d_logits.cpu().clone(), self.d_vf.cpu().clone()
+
+
+def _errors(stats, dl, dv, want, keep):
+    """largest absolute differences against the float64 reference: (statistics, d_logits, d_vf), gradients over the kept rows"""
+    ws, wdl, wdv, _ = want
+    e_s = max(abs(float(a) - b) for a, b in zip(stats[:5], ws[:5]))
+    e_l = (dl.double()[keep] - wdl[keep]).abs().max().item() if keep.any() else 0.0
+    e_v = (dv.double()[keep] - wdv[keep]).abs().max().item() if keep.any() else 0.0
+    return e_s, e_l, e_v
+
+
+@pytest.mark.parametrize("R,n_comp,masked,klc,ec", CASES)
+def test_kernel_against_float64_restatement(R, n_comp, masked, klc, ec):
+    kw = _kw(n_comp, klc, ec)
+    ld = _ld(R, n_comp)
+    n_out = sum(REF.SPLITS[n_comp])
+    inp = REF.make_inputs(R, n_comp, ld, masked, 0)
+    want = REF.reference(inp, torch.float64, **kw)
+    s32, dl32, dv32, _ = REF.reference(inp, torch.float32, **kw)
+    keep = ~REF.near_kink(want[3], CLIP, VCLIP)
+    assert (~keep).sum().item() <= 0.01 * R
+    raw = Raw(inp, kw)
+    raw.run()
+    stats, dl, dv = raw.outputs()
+    assert torch.isfinite(stats).all() and torch.isfinite(dl).all() and torch.isfinite(dv).all()
+    assert stats[5].item() == want[0][5]
+    # exactly zero: masked rows, and the columns beyond the policy's logits (the restatement's autograd gives them 0.0 as well)
+    assert torch.equal(dl[:, n_out:], torch.zeros((R, ld - n_out)))
+    if masked:
+        off = ~inp["mask"]
+        assert torch.equal(dl[off], torch.zeros((int(off.sum()), ld))) and torch.equal(dv[off], torch.zeros(int(off.sum())))
+    if klc == 0.0:
+        assert stats[3].item() == 0.0
+    e32 = _errors(torch.tensor(s32), dl32, dv32, want, keep)
+    err = _errors(stats, dl, dv, want, keep)
+    print(f"R={R} n_comp={n_comp} masked={masked} kl_coeff={klc} entropy_coeff={ec}: e32 (stats, d_logits, d_vf) = "
+          f"{e32[0]:.3e} {e32[1]:.3e} {e32[2]:.3e}; kernel = {err[0]:.3e} {err[1]:.3e} {err[2]:.3e}")
+    for name, e, b in zip(("stats", "d_logits", "d_vf"), err, e32):
+        assert e <= 4.0 * b, f"{name}: kernel error {e:.3e} above 4 x e32 = {4 * b:.3e}"
+
+
+@pytest.mark.parametrize("R,n_comp,masked", [(100003, 4, True), (4096, 3, False), (63, 4, True)])
+def test_same_bytes_every_run_and_from_a_graph(R, n_comp, masked):
+    kw = _kw(n_comp, 0.2, 0.01)
+    inp = REF.make_inputs(R, n_comp, _ld(R, n_comp), masked, 1)
+    raw = Raw(inp, kw)
+    raw.run()
+    first = raw.outputs()
+    bits = lambda xs: [x.view(torch.int64 if x.dtype == torch.float64 else torch.int32) for x in xs]
+    for x in (raw.stats, raw.d_logits, raw.d_vf, raw.scratch):
+        x.fill_(float("nan"))
+    raw.run()
+    second = raw.outputs()
+    assert all(torch.equal(a, b) for a, b in zip(bits(first), bits(second)))
+    # captured and replayed: the same bytes as eager
+    for x in (raw.stats, raw.d_logits, raw.d_vf, raw.scratch):
+        x.fill_(float("nan"))
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        raw.run()
+    for x in (raw.stats, raw.d_logits, raw.d_vf, raw.scratch):
+        x.fill_(float("nan"))
+    graph.replay()
+    replayed = raw.outputs()
+    assert all(torch.equal(a, b) for a, b in zip(bits(first), bits(replayed)))
+    graph.replay()
+    assert all(torch.equal(a, b) for a, b in zip(bits(first), bits(raw.outputs())))
+
+
+def test_bad_arguments_are_refused():
+    from hhmarl_2d_amd import _lib as L
+    inp = REF.make_inputs(63, 4, 26, False, 0)
+    raw = Raw(inp, _kw(4, 0.2, 0.0))
+    raw.ld = 25                                   # fewer columns than the policy has logits
+    with pytest.raises(RuntimeError):
+        raw.run()
+    raw.ld = 26
+    raw.nb = 8                                    # scratch too small
+    with pytest.raises(RuntimeError):
+        raw.run()
+    raw = Raw(inp, _kw(4, 0.2, 0.0))
+    raw.prm.n_comp = 5
+    with pytest.raises(RuntimeError):
+        raw.run()
+    assert L.lib().hh_last_error()
+
+
+@pytest.mark.parametrize("kind,masked", [(0, True), (1, True), (2, False), (3, False)])
+def test_autograd_into_the_network_fused_against_unfused(kind, masked):
+    """gradients of a TrainableNet's parameters through learner.ppo_loss (hh_ppo_loss) and through learner.ppo_loss_torch, both against a
+    float64 run of the same module and loss: the fused path's largest error is at most 4 x the unfused path's"""
+    from hhmarl_2d_amd import learner as LR
+    from hhmarl_2d_amd import policy_nets as PN
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(40 + kind)
+    d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
+    S, Lc = (96, 20) if PN.HAS_ATT[kind] else (1920, 1)
+    n_comp = LR.n_comp_of(kind)
+    own = torch.rand((S, Lc, d1), generator=g)
+    crit = torch.cat([torch.rand((S, Lc, a1 + a2), generator=g), own, torch.rand((S, Lc, d2), generator=g)], dim=-1)
+    seq_len = torch.randint(1, Lc + 1, (S,), generator=g)
+    mask = LR.chunk_mask(seq_len, Lc)
+    if masked:
+        own, crit = own * mask[..., None], crit * mask[..., None]
+    if not PN.HAS_ATT[kind]:
+        own, crit, mask = own[:, 0], crit[:, 0], mask[:, 0]
+    lead = tuple(own.shape[:-1])
+    R = S * Lc
+    w = dict(PN.random_weights(kind, 9), **PN.random_critic_weights(kind, 9))
+    net = LR.TrainableNet(kind).load_numpy(w).to(dev)
+    net64 = LR.TrainableNet(kind).load_numpy(w).double().to(dev)
+    with torch.no_grad():
+        old, _ = net(own.to(dev), crit.to(dev))
+    splits = PN.ACTION_SPLIT[:n_comp]
+    old = old + 0.3 * torch.randn(old.shape, generator=g).to(dev)      # the sampler's logits: near the learner's, not equal
+    actions = torch.zeros(lead + (4,), dtype=torch.int8)
+    for i, wd in enumerate(splits):
+        actions[..., i] = torch.randint(0, wd, lead, generator=g).to(torch.int8)
+    old32 = torch.zeros(lead + (32,), device=dev)
+    old32[..., :old.shape[-1]] = old
+    lo, old_logp = 0, torch.zeros(lead, device=dev)
+    for i, wd in enumerate(splits):
+        old_logp += torch.log_softmax(old[..., lo:lo + wd], dim=-1).gather(-1, actions[..., i:i + 1].long().to(dev)).squeeze(-1)
+        lo += wd
+    batch = {"old_logits": old32, "actions": actions.to(dev), "old_logp": old_logp, "adv": torch.randn(lead, generator=g).to(dev),
+             "target": torch.randn(lead, generator=g).to(dev) * 2.0}
+    if masked:
+        batch["mask"] = mask.to(dev)
+    kw = dict(n_comp=n_comp, clip_param=CLIP, vf_clip_param=VCLIP, vf_loss_coeff=1.0, entropy_coeff=0.01, kl_coeff=0.2)
+
+    def grads(module, loss_fn, dt):
+        module.zero_grad(set_to_none=True)
+        logits, vf = module(own.to(dev, dt), crit.to(dev, dt))
+        total, stats = loss_fn(logits, vf, batch, **kw)
+        total.backward()
+        return {k: p.grad.double().clone() for k, p in module.named_parameters()}, stats.clone()
+
+    g64, s64 = grads(net64, LR.ppo_loss_torch, torch.float64)
+    gun, sun = grads(net, LR.ppo_loss_torch, torch.float32)
+    gfu, sfu = grads(net, LR.ppo_loss, torch.float32)
+    assert set(gfu) == set(g64) and all(torch.isfinite(v).all() for v in gfu.values())
+    e_un = max((gun[k] - g64[k]).abs().max().item() for k in g64)
+    e_fu = max((gfu[k] - g64[k]).abs().max().item() for k in g64)
+    scale = max(g64[k].abs().max().item() for k in g64)
+    print(f"{PN.KIND_NAMES[kind]} R={R}: largest parameter gradient {scale:.3e}; error against float64: unfused {e_un:.3e}, fused {e_fu:.3e}; "
+          f"stats error unfused {(sun - s64).abs().max().item():.3e}, fused {(sfu - s64).abs().max().item():.3e}")
+    assert e_fu <= 4.0 * e_un
+    assert (sfu - s64).abs()[:5].max().item() <= 4.0 * (sun - s64).abs()[:5].max().item()

@@ -1,0 +1,166 @@
+"""Where the time of a PPO update goes on the MI355X (16384 arenas, T = 64, level-3 fight by default), and how exact the loss kernel is:
+  errors  hh_ppo_loss and the float32 torch restatement against the float64 one (tests/ppo_loss_ref.py), on the GPU test's inputs
+  loss    hh_ppo_loss alone against the torch-op loss alone (forward + backward to logits / vf) on the same tensors, device events;
+          the kernel's achieved GB/s against its algorithmic bytes (ld + 32 logits in, ld out, 25 B of row scalars in, 4 B out)
+  step    one minibatch step (forward, loss, backward, Adam) with fused = True and fused = False at 256 and at 65536 rows
+  update  one collect next to one whole update.  The update is timed with num_sgd_iter = 1 and sgd_minibatch_size = 65536 by default
+          (--passes / --minibatch): RLlib's 30 passes of 256-row minibatches over a million rows are a quarter of a million optimizer
+          steps, the per-step figure above times the number of steps
+The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
+    python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+import ppo_loss_ref as REF  # noqa: E402
+from hhmarl_2d_amd import learner as LR  # noqa: E402
+from hhmarl_2d_amd.pilots import PolicyBank  # noqa: E402
+from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
+from hhmarl_2d_amd.world import World, make_config  # noqa: E402
+
+KW = dict(clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arenas", type=int, default=16384)
+    ap.add_argument("--T", type=int, default=64)
+    ap.add_argument("--horizon", type=int, default=300)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=1)
+    ap.add_argument("--minibatch", type=int, default=65536)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    def events(fn, iters=a.iters):
+        for _ in range(a.warmup):
+            fn()
+        out = []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(iters):
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1))
+        return out
+
+    q = lambda v: f"median {statistics.median(v):.3f} ms (min {min(v):.3f}, max {max(v):.3f})"
+    say(f"# tools/ppo_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.arenas} arenas, T = {a.T}, level 3 fight; {a.iters} timed "
+        f"iterations after {a.warmup} warm-up, device events")
+
+    # ---- errors against float64 (the GPU test's generator and bound: kernel <= 4 x e32 per quantity)
+    say("errors against the float64 restatement, largest absolute difference (statistics | d_logits | d_vf), entropy_coeff 0.01, kl_coeff 0.2:")
+    for R, n_comp, masked in ((63, 4, True), (4096, 3, False), (100003, 4, True), (100003, 3, False)):
+        ld = {4: 26, 3: 24}[n_comp] if R % 2 else 32
+        kw = dict(KW, n_comp=n_comp, entropy_coeff=0.01)
+        inp = REF.make_inputs(R, n_comp, ld, masked, 0)
+        want = REF.reference(inp, torch.float64, **kw)
+        s32, dl32, dv32, _ = REF.reference(inp, torch.float32, **kw)
+        keep = ~REF.near_kink(want[3], kw["clip_param"], kw["vf_clip_param"])
+        logits, vf = inp["logits"].to(dev).requires_grad_(True), inp["vf"].to(dev).requires_grad_(True)
+        batch = {k: inp[k].to(dev) for k in ("old_logits", "actions", "old_logp", "adv", "target")}
+        if masked:
+            batch["mask"] = inp["mask"].to(dev)
+        total, stats = LR.ppo_loss(logits, vf, batch, **kw)
+        total.backward()
+
+        def err(s, dl, dv):
+            return (max(abs(float(x) - y) for x, y in zip(s[:5], want[0][:5])), (dl.double().cpu()[keep] - want[1][keep]).abs().max().item(),
+                    (dv.double().cpu()[keep] - want[2][keep]).abs().max().item())
+        e32, ek = err(s32, dl32, dv32), err(stats.cpu(), logits.grad, vf.grad)
+        say(f"  R = {R:6d} n_comp = {n_comp} mask = {masked!s:5}: e32 = {e32[0]:.3e} | {e32[1]:.3e} | {e32[2]:.3e}   "
+            f"hh_ppo_loss = {ek[0]:.3e} | {ek[1]:.3e} | {ek[2]:.3e}   ({int((~keep).sum())} rows at a kink left out)")
+
+    # ---- the loss alone
+    for R in (256, 65536, 1 << 20):
+        for n_comp, ld in ((4, 26), (3, 24)):
+            kw = dict(KW, n_comp=n_comp)
+            inp = REF.make_inputs(R, n_comp, ld, True, 2)
+            logits, vf = inp["logits"].to(dev).requires_grad_(True), inp["vf"].to(dev).requires_grad_(True)
+            batch = {k: inp[k].to(dev) for k in ("old_logits", "actions", "old_logp", "adv", "target")}
+            batch["mask"] = inp["mask"].to(dev).to(torch.uint8)
+            batch["n_valid"] = batch["mask"].sum(dtype=torch.int32).reshape(1)
+
+            def run(fn):
+                logits.grad = vf.grad = None
+                total, _ = fn(logits, vf, batch, **kw)
+                total.backward()
+
+            def fwd(fn):
+                with torch.no_grad():
+                    fn(logits, vf, batch, **kw)
+            t_k, t_t = events(lambda: run(LR.ppo_loss)), events(lambda: run(LR.ppo_loss_torch))
+            t_kf = events(lambda: fwd(LR.ppo_loss))
+            nbytes = R * (ld * 4 * 2 + 128 + 4 + 16 + 1 + 4)
+            say(f"loss alone, R = {R:7d}, ld = {ld}: hh_ppo_loss + backward scaling {q(t_k)}; torch-op loss + autograd {q(t_t)}; "
+                f"ratio {statistics.median(t_t) / statistics.median(t_k):.1f}x")
+            say(f"    the kernel call alone (two launches + torch's output allocations; gradients included): {q(t_kf)} = "
+                f"{nbytes / statistics.median(t_kf) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB algorithmic bytes "
+                f"({100 * nbytes / statistics.median(t_kf) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+
+    # ---- a world, a collect, the batch
+    w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+    bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+    ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+    for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):     # until whole episodes arrive in every collect
+        ro.collect()
+    t_collect = events(ro.collect, iters=5)
+    rows = ro.episodes.rows()
+    say(f"collect ({a.T} ticks x {a.arenas} arenas, one graph replay): {q(t_collect)}; the batch of the last collect: {rows['obs'].shape[0]} rows, "
+        f"{rows['ep_len'].shape[0]} episodes")
+
+    # ---- one minibatch step
+    for fused in (True, False):
+        learner = LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, fused=fused)
+        with torch.no_grad():
+            old = learner.old_logits(rows["obs"], bank, ro.episodes.N)
+            b = learner.policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 65536):
+            parts = LR.minibatch_partition(seq_len, size)
+            s0, s1 = parts[0]
+            mb = {k: v[s0:s1] for k, v in b.items() if k != "seq_len"}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            t = events(lambda: learner.minibatch_step(0, mb))
+            say(f"minibatch step (Fight1, forward + loss + backward + Adam), fused = {fused!s:5}, {int(seq_len[s0:s1].sum())} unpadded rows in "
+                f"{s1 - s0} chunks of 20: {q(t)}")
+
+    # ---- one whole update
+    learner = LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    st = learner.update(ro.episodes, bank)
+    torch.cuda.synchronize()
+    t_up = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    st = learner.update(ro.episodes, bank)
+    learner.publish(bank)
+    torch.cuda.synchronize()
+    t_up2 = (time.perf_counter() - t0) * 1e3
+    say(f"one update + publish of both policies ({a.passes} pass(es), minibatches of >= {a.minibatch} rows: {st[0]['steps']} + {st[1]['steps']} steps over "
+        f"{st[0]['rows']} rows each), host clock to a synchronise: first {t_up:.1f} ms, second {t_up2:.1f} ms; next to one collect of "
+        f"{statistics.median(t_collect):.1f} ms")
+    say(f"    statistics of the second update: {st}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
