@@ -103,7 +103,8 @@ COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commande
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
                      "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name"]  # include/hh_commander.h
 
-LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss"]  # include/hh_learner.h
+LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
+                   "hh_gru_seq_backward"]  # include/hh_learner.h
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
 
@@ -111,6 +112,11 @@ class HHPpoLossParams(C.Structure):
     """hh_ppo_loss_params (include/hh_learner.h); field order is ABI"""
     _fields_ = [("n_comp", C.c_int32), ("reserved0", C.c_int32), ("clip_param", C.c_float), ("vf_clip_param", C.c_float),
                 ("vf_loss_coeff", C.c_float), ("entropy_coeff", C.c_float), ("kl_coeff", C.c_float), ("reserved1", C.c_float)]
+
+
+class HHGruSeqIO(C.Structure):
+    """hh_gru_seq_io (include/hh_learner.h): one GRU's device pointers; field order is ABI"""
+    _fields_ = [(name, C.c_void_p) for name in ("gi", "h0", "w_hh", "b_hh", "y", "dy", "d_gi", "d_gh", "d_h0")]
 
 
 _lib = None
@@ -191,6 +197,10 @@ def lib():
         L.hh_commander_chain_kernel_name.argtypes = [vp, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
         L.hh_ppo_loss_scratch_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
         L.hh_ppo_loss.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(HHPpoLossParams), vp, vp, vp, vp, C.c_int64, vp]
+        L.hh_ppo_loss_categorical.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(HHPpoLossParams), vp, vp, vp, vp, C.c_int64, vp]
+        L.hh_gru_seq_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_gru_seq_forward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
+        L.hh_gru_seq_backward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
         _lib = L
     return _lib
 

@@ -23,6 +23,9 @@
  * — the part that needs the row's ratio (all components' logp) is applied in a second sweep over the lane's own LDS row, no exp in it.
  * Reductions: each lane's four row terms (-surrogate, vf_loss, kl, entropy) go to float64, a fixed shuffle tree per wave, the four
  * waves in index order, one partial per workgroup into `scratch`; hh_k_ppo_loss_final adds the partials in a fixed order.  No atomics.
+ *
+ * The commander's Categorical (hh_ppo_loss_categorical) is the instance NCOMP = 1 of the same kernel: one component of 3 logits, the
+ * sampler's rows 4 floats wide instead of 32, one action byte per row instead of a word of four.
  */
 #ifndef HH_PPO_LOSS_H
 #define HH_PPO_LOSS_H
@@ -30,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hh_commander.h"
 #include "hh_learner.h"
 
 #define HHL_ROWS 256       /* rows per workgroup tile = lanes per workgroup */
@@ -87,13 +91,14 @@ __device__ __forceinline__ void hhl_component(float *__restrict__ rn, float *__r
 
 template <int NCOMP>
 __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, const float *__restrict__ logits, const float *__restrict__ old_logits,
-                                                          const int32_t *__restrict__ actions /* i8 [R, 4] as one word per row */,
+                                                          const int32_t *__restrict__ actions /* i8 [R, 4] as one word per row; NCOMP = 1: i8 [R] */,
                                                           const float *__restrict__ old_logp, const float *__restrict__ adv,
                                                           const float *__restrict__ vf, const float *__restrict__ target,
                                                           const uint8_t *__restrict__ mask, const int32_t *__restrict__ n_valid, float clip,
                                                           float vf_clip, float vf_coeff, float ent_coeff, float kl_coeff,
                                                           double *__restrict__ partial, float *__restrict__ d_logits, float *__restrict__ d_vf) {
-    constexpr int NOUT = NCOMP == 4 ? 26 : 24;
+    constexpr int NOUT = NCOMP == 4 ? 26 : (NCOMP == 3 ? 24 : HH_CMD_ACTIONS);
+    constexpr int OLD_LD = NCOMP == 1 ? HH_CMD_LOGITS : HHL_OLD_LD;   /* row width of the sampler's logits */
     __shared__ float s_new[HHL_ROWS * HHL_NEW_STRIDE_MAX];
     __shared__ float s_old[HHL_ROWS * HHL_OLD_STRIDE];
     __shared__ double s_red[4][4];
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, con
     const int64_t row0 = (int64_t)blockIdx.x * HHL_ROWS;
     const int rows = (int)((R - row0) < HHL_ROWS ? (R - row0) : HHL_ROWS);   /* >= 1: the grid is ceil(R / 256) */
     const int sn = ld | 1;
-    const int nf = rows * ld, nfo = rows * HHL_OLD_LD;
+    const int nf = rows * ld, nfo = rows * OLD_LD;
 
     /* ---- the tile in: flat element order, 16 B per lane; the last elements of a partial tile one by one */
     {
@@ -121,10 +126,10 @@ __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, con
                 if (++c == ld) { c = 0; r++; }
             }
         }
-        const float *__restrict__ go = old_logits + row0 * HHL_OLD_LD;
-        for (int e0 = tid * 4; e0 < nfo; e0 += HHL_ROWS * 4) {   /* nfo is a multiple of 32 */
+        const float *__restrict__ go = old_logits + row0 * OLD_LD;
+        for (int e0 = tid * 4; e0 < nfo; e0 += HHL_ROWS * 4) {   /* nfo is a multiple of 4 */
             const float4 q = *reinterpret_cast<const float4 *>(go + e0);
-            const int r = e0 >> 5, c = e0 & 31;
+            const int r = e0 / OLD_LD, c = e0 % OLD_LD;
             float *d = s_old + r * HHL_OLD_STRIDE + c;
             if (c + 0 < NOUT) d[0] = q.x;
             if (c + 1 < NOUT) d[1] = q.y;
@@ -146,12 +151,16 @@ __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, con
             const float inv_n = 1.0f / (float)n_valid[0];
             const bool want_kl = kl_coeff > 0.0f;
             const float cE = ent_coeff * inv_n, cK = kl_coeff * inv_n;
-            const int32_t aw = actions[row];
             float logp = 0.0f, ent = 0.0f, kl = 0.0f;
-            hhl_component<13, 0>(rn, ro, (int)(int8_t)(aw & 0xff), cE, cK, want_kl, logp, ent, kl);
-            hhl_component<9, 13>(rn, ro, (int)(int8_t)((aw >> 8) & 0xff), cE, cK, want_kl, logp, ent, kl);
-            hhl_component<2, 22>(rn, ro, (int)(int8_t)((aw >> 16) & 0xff), cE, cK, want_kl, logp, ent, kl);
-            if (NCOMP == 4) hhl_component<2, 24>(rn, ro, (int)(int8_t)((aw >> 24) & 0xff), cE, cK, want_kl, logp, ent, kl);
+            if constexpr (NCOMP == 1) {
+                hhl_component<HH_CMD_ACTIONS, 0>(rn, ro, (int)reinterpret_cast<const int8_t *>(actions)[row], cE, cK, want_kl, logp, ent, kl);
+            } else {
+                const int32_t aw = actions[row];
+                hhl_component<13, 0>(rn, ro, (int)(int8_t)(aw & 0xff), cE, cK, want_kl, logp, ent, kl);
+                hhl_component<9, 13>(rn, ro, (int)(int8_t)((aw >> 8) & 0xff), cE, cK, want_kl, logp, ent, kl);
+                hhl_component<2, 22>(rn, ro, (int)(int8_t)((aw >> 16) & 0xff), cE, cK, want_kl, logp, ent, kl);
+                if (NCOMP == 4) hhl_component<2, 24>(rn, ro, (int)(int8_t)((aw >> 24) & 0xff), cE, cK, want_kl, logp, ent, kl);
+            }
             const float A = adv[row];
             const float ratio = expf(logp - old_logp[row]);
             const float lo = 1.0f - clip, hi = 1.0f + clip;
@@ -271,6 +280,32 @@ extern "C" int hh_ppo_loss(int64_t n_rows, int32_t ld, const float *logits, cons
     else
         hipLaunchKernelGGL(hh_k_ppo_loss<3>, dim3((unsigned)nb), dim3(HHL_ROWS), 0, st, n_rows, ld, logits, old_logits, aw, old_logp, adv, vf, target, mask,
                            n_valid, prm->clip_param, prm->vf_clip_param, prm->vf_loss_coeff, prm->entropy_coeff, prm->kl_coeff, partial, d_logits, d_vf);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hh_k_ppo_loss_final, dim3(1), dim3(256), 0, st, (int)nb, partial, n_valid, prm->vf_loss_coeff, prm->entropy_coeff, prm->kl_coeff, stats);
+    HIPCHK(hipGetLastError());
+    return HH_OK;
+}
+
+extern "C" int hh_ppo_loss_categorical(int64_t n_rows, const float *logits, const float *old_logits, const int8_t *actions, const float *old_logp,
+                                       const float *adv, const float *vf, const float *target, const uint8_t *mask, const int32_t *n_valid,
+                                       const hh_ppo_loss_params *prm, double *stats, float *d_logits, float *d_vf, void *scratch,
+                                       int64_t scratch_bytes, void *stream) {
+    if (n_rows <= 0 || n_rows > ((int64_t)1 << 30) || !logits || !old_logits || !actions || !old_logp || !adv || !vf || !target || !n_valid || !prm ||
+        !stats || !d_logits || !d_vf || !scratch) { g_err = "hh_ppo_loss_categorical: null or out-of-range argument"; return HH_E_ARG; }
+    if (prm->n_comp != 1 || prm->reserved0 != 0 || prm->reserved1 != 0.0f) {
+        g_err = "hh_ppo_loss_categorical: n_comp must be 1 (one Categorical over 3 logits) and the reserved fields 0"; return HH_E_ARG;
+    }
+    if ((reinterpret_cast<uintptr_t>(logits) & 15) || (reinterpret_cast<uintptr_t>(old_logits) & 15) || (reinterpret_cast<uintptr_t>(d_logits) & 15) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(stats) & 7)) {
+        g_err = "hh_ppo_loss_categorical: logits / old_logits / d_logits must be 16-byte aligned, scratch / stats 8-byte"; return HH_E_ARG;
+    }
+    const int64_t nb = hhl_blocks(n_rows);
+    if (scratch_bytes < nb * 4 * (int64_t)sizeof(double)) { g_err = "hh_ppo_loss_categorical: scratch is smaller than hh_ppo_loss_scratch_bytes(n_rows)"; return HH_E_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    double *partial = static_cast<double *>(scratch);
+    hipLaunchKernelGGL(hh_k_ppo_loss<1>, dim3((unsigned)nb), dim3(HHL_ROWS), 0, st, n_rows, (int)HH_CMD_LOGITS, logits, old_logits,
+                       reinterpret_cast<const int32_t *>(actions), old_logp, adv, vf, target, mask, n_valid, prm->clip_param, prm->vf_clip_param,
+                       prm->vf_loss_coeff, prm->entropy_coeff, prm->kl_coeff, partial, d_logits, d_vf);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(hh_k_ppo_loss_final, dim3(1), dim3(256), 0, st, (int)nb, partial, n_valid, prm->vf_loss_coeff, prm->entropy_coeff, prm->kl_coeff, stats);
     HIPCHK(hipGetLastError());

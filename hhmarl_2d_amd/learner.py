@@ -1,4 +1,4 @@
-"""The learner half of train_hetero.py's PPO on the device (train_hetero.py:206-243 with RLlib 2.4's PPO): the fused loss kernel
+"""The learner half of train_hetero.py's and train_hier.py's PPO on the device (train_hetero.py:206-243 with RLlib 2.4's PPO): the fused loss kernel
 `hh_ppo_loss` (include/hh_learner.h) behind a torch.autograd.Function, the four trainable networks as torch modules in TRAINING form, and
 `PPOLearner`, which turns the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")` into one PPO update of ac1_policy and
 ac2_policy and hands the new weights back to the sampler's `PolicyBank` — collect -> update -> publish -> collect on one GPU, the
@@ -14,7 +14,11 @@ The reference's learner does not compute what its sampler computes, and this mod
   * The critic is trained on rows with the actions filled in (rollout.central_critic_rows), while the batch's `vf` was predicted with
     zero action inputs.
   * ac1_policy and ac2_policy hold the same 500 x 500 shared_layer tensor (models/ac_models_hetero.py:22) and each has its own optimizer.
-A learner for `commander.CommanderRollout` (train_hier.py) is out of scope here."""
+
+The commander half (train_hier.py with models/ac_models_hier.py:CommanderGru) is the second part of this file: `gru_sequence`, both
+200-wide GRUs over whole chunks of max_seq_len steps in one fused launch each way (hh_gru_seq_forward / hh_gru_seq_backward),
+`ppo_loss_categorical` (hh_ppo_loss_categorical), `CommanderTrainable` and `CommanderLearner`, which does for
+`commander.CommanderRollout(batch_mode="complete_episodes")` what `PPOLearner` does for `PPORollout`."""
 import ctypes as C
 
 import numpy as np
@@ -25,7 +29,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import pilots
 from . import policy_nets as PN
-from .rollout import central_critic_rows
+from .rollout import central_critic_rows, central_critic_rows_hl
 
 OLD_LD = 32   # HH_POLICY_LOGITS: row width of the sampler's logits
 
@@ -301,7 +305,7 @@ class PPOLearner:
       * after the passes KLCoeffMixin.update_kl on the mean of the minibatches' mean_kl.
     fused = False computes the loss with torch ops (ppo_loss_torch) instead of hh_ppo_loss; nothing else differs.
     Inside a minibatch step nothing synchronises with the host (beyond what torch.optim.Adam does by itself); `update` itself synchronises
-    when it reads the batch's row count, cuts the minibatches and reads the statistics.  CommanderRollout's batches are out of scope."""
+    when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
                  vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True):
@@ -430,3 +434,421 @@ class PPOLearner:
     def publish(self, bank):
         """the new weights into the sampler's bank on the current stream (PolicyBank.refresh_trainable): captured collects replay with them"""
         bank.refresh_trainable(self.modules)
+
+
+# =================================================================================================================== the commander
+CMD_LD = 4      # HH_CMD_LOGITS: row width of hh_commander_sample's logits and of hh_ppo_loss_categorical's
+GRU_H = 200     # HH_GRU_HIDDEN
+
+
+# ------------------------------------------------------------------------------------------------------------------ the GRU
+def _gru_io(n):
+    return (L.HHGruSeqIO * n)()
+
+
+def _gru_scratch_bytes(G, S, Lm):
+    nbytes = C.c_int64()
+    L.check(L.lib().hh_gru_seq_scratch_bytes(G, S, Lm, C.byref(nbytes)))
+    return nbytes.value
+
+
+def gru_seq_forward(parts, seq_len):
+    """hh_gru_seq_forward on G = len(parts) GRUs: parts = [(gi [S, L, 600], h0 [S, 200], w_hh [600, 200], b_hh [600]), ...] contiguous
+    float32 CUDA tensors, seq_len i32 [S] -> (ys: list of [S, L, 200], scratch: what gru_seq_backward needs).  No autograd."""
+    G = len(parts)
+    S, Lm = parts[0][0].shape[:2]
+    dev = parts[0][0].device
+    nbytes = _gru_scratch_bytes(G, S, Lm)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    ys = [torch.empty((S, Lm, GRU_H), dtype=torch.float32, device=dev) for _ in range(G)]
+    io = _gru_io(G)
+    for g, ((gi, h0, w_hh, b_hh), y) in enumerate(zip(parts, ys)):
+        io[g].gi, io[g].h0, io[g].w_hh, io[g].b_hh, io[g].y = gi.data_ptr(), h0.data_ptr(), w_hh.data_ptr(), b_hh.data_ptr(), y.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(L.lib().hh_gru_seq_forward(G, S, Lm, io, _p(seq_len), _p(scratch), nbytes, st))
+    return ys, scratch
+
+
+def gru_seq_backward(parts, ys, dys, seq_len, scratch):
+    """hh_gru_seq_backward: parts / ys / scratch of gru_seq_forward, dys = d loss / d y per GRU
+    -> per GRU (d_gi [S, L, 600], d_gh [S, L, 600], d_h0 [S, 200])"""
+    G = len(parts)
+    S, Lm = parts[0][0].shape[:2]
+    dev = parts[0][0].device
+    out = [(torch.empty((S, Lm, 3 * GRU_H), dtype=torch.float32, device=dev), torch.empty((S, Lm, 3 * GRU_H), dtype=torch.float32, device=dev),
+            torch.empty((S, GRU_H), dtype=torch.float32, device=dev)) for _ in range(G)]
+    io = _gru_io(G)
+    for g, ((gi, h0, w_hh, b_hh), y, dy, (d_gi, d_gh, d_h0)) in enumerate(zip(parts, ys, dys, out)):
+        io[g].h0, io[g].w_hh, io[g].y, io[g].dy = h0.data_ptr(), w_hh.data_ptr(), y.data_ptr(), dy.data_ptr()
+        io[g].d_gi, io[g].d_gh, io[g].d_h0 = d_gi.data_ptr(), d_gh.data_ptr(), d_h0.data_ptr()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(L.lib().hh_gru_seq_backward(G, S, Lm, io, _p(seq_len), _p(scratch), scratch.numel() * 4, st))
+    return out
+
+
+class _GruSeq(torch.autograd.Function):
+    """forward: hh_gru_seq_forward over G GRUs; backward: hh_gru_seq_backward, then dW_hh = d_gh^T h_prev (one batched GEMM) and db_hh =
+    the column sums of d_gh per GRU"""
+
+    @staticmethod
+    def forward(ctx, seq_len, *flat):
+        parts = [tuple(t.detach().contiguous() for t in flat[4 * g:4 * g + 4]) for g in range(len(flat) // 4)]
+        ys, scratch = gru_seq_forward(parts, seq_len)
+        ctx.parts, ctx.seq_len, ctx.scratch = parts, seq_len, scratch
+        ctx.save_for_backward(*ys)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        ys = ctx.saved_tensors
+        dys = [torch.zeros_like(y) if d is None else d.contiguous() for d, y in zip(dys, ys)]
+        grads = [None]
+        for (gi, h0, w_hh, b_hh), y, (d_gi, d_gh, d_h0) in zip(ctx.parts, ys, gru_seq_backward(ctx.parts, ys, dys, ctx.seq_len, ctx.scratch)):
+            h_prev = torch.cat((h0[:, None], y[:, :-1]), dim=1)       # beyond seq_len d_gh is 0, whatever h_prev holds there
+            # dW_hh step by step (a batch of L GEMMs over the S sequences, then their sum), as autograd accumulates it for the stepped cell:
+            # one reduction over all S L rows loses about three times as much in float32 (measured against float64 at S = 1000)
+            d_w = torch.bmm(d_gh.permute(1, 2, 0), h_prev.transpose(0, 1)).sum(dim=0)
+            grads += [d_gi, d_h0, d_w, d_gh.sum(dim=(0, 1))]
+        return tuple(grads)
+
+
+def _check_gru(gi, h0, w_hh, b_hh, seq_len):
+    S, Lm = gi.shape[:2]
+    ok = (gi.is_cuda and all(t.dtype == torch.float32 and t.device == gi.device for t in (gi, h0, w_hh, b_hh)) and seq_len.dtype == torch.int32
+          and seq_len.device == gi.device and tuple(gi.shape) == (S, Lm, 3 * GRU_H) and tuple(h0.shape) == (S, GRU_H)
+          and tuple(w_hh.shape) == (3 * GRU_H, GRU_H) and tuple(b_hh.shape) == (3 * GRU_H,) and tuple(seq_len.shape) == (S,))
+    if not ok:
+        raise ValueError("gru_sequence: float32 CUDA tensors gi [S, L, 600], h0 [S, 200], w_hh [600, 200], b_hh [600] and seq_len int32 [S] on "
+                         "one device (the torch-op form for other dtypes and devices is gru_sequence_torch)")
+
+
+def gru_sequence(gi, h0, w_hh, b_hh, seq_len):
+    """One nn.GRU(200, 200) layer over S padded sequences with the input projection already applied, fused (hh_gru_seq_forward /
+    hh_gru_seq_backward, include/hh_learner.h): gi f32 [S, L, 600] = x W_ih^T + b_ih, h0 f32 [S, 200], w_hh f32 [600, 200], b_hh f32 [600]
+    (gate rows r | z | n), seq_len i32 [S] with 1 <= seq_len <= L <= 32, all CUDA -> y f32 [S, L, 200], exactly 0 at steps t >= seq_len;
+    differentiable with respect to gi, h0, w_hh and b_hh.  No host synchronisation; a missing library or GPU is an error."""
+    _check_gru(gi, h0, w_hh, b_hh, seq_len)
+    return _GruSeq.apply(seq_len.contiguous(), gi, h0, w_hh, b_hh)[0]
+
+
+def gru_sequence_pair(act, val, seq_len):
+    """two GRUs over the same sequences in the same two launches (CommanderGru's rnn_act and rnn_val): act, val = (gi, h0, w_hh, b_hh)
+    as for gru_sequence -> (y_act, y_val)"""
+    _check_gru(*act, seq_len)
+    _check_gru(*val, seq_len)
+    if act[0].shape != val[0].shape:
+        raise ValueError("gru_sequence_pair: both GRUs run over the same [S, L] sequences")
+    return _GruSeq.apply(seq_len.contiguous(), *act, *val)
+
+
+def gru_cell_torch(gi_t, h, w_hh, b_hh):
+    """one step of torch.nn.GRU from the projected input gi_t [S, 600] (gate columns r | z | n), with torch ops"""
+    gh = h @ w_hh.T + b_hh
+    ir, iz, inn = gi_t.split(GRU_H, dim=-1)
+    hr, hz, hn = gh.split(GRU_H, dim=-1)
+    r, z = torch.sigmoid(ir + hr), torch.sigmoid(iz + hz)
+    n = torch.tanh(inn + r * hn)
+    return (1.0 - z) * n + z * h
+
+
+def gru_sequence_torch(gi, h0, w_hh, b_hh, seq_len):
+    """gru_sequence with torch ops, any dtype and device (the A/B partner): the same cell stepped L times; a sequence's state stops at
+    its seq_len and y is 0 from there on"""
+    h, ys = h0, []
+    for t in range(gi.shape[1]):
+        on = (seq_len > t)[:, None]
+        hn = gru_cell_torch(gi[:, t], h, w_hh, b_hh)
+        h = torch.where(on, hn, h)
+        ys.append(torch.where(on, hn, torch.zeros_like(hn)))
+    return torch.stack(ys, dim=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the loss
+class _PPOLossCat(torch.autograd.Function):
+    """_PPOLoss for the commander's Categorical (hh_ppo_loss_categorical)"""
+
+    @staticmethod
+    def forward(ctx, logits, vf, old_logits, actions, old_logp, adv, target, mask, n_valid, prm):
+        R = logits.shape[0]
+        dev = logits.device
+        stats = torch.empty((len(L.PPO_STATS),), dtype=torch.float64, device=dev)
+        d_logits, d_vf = torch.empty_like(logits), torch.empty_like(vf)
+        nbytes = C.c_int64()
+        lib = L.lib()
+        L.check(lib.hh_ppo_loss_scratch_bytes(R, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(lib.hh_ppo_loss_categorical(R, _p(logits), _p(old_logits), _p(actions), _p(old_logp), _p(adv), _p(vf), _p(target), _p(mask),
+                                            _p(n_valid), C.byref(prm), _p(stats), _p(d_logits), _p(d_vf), _p(scratch), nbytes.value, st))
+        ctx.save_for_backward(d_logits, d_vf)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].float(), stats
+
+    @staticmethod
+    def backward(ctx, g_total, g_stats):
+        d_logits, d_vf = ctx.saved_tensors
+        return (d_logits * g_total, d_vf * g_total) + (None,) * 8
+
+
+def _flat_batch_cat(logits, vf, batch):
+    """_flat_batch for the commander: logits [..., 3 | 4] -> [R, 4] rows (a zero column added to 3), old_logits [R, 4], actions i8 [R]"""
+    if logits.shape[-1] == CMD_LD - 1:
+        logits = F.pad(logits, (0, 1))
+    if logits.shape[-1] != CMD_LD:
+        raise ValueError("the commander's logits are rows of 3 (or 4, the last ignored) floats")
+    logits = logits.reshape(-1, CMD_LD)
+    R = logits.shape[0]
+    col = lambda k, dt, w=None: batch[k].reshape((R,) if w is None else (R, w)).to(dt).contiguous()
+    mask = batch.get("mask")
+    mask = None if mask is None else col("mask", torch.uint8)
+    n_valid = batch.get("n_valid")
+    if n_valid is None:
+        n_valid = (torch.full((1,), R, dtype=torch.int32, device=logits.device) if mask is None
+                   else mask.ne(0).sum(dtype=torch.int32).reshape(1))
+    return (logits, vf.reshape(R), col("old_logits", torch.float32, CMD_LD), col("actions", torch.int8), col("old_logp", torch.float32),
+            col("adv", torch.float32), col("target", torch.float32), mask, n_valid.reshape(1))
+
+
+def ppo_loss_categorical(logits, vf, batch, *, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2):
+    """ppo_loss for the commander's TorchCategorical over 3 actions, fused (hh_ppo_loss_categorical).  logits f32 [..., 3] or [..., 4]
+    (column 3 ignored, gradient exactly 0) and vf f32 [...]: CUDA, with autograd history.  batch: old_logits f32 [..., 4] (the sampler's
+    logits rows), actions i8 [...], old_logp / adv / target f32 [...]; optional mask and n_valid as for ppo_loss.
+    -> (total loss, stats f64 [6]) as ppo_loss.  No host synchronisation, no fallback."""
+    if not (logits.is_cuda and logits.dtype == torch.float32 and vf.dtype == torch.float32):
+        raise ValueError("ppo_loss_categorical: logits and vf are float32 CUDA tensors (the torch-op form for other dtypes is ppo_loss_categorical_torch)")
+    flat = _flat_batch_cat(logits, vf.contiguous(), batch)
+    prm = L.HHPpoLossParams(n_comp=1, reserved0=0, clip_param=clip_param, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff,
+                            entropy_coeff=entropy_coeff, kl_coeff=kl_coeff, reserved1=0.0)
+    return _PPOLossCat.apply(flat[0].contiguous(), *flat[1:], prm)
+
+
+def ppo_loss_categorical_torch(logits, vf, batch, *, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2):
+    """the same loss with torch ops in the dtype of `logits` (CommanderLearner(fused=False)); same arguments, same results up to rounding"""
+    logits, vf, old_logits, actions, old_logp, adv, target, mask, n_valid = _flat_batch_cat(logits, vf, batch)
+    dt = logits.dtype
+    lp, lq = F.log_softmax(logits[:, :CMD_LD - 1], dim=1), F.log_softmax(old_logits[:, :CMD_LD - 1].to(dt), dim=1)
+    a = actions.long().clamp(0, CMD_LD - 2)
+    logp = lp.gather(1, a[:, None]).squeeze(1)
+    ent = -(lp.exp() * lp).sum(dim=1)
+    kl = (lq.exp() * (lq - lp)).sum(dim=1)
+    ratio = torch.exp(logp - old_logp.to(dt))
+    A = adv.to(dt)
+    surrogate = torch.min(A * ratio, A * torch.clamp(ratio, 1 - clip_param, 1 + clip_param))
+    vf_loss = torch.clamp(torch.pow(vf - target.to(dt), 2.0), 0, vf_clip_param)
+    w = torch.ones_like(ratio) if mask is None else mask.ne(0).to(dt)
+    n = n_valid.to(dt)[0]
+    mean = lambda t: (t * w).sum() / n
+    total = mean(-surrogate + vf_loss_coeff * vf_loss - entropy_coeff * ent)
+    mean_kl = mean(kl) if kl_coeff > 0.0 else torch.zeros((), dtype=dt, device=logits.device)
+    if kl_coeff > 0.0:
+        total = total + kl_coeff * mean_kl
+    stats = torch.stack([total, mean(-surrogate), mean(vf_loss), mean_kl, mean(ent), n]).detach().double()
+    return total, stats
+
+
+# ------------------------------------------------------------------------------------------------------------------ the network
+class _GRUWeights(nn.Module):
+    """the four tensors of an nn.GRU(200, 200) layer under nn.GRU's names and its initialisation (uniform in +- 1 / sqrt(200))"""
+
+    def __init__(self, n_in=GRU_H, hidden=GRU_H):
+        super().__init__()
+        k = hidden ** -0.5
+        u = lambda *shape: nn.Parameter(torch.empty(shape).uniform_(-k, k))
+        self.weight_ih_l0, self.weight_hh_l0 = u(3 * hidden, n_in), u(3 * hidden, hidden)
+        self.bias_ih_l0, self.bias_hh_l0 = u(3 * hidden), u(3 * hidden)
+
+
+class CommanderTrainable(nn.Module):
+    """models/ac_models_hier.py:CommanderGru in training form, written from commander.state_keys() and the restatement of its forward in
+    tests/commander_ref.py; `state_dict()` has exactly commander.state_keys()' keys and shapes, in that order, so it goes straight into
+    `CommanderNet.refresh_weights`.  ONE shared_layer object serves the actor and the value branch.
+
+    forward(obs_own [S, L, 34], critic_row [S, L, 105], state_in [S, 2, 200], seq_len [S], fused_gru=True) -> (logits [S, L, 3], value [S, L]):
+    S sequences of L steps of one agent each, sequence s holding seq_len[s] steps and then padding; state_in[:, 0] / [:, 1] are the states
+    rnn_act / rnn_val start from.  critic_row is rollout.central_critic_rows_hl's layout [a_own, a_o1, a_o2 | obs_own | obs_o1 | obs_o2];
+    v1..v3 see [obs_k | act_k], v4 all three.  The GRU outputs are 0 at padded steps, whose logits and values mean nothing.
+    fused_gru=True runs both GRUs through gru_sequence_pair (CUDA, float32, seq_len int32); False steps the same cell with torch ops on
+    any device and dtype.  return_states=True appends (h_act, h_val) [S, 200] each: the states after each sequence's last step."""
+
+    def __init__(self):
+        super().__init__()
+        self.shared_layer = _FC(500, 500)
+        self.rnn_act, self.rnn_val = _GRUWeights(), _GRUWeights()
+        self.inp1, self.inp2, self.inp3, self.inp4 = _FC(4, 50), _FC(20, 200), _FC(10, 50), _FC(34, 200)
+        self.act_out = _FC(500, 3)
+        self.v1, self.v2, self.v3, self.v4 = _FC(35, 100), _FC(35, 100), _FC(35, 100), _FC(105, 200)
+        self.val_out = _FC(500, 1)
+
+    def forward(self, obs_own, critic_row, state_in, seq_len, fused_gru=True, return_states=False):
+        x = torch.cat((torch.tanh(self.inp1(obs_own[..., :4])), torch.tanh(self.inp2(obs_own[..., 4:24])),
+                       torch.tanh(self.inp3(obs_own[..., 24:]))), dim=-1)
+        x_full = torch.tanh(self.inp4(obs_own))
+        a = critic_row[..., :3]
+        o = [critic_row[..., 3 + 34 * k:3 + 34 * (k + 1)] for k in range(3)]
+        v = [torch.cat((o[k], a[..., k:k + 1]), dim=-1) for k in range(3)]
+        z = torch.cat([torch.tanh(m(vk)) for m, vk in zip((self.v1, self.v2, self.v3), v)], dim=-1)
+        z_full = torch.tanh(self.v4(torch.cat(v, dim=-1)))
+        ra, rv = self.rnn_act, self.rnn_val
+        gi_a = x_full @ ra.weight_ih_l0.T + ra.bias_ih_l0
+        gi_v = z_full @ rv.weight_ih_l0.T + rv.bias_ih_l0
+        act = (gi_a, state_in[:, 0], ra.weight_hh_l0, ra.bias_hh_l0)
+        val = (gi_v, state_in[:, 1], rv.weight_hh_l0, rv.bias_hh_l0)
+        if fused_gru:
+            y_a, y_v = gru_sequence_pair(act, val, seq_len)
+        else:
+            y_a, y_v = gru_sequence_torch(*act, seq_len), gru_sequence_torch(*val, seq_len)
+        x_full = F.normalize(x_full + y_a, dim=-1)
+        z_full = F.normalize(z_full + y_v, dim=-1)
+        logits = self.act_out(torch.tanh(self.shared_layer(torch.cat((x, x_full), dim=-1))))
+        value = self.val_out(torch.tanh(self.shared_layer(torch.cat((z, z_full), dim=-1)))).squeeze(-1)
+        if not return_states:
+            return logits, value
+        last = (seq_len.long() - 1).clamp(min=0)[:, None, None].expand(-1, 1, GRU_H)
+        return logits, value, y_a.gather(1, last)[:, 0], y_v.gather(1, last)[:, 0]
+
+    load_numpy = TrainableNet.load_numpy
+
+
+# ------------------------------------------------------------------------------------------------------------------ the learner
+def standardize_masked(adv, mask):
+    """`standardize` over the rows that `mask` keeps (RLlib standardises the train batch before it is padded); 0 elsewhere"""
+    w = mask.to(adv.dtype)
+    n = w.sum()
+    mean = (adv * w).sum() / n
+    std = torch.sqrt((((adv - mean) * w) ** 2).sum() / n)
+    return (adv - mean) / torch.clamp(std, min=1e-4) * w
+
+
+class CommanderLearner:
+    """One PPO update of train_hier.py's commander_policy from the `CommanderEpisodeBatch` of a
+    `CommanderRollout(batch_mode="complete_episodes")` — for the commander what `PPOLearner` is for the 2-vs-2 policies:
+
+        learner = CommanderLearner.trainable_init(device, seed=6)          # the weights of commander.random_weights(6)
+        stats = learner.update(ro.episodes, net)
+        learner.publish(net)                                               # CommanderNet.refresh_weights: captured collects replay with them
+
+    Defaults: train_hier.py:186 (lr 1e-4, clip_param 0.25, kl_target 0.05, sgd_minibatch_size 256) and RLlib 2.4's PPO defaults for the
+    rest (kl_coeff 0.2, vf_clip_param 10, num_sgd_iter 30, max_seq_len 20 — the rollout cuts the sequences, with the same max_seq_len:
+    `update` refuses a batch cut to another length).
+      * the three agents map to ONE policy: one module, one Adam.  The batch is the three agents' trajectories: 3 S sequences from
+        `episodes.sequences()`'s S, AGENT-MAJOR — sequence a S + s is agent a's column of arena-row sequence s, with that agent's
+        state_in[s, a], its own observation, and critic rows from central_critic_rows_hl (actions filled in, while the batch's `vf` and
+        the stored rnn_val states were sampled with zero action inputs: RLlib has that difference, and so does this);
+      * nothing is masked by `valid`; the mask is the unpadded steps.  Advantages are standardised over the whole batch (all three
+        agents' unpadded rows);
+      * old_logits: recomputed once per update, under no_grad, by the module's own forward with the pre-update weights from the stored
+        sequence-start states (the rollout stores no logits).  Rows that a collect carried over from before the last publish (the head
+        of an episode that was still running) were sampled by older weights: their stored logp, and so the ratio, is exact, but their
+        recomputed old_logits are the newer weights', so the KL term sees them as on-policy.  RLlib never mixes weight versions inside
+        an episode; `rollout.start()` after `publish` gives the same (fresh episodes, nothing carried);
+      * num_sgd_iter passes; in each the sequences, in batch order, are split into consecutive minibatches of at least
+        sgd_minibatch_size unpadded rows (minibatch_partition), visited in the order of minibatch_order(seed, update count, 0, pass);
+      * after the passes KLCoeffMixin.update_kl (kl_coeff_update) on the mean of the minibatches' mean_kl.
+    fused = False computes the loss with torch ops (ppo_loss_categorical_torch) and steps the GRU cell with torch ops
+    (gru_sequence_torch) instead of hh_ppo_loss_categorical and hh_gru_seq_*; nothing else differs."""
+
+    def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
+                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True):
+        """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys()"""
+        if not torch.cuda.is_available():
+            raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
+        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.module = CommanderTrainable().load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+                                                       for k, v in state_dict.items()}).to(self.device)
+        self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
+        self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
+        self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
+        self.use_kl = kl_coeff > 0.0
+        self.kl_coeff = float(kl_coeff)
+        self.num_sgd_iter, self.sgd_minibatch_size, self.max_seq_len = int(num_sgd_iter), int(sgd_minibatch_size), int(max_seq_len)
+        self.seed, self.fused, self.updates = int(seed), bool(fused), 0
+
+    @classmethod
+    def trainable_init(cls, device, seed=0, **kw):
+        """the learner whose weights equal commander.random_weights(seed)'s (what CommanderNet.set_weights(random_weights(seed)) samples with)"""
+        from .commander import random_weights
+        return cls(random_weights(seed), device, seed=seed, **kw)
+
+    # ---- the batch
+    @staticmethod
+    def policy_batch(seqs, old_logits=None):
+        """the training batch from CommanderEpisodeBatch.sequences()' dict (S arena-row sequences of L steps): dict of agent-major
+        [3 S, L, ...] tensors — obs [.., 34], critic [.., 105], actions i8, old_logp, adv (standardised over all unpadded rows), target,
+        mask u8, and per sequence state_in [3 S, 2, 200] and seq_len i32 [3 S]; old_logits f32 [3 S, L, 4] where given"""
+        obs, actions, mask = seqs["obs"], seqs["actions"], seqs["mask"]
+        agents = range(obs.shape[2])
+        cat = lambda f: torch.cat([f(a) for a in agents], dim=0).contiguous()
+        m3 = cat(lambda a: mask)
+        b = {"obs": cat(lambda a: obs[:, :, a]),
+             "critic": cat(lambda a: central_critic_rows_hl(obs, actions, a + 1)),
+             "actions": cat(lambda a: actions[:, :, a]), "old_logp": cat(lambda a: seqs["logp"][:, :, a]),
+             "adv": standardize_masked(cat(lambda a: seqs["adv"][:, :, a]), m3), "target": cat(lambda a: seqs["target"][:, :, a]),
+             "mask": m3.to(torch.uint8), "state_in": cat(lambda a: seqs["state_in"][:, a]),
+             "seq_len": cat(lambda a: seqs["seq_lens"]).to(torch.int32)}
+        if old_logits is not None:
+            b["old_logits"] = old_logits
+        return b
+
+    def old_logits(self, b, chunk=4096):
+        """the module's logits of every row of policy_batch's dict with the weights as they stand, no autograd -> f32 [3 S, L, 4] (column 3 zero)"""
+        out = []
+        with torch.no_grad():
+            for s0 in range(0, b["obs"].shape[0], chunk):
+                sl = slice(s0, s0 + chunk)
+                lg, _ = self.module(b["obs"][sl], b["critic"][sl], b["state_in"][sl], b["seq_len"][sl], fused_gru=self.fused)
+                out.append(F.pad(lg, (0, 1)))
+        return torch.cat(out, dim=0) if out else torch.zeros(tuple(b["obs"].shape[:2]) + (CMD_LD,), device=b["obs"].device)
+
+    # ---- one minibatch step
+    def loss(self, logits, vf, mb):
+        kw = dict(clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
+                  entropy_coeff=self.entropy_coeff, kl_coeff=self.kl_coeff if self.use_kl else 0.0)
+        return (ppo_loss_categorical if self.fused else ppo_loss_categorical_torch)(logits, vf, mb, **kw)
+
+    def minibatch_step(self, mb):
+        """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with old_logits and n_valid)
+        -> stats f64 [6] (device)"""
+        logits, vf = self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused)
+        total, stats = self.loss(logits, vf, mb)
+        self.optimizer.zero_grad(set_to_none=True)
+        total.backward()
+        self.optimizer.step()
+        return stats
+
+    # ---- one update
+    def update(self, episodes, net=None):
+        """one PPO update of commander_policy from episodes (a CommanderEpisodeBatch after a collect) -> dict: total_loss, policy_loss,
+        vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows (unpadded,
+        all three agents).  `net` (the sampler's CommanderNet) is not read: the old logits come from the module, which holds the weights
+        the sampler was given at the last publish."""
+        seqs = episodes.sequences()
+        if seqs["obs"].shape[1] != self.max_seq_len:
+            raise ValueError(f"CommanderLearner(max_seq_len={self.max_seq_len}) was given sequences of {seqs['obs'].shape[1]} steps: the rollout "
+                             "cuts them, so both take the same max_seq_len")
+        if seqs["obs"].shape[0] == 0:
+            return dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
+                        kl_coeff=self.kl_coeff, steps=0, rows=0)
+        with torch.no_grad():
+            b = self.policy_batch(seqs)
+            b["old_logits"] = self.old_logits(b)
+        seq_len = b["seq_len"].cpu().numpy()
+        parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+        csum = np.concatenate([[0], np.cumsum(seq_len)])
+        n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
+        all_stats = []
+        for sgd_pass in range(self.num_sgd_iter):
+            for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
+                s0, s1 = parts[i]
+                mb = {k: v[s0:s1] for k, v in b.items()}
+                mb["n_valid"] = n_valid[i:i + 1]
+                all_stats.append(self.minibatch_step(mb))
+        m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
+        if self.use_kl and all_stats:
+            self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
+        self.updates += 1
+        return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=len(all_stats),
+                    rows=int(seq_len.sum()))
+
+    def publish(self, net):
+        """the new weights into the sampler's CommanderNet on the current stream (refresh_weights): captured collects replay with them"""
+        net.refresh_weights(self.module.state_dict())

@@ -1,6 +1,7 @@
 /*
- * hh_learner.h — C ABI of the learner side of train_hetero.py's PPO (part of libhh_world.so): the fused PPO loss, forward and
- * backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies.
+ * hh_learner.h — C ABI of the learner side of train_hetero.py's and train_hier.py's PPO (part of libhh_world.so): the fused PPO loss,
+ * forward and backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies and for the commander's Categorical,
+ * and the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*, at the end of this file).
  *
  * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
  * predictions, per row that the mask keeps (n = number of such rows):
@@ -58,6 +59,57 @@ int hh_ppo_loss_scratch_bytes(int64_t n_rows, int64_t *bytes);
 int hh_ppo_loss(int64_t n_rows, int32_t ld, const float *logits, const float *old_logits, const int8_t *actions, const float *old_logp,
                 const float *adv, const float *vf, const float *target, const uint8_t *mask, const int32_t *n_valid,
                 const hh_ppo_loss_params *prm, double *stats, float *d_logits, float *d_vf, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* The same loss, statistics, determinism and kink conventions for ONE Categorical over HH_CMD_ACTIONS = 3 logits (the commander of
+ * train_hier.py: TorchCategorical), another instance of the same row kernel.  The differences from hh_ppo_loss:
+ *   logits, old_logits, d_logits  f32 [n_rows, HH_CMD_LOGITS = 4] (hh_commander_sample's logits rows); column 3 is ignored and its
+ *                                 gradient is exactly 0.0f
+ *   actions                       i8  [n_rows] (values outside 0..2 are clamped into it), no alignment requirement
+ *   prm->n_comp                   must be 1 (one component)
+ * scratch as for hh_ppo_loss (hh_ppo_loss_scratch_bytes). */
+int hh_ppo_loss_categorical(int64_t n_rows, const float *logits, const float *old_logits, const int8_t *actions, const float *old_logp,
+                            const float *adv, const float *vf, const float *target, const uint8_t *mask, const int32_t *n_valid,
+                            const hh_ppo_loss_params *prm, double *stats, float *d_logits, float *d_vf, void *scratch, int64_t scratch_bytes,
+                            void *stream);
+
+/* ---- the learner's GRU over whole sequences (CommanderGru's rnn_act and rnn_val under RLlib's max_seq_len chunks) ----
+ *
+ * n_gru = 1 | 2 GRUs of width HH_GRU_HIDDEN = 200 (two: the actor's and the critic's in one launch, over the same sequences), n_seq
+ * sequences of max_len <= HH_GRU_MAX_LEN steps, sequence s holding seq_len[s] steps (1..max_len) followed by padding.  Per step,
+ * torch.nn.GRU's cell with the input projection taken out (it is time-parallel: one GEMM in front):
+ *     gh = W_hh h + b_hh;  r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r gh_n);  h' = (1 - z) n + z h
+ * Everything is float32 and ordered on `stream`; no allocation, no host synchronisation, no floating-point atomics, HIP-graph capturable;
+ * the same inputs give the same bytes on every run.  All pointers are [dev], 16-byte aligned (seq_len: 4-byte); an output may not overlap
+ * any other tensor of the call.  The fields a call does not use are ignored. */
+#define HH_GRU_HIDDEN 200
+#define HH_GRU_MAX_LEN 32
+
+typedef struct hh_gru_seq_io {
+    const float *gi;   /* [n_seq, max_len, 600]  x W_ih^T + b_ih, gate columns r | z | n                      forward */
+    const float *h0;   /* [n_seq, 200]           the state each sequence starts from                          forward, backward */
+    const float *w_hh; /* [600, 200]             gate rows r | z | n, as nn.GRU holds weight_hh_l0            forward, backward */
+    const float *b_hh; /* [600]                                                                               forward */
+    float *y;          /* [n_seq, max_len, 200]  h after every step; exactly 0.0f at steps t >= seq_len       forward out, backward in */
+    const float *dy;   /* [n_seq, max_len, 200]  d loss / d y; steps t >= seq_len are not read                backward */
+    float *d_gi;       /* [n_seq, max_len, 600]  d loss / d gi                                                backward out */
+    float *d_gh;       /* [n_seq, max_len, 600]  d loss / d gh: d_gi's r and z columns, its n columns times r backward out */
+    float *d_h0;       /* [n_seq, 200]                                                                        backward out */
+} hh_gru_seq_io;
+
+/* bytes of `scratch`: the k-major copy of every W_hh that the forward makes, then r, z, n and gh_n of every (GRU, sequence, step, unit) */
+int hh_gru_seq_scratch_bytes(int32_t n_gru, int64_t n_seq, int32_t max_len, int64_t *bytes);
+
+/* io[n_gru] (host array of device pointers), seq_len [dev] i32 [n_seq].  Writes y and `scratch`.  Steps t >= seq_len[s] compute nothing
+ * that a valid step depends on (padding is at the tail) and leave their part of `scratch` unwritten. */
+int hh_gru_seq_forward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_gru_seq_io *io, const int32_t *seq_len, void *scratch,
+                       int64_t scratch_bytes, void *stream);
+
+/* From the forward's `scratch`, y, h0 and w_hh: d_gi, d_gh and d_h0, the recursion dh <- dh z + d_gh W_hh running inside the kernel.
+ * Exactly 0.0f at steps t >= seq_len[s].  d_gi and d_gh are separate tensors (they differ in the n columns only; sharing the other two
+ * thirds would save 1600 B per step of the 4800 B written).  What is left to the caller: dW_hh = sum over steps of d_gh^T h_prev (one
+ * GEMM), db_hh = the column sums of d_gh, and everything upstream of gi. */
+int hh_gru_seq_backward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_gru_seq_io *io, const int32_t *seq_len, const void *scratch,
+                        int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,195 @@
+"""Where the time of the commander's PPO update goes on the MI355X, per minibatch step, at 256 and at 16384 unpadded rows:
+  gru     forward + backward of both GRUs over sequences of 20 steps, input projection x W_ih^T + b_ih and its gradients included in all
+          three: gru_sequence_pair (hh_gru_seq_forward / hh_gru_seq_backward) against the torch-op cell (gru_sequence_torch) and against
+          torch.nn.GRU (MIOpen) with the same weights, device events
+  step    one minibatch step of CommanderLearner (forward, loss, backward, Adam), fused against unfused
+  update  one whole update, fused against unfused, at N arenas and T commander steps per collect
+Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
+that fails or runs out of time ends the run, nothing is retried.
+    python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STEPS = (("gru", 240), ("step", 300), ("update", 480))     # step -> its time limit in seconds
+
+
+def events(fn, iters, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    out = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(iters):
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def q(v):
+    return f"median {statistics.median(v):.3f} ms (min {min(v):.3f}, max {max(v):.3f})"
+
+
+def sequences(rows, L, seed, device):
+    """ragged sequence lengths like a batch of episodes cut into chunks of L: about 13 sequences per 256 rows"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    lens, total = [], 0
+    while total < rows:
+        n = min(L if torch.rand((), generator=g) < 0.9 else int(torch.randint(1, L + 1, (), generator=g)), rows - total)
+        lens.append(n)
+        total += n
+    return torch.tensor(lens, dtype=torch.int32, device=device)
+
+
+def step_gru(a, say):
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    Lm, H = 20, 200
+    for rows in (256, 16384):
+        seq_len = sequences(rows, Lm, 1, dev)
+        S = seq_len.numel()
+        g = torch.Generator().manual_seed(2)
+        mk = lambda *shape, s=1.0: (s * torch.randn(shape, generator=g)).to(dev).requires_grad_(True)
+        tail = [(mk(S, H, s=0.5), mk(3 * H, H, s=H ** -0.5), mk(3 * H, s=0.1)) for _ in range(2)]      # h0, w_hh, b_hh
+        w_ih, b_ih = [mk(3 * H, H, s=H ** -0.5) for _ in range(2)], [mk(3 * H, s=0.1) for _ in range(2)]
+        wy = [torch.randn((S, Lm, H), generator=g).to(dev) for _ in range(2)]
+        grus = [torch.nn.GRU(H, H, batch_first=True).to(dev) for _ in range(2)]
+        xs = [torch.randn((S, Lm, H), generator=g).to(dev).requires_grad_(True) for _ in range(2)]
+        with torch.no_grad():
+            for gru, (h0, w_hh, b_hh), wi, bi in zip(grus, tail, w_ih, b_ih):
+                gru.weight_hh_l0.copy_(w_hh)
+                gru.bias_hh_l0.copy_(b_hh)
+                gru.weight_ih_l0.copy_(wi)
+                gru.bias_ih_l0.copy_(bi)
+
+        def clear():
+            for t in [t for p in tail for t in p] + w_ih + b_ih:
+                t.grad = None
+            for gru, x in zip(grus, xs):
+                gru.zero_grad(set_to_none=True)
+                x.grad = None
+
+        def parts():      # the time-parallel input projection, one GEMM per GRU
+            return [(x @ wi.T + bi,) + p for x, wi, bi, p in zip(xs, w_ih, b_ih, tail)]
+
+        def fused():
+            clear()
+            ya, yv = LR.gru_sequence_pair(*parts(), seq_len)
+            ((ya * wy[0]).sum() + (yv * wy[1]).sum()).backward()
+
+        def cell():
+            clear()
+            ys = [LR.gru_sequence_torch(*p, seq_len) for p in parts()]
+            ((ys[0] * wy[0]).sum() + (ys[1] * wy[1]).sum()).backward()
+
+        def miopen():     # nn.GRU over the padded [S, L] batch, all L steps of every sequence
+            clear()
+            ys = [gru(x, p[0][None].detach())[0] for gru, x, p in zip(grus, xs, tail)]
+            ((ys[0] * wy[0]).sum() + (ys[1] * wy[1]).sum()).backward()
+
+        t_f, t_c, t_m = (events(fn, a.iters, a.warmup) for fn in (fused, cell, miopen))
+        mf, mc, mm = (statistics.median(t) for t in (t_f, t_c, t_m))
+        say(f"both GRUs forward + backward with their input projections, {rows} rows in {S} sequences of <= {Lm} steps: fused (hh_gru_seq_*) "
+            f"{q(t_f)}; torch-op cell {q(t_c)} ({mc / mf:.2f}x the fused time); torch.nn.GRU (MIOpen) {q(t_m)} ({mm / mf:.2f}x the fused time)")
+        if mm < mf:
+            say(f"    the fused kernels are SLOWER than torch.nn.GRU at {rows} rows")
+
+
+def _rollout(a):
+    import torch
+    from hhmarl_2d_amd import _lib as L
+    from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weights
+    from hhmarl_2d_amd.pilots import VariantNetPilot
+    from hhmarl_2d_amd.world import World, make_config
+    w = World(make_config(n_arenas=a.arenas, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=21, auto_reset=True, horizon=a.horizon), device=0)
+    net = CommanderNet(0, 3 * a.arenas).set_weights(random_weights(6))
+    ro = CommanderRollout(w, net, VariantNetPilot(w, seed=8), a.T, batch_mode="complete_episodes", max_seq_len=20)
+    for _ in range(max(3, a.horizon // (12 * a.T) + 2)):
+        ro.collect()
+    torch.cuda.synchronize()
+    return ro, net
+
+
+def step_step(a, say):
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    ro, net = _rollout(a)
+    dev = torch.device("cuda", 0)
+    for fused in (True, False):
+        learner = LR.CommanderLearner.trainable_init(dev, seed=6, fused=fused)
+        with torch.no_grad():
+            b = learner.policy_batch(ro.episodes.sequences())
+            b["old_logits"] = learner.old_logits(b)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 16384):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            mb = {k: v[s0:s1] for k, v in b.items()}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            t = events(lambda: learner.minibatch_step(mb), a.iters, a.warmup)
+            say(f"minibatch step (forward + loss + backward + Adam), fused = {fused!s:5}, {int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} "
+                f"sequences: {q(t)}")
+
+
+def step_update(a, say):
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    ro, net = _rollout(a)
+    dev = torch.device("cuda", 0)
+    for fused in (True, False):
+        learner = LR.CommanderLearner.trainable_init(dev, seed=6, fused=fused, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+        times = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = learner.update(ro.episodes, net)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+        say(f"one update at {a.arenas} arenas, T = {a.T} ({a.passes} pass(es), minibatches of >= {a.minibatch} rows: {st['steps']} steps over "
+            f"{st['rows']} rows), fused = {fused!s:5}, host clock to a synchronise: first {times[0]:.1f} ms, second {times[1]:.1f} ms")
+        say(f"    statistics of the second update: {st}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arenas", type=int, default=8192)
+    ap.add_argument("--T", type=int, default=16)
+    ap.add_argument("--horizon", type=int, default=500)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=1)
+    ap.add_argument("--minibatch", type=int, default=16384)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_learner.log"))
+    ap.add_argument("--step", choices=[s for s, _ in STEPS], help="run one step in this process (what the parent starts)")
+    a = ap.parse_args()
+    if a.step:
+        sys.path.insert(0, ROOT)
+        import torch
+
+        def say(s):
+            print(s, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(s + "\n")
+        if a.step == "gru":
+            say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
+        {"gru": step_gru, "step": step_step, "update": step_update}[a.step](a, say)
+        return
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").close()
+    fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
+    cmd = " && ".join(f"timeout -k 10 {limit} '{sys.executable}' '{os.path.abspath(__file__)}' --step {s} {' '.join(fwd)}" for s, limit in STEPS)
+    sys.exit(subprocess.call(cmd, shell=True))
+
+
+if __name__ == "__main__":
+    main()
