@@ -137,8 +137,19 @@ struct QSlimMail { int flags[64], w5[64], w6[64], w7[64]; double rew[64]; int fu
  * pursuing: which one applies is decided in tick t + 1), and the rounded sine / cosine of the heading after the turn that _correct_angle_sign
  * (env_base.py:464-487) takes.  `ok` is wave-uniform: false on the first tick of a launch and after a tick that reset an arena of the wave
  * (episode / steps / heading changed behind the prediction); the tick then computes them itself, the same expressions. */
+/* The output wave's IDLE window — after its row stores of tick t, before barrier X of tick t + 1 (profiles/r06_quad_phase_profile.log: 1183 cycles
+ * per tick) — takes what the simulation wave would otherwise draw on its own chain between Y and X: the keyed draws of tick t + 2 that depend on
+ * nothing but the tick key, i.e. on (episode, steps) as posted at X of tick t.  8-arena form only: the main lane draws the rocket guidance noise of
+ * its unit (HH_SITE_ROCKET_NOISE), its helper lane the missile-wait draw (HH_SITE_MISSILE_WAIT) — one pass of the mixer for both.  Double-buffered
+ * by tick parity: slot t & 1 is written between Y of tick t and X of tick t + 1 and read by tick t + 2, i.e. between Y of tick t + 1 and Y of tick
+ * t + 2; the other wave's accesses to the same slot are always a barrier away.  Valid (QPre.a_ok, wave-uniform) when ticks t and t + 1 both ran in
+ * this launch and neither reset an arena of the wave: the arena's (episode, steps) of tick t + 2 is then (episode, steps + 2) of tick t for every
+ * arena that runs tick t + 2 — an arena that does not run (done, no auto-reset) draws nothing.  Otherwise the tick draws for itself. */
+struct QAheadMail { double u[2][64]; }; /* (the 16-arena two-wave forms carry its 1 KB unused: one mailbox layout for every two-wave instance) */
 struct QPre {
     bool ok;
+    bool a_ok;            /* wave-uniform: slot a_par of QAheadMail holds this tick's draws */
+    int a_par;            /* this tick's slot (its parity): [lane] rocket noise, [32 + lane] missile wait */
     bool spec;            /* wave-uniform: ok, and the tick before changed no alive mask in this wave — the prediction the output wave ran the level-3 script on */
     double sp_hdg, sp_spd; /* the script's commanded heading / speed for this lane's opponent */
     int sp_w;             /* fire | fire_m << 1 | (target slot + 1) << 2 | arena escape flag << 8 | escape timer << 16 (after the script's tick) */
@@ -423,7 +434,7 @@ __device__ __forceinline__ void quad_l3_script(const DevCfg &c, double lat, doub
 template <bool IX, bool DUAL, bool OWT = false>
 __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, int tid, int g, int s, int base, bool active, bool helper, Unit &m,
                                           Arena &ar, const int8_t *act, QTab &tb, QPub &pub, Near2 &nbc, const QTgt &tg, StepOut &out,
-                                          uint32_t &ev_mask_out, QPosMail *pos, const QPre &pre HH_PROF_ARGS) {
+                                          uint32_t &ev_mask_out, QPosMail *pos, const QAheadMail *ahd, const QPre &pre HH_PROF_ARGS) {
     /* OWT: tb.dist / foc / focr are NOT valid in here — the entries of the lane's target travel in `tg` (QTgt above) */
     /* OWT: the post-tick pair table is built by the output wave (QPosMail above).  This function then posts the moved positions and meets the
      * output wave at barrier X after phase B, and returns with tb.lat / lon / amask refreshed but tb.dist / foc / focr and nbc still the PRE-tick
@@ -451,6 +462,12 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
     int want_launch = 0, launch_tgt = 0;
     int wait_after = -1;
     bool base_gate = false;
+    /* the rocket-noise uniform of this tick as the output wave drew it (QAheadMail): requested here, unconditionally, two phases before its use.
+     * While !a_ok the slot holds a stale draw or, on the first two ticks of a launch, LDS nobody has written: the value is then never used. */
+    constexpr bool AHEAD = OWT && DUAL;
+    double u_noise_ahead = 0.0;
+    if constexpr (AHEAD) u_noise_ahead = ahd->u[pre.a_par][tid & 31];
+    const bool a_ok = AHEAD && pre.a_ok; /* wave-uniform */
 
     /* ---------------- phase A: commands (env_hetero.py:160-182) ---------------- */
     /* Control flow of the tick: at one wave per SIMD a region under the exec mask costs ~45 cycles entered and ~55 skipped
@@ -623,7 +640,11 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
         }
         { /* ac1.py:117-128, rocket launched in an earlier step */
             const bool steer = (m.has_missile != 0) & (m.rk_alive != 0);
-            if (HH_USUAL(steer)) m.rk_cmd = hh_clip(m.rk_hdg * hh_rng_uniform(d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0), 0.95, 1.05), 0.0, 359.0);
+            if (HH_USUAL(steer)) {
+                double un = u_noise_ahead;
+                if (HH_RARE(!a_ok)) un = d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0); /* wave-uniform */
+                m.rk_cmd = hh_clip(m.rk_hdg * hh_rng_uniform(un, 0.95, 1.05), 0.0, 359.0);
+            }
             m.has_missile = ((m.has_missile != 0) & (m.rk_alive == 0)) ? 0 : m.has_missile;
         }
     }
@@ -639,7 +660,11 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
             r_hdg = rk_pre ? m.rk_hdg : hdg_old;
             rk_ncmd = m.rk_cmd;
             if (HH_RARE(q_any(!rk_pre & rk_spec))) /* a launch in this tick: rare */
-                if (!rk_pre) rk_ncmd = hh_clip(hdg_old * hh_rng_uniform(d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0), 0.95, 1.05), 0.0, 359.0);
+                if (!rk_pre) {
+                    double un = u_noise_ahead;
+                    if (HH_RARE(!a_ok)) un = d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0); /* wave-uniform */
+                    rk_ncmd = hh_clip(hdg_old * hh_rng_uniform(un, 0.95, 1.05), 0.0, 359.0);
+                }
             {
                 const double delta = d_signed_heading_diff(r_hdg, rk_ncmd);
                 const double stepped = r_hdg + (delta >= 0.0 ? HH_ROCKET_TURN_RATE : -HH_ROCKET_TURN_RATE);
@@ -809,7 +834,9 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
         m.rk_cmd = rk_ncmd; /* the launcher's own update in this tick already steers it (ac1.py:127) */
     }
     if (q_any(base_gate)) if (base_gate) {
-        double uu = d_rng(ar, id, HH_SITE_MISSILE_WAIT, 0);
+        double uu;
+        if (HH_USUAL(a_ok)) uu = ahd->u[pre.a_par][32 + (tid & 31)]; /* wave-uniform; read at its (rare) point of use: the slot is this tick's until barrier Y */
+        else uu = d_rng(ar, id, HH_SITE_MISSILE_WAIT, 0);
         m.missile_wait = hh_rng_randint(uu, 7, 17);
         if (agent && c.agent_mode == HH_MODE_ESCAPE && m.missile_remain < 3) out.reward -= 0.1;
     }
@@ -1105,6 +1132,7 @@ template <bool TWO> struct QuadMailbox { /* LDS of the two-wave form only */
     QPosMail pos;   /* the three mailboxes of the preset instances (pair table on the output wave) */
     QTabMail tab;
     QSlimMail slim;
+    QAheadMail ahead;
 };
 template <> struct QuadMailbox<false> {};
 
@@ -1204,7 +1232,8 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
                 /* ahead of the simulation wave (QPre), first what does not need the table — so that it shares the table's long dependent chains' shadow:
                  * the next tick's key, the arena's escape flag for that tick, this lane's script draw */
                 const int steps_t = mbx.pos.steps[mt]; /* read HERE: after Y the simulation wave posts the next tick's */
-                const unsigned long long tk1 = hh_rng_tick_key(akey, (uint32_t)mbx.pos.episode[mt], (uint32_t)(steps_t + 1));
+                const int episode_t = mbx.pos.episode[mt];
+                const unsigned long long tk1 = hh_rng_tick_key(akey, (uint32_t)episode_t, (uint32_t)(steps_t + 1));
                 const bool l3 = !c.ext_opp && c.level >= 3; /* configuration: the level-3 script of tick t + 1, on the prediction that tick t removes nobody (QPre.spec) */
                 const int ew = mbx.pos.escw[mt];
                 int esc = ew & 0xff, esc_t = (int)(int8_t)((ew >> 8) & 0xff);
@@ -1290,6 +1319,12 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
                 }
                 q_wave_sync();
                 if (obs_out) quad_store_rows<GPB>(obs_out, mbx.tile, t, c.N, D, tid);
+                if constexpr (DUAL) { /* the idle window before barrier X: the key-only draws of tick t + 2 (QAheadMail) */
+                    int steps_2 = steps_t + 2;
+                    asm volatile("" : "+v"(steps_2)); /* the chain starts HERE, behind the row stores, not in the X -> Y interval above */
+                    const unsigned long long tk2 = hh_rng_tick_key(akey, (uint32_t)episode_t, (uint32_t)steps_2);
+                    mbx.ahead.u[t & 1][tid] = hh_rng_u01(tk2, (uint32_t)(s + 1), (uint32_t)(helper ? HH_SITE_MISSILE_WAIT : HH_SITE_ROCKET_NOISE), 0u);
+                }
                 q_wave_sync(); /* the tile is free again */
                 HH_OPROF(3);
             }
@@ -1371,6 +1406,8 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
     QPre pre;
     pre.ok = false; pre.spec = false; pre.sp_hdg = pre.sp_spd = 0.0; pre.sp_w = 0;
     pre.tkey = 0ULL; pre.sx = pre.sy = 0.0;
+    pre.a_ok = false; pre.a_par = 0;
+    bool noreset_prev = false; /* the tick before ran in this launch and reset nothing: with the same of this tick, what QAheadMail's validity asks */
     const size_t act_stride = (size_t)c.N * c.n_ctrl * 4;
     const int8_t *act_ptr = has_act ? actions + ((size_t)n * c.n_ctrl + s) * 4 : actions; /* lanes without a row re-read row 0, unused */
     int act_cur = *reinterpret_cast<const int *>(act_ptr);
@@ -1382,9 +1419,10 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
         const bool was_running = active && !ar.done;
         hh_act_unpack(act_cur, act, act_fault, has_act & was_running & (m.alive != 0));
         QPosMail *posmail = nullptr;
-        if constexpr (OWT) posmail = &mbx.pos;
+        const QAheadMail *ahdmail = nullptr;
+        if constexpr (OWT) { posmail = &mbx.pos; ahdmail = &mbx.ahead; }
         const int amask_before = tb.amask; /* alive at tick start: QPre.spec holds when the tick leaves it as it is */
-        tick_quad<(W >= 2), DUAL, OWT>(c, sh, tid, g, s, base, active, helper, m, ar, act, tb, pub, nbc, tg, so, evm_last, posmail, pre HH_PROF_PASS);
+        tick_quad<(W >= 2), DUAL, OWT>(c, sh, tid, g, s, base, active, helper, m, ar, act, tb, pub, nbc, tg, so, evm_last, posmail, ahdmail, pre HH_PROF_PASS);
         const int done_now = ar.done;
         if constexpr (TWO && !OWT) { /* post the agents' rows as early as they exist: the LDS stores drain behind the work below */
             if (!helper && s < 2) mail_post(mbx.mail[t & 1], g * 2 + s, tb, pub, m, so, done_now);
@@ -1447,6 +1485,9 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
             __syncthreads(); /* barrier Y */
             HH_PROF(13);
             pre.ok = !reset_tick;
+            pre.a_ok = !reset_tick && noreset_prev;
+            noreset_prev = !reset_tick;
+            pre.a_par = (t + 1) & 1;
             pre.spec = !reset_tick && !q_any(active && tb.amask != amask_before);
             if (HH_USUAL(!reset_tick)) { /* wave-uniform: take what the output wave built while this wave ran the envelope phases, and what it computed ahead */
                 pre.tkey = mbx.tab.tk[tid]; pre.sx = mbx.tab.sx[tid]; pre.sy = mbx.tab.sy[tid];

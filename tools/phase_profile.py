@@ -11,6 +11,9 @@ T = 250
 w = World(make_config(n_arenas=N, level=3, seed=1234, auto_reset=True)); w.reset()
 hi = torch.tensor([13, 9, 2, 2], device="cuda")
 act = (torch.rand((T, N, 2, 4), device="cuda") * hi).to(torch.int8)
+if os.environ.get("HH_PHASE_TAPE") == "keyed":   # the benchmark's tape (bench.py: hh_action_tape_uniform, seed 1234) instead of torch's generator
+    from hhmarl_2d_amd.world import action_tape_uniform
+    act = action_tape_uniform(1234, 0, 0, T, N)
 out = w.alloc_outputs(T)
 w.rollout(act, out=out)
 buf = (C.c_ulonglong * 24)()
