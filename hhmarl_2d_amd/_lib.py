@@ -10,6 +10,7 @@ ENV_LOWLEVEL, ENV_HIGHLEVEL = 0, 1
 MODE_FIGHT, MODE_ESCAPE = 0, 1
 OPP_MODE_EPISODE = -1  # hh_step_begin: every arena observes in the mode of its own level-5 draw
 ACF_K, ACI_K, RKF_K, RKI_K, ARI_K, TGT_K = 6, 10, 4, 4, 6, 3
+POLICY_LOGITS, CMD_LOGITS, EP_AUX_MAX_DIM = 32, 4, 32  # HH_POLICY_LOGITS (hh_policy.h), HH_CMD_LOGITS (hh_commander.h), HH_EP_AUX_MAX_DIM (hh_abi.h)
 
 
 def hl_slots(n_agents, n_opps):
@@ -91,6 +92,11 @@ class HHCommanderEpisodeBufs(C.Structure):
             "ep_start", "ep_len", "ep_arena", "seq_start", "seq_len", "seq_ep", "o_state_in", "counts")]
 
 
+class HHEpisodeAux(C.Structure):
+    """hh_episode_aux (include/hh_abi.h): the optional per-agent float column of the _aux emitters; field order is ABI"""
+    _fields_ = [("aux_dim", C.c_int32), ("reserved0", C.c_int32), ("aux", C.c_void_p), ("c_aux", C.c_void_p), ("o_aux", C.c_void_p)]
+
+
 EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim", "hh_n_ctrl", "hh_reset", "hh_step",
            "hh_rollout", "hh_episode_stats", "hh_get_state", "hh_set_state", "hh_get_event_masks", "hh_observe",
            "hh_hl_begin", "hh_hl_agents_act", "hh_hl_tick", "hh_hl_end", "hh_step_begin", "hh_step_finish", "hh_gae", "hh_hl_commands",
@@ -98,10 +104,10 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_create", "hh_policy_destroy", "hh_policy_set_net", "hh_policy_set_lut", "hh_policy_set_tile_rows", "hh_policy_act",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
-           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed"]
+           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
-                     "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name"]  # include/hh_commander.h
+                     "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux"]  # include/hh_commander.h
 
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
                    "hh_gru_seq_backward"]  # include/hh_learner.h
@@ -166,6 +172,7 @@ def lib():
         L.hh_gae.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
         L.hh_gae_rllib.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
         L.hh_episodes_emit.argtypes = [C.POINTER(HHEpisodeBufs), vp]
+        L.hh_episodes_emit_aux.argtypes = [C.POINTER(HHEpisodeBufs), C.POINTER(HHEpisodeAux), vp]
         L.hh_math_eval.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
         L.hh_policy_destroy.argtypes = [vp]
@@ -191,6 +198,7 @@ def lib():
         L.hh_commander_sample.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_commander_kernel_name.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32]
         L.hh_commander_episodes_emit.argtypes = [C.POINTER(HHCommanderEpisodeBufs), vp]
+        L.hh_commander_episodes_emit_aux.argtypes = [C.POINTER(HHCommanderEpisodeBufs), C.POINTER(HHEpisodeAux), vp]
         L.hh_commander_refresh_weights.argtypes = [vp, C.POINTER(HHCommanderWeights), vp]
         L.hh_commander_copy_packed.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
         L.hh_commander_act_chain.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]

@@ -228,16 +228,22 @@ class CommanderEpisodeBatch(EpisodeBatch):
       450 C + 4800 ceil(C / L) (carry) + 487 (C + T) (rows) + 12 T (episode table) + 4812 (T + C // L) (sequences and their states).
     N = 8192, T = 16, H = 500 (C = 47), L = 20: 173 MB of row carry, 118 MB of state carry, 251 MB of rows, 2 MB of episode table
     and 710 MB of sequences: 1.25 GB in all.  Nothing overflows under that rule; if something did anyway (a carry_cap below it), a
-    sticky device flag is set and `rows()` raises."""
+    sticky device flag is set and `rows()` raises.
+
+    aux = (name, f32 [T, N, 3, d]): EpisodeBatch's optional column (hh_commander_episodes_emit_aux) — `name` f32 [R, 3, d] in `rows()`
+    and, zero padded like the other columns, [S, L, 3, d] in `sequences()`.  CommanderRollout(record_logits=True) puts the sampler's
+    logits there (d = 4): 48 B per row on top of 450 (carry) / 487 (batch) — at N = 8192, T = 16, C = 47: 18 MB more carry, 25 MB more
+    batch."""
 
     SEQ_TABLE = ("seq_start", "seq_len", "seq_ep")
     _EMIT, _SCRATCH, _N_COUNTS = "hh_commander_episodes_emit", (10, 4), 4
     _critic_rows = staticmethod(central_critic_rows_hl)
 
-    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam):
-        """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS, done and state_in) that every emission reads"""
+    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam, aux=None):
+        """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS, done and state_in) that every emission reads; aux: None or
+        (name, f32 [T, N, 3, d]) as EpisodeBatch takes it"""
         self.L = int(max_seq_len)
-        super().__init__(collect, carry_cap, gamma, lam)
+        super().__init__(collect, carry_cap, gamma, lam, aux=aux)
         S, sc = self._bufs.seq_cap, max(-(-self.carry_cap // self.L), 1)
         z = lambda shape: torch.zeros(shape, dtype=torch.int32, device=self._device)
         self.seq_start, self.seq_len, self.seq_ep = z((S,)), z((S,)), z((S,))
@@ -257,14 +263,15 @@ class CommanderEpisodeBatch(EpisodeBatch):
     def sequences(self):
         """the learner's padded form (RLlib's chop_into_sequences, all three agents of an arena row side by side; per agent it is the slice
         [..., a, ...]), gathered on the device through the sequence table: obs f32 [S, L, 3, 34], actions i8 / logp / vf / adv / target
-        [S, L, 3] (zero past seq_len), seq_lens i32 [S], mask bool [S, L], state_in f32 [S, 3, 2, 200]"""
+        [S, L, 3] (zero past seq_len), seq_lens i32 [S], mask bool [S, L], state_in f32 [S, 3, 2, 200]; with an aux column also that one,
+        f32 [S, L, 3, d]"""
         r = self.rows()
         S, sl = r["seq_start"].shape[0], self.L
         steps = torch.arange(sl, dtype=torch.int64, device=self._device)
         mask = steps[None, :] < r["seq_len"].long()[:, None]
         idx = torch.where(mask, r["seq_start"].long()[:, None] + steps[None, :], torch.zeros((), dtype=torch.int64, device=self._device))
         out = {}
-        for k in ("obs", "actions", "logp", "vf", "adv", "target"):
+        for k in ("obs", "actions", "logp", "vf", "adv", "target") + ((self.aux_name,) if self.aux_name else ()):
             col = r[k]
             g = col[idx] if col.shape[0] > 0 else torch.zeros((S, sl) + tuple(col.shape[1:]), dtype=col.dtype, device=self._device)
             m = mask.view(S, sl, *([1] * (g.dim() - 2)))
@@ -290,10 +297,18 @@ class CommanderRollout:
 
     batch_mode = "truncate_episodes" (default): the buffers above are the result.  batch_mode = "complete_episodes" (train_hier.py:182):
     every collect still fills them exactly the same way, and then also `episodes`, a `CommanderEpisodeBatch` of every episode that ended
-    in it, whole and cut into GRU sequences of at most `max_seq_len` steps; its launches join the collect's graph after the GAE."""
+    in it, whole and cut into GRU sequences of at most `max_seq_len` steps; its launches join the collect's graph after the GAE.
+
+    record_logits = True: every step's sampler call also writes its logits — the split-fp16 MFMA forward's own, the rows the actions were
+    drawn from and `logp` was taken of: RLlib's ACTION_DIST_INPUTS — into `logits` f32 [T, N, 3, 4] (column 3 zero), and with
+    batch_mode = "complete_episodes" the column travels with the rows (`episodes.rows()["logits"]` [R, 3, 4], `sequences()["logits"]`
+    [S, L, 3, 4]): every emitted row carries the logits of the forward that sampled it, whatever weights the sampler held then, and
+    `CommanderLearner.update` uses them.  The bootstrap evaluation keeps discarding its logits.  Cost: 48 T N bytes of collect buffer and
+    48 B per row of carry and batch (on top of 450 / 487).  With the default False nothing is allocated and the launches, the graph and
+    the results are what they were."""
 
     def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
-                 carry_cap=None):
+                 carry_cap=None, record_logits=False):
         """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world)"""
         if batch_mode not in ("truncate_episodes", "complete_episodes"):
             raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes cut into GRU "
@@ -323,11 +338,15 @@ class CommanderRollout:
         self._tmp_act, self._tmp_logp = z((N, N_AGENTS), torch.int8), z((N, N_AGENTS), torch.float32)
         self._pbuf = world.alloc_pilot_variants() if getattr(pilot, "variants", False) else world.alloc_pilot()
         self.batch_mode, self.max_seq_len = batch_mode, int(max_seq_len)
+        self.record_logits = bool(record_logits)
+        if self.record_logits:
+            self.logits = z((T, N, N_AGENTS, L.CMD_LOGITS), torch.float32)
         self.episodes = None
         if batch_mode == "complete_episodes":
             cap = default_carry_cap(world.cfg.horizon, world.cfg.n_agents, world.cfg.n_opps) if carry_cap is None else int(carry_cap)
             self.episodes = CommanderEpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done", "state_in")},
-                                                  self.max_seq_len, cap, self.gamma, self.lam)
+                                                  self.max_seq_len, cap, self.gamma, self.lam,
+                                                  aux=("logits", self.logits) if self.record_logits else None)
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -353,7 +372,7 @@ class CommanderRollout:
         for t in range(T):
             fresh = self._fresh if t == 0 else self.done[t - 1]
             self.net.sample(self.obs[t], self.state_in[t], self.state_in[t + 1], fresh=fresh, world=w, actions=self.actions[t],
-                            logp=self.logp[t], vf=self.vf[t])
+                            logp=self.logp[t], vf=self.vf[t], logits=self.logits[t] if self.record_logits else None)
             macro_step(w, self.actions[t], self.pilot, out=(self.obs[t + 1], self.reward[t], self.valid[t], self.done[t]),
                        pilot_buf=self._pbuf, early_exit=False)
         # the bootstrap value of every arena's unfinished tail; its state_out goes to scratch (the carried state does not advance), arenas

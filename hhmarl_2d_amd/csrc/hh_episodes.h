@@ -9,6 +9,8 @@
  * episode into sequences of at most L = max_seq_len steps, each carrying the GRU states (state_in_0 / state_in_1) of its first step.
  * Its carry holds, besides the running episode's rows, only the states at its sequence starts (ceil(carry_cap / L) per arena).
  * Each entry point fills the internal descriptor hh_ep_desc from its own struct; the kernels below take only that.
+ * hh_episodes_emit_aux / hh_commander_episodes_emit_aux are the same two with one optional per-agent float column (hh_episode_aux:
+ * the rollouts' sampler logits) that moves with obs in the emit kernel's AUX instances; without it they are the entry points above.
  *
  * One call = four launches on one stream, no host synchronisation, no allocation, so it can be captured into the collect's graph:
  *   1. hh_k_ep_count  one lane per arena: last done tick, episodes ending in the window, rows to emit (carry + last_done + 1, or 0)
@@ -31,6 +33,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "hh_abi.h"
 #include "hh_commander.h"
@@ -76,6 +80,10 @@ struct hh_ep_desc {
     int32_t *o_arena, *o_episode, *o_t, *ep_start, *ep_len, *ep_arena, *seq_start, *seq_len, *seq_ep;
     float *o_state_in;
     int32_t *counts;
+    /* the optional per-agent float column of the _aux entry points ([.., n_agents, aux_dim]); read by the AUX instances of hh_k_ep_emit only */
+    const float *aux;
+    float *c_aux, *o_aux;
+    int32_t aux_dim;
 };
 
 template <bool SEQ>
@@ -204,8 +212,11 @@ __device__ __forceinline__ void hh_ep_stash(U *carry, const U *coll, int upr, in
 }
 
 /* OBS / ACT: the access units of the observation and action columns (an action row holds one ACT per agent); SEQ: cut sequences —
- * the commander's instance, whose row geometry (3 x 34) and states (3 x 2 x 200) are compile-time constants */
-template <typename OBS, typename ACT, bool SEQ>
+ * the commander's instance, whose row geometry (3 x 34) and states (3 x 2 x 200) are compile-time constants; AUX: floats per access
+ * unit of the optional aux column (0: no such column — the instances of the entry points without it; 1: dword; 4: dwordx4, when a row
+ * of n_agents aux_dim floats is a multiple of 16 B and the three bases are 16-byte aligned).  The column moves with obs: same passes,
+ * same row order */
+template <typename OBS, typename ACT, bool SEQ, int AUX = 0>
 __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_ep_desc b) {
     extern __shared__ int ep_lds[];
     const int T = b.T, N = b.N, nA = SEQ ? HH_CMD_AGENTS : b.n_agents, D = SEQ ? HH_CMD_OBS : b.obs_dim, cap = b.carry_cap, L = b.max_seq_len;
@@ -285,8 +296,11 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_ep_desc b) {
     if (emit > 0 && (long long)ro + emit > b.row_cap) emit = ro < b.row_cap ? (int)(b.row_cap - ro) : 0;   // flagged by the scan
     const size_t crow0 = (size_t)n * cap, orow0 = (size_t)ro;
     const int obs_units = nA * D / (int)(sizeof(OBS) / sizeof(float));
+    using AUXU = typename std::conditional<AUX == 4, float4, float>::type;
+    const int aux_units = AUX ? nA * b.aux_dim / AUX : 0;
     if (emit > 0) {
         hh_ep_gather((OBS *)b.o_obs, (const OBS *)b.c_obs, (const OBS *)b.obs, obs_units, emit, cl, crow0, N, n, orow0);
+        if constexpr (AUX != 0) hh_ep_gather((AUXU *)b.o_aux, (const AUXU *)b.c_aux, (const AUXU *)b.aux, aux_units, emit, cl, crow0, N, n, orow0);
         hh_ep_gather((ACT *)b.o_actions, (const ACT *)b.c_actions, (const ACT *)b.actions, nA, emit, cl, crow0, N, n, orow0);
         hh_ep_gather(b.o_logp, b.c_logp, b.logp, nA, emit, cl, crow0, N, n, orow0);
         hh_ep_gather(b.o_vf, b.c_vf, b.vf, nA, emit, cl, crow0, N, n, orow0);
@@ -321,6 +335,7 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_ep_desc b) {
     if (keep > 0) {
         const size_t c = crow0 + c0;
         hh_ep_stash((OBS *)b.c_obs, (const OBS *)b.obs, obs_units, keep, t0, c, N, n);
+        if constexpr (AUX != 0) hh_ep_stash((AUXU *)b.c_aux, (const AUXU *)b.aux, aux_units, keep, t0, c, N, n);
         hh_ep_stash((ACT *)b.c_actions, (const ACT *)b.actions, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_logp, b.logp, nA, keep, t0, c, N, n);
         hh_ep_stash(b.c_vf, b.vf, nA, keep, t0, c, N, n);
@@ -429,22 +444,39 @@ static int hh_ep_check_ptrs(const char *fn, const hh_ep_desc &d) {
     return HH_OK;
 }
 
-template <typename OBS, typename ACT, bool SEQ>
+template <typename OBS, typename ACT, bool SEQ, int AUX = 0>
 static int hh_ep_launch(const hh_ep_desc &d, size_t lds, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(hh_k_ep_count<SEQ>, dim3((d.N + 255) / 256), dim3(256), 0, st, d);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(hh_k_ep_scan<SEQ>, dim3(1), dim3(1024), 0, st, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL((hh_k_ep_emit<OBS, ACT, SEQ>), dim3(d.N), dim3(256), lds, st, d);
+    hipLaunchKernelGGL((hh_k_ep_emit<OBS, ACT, SEQ, AUX>), dim3(d.N), dim3(256), lds, st, d);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(hh_k_ep_gae, dim3(d.ep_cap < 8192 ? (int)d.ep_cap : 8192), dim3(64), 0, st, d);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }
 
-extern "C" int hh_episodes_emit(const hh_episode_bufs *b, void *stream) {
-    const char *fn = "hh_episodes_emit";
+/* the aux column's instance: 0 without one, dwordx4 where a row's bytes and the three bases allow it, dword otherwise */
+template <typename OBS, typename ACT, bool SEQ>
+static int hh_ep_launch_aux(const hh_ep_desc &d, size_t lds, void *stream) {
+    if (!d.aux) return hh_ep_launch<OBS, ACT, SEQ, 0>(d, lds, stream);
+    const bool aux4 = (d.n_agents * d.aux_dim) % 4 == 0 && !(((uintptr_t)d.aux | (uintptr_t)d.c_aux | (uintptr_t)d.o_aux) & 15);
+    return aux4 ? hh_ep_launch<OBS, ACT, SEQ, 4>(d, lds, stream) : hh_ep_launch<OBS, ACT, SEQ, 1>(d, lds, stream);
+}
+
+/* the _aux entry points' own argument checks (x != NULL), made after the struct's; fills the descriptor's aux fields */
+static int hh_ep_check_aux(const char *fn, const hh_episode_aux *x, hh_ep_desc &d) {
+    if (x->aux_dim < 1 || x->aux_dim > HH_EP_AUX_MAX_DIM) return hh_ep_fail(fn, "aux_dim must be 1 .. 32");
+    if (x->reserved0 != 0) return hh_ep_fail(fn, "hh_episode_aux.reserved0 must be 0");
+    if (!x->aux || !x->c_aux || !x->o_aux) return hh_ep_fail(fn, "null aux buffer");
+    if (((uintptr_t)x->aux | (uintptr_t)x->c_aux | (uintptr_t)x->o_aux) & 3) return hh_ep_fail(fn, "aux buffers must be 4-byte aligned");
+    d.aux = x->aux; d.c_aux = x->c_aux; d.o_aux = x->o_aux; d.aux_dim = x->aux_dim;
+    return HH_OK;
+}
+
+static int hh_ep_emit_any(const char *fn, const hh_episode_bufs *b, const hh_episode_aux *x, void *stream) {
     if (!b) return hh_ep_fail(fn, "bad sizes");
     hh_ep_desc d = hh_ep_common(b);
     d.n_agents = b->n_agents; d.obs_dim = b->obs_dim;
@@ -454,12 +486,18 @@ extern "C" int hh_episodes_emit(const hh_episode_bufs *b, void *stream) {
     const bool obs4 = (b->n_agents * b->obs_dim) % 4 == 0;   // an obs row is 2 D floats = 16 B aligned for D = 26 | 30: dwordx4
     if (obs4 && (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 15)) return hh_ep_fail(fn, "obs buffers must be 16-byte aligned");
     if ((((uintptr_t)b->actions | (uintptr_t)b->c_actions | (uintptr_t)b->o_actions) & 3)) return hh_ep_fail(fn, "action buffers must be 4-byte aligned");
+    if (x && (rc = hh_ep_check_aux(fn, x, d)) != HH_OK) return rc;
     const size_t lds = 3 * (size_t)b->T * sizeof(int);
-    return obs4 ? hh_ep_launch<float4, uint32_t, false>(d, lds, stream) : hh_ep_launch<float, uint32_t, false>(d, lds, stream);
+    return obs4 ? hh_ep_launch_aux<float4, uint32_t, false>(d, lds, stream) : hh_ep_launch_aux<float, uint32_t, false>(d, lds, stream);
 }
 
-extern "C" int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream) {
-    const char *fn = "hh_commander_episodes_emit";
+extern "C" int hh_episodes_emit(const hh_episode_bufs *b, void *stream) { return hh_ep_emit_any("hh_episodes_emit", b, NULL, stream); }
+
+extern "C" int hh_episodes_emit_aux(const hh_episode_bufs *b, const hh_episode_aux *x, void *stream) {
+    return hh_ep_emit_any("hh_episodes_emit_aux", b, x, stream);
+}
+
+static int hh_cep_emit_any(const char *fn, const hh_commander_episode_bufs *b, const hh_episode_aux *x, void *stream) {
     if (!b) return hh_ep_fail(fn, "bad sizes");
     hh_ep_desc d = hh_ep_common(b);
     d.n_agents = HH_CMD_AGENTS; d.obs_dim = HH_CMD_OBS; d.max_seq_len = b->max_seq_len; d.seq_cap = b->seq_cap;
@@ -475,7 +513,16 @@ extern "C" int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, vo
     if ((rc = hh_ep_check_ptrs(fn, d)) != HH_OK) return rc;
     if (((uintptr_t)b->state_in | (uintptr_t)b->c_state | (uintptr_t)b->o_state_in) & 15) return hh_ep_fail(fn, "state buffers must be 16-byte aligned");
     if (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 7) return hh_ep_fail(fn, "obs buffers must be 8-byte aligned");
-    return hh_ep_launch<float2, uint8_t, true>(d, (size_t)lds, stream);
+    if (x && (rc = hh_ep_check_aux(fn, x, d)) != HH_OK) return rc;
+    return hh_ep_launch_aux<float2, uint8_t, true>(d, (size_t)lds, stream);
+}
+
+extern "C" int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream) {
+    return hh_cep_emit_any("hh_commander_episodes_emit", b, NULL, stream);
+}
+
+extern "C" int hh_commander_episodes_emit_aux(const hh_commander_episode_bufs *b, const hh_episode_aux *x, void *stream) {
+    return hh_cep_emit_any("hh_commander_episodes_emit_aux", b, x, stream);
 }
 
 #endif /* HH_EPISODES_H */

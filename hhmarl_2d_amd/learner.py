@@ -291,12 +291,17 @@ class PPOLearner:
     rest.  Per policy (agent 1, then agent 2; each with its own Adam over its module's parameters, the tied shared layer in both):
       * rows: the agent's column of every emitted row — nothing is masked by `valid` (semantics = "rllib"); own observation cut to the
         kind's width, critic rows from central_critic_rows (actions filled in);
-      * old_logits: recomputed once per update from `bank`, which still holds the pre-update weights — the sampler's sequence-length-1
-        forward, which is what RLlib's ACTION_DIST_INPUTS column holds.  Every bank call has the rollout's own shape ([N, 2] rows, the
-        same selectors), so the row lists a captured collect re-uses stay what they were.  Rows that a collect carried over from before
-        the last publish (the head of an episode that was still running) were sampled by older weights: their stored logp, and so the
-        ratio, is exact, but their recomputed old_logits are the newer weights', so the KL term sees them as on-policy.  RLlib never
-        mixes weight versions inside an episode; `rollout.start()` after `publish` gives the same (fresh episodes, nothing carried);
+      * old_logits (RLlib's ACTION_DIST_INPUTS, which the KL term and so kl_coeff are computed from): `batch_old_logits`.  With
+        PPORollout(record_logits=True) the batch carries a `logits` column — for every row the logits of the sampler call that drew its
+        action and wrote its logp, whatever weights the bank held at that tick — and that column is used as it stands: no bank call,
+        and rows sampled before the last publish (the head of an episode that was still running then) keep the logits of the weights
+        that sampled them, so old_logp and old_logits of a row always come from one forward.
+        Without the column they are recomputed once per update from `bank`, which still holds the pre-update weights, in
+        ceil(R / N) greedy calls of the rollout's own shape ([N, 2] rows, the same selectors, so the row lists a captured collect
+        re-uses stay what they were).  Only then does this approximation apply: rows carried over from before the last publish were
+        sampled by older weights — their stored logp, and so the ratio, is exact, but their recomputed old_logits are the newer
+        weights', so the KL term sees them as on-policy (`rollout.start()` after `publish` avoids it by throwing the running episodes
+        away; record_logits = True makes that unnecessary);
       * advantages standardised over the policy's whole batch;
       * fight kinds: each episode cut into chunks of max_seq_len, zero-padded, mask = the unpadded rows;
       * num_sgd_iter passes; in each the chunks (escape: rows), in batch order, are split into consecutive minibatches of at least
@@ -362,6 +367,18 @@ class PPOLearner:
             bank.sample(src, sel, greedy=True, actions=act, logp=logp, logits=out[i * N:(i + 1) * N], want_vf=False)
         return out[:R]
 
+    def batch_old_logits(self, rows, bank, n_arenas=None):
+        """old_logits f32 [R, 2, 32] of an emitted batch (`rows`: EpisodeBatch.rows()): the batch's own `logits` column where the
+        rollout recorded one (the very tensor, no bank call); otherwise recomputed from `bank` (old_logits; n_arenas: the rollout's N)"""
+        if "logits" in rows:
+            lg = rows["logits"]
+            if lg.dtype != torch.float32 or tuple(lg.shape) != (rows["obs"].shape[0], 2, OLD_LD):
+                raise ValueError(f"the batch's logits column must be f32 [R, 2, {OLD_LD}], got {lg.dtype} {tuple(lg.shape)}")
+            return lg
+        if bank is None or n_arenas is None:
+            raise ValueError("the batch has no logits column (PPORollout(record_logits=True)): a bank and n_arenas are needed to recompute them")
+        return self.old_logits(rows["obs"], bank, n_arenas)
+
     def policy_batch(self, rows, old_logits, agent):
         """the training batch of policy `agent` (0 | 1) from the emitted rows: dict of [S, L, ...] chunks (fight) or [R, ...] rows (escape)
         and, for chunks, seq_len [S] and mask [S, L]"""
@@ -396,16 +413,17 @@ class PPOLearner:
         return stats
 
     # ---- one update
-    def update(self, episodes, bank):
+    def update(self, episodes, bank=None):
         """one PPO update of both policies from episodes (an EpisodeBatch after a collect) -> per policy a dict: total_loss, policy_loss,
-        vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows"""
+        vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows.
+        `bank` is read only when the batch has no `logits` column (batch_old_logits)."""
         rows = episodes.rows()
         out = []
         if rows["obs"].shape[0] == 0:
             return [dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
                          kl_coeff=self.kl_coeff[a], steps=0, rows=0) for a in range(2)]
         with torch.no_grad():
-            old = self.old_logits(rows["obs"], bank, episodes.N)
+            old = self.batch_old_logits(rows, bank, episodes.N)
             batches = [self.policy_batch(rows, old, a) for a in range(2)]
         for agent, b in enumerate(batches):
             if self.recurrent:
@@ -736,11 +754,15 @@ class CommanderLearner:
         the stored rnn_val states were sampled with zero action inputs: RLlib has that difference, and so does this);
       * nothing is masked by `valid`; the mask is the unpadded steps.  Advantages are standardised over the whole batch (all three
         agents' unpadded rows);
-      * old_logits: recomputed once per update, under no_grad, by the module's own forward with the pre-update weights from the stored
-        sequence-start states (the rollout stores no logits).  Rows that a collect carried over from before the last publish (the head
-        of an episode that was still running) were sampled by older weights: their stored logp, and so the ratio, is exact, but their
-        recomputed old_logits are the newer weights', so the KL term sees them as on-policy.  RLlib never mixes weight versions inside
-        an episode; `rollout.start()` after `publish` gives the same (fresh episodes, nothing carried);
+      * old_logits (RLlib's ACTION_DIST_INPUTS): `batch_old_logits`.  With CommanderRollout(record_logits=True) the sequences carry a
+        `logits` column — for every step the logits of the sampler's own forward (the split-fp16 MFMA kernel that drew the action
+        and wrote logp), with the weights it held at that step — and it is used as it stands, agent-major like the other columns:
+        old_logp and old_logits of a row come from one forward, also for rows sampled before the last publish.
+        Without the column they are recomputed once per update, under no_grad, by the module's own float32 forward with the
+        pre-update weights from the stored sequence-start states.  Only then does this approximation apply: that forward is not the
+        sampler's, and rows carried over from before the last publish (the head of an episode that was still running) were sampled
+        by older weights — their stored logp, and so the ratio, is exact, but their recomputed old_logits are the newer weights', so
+        the KL term sees them as on-policy (`rollout.start()` after `publish` avoids that part by throwing the running episodes away);
       * num_sgd_iter passes; in each the sequences, in batch order, are split into consecutive minibatches of at least
         sgd_minibatch_size unpadded rows (minibatch_partition), visited in the order of minibatch_order(seed, update count, 0, pass);
       * after the passes KLCoeffMixin.update_kl (kl_coeff_update) on the mean of the minibatches' mean_kl.
@@ -799,6 +821,16 @@ class CommanderLearner:
                 out.append(F.pad(lg, (0, 1)))
         return torch.cat(out, dim=0) if out else torch.zeros(tuple(b["obs"].shape[:2]) + (CMD_LD,), device=b["obs"].device)
 
+    def batch_old_logits(self, seqs, b=None):
+        """old_logits f32 [3 S, L, 4], agent-major, of CommanderEpisodeBatch.sequences()' dict: its own `logits` column [S, L, 3, 4] where
+        the rollout recorded one (no forward); otherwise the module's (old_logits; b: policy_batch(seqs), built when not given)"""
+        if "logits" in seqs:
+            lg = seqs["logits"]
+            if lg.dtype != torch.float32 or tuple(lg.shape) != tuple(seqs["obs"].shape[:3]) + (CMD_LD,):
+                raise ValueError(f"the sequences' logits column must be f32 [S, L, 3, {CMD_LD}], got {lg.dtype} {tuple(lg.shape)}")
+            return torch.cat([lg[:, :, a] for a in range(lg.shape[2])], dim=0).contiguous()
+        return self.old_logits(self.policy_batch(seqs) if b is None else b)
+
     # ---- one minibatch step
     def loss(self, logits, vf, mb):
         kw = dict(clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
@@ -819,8 +851,8 @@ class CommanderLearner:
     def update(self, episodes, net=None):
         """one PPO update of commander_policy from episodes (a CommanderEpisodeBatch after a collect) -> dict: total_loss, policy_loss,
         vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows (unpadded,
-        all three agents).  `net` (the sampler's CommanderNet) is not read: the old logits come from the module, which holds the weights
-        the sampler was given at the last publish."""
+        all three agents).  `net` (the sampler's CommanderNet) is not read: the old logits are the batch's own `logits` column or, without
+        one, come from the module, which holds the weights the sampler was given at the last publish (batch_old_logits)."""
         seqs = episodes.sequences()
         if seqs["obs"].shape[1] != self.max_seq_len:
             raise ValueError(f"CommanderLearner(max_seq_len={self.max_seq_len}) was given sequences of {seqs['obs'].shape[1]} steps: the rollout "
@@ -830,7 +862,7 @@ class CommanderLearner:
                         kl_coeff=self.kl_coeff, steps=0, rows=0)
         with torch.no_grad():
             b = self.policy_batch(seqs)
-            b["old_logits"] = self.old_logits(b)
+            b["old_logits"] = self.batch_old_logits(seqs, b)
         seq_len = b["seq_len"].cpu().numpy()
         parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
         csum = np.concatenate([[0], np.cumsum(seq_len)])

@@ -109,7 +109,13 @@ class EpisodeBatch:
     Capacity, with H = world.cfg.horizon (an episode has at most H rows): the carry holds N (H - 1) rows, the batch R = N (H - 1 + T)
     rows and E = N T episodes — for two agents about (H - 1) (8 D + 26) + (H - 1 + T) (8 D + 47) + 12 T bytes per arena (N = 16384,
     H = 300, T = 64, fight D = 26: 1.17 GB of carry, 1.60 GB of batch).  Nothing overflows under that rule; if something did anyway, a
-    sticky device flag is set and `rows()` raises."""
+    sticky device flag is set and `rows()` raises.
+
+    aux = (name, tensor): one more per-agent float column of the collect, f32 [T, N, n_agents, d] with 1 <= d <= 32, that travels with the
+    rows (hh_episodes_emit_aux): through the carry, into the batch `name` f32 [R, n_agents, d] in the same row order, bit for bit, and
+    into `rows()` under that name.  PPORollout(record_logits=True) puts the sampler's logits there (name "logits", d = 32: RLlib's
+    ACTION_DIST_INPUTS).  It costs 4 n_agents d bytes per row of the carry and of the batch: 256 B for the logits, next to the 8 D + 47
+    of the other columns (N = 16384, H = 300, T = 64: 1.25 GB more carry, 1.52 GB more batch)."""
 
     COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
     TABLES = ("ep_start", "ep_len", "ep_arena")
@@ -117,13 +123,32 @@ class EpisodeBatch:
     _EMIT, _SCRATCH, _N_COUNTS = "hh_episodes_emit", (5, 0), 3       # entry point; scratch i32 [5 N + 0]; counts
     _critic_rows = staticmethod(central_critic_rows)
 
-    def __init__(self, collect, carry_cap, gamma, lam):
+    @classmethod
+    def check_aux(cls, aux, T, N, n_agents, device):
+        """aux = (name, tensor) as the constructor takes it -> (name, tensor), or ValueError"""
+        if not (isinstance(aux, (tuple, list)) and len(aux) == 2 and isinstance(aux[0], str) and isinstance(aux[1], torch.Tensor)):
+            raise ValueError("aux: a (name, tensor) pair, e.g. ('logits', f32 [T, N, n_agents, 32])")
+        name, t = aux
+        taken = set(cls.COLUMNS) | set(cls.TABLES) | set(getattr(cls, "SEQ_TABLE", ())) | {"state_in", "carried", "n_rows", "n_episodes", "n_sequences"}
+        if not name.isidentifier() or name.startswith("_") or name in taken or hasattr(cls, name):
+            raise ValueError(f"aux: the name {name!r} is not a free column name")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"aux: {name} must be a contiguous float32 tensor on {device}")
+        if t.dim() != 4 or tuple(t.shape[:3]) != (T, N, n_agents) or not 1 <= t.shape[3] <= L.EP_AUX_MAX_DIM:
+            raise ValueError(f"aux: {name} must be [T, N, n_agents, d] = [{T}, {N}, {n_agents}, 1 .. {L.EP_AUX_MAX_DIM}], got {tuple(t.shape)}")
+        return name, t
+
+    def __init__(self, collect, carry_cap, gamma, lam, aux=None):
         """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS and done) that every emission reads; every row column of the batch and
-        of the carry takes its per-row shape and dtype from the collect's.  carry_cap: rows the carry holds per arena (horizon - 1)."""
+        of the carry takes its per-row shape and dtype from the collect's.  carry_cap: rows the carry holds per arena (horizon - 1).
+        aux: None, or (name, f32 [T, N, n_agents, d]) — one more column that travels with the rows (see the class)."""
         T, N = collect["done"].shape
         self.N, self.T, self.carry_cap = int(N), int(T), int(carry_cap)
         self.n_agents, self.D = int(collect["obs"].shape[2]), int(collect["obs"].shape[-1])
         self._device = collect["done"].device
+        self.aux_name, self._aux = None, None
+        if aux is not None:
+            self.aux_name, aux_t = self.check_aux(aux, self.T, self.N, self.n_agents, self._device)
         N, T, cap = self.N, self.T, max(self.carry_cap, 1)
         R, E = N * (self.carry_cap + T), N * T
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self._device)
@@ -146,6 +171,13 @@ class EpisodeBatch:
         self._bufs, self._collect = b, collect   # the struct holds raw pointers: keep the tensors alive
         self._bind(collect, self._carry, ("done",) + self.ROW_INPUTS, self.COLUMNS, self.TABLES)
         b.carried, b.episode, b.scratch, b.counts = (x.data_ptr() for x in (self.carried, self._finished, self._scratch, self._counts))
+        if self.aux_name is not None:
+            row = tuple(aux_t.shape[2:])
+            setattr(self, self.aux_name, z((R,) + row, torch.float32))
+            self._carry[self.aux_name] = z((N, cap) + row, torch.float32)
+            self._aux_collect = aux_t            # the struct holds raw pointers: keep the tensor alive
+            self._aux = L.HHEpisodeAux(aux_dim=row[1], reserved0=0, aux=aux_t.data_ptr(), c_aux=self._carry[self.aux_name].data_ptr(),
+                                       o_aux=getattr(self, self.aux_name).data_ptr())
 
     def _struct(self, R, E, gamma, lam):
         return L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=self.n_agents, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R,
@@ -166,7 +198,7 @@ class EpisodeBatch:
 
     def _parts(self):
         """(names, index in the counts of the length they are cut to) for rows()"""
-        return ((self.COLUMNS, 0), (self.TABLES, 1))
+        return ((self.COLUMNS + ((self.aux_name,) if self.aux_name else ()), 0), (self.TABLES, 1))
 
     def reset(self):
         """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
@@ -176,7 +208,10 @@ class EpisodeBatch:
         self._counts[3:].zero_()
 
     def emit(self, stream):
-        L.check(getattr(L.lib(), self._EMIT)(C.byref(self._bufs), stream))
+        if self._aux is None:
+            L.check(getattr(L.lib(), self._EMIT)(C.byref(self._bufs), stream))
+        else:
+            L.check(getattr(L.lib(), self._EMIT + "_aux")(C.byref(self._bufs), C.byref(self._aux), stream))
 
     def rows(self):
         """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES) and a subclass's own
@@ -227,9 +262,19 @@ class PPORollout:
     semantics = "rllib" only): every collect still fills the buffers above exactly the same way, and then also `episodes`, an
     `EpisodeBatch` of every episode that ended in it — whole, its earlier rows carried on the device from the collects before — with
     advantages / value targets over the whole episode (last_r = 0): the batch RLlib hands its learner.  Its 4 launches are part of the
-    collect's graph."""
+    collect's graph.
 
-    def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes"):
+    record_logits = True: every tick's sampler call also writes its logits — the rows its actions were drawn from and its logp was taken
+    of, RLlib's ACTION_DIST_INPUTS — into `logits` f32 [T, N, 2, 32] (zero padded past the kind's 26 | 24), and with batch_mode =
+    "complete_episodes" the column travels with the rows: `episodes.rows()["logits"]` f32 [R, 2, 32] holds, for every emitted row,
+    the logits of the forward that sampled it, whatever weights the bank held then — also for the head of an episode that was running at
+    a `publish`.  `PPOLearner.update` then takes its old logits from there instead of recomputing them.  The bootstrap evaluation and
+    `start()` keep discarding theirs.  Opt-in because of its size: 256 B per row, next to 8 D + 47 — 256 T N bytes of collect buffer,
+    and at N = 16384, H = 300, T = 64 about 1.25 GB more carry and 1.52 GB more batch.  With the default False nothing is allocated and
+    the launches, the graph and the results are what they were."""
+
+    def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes",
+                 record_logits=False):
         """opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
         a `pilots.OpponentNets(world, skip_first=False)` (its bank bound, so that hh_step_begin lists the opponents' rows itself) or any
         callable(opp_obs f32 [N, 2, 30] on the device, None) -> int8 [N, 2, 4] that only enqueues work on the current stream"""
@@ -272,10 +317,13 @@ class PPORollout:
         # level 5 in fight mode: every arena observes in the mode of its own episode's draw (HH_OPP_MODE_EPISODE); otherwise fight mode
         self._opp_mode = L.OPP_MODE_EPISODE if (world.cfg.level == 5 and world.cfg.agent_mode == L.MODE_FIGHT) else 0
         self.batch_mode = batch_mode
+        self.record_logits = bool(record_logits)
+        if self.record_logits:
+            self.logits = z((self.T, N, 2, L.POLICY_LOGITS), torch.float32)
         self.episodes = None
         if batch_mode == "complete_episodes":
             self.episodes = EpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done",)}, max(world.cfg.horizon - 1, 0),
-                                         self.gamma, self.lam)
+                                         self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None)
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -293,7 +341,8 @@ class PPORollout:
         T = self.T
         self.obs[0].copy_(self.obs[T])      # where the previous collect (or start) left every arena
         for t in range(T):                  # every launch reads and writes its tick's rows of the [T, ...] buffers in place
-            self.bank.sample(self.obs[t], None, world=self.w, actions=self.actions[t], logp=self.logp[t], vf=self.vf[t])
+            self.bank.sample(self.obs[t], None, world=self.w, actions=self.actions[t], logp=self.logp[t], vf=self.vf[t],
+                             logits=self.logits[t] if self.record_logits else None)
             out = (self.obs[t + 1], self.reward[t], self.valid[t], self.done[t])
             if self.split:   # agents act -> the frozen opponents observe (the agents' same-tick weapon flags included) and act -> tick
                 self.w.step_begin(self.actions[t], self._opp_mode, opp_obs=self._opp_obs)

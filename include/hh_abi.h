@@ -321,6 +321,24 @@ typedef struct hh_episode_bufs {
 
 int hh_episodes_emit(const hh_episode_bufs *b, void *stream);
 
+/* One optional per-agent float column that travels with the rows of a whole-episode batch (hh_episodes_emit_aux, and
+ * hh_commander_episodes_emit_aux of hh_commander.h): aux_dim floats per agent and row, moved in the same pass and into the same row
+ * order as obs — through the carry, into the batch, bit for bit.  The emitter does not interpret it (the rollouts put the sampler's
+ * logits there: RLlib's ACTION_DIST_INPUTS).  4-byte alignment suffices; where a row of n_agents aux_dim floats is a multiple of 16
+ * bytes and all three bases are 16-byte aligned the column moves in 16-byte units.  All pointers [dev]. */
+#define HH_EP_AUX_MAX_DIM 32
+typedef struct hh_episode_aux {
+    int32_t aux_dim;          /* floats per agent: 1 .. HH_EP_AUX_MAX_DIM */
+    int32_t reserved0;        /* must be 0 */
+    const float *aux;         /* one collect (read): [T, N, n_agents, aux_dim] */
+    float *c_aux;             /* carry (read and written): [N, carry_cap, n_agents, aux_dim] */
+    float *o_aux;             /* batch (written): [row_cap, n_agents, aux_dim] */
+} hh_episode_aux;
+
+/* hh_episodes_emit with the aux column; x = NULL: hh_episodes_emit exactly.  The same launches, capacities and overflow flag (a row
+ * that is not written is not written in any column); HH_E_ARG for aux_dim out of range, reserved0 != 0, a null or misaligned buffer. */
+int hh_episodes_emit_aux(const hh_episode_bufs *b, const hh_episode_aux *x, void *stream);
+
 /* Test probe: the shared math of include/hh_math.h / hh_geodesic.h evaluated ON THE DEVICE over arrays of operands, so that a
  * -m gpu test can compare the kernels' arithmetic with the CPU oracle's bit for bit (tests/test_gpu_math.py), not only through
  * trajectories.  fn: 0 sincos(a) -> o0, o1 | 1 atan2(a, b) | 2 acos(a) | 3 sincosd(a) -> o0, o1 | 4 atan2d(a, b) | 5 pymod(a, b) |

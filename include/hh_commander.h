@@ -174,6 +174,11 @@ typedef struct hh_commander_episode_bufs {
 
 int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream);
 
+/* hh_commander_episodes_emit with one optional per-agent float column (hh_episode_aux, hh_abi.h: aux [T, N, 3, aux_dim], c_aux
+ * [N, carry_cap, 3, aux_dim], o_aux [row_cap, 3, aux_dim]) that moves with the rows; x = NULL: hh_commander_episodes_emit exactly. */
+struct hh_episode_aux;
+int hh_commander_episodes_emit_aux(const hh_commander_episode_bufs *b, const struct hh_episode_aux *x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

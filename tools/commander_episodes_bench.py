@@ -2,8 +2,9 @@
 against today's fixed windows: two rollouts of the same world configuration (N arenas, T commander steps, VariantNetPilot, horizon H),
 timed alternately with device events after a warm-up; the emission's share of a collect; the share of the collected rows that leave as
 whole episodes in steady state; and the bytes the emission moves per collect (for the bandwidth of a separate rocprofv3 --kernel-trace run).
+--logits adds both modes with record_logits=True (the sampler's logits as a batch column, 48 B more per row).
     python tools/commander_episodes_bench.py [--arenas 8192] [--steps 16] [--horizon 500] [--warmup 8] [--collects 10] [--rounds 3]
-        [--out profiles/commander_episodes.log]"""
+        [--logits] [--out profiles/commander_episodes.log]"""
 import argparse
 import math
 import os
@@ -24,10 +25,11 @@ ROW_OUT = ROW_IN + 3 * 4 * 2 + 1 + 3 * 4          # + adv / target, done, arena 
 STATE = 3 * 2 * 200 * 4                          # the GRU states of one arena row
 
 
-def make(N, T, H, batch_mode):
+def make(N, T, H, mode):
     w = World(make_config(n_arenas=N, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=1, auto_reset=True, horizon=H), device=0)
     net = CommanderNet(0, 3 * N).set_weights(random_weights(6))
-    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=batch_mode)
+    rec = mode.endswith("+logits")
+    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode[:-len("+logits")] if rec else mode, record_logits=rec)
 
 
 def ms_per_collect(ro, n):
@@ -50,7 +52,8 @@ def emission_bytes(ep, done, carried_before, carried_after, rows, seqs):
     new_rows = torch.where(fin, ca, ca - cb).sum().item()
     slots = lambda c: (c + Lq - 1) // Lq
     new_states = torch.where(fin, slots(ca), slots(ca) - slots(cb)).sum().item()
-    return rows * (ROW_IN + ROW_OUT) + seqs * 2 * STATE + new_rows * 2 * ROW_IN + new_states * 2 * STATE
+    aux = 3 * 4 * getattr(ep, ep.aux_name).shape[-1] if ep.aux_name else 0
+    return rows * (ROW_IN + ROW_OUT + 2 * aux) + seqs * 2 * STATE + new_rows * 2 * (ROW_IN + aux) + new_states * 2 * STATE
 
 
 def main():
@@ -61,6 +64,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--collects", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_episodes.log"))
     a = ap.parse_args()
     N, T, H = a.arenas, a.steps, a.horizon
@@ -70,7 +74,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    runs = {m: make(N, T, H, m) for m in ("truncate_episodes", "complete_episodes")}
+    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ())
+    runs = {m: make(N, T, H, m) for m in modes}
     ro = runs["complete_episodes"]
     ep = ro.episodes
     say(f"# tools/commander_episodes_bench.py on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per collect, VariantNetPilot, "
@@ -88,6 +93,20 @@ def main():
     tr, ce = statistics.median(times["truncate_episodes"]), statistics.median(times["complete_episodes"])
     say(f"median ms per collect: truncate_episodes {tr:.3f} | complete_episodes {ce:.3f} | emission {ce - tr:.3f} ms = "
         f"{100 * (ce - tr) / ce:.2f} % of a complete_episodes collect (target: 0.5 ms)")
+    if a.logits:
+        trl, cel = statistics.median(times["truncate_episodes+logits"]), statistics.median(times["complete_episodes+logits"])
+        say(f"with the logits column: truncate_episodes+logits {trl:.3f} (the sampler's logits stores: {trl - tr:+.3f} ms) | complete_episodes+logits "
+            f"{cel:.3f} | emission {cel - trl:.3f} ms; {(cel - trl) / max(ce - tr, 1e-9):.2f} x the emission without the column")
+        rl = runs["complete_episodes+logits"]
+        nb = []
+        for _ in range(a.collects):
+            cb = rl.episodes.carried.clone()
+            rl.collect()
+            b = rl.episodes.rows()
+            nb.append(emission_bytes(rl.episodes, rl.done, cb, rl.episodes.carried, len(b["t"]), len(b["seq_start"])))
+        rate = f"over the measured emission {statistics.mean(nb) / 1e6 / (cel - trl):.0f} GB/s" if cel - trl > 0.02 else \
+            "the measured emission is below what the difference of two collects resolves"
+        say(f"with the logits column hh_k_ep_emit moves {statistics.mean(nb) / 1e6:.1f} MB per collect: {rate}")
     # yield and bytes over the next steady-state collects
     rows = seqs = eps = 0
     nbytes = []

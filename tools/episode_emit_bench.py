@@ -2,7 +2,11 @@
 windows (batch_mode = "truncate_episodes"): two rollouts of the same world configuration, timed alternately with device events over
 `--collects` collects each round after a warm-up, and the share of the collected rows that leave as whole episodes over the steady-state
 collects.  Level 3 fight (horizon 300), random-init Fight1/Fight2 policies, one HIP graph per collect.
-    python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3]"""
+--logits adds both modes with record_logits=True (the sampler's logits as a batch column: 256 B more per row): the truncate pair
+gives what writing the logits costs the sampler, the complete pair what the emission costs with the column.  The bytes the emission moves
+per collect are counted from the batch and carry counts, so that a time (this tool's difference, or hh_k_ep_emit's in a separate
+rocprofv3 --kernel-trace run) becomes bytes/s.
+    python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]"""
 import argparse
 import os
 import statistics
@@ -16,10 +20,24 @@ from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
 
 
-def make(N, T, batch_mode):
+def make(N, T, mode):
     w = World(make_config(n_arenas=N, level=3, seed=1, auto_reset=True), device=0)
     bank = pilots.PolicyBank.trainable_init(w.device, seed=0, max_rows=2 * N)
-    return PPORollout(w, bank, T, batch_mode=batch_mode)
+    if mode.endswith("+logits"):
+        return PPORollout(w, bank, T, batch_mode=mode[:-len("+logits")], record_logits=True)
+    return PPORollout(w, bank, T, batch_mode=mode)
+
+
+def emission_bytes(ep, done, carried_before, carried_after, rows):
+    """bytes hh_k_ep_emit reads and writes in one collect: every emitted row once in (carry or window) and once out with its metadata,
+    every row that enters the carry once in and once out; the count / scan / GAE traffic is left out"""
+    D, nA = ep.D, ep.n_agents
+    aux = 4 * nA * getattr(ep, ep.aux_name).shape[-1] if ep.aux_name else 0
+    row_in = nA * (4 * D + 4 + 3 * 4 + 1) + aux            # obs, actions, logp / vf / reward, valid (, aux)
+    row_out = row_in + 1 + 3 * 4                          # + done, arena / episode / t (adv / target are the GAE kernel's)
+    fin = done.bool().any(dim=0)
+    new_rows = torch.where(fin, carried_after, carried_after - carried_before).sum().item()
+    return rows * (row_in + row_out) + new_rows * 2 * row_in
 
 
 def ms_per_collect(ro, n):
@@ -40,9 +58,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--collects", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
     a = ap.parse_args()
     N, T = a.arenas, a.ticks
-    runs = {m: make(N, T, m) for m in ("truncate_episodes", "complete_episodes")}
+    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ())
+    runs = {m: make(N, T, m) for m in modes}
     ep = runs["complete_episodes"].episodes
     print(f"{N} arenas x {T} ticks per collect, level 3 fight, horizon {runs['complete_episodes'].w.cfg.horizon}; "
           f"EpisodeBatch capacity {ep.obs.shape[0]} rows, carry {ep.carry_cap} rows per arena")
@@ -58,6 +78,23 @@ def main():
     tr, ce = statistics.median(times["truncate_episodes"]), statistics.median(times["complete_episodes"])
     print(f"median ms per collect: truncate_episodes {tr:.3f} | complete_episodes {ce:.3f} | emission overhead {ce - tr:.3f} ms = "
           f"{100 * (ce - tr) / tr:.2f} % of a collect")
+    over = {"complete_episodes": ce - tr}
+    if a.logits:
+        trl, cel = statistics.median(times["truncate_episodes+logits"]), statistics.median(times["complete_episodes+logits"])
+        over["complete_episodes+logits"] = cel - trl
+        print(f"with the logits column: truncate_episodes+logits {trl:.3f} (the sampler's logits stores: {trl - tr:+.3f} ms) | complete_episodes+logits "
+              f"{cel:.3f} | emission overhead {cel - trl:.3f} ms = {100 * (cel - trl) / trl:.2f} % of a collect; {(cel - trl) / max(ce - tr, 1e-9):.2f} x the "
+              f"emission without the column")
+    for m, dt in over.items():      # the bytes the emission moves, over a few steady-state collects of that rollout
+        r, e = runs[m], runs[m].episodes
+        nb = []
+        for _ in range(5):
+            cb = e.carried.clone()
+            r.collect()
+            nb.append(emission_bytes(e, r.done, cb, e.carried, int(e.n_rows)))
+        mb = statistics.mean(nb) / 1e6
+        print(f"{m}: hh_k_ep_emit moves {mb:.1f} MB per collect (row gather, carry rewrite): at 6.3 TB/s that is {mb / 6.3e3 * 1e3:.1f} us; over the "
+              f"measured emission overhead (four kernels) {mb / max(dt, 1e-9):.0f} GB/s")
     # yield: rows that leave as whole episodes over the next steady-state collects (one device count per collect, read once at the end)
     ro = runs["complete_episodes"]
     counts = torch.zeros((a.collects, 2), dtype=torch.int64, device=ro.w.device)

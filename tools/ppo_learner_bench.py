@@ -6,6 +6,12 @@
   update  one collect next to one whole update.  The update is timed with num_sgd_iter = 1 and sgd_minibatch_size = 65536 by default
           (--passes / --minibatch): RLlib's 30 passes of 256-row minibatches over a million rows are a quarter of a million optimizer
           steps, the per-step figure above times the number of steps
+  old     the old_logits pass of an update (ceil(R / N) greedy bank calls over the whole batch), which a batch that carries the sampler's
+          logits (PPORollout(record_logits=True)) saves: PPOLearner.batch_old_logits then returns the column.  --old-logits-only runs this
+          section alone and appends its lines to --out.  The section builds two worlds and two complete_episodes rollouts of its own,
+          one of them with the logits column: at the default N = 16384, T = 64, H = 300 about 2.8 GB (rows and carry without the
+          column) + 5.8 GB (with it: 2.8 GB of that the column's carry and batch, 0.27 GB its collect buffer), on top of the full
+          run's own rollout when it runs at its end
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--passes", type=int, default=1)
     ap.add_argument("--minibatch", type=int, default=65536)
+    ap.add_argument("--old-logits-only", action="store_true", help="only the old_logits section; its lines are appended to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -62,6 +69,33 @@ def main():
     q = lambda v: f"median {statistics.median(v):.3f} ms (min {min(v):.3f}, max {max(v):.3f})"
     say(f"# tools/ppo_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.arenas} arenas, T = {a.T}, level 3 fight; {a.iters} timed "
         f"iterations after {a.warmup} warm-up, device events")
+
+    def old_logits_section():
+        """the per-update pass that a recorded logits column saves, and what recording costs a collect"""
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ros = {rec: PPORollout(w if not rec else World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0),
+                               bank, a.T, batch_mode="complete_episodes", record_logits=rec) for rec in (False, True)}
+        for ro in ros.values():
+            for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+                ro.collect()
+        t_c = {rec: events(ro.collect, iters=5) for rec, ro in ros.items()}
+        learner = LR.PPOLearner.trainable_init(dev, mode="fight", seed=1)
+        rows, rows_l = ros[False].episodes.rows(), ros[True].episodes.rows()
+        R, N = rows["obs"].shape[0], a.arenas
+        with torch.no_grad():
+            t_old = events(lambda: learner.batch_old_logits(rows, bank, N), iters=5)
+            t_col = events(lambda: learner.batch_old_logits(rows_l, None), iters=5)
+        say(f"old_logits of one update's batch ({R} rows): recomputed from the bank in {(R + N - 1) // N} greedy calls of [{N}, 2] rows: {q(t_old)}; "
+            f"taken from the batch's logits column (record_logits=True, {rows_l['obs'].shape[0]} rows): {q(t_col)}")
+        say(f"    collect with record_logits=False: {q(t_c[False])}; with record_logits=True (sampler writes 256 B per row, emission moves them): {q(t_c[True])}")
+
+    if a.old_logits_only:
+        old_logits_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines[1:]) + "\n")
+        return
 
     # ---- errors against float64 (the GPU test's generator and bound: kernel <= 4 x e32 per quantity)
     say("errors against the float64 restatement, largest absolute difference (statistics | d_logits | d_vf), entropy_coeff 0.01, kl_coeff 0.2:")
@@ -156,6 +190,8 @@ def main():
         f"{st[0]['rows']} rows each), host clock to a synchronise: first {t_up:.1f} ms, second {t_up2:.1f} ms; next to one collect of "
         f"{statistics.median(t_collect):.1f} ms")
     say(f"    statistics of the second update: {st}")
+    del ro, learner, rows
+    old_logits_section()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
