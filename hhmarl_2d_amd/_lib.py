@@ -97,6 +97,21 @@ class HHEpisodeAux(C.Structure):
     _fields_ = [("aux_dim", C.c_int32), ("reserved0", C.c_int32), ("aux", C.c_void_p), ("c_aux", C.c_void_p), ("o_aux", C.c_void_p)]
 
 
+class HHEpisodeMetricsBufs(C.Structure):
+    """hh_episode_metrics_bufs (include/hh_abi.h): sizes, then device pointers; field order is ABI"""
+    _fields_ = [("n_agents", C.c_int32), ("reserved0", C.c_int32), ("row_cap", C.c_int64), ("ep_cap", C.c_int64)] + [
+        (name, C.c_void_p) for name in ("reward", "vf", "target", "ep_start", "ep_len", "counts", "ep_return", "summary", "totals", "scratch")] + [
+        ("scratch_bytes", C.c_int64)]
+
+
+EP_METRICS_MAX_AGENTS = 5  # HH_EP_METRICS_MAX_AGENTS
+# slot names of hh_episodes_metrics's summary f64 [HH_EP_METRICS], in slot order (HH_EPM_*: the per-agent blocks hold 5 slots each)
+EP_METRICS = ("episodes", "rows", "episode_reward_mean", "episode_reward_min", "episode_reward_max",
+              "episode_len_mean", "episode_len_min", "episode_len_max") + tuple(
+    f"{k}_{a}" for k in ("agent_return_mean", "agent_return_min", "agent_return_max", "vf_explained_var") for a in range(EP_METRICS_MAX_AGENTS))
+EP_METRICS_SLOT = {name: i for i, name in enumerate(EP_METRICS)}
+
+
 EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim", "hh_n_ctrl", "hh_reset", "hh_step",
            "hh_rollout", "hh_episode_stats", "hh_get_state", "hh_set_state", "hh_get_event_masks", "hh_observe",
            "hh_hl_begin", "hh_hl_agents_act", "hh_hl_tick", "hh_hl_end", "hh_step_begin", "hh_step_finish", "hh_gae", "hh_hl_commands",
@@ -104,7 +119,8 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_create", "hh_policy_destroy", "hh_policy_set_net", "hh_policy_set_lut", "hh_policy_set_tile_rows", "hh_policy_act",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
-           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux"]
+           "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux",
+           "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
                      "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux"]  # include/hh_commander.h
@@ -173,6 +189,8 @@ def lib():
         L.hh_gae_rllib.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
         L.hh_episodes_emit.argtypes = [C.POINTER(HHEpisodeBufs), vp]
         L.hh_episodes_emit_aux.argtypes = [C.POINTER(HHEpisodeBufs), C.POINTER(HHEpisodeAux), vp]
+        L.hh_episodes_metrics_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_episodes_metrics.argtypes = [C.POINTER(HHEpisodeMetricsBufs), vp]
         L.hh_math_eval.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
         L.hh_policy_destroy.argtypes = [vp]

@@ -238,12 +238,13 @@ class CommanderEpisodeBatch(EpisodeBatch):
     SEQ_TABLE = ("seq_start", "seq_len", "seq_ep")
     _EMIT, _SCRATCH, _N_COUNTS = "hh_commander_episodes_emit", (10, 4), 4
     _critic_rows = staticmethod(central_critic_rows_hl)
+    AGENT_KEYS = (1, 2, 3)   # metrics(): the three agents of the one commander policy, by agent id
 
-    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam, aux=None):
+    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam, aux=None, metrics=False):
         """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS, done and state_in) that every emission reads; aux: None or
-        (name, f32 [T, N, 3, d]) as EpisodeBatch takes it"""
+        (name, f32 [T, N, 3, d]) as EpisodeBatch takes it; metrics: EpisodeBatch's episode metrics (per-agent entries keyed 1..3)"""
         self.L = int(max_seq_len)
-        super().__init__(collect, carry_cap, gamma, lam, aux=aux)
+        super().__init__(collect, carry_cap, gamma, lam, aux=aux, metrics=metrics)
         S, sc = self._bufs.seq_cap, max(-(-self.carry_cap // self.L), 1)
         z = lambda shape: torch.zeros(shape, dtype=torch.int32, device=self._device)
         self.seq_start, self.seq_len, self.seq_ep = z((S,)), z((S,)), z((S,))
@@ -305,14 +306,21 @@ class CommanderRollout:
     [S, L, 3, 4]): every emitted row carries the logits of the forward that sampled it, whatever weights the sampler held then, and
     `CommanderLearner.update` uses them.  The bootstrap evaluation keeps discarding its logits.  Cost: 48 T N bytes of collect buffer and
     48 B per row of carry and batch (on top of 450 / 487).  With the default False nothing is allocated and the launches, the graph and
-    the results are what they were."""
+    the results are what they were.
+
+    metrics = True (batch_mode = "complete_episodes" only): `episodes.metrics()` gives the collect's line of RLlib's training result
+    (`episode_reward_mean` and the rest, train_hier.py's print) from three more launches behind the emitter; the per-agent entries are
+    keyed by agent id 1..3 (the three agents share the one commander policy); see EpisodeBatch."""
 
     def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
-                 carry_cap=None, record_logits=False):
-        """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world)"""
+                 carry_cap=None, metrics=False, record_logits=False):
+        """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world); metrics /
+        record_logits: pass them by keyword (record_logits stays the last parameter)"""
         if batch_mode not in ("truncate_episodes", "complete_episodes"):
             raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes cut into GRU "
                              "sequences: CommanderEpisodeBatch)")
+        if metrics and batch_mode != "complete_episodes":
+            raise ValueError("metrics=True needs batch_mode='complete_episodes': the episode metrics are those of the whole-episode batch")
         if int(max_seq_len) < 1:
             raise ValueError("max_seq_len must be at least 1")
         if carry_cap is not None and int(carry_cap) < 0:
@@ -346,7 +354,7 @@ class CommanderRollout:
             cap = default_carry_cap(world.cfg.horizon, world.cfg.n_agents, world.cfg.n_opps) if carry_cap is None else int(carry_cap)
             self.episodes = CommanderEpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done", "state_in")},
                                                   self.max_seq_len, cap, self.gamma, self.lam,
-                                                  aux=("logits", self.logits) if self.record_logits else None)
+                                                  aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics))
         self.use_graph = use_graph
         self._graph = None
         self._started = False

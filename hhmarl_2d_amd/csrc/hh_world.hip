@@ -807,6 +807,9 @@ extern "C" int hh_gae_rllib(int32_t T, int32_t N, int32_t n_agents, const float 
  * include/hh_commander.h) ---- */
 #include "hh_episodes.h"
 
+/* ---- RLlib's episode metrics of an emitted whole-episode batch (C ABI in include/hh_abi.h: hh_episodes_metrics) ---- */
+#include "hh_episode_metrics.h"
+
 /* ---- the fused PPO loss of the learner, forward and backward (C ABI in include/hh_learner.h) ---- */
 #include "hh_ppo_loss.h"
 

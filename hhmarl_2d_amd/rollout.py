@@ -115,13 +115,25 @@ class EpisodeBatch:
     rows (hh_episodes_emit_aux): through the carry, into the batch `name` f32 [R, n_agents, d] in the same row order, bit for bit, and
     into `rows()` under that name.  PPORollout(record_logits=True) puts the sampler's logits there (name "logits", d = 32: RLlib's
     ACTION_DIST_INPUTS).  It costs 4 n_agents d bytes per row of the carry and of the batch: 256 B for the logits, next to the 8 D + 47
-    of the other columns (N = 16384, H = 300, T = 64: 1.25 GB more carry, 1.52 GB more batch)."""
+    of the other columns (N = 16384, H = 300, T = 64: 1.25 GB more carry, 1.52 GB more batch).
+
+    metrics = True: RLlib's per-iteration episode metrics of every emitted batch, computed on the device right behind the emitter
+    (hh_episodes_metrics, include/hh_abi.h: three more launches in the collect's graph, float64, fixed summation order): `ep_return` f64
+    [E, n_agents] (every episode's per-agent reward sum; also in `rows()`), a summary block and running totals.  `metrics()` copies the
+    summary and the totals to the host (a few hundred bytes, one synchronisation) and names them as RLlib's result dict does;
+    `metrics_device()` hands out the device tensors without synchronising.  `reset()` zeroes the totals.  Two differences from RLlib:
+    the means / min / max are over the episodes emitted by THIS collect (RLlib smooths over the last 100 episodes; here a collect
+    without a finished episode reports nan), and `vf_explained_var` is that of the sampler's VF_PREDS (the `vf` column: zero action
+    inputs) against the value targets, not of the learner's re-evaluation with the actions filled in.  `timesteps_total` counts
+    environment steps (rows), not agent steps.  With the default False nothing is allocated and the launches, the graph and `rows()`
+    are what they were."""
 
     COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
     TABLES = ("ep_start", "ep_len", "ep_arena")
     ROW_INPUTS = ("obs", "actions", "logp", "vf", "reward", "valid")   # the collect's columns the rows carry (and the carry holds)
     _EMIT, _SCRATCH, _N_COUNTS = "hh_episodes_emit", (5, 0), 3       # entry point; scratch i32 [5 N + 0]; counts
     _critic_rows = staticmethod(central_critic_rows)
+    AGENT_KEYS = ("ac1_policy", "ac2_policy")   # metrics(): the keys of the per-agent entries (RLlib's policy ids in train_hetero.py)
 
     @classmethod
     def check_aux(cls, aux, T, N, n_agents, device):
@@ -129,7 +141,7 @@ class EpisodeBatch:
         if not (isinstance(aux, (tuple, list)) and len(aux) == 2 and isinstance(aux[0], str) and isinstance(aux[1], torch.Tensor)):
             raise ValueError("aux: a (name, tensor) pair, e.g. ('logits', f32 [T, N, n_agents, 32])")
         name, t = aux
-        taken = set(cls.COLUMNS) | set(cls.TABLES) | set(getattr(cls, "SEQ_TABLE", ())) | {"state_in", "carried", "n_rows", "n_episodes", "n_sequences"}
+        taken = set(cls.COLUMNS) | set(cls.TABLES) | set(getattr(cls, "SEQ_TABLE", ())) | {"state_in", "carried", "n_rows", "n_episodes", "n_sequences", "ep_return"}
         if not name.isidentifier() or name.startswith("_") or name in taken or hasattr(cls, name):
             raise ValueError(f"aux: the name {name!r} is not a free column name")
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
@@ -138,10 +150,11 @@ class EpisodeBatch:
             raise ValueError(f"aux: {name} must be [T, N, n_agents, d] = [{T}, {N}, {n_agents}, 1 .. {L.EP_AUX_MAX_DIM}], got {tuple(t.shape)}")
         return name, t
 
-    def __init__(self, collect, carry_cap, gamma, lam, aux=None):
+    def __init__(self, collect, carry_cap, gamma, lam, aux=None, metrics=False):
         """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS and done) that every emission reads; every row column of the batch and
         of the carry takes its per-row shape and dtype from the collect's.  carry_cap: rows the carry holds per arena (horizon - 1).
-        aux: None, or (name, f32 [T, N, n_agents, d]) — one more column that travels with the rows (see the class)."""
+        aux: None, or (name, f32 [T, N, n_agents, d]) — one more column that travels with the rows (see the class).
+        metrics: also compute the episode metrics of every emitted batch on the device (see the class)."""
         T, N = collect["done"].shape
         self.N, self.T, self.carry_cap = int(N), int(T), int(carry_cap)
         self.n_agents, self.D = int(collect["obs"].shape[2]), int(collect["obs"].shape[-1])
@@ -178,6 +191,23 @@ class EpisodeBatch:
             self._aux_collect = aux_t            # the struct holds raw pointers: keep the tensor alive
             self._aux = L.HHEpisodeAux(aux_dim=row[1], reserved0=0, aux=aux_t.data_ptr(), c_aux=self._carry[self.aux_name].data_ptr(),
                                        o_aux=getattr(self, self.aux_name).data_ptr())
+        self._metrics = None
+        if metrics:
+            if not 1 <= self.n_agents <= L.EP_METRICS_MAX_AGENTS or len(self.AGENT_KEYS) != self.n_agents:
+                raise ValueError(f"metrics: {type(self).__name__} names {len(self.AGENT_KEYS)} agents, the collect has {self.n_agents}")
+            nbytes = C.c_int64(0)
+            L.check(L.lib().hh_episodes_metrics_scratch_bytes(E, R, self.n_agents, C.byref(nbytes)))
+            self.ep_return = z((E, self.n_agents), torch.float64)
+            self._summary = torch.full((len(L.EP_METRICS),), float("nan"), dtype=torch.float64, device=self._device)
+            self._summary[:2] = 0.0                  # no collect yet: what a collect without a finished episode leaves
+            self._totals = z((2,), torch.int64)      # episodes_total, timesteps_total since start() / reset()
+            self._m_scratch = z((nbytes.value // 8,), torch.float64)
+            self._m_host = None                      # pinned host copies (summary, totals, counts), made by the first metrics()
+            self._metrics = L.HHEpisodeMetricsBufs(
+                n_agents=self.n_agents, reserved0=0, row_cap=R, ep_cap=E, reward=self.reward.data_ptr(), vf=self.vf.data_ptr(),
+                target=self.target.data_ptr(), ep_start=self.ep_start.data_ptr(), ep_len=self.ep_len.data_ptr(), counts=self._counts.data_ptr(),
+                ep_return=self.ep_return.data_ptr(), summary=self._summary.data_ptr(), totals=self._totals.data_ptr(),
+                scratch=self._m_scratch.data_ptr(), scratch_bytes=nbytes.value)
 
     def _struct(self, R, E, gamma, lam):
         return L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=self.n_agents, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R,
@@ -198,10 +228,16 @@ class EpisodeBatch:
 
     def _parts(self):
         """(names, index in the counts of the length they are cut to) for rows()"""
-        return ((self.COLUMNS + ((self.aux_name,) if self.aux_name else ()), 0), (self.TABLES, 1))
+        return ((self.COLUMNS + ((self.aux_name,) if self.aux_name else ()), 0), (self.TABLES + (("ep_return",) if self._metrics else ()), 1))
 
     def reset(self):
-        """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays)"""
+        """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays); with metrics, the
+        running totals start
+        again and the summary is that of a collect without a finished episode (0 episodes, 0 rows, nan) until the next collect"""
+        if self._metrics is not None:
+            self._totals.zero_()
+            self._summary.fill_(float("nan"))    # no collect since the reset: what a collect without a finished episode leaves
+            self._summary[:2] = 0.0
         self.carried.zero_()
         self._finished.zero_()
         self._counts[:2].zero_()
@@ -212,6 +248,54 @@ class EpisodeBatch:
             L.check(getattr(L.lib(), self._EMIT)(C.byref(self._bufs), stream))
         else:
             L.check(getattr(L.lib(), self._EMIT + "_aux")(C.byref(self._bufs), C.byref(self._aux), stream))
+        if self._metrics is not None:
+            self.enqueue_metrics(stream)
+
+    def enqueue_metrics(self, stream):
+        """hh_episodes_metrics over the batch as it stands, on `stream` (what emit() does right behind the emitter; a second call adds the
+        batch to the totals again: tools/episode_metrics_timing.py times the launches with it and puts the totals back)"""
+        if self._metrics is None:
+            raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
+        L.check(L.lib().hh_episodes_metrics(C.byref(self._metrics), stream))
+
+    def _overflow(self):
+        return RuntimeError(f"{type(self).__name__}: an episode outgrew the carry or a batch capacity (more rows than carry_cap + 1?): "
+                            "the batches since that collect are incomplete")
+
+    def metrics_device(self):
+        """the device tensors of the last collect's metrics, without synchronising (for a loop that logs asynchronously): `summary` f64
+        [len(_lib.EP_METRICS)] (slots: _lib.EP_METRICS_SLOT), `totals` i64 [2] (episodes_total, timesteps_total), `ep_return` f64 [E,
+        n_agents] (the first n_episodes entries are valid).  Overwritten by the next collect."""
+        if self._metrics is None:
+            raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
+        return {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return}
+
+    def metrics(self):
+        """-> the last collect's metrics under RLlib's result names (see the class for the two differences); copies the summary, the totals
+        and the counts to the host: one synchronisation of the current stream.  Raises like `rows()` after an overflow.
+        Keys: episode_reward_mean / _min / _max, episode_len_mean, episodes_this_iter, policy_reward_mean / _min / _max, vf_explained_var,
+        episodes_total, timesteps_total (RLlib's), and from the same summary episode_len_min / _max and timesteps_this_iter (the batch's
+        rows).  The per-agent entries (policy_reward_*, vf_explained_var) are dicts keyed by AGENT_KEYS.  After reset() / start() and
+        before the next collect: 0 episodes, nan, totals 0."""
+        if self._metrics is None:
+            raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
+        if self._m_host is None:
+            self._m_host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in (self._summary, self._totals, self._counts))
+        for h, d in zip(self._m_host, (self._summary, self._totals, self._counts)):
+            h.copy_(d, non_blocking=True)
+        torch.cuda.current_stream(self._device).synchronize()
+        s, totals, counts = (h.tolist() for h in self._m_host)
+        if counts[2]:
+            raise self._overflow()
+        slot = L.EP_METRICS_SLOT
+        per_agent = lambda name: {k: s[slot[name + "_0"] + a] for a, k in enumerate(self.AGENT_KEYS)}
+        out = {k: s[slot[k]] for k in ("episode_reward_mean", "episode_reward_min", "episode_reward_max", "episode_len_mean", "episode_len_min",
+                                       "episode_len_max")}
+        out.update(episodes_this_iter=int(s[slot["episodes"]]), timesteps_this_iter=int(s[slot["rows"]]),
+                   policy_reward_mean=per_agent("agent_return_mean"), policy_reward_min=per_agent("agent_return_min"),
+                   policy_reward_max=per_agent("agent_return_max"), vf_explained_var=per_agent("vf_explained_var"),
+                   episodes_total=int(totals[0]), timesteps_total=int(totals[1]))
+        return out
 
     def rows(self):
         """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES) and a subclass's own
@@ -219,8 +303,7 @@ class EpisodeBatch:
         torch.cuda.synchronize(self._device)
         counts = self._counts.tolist()
         if counts[2]:
-            raise RuntimeError(f"{type(self).__name__}: an episode outgrew the carry or a batch capacity (more rows than carry_cap + 1?): "
-                               "the batches since that collect are incomplete")
+            raise self._overflow()
         return {k: getattr(self, k)[:counts[i]] for names, i in self._parts() for k in names}
 
     def critic_rows(self, agent):
@@ -271,17 +354,23 @@ class PPORollout:
     a `publish`.  `PPOLearner.update` then takes its old logits from there instead of recomputing them.  The bootstrap evaluation and
     `start()` keep discarding theirs.  Opt-in because of its size: 256 B per row, next to 8 D + 47 — 256 T N bytes of collect buffer,
     and at N = 16384, H = 300, T = 64 about 1.25 GB more carry and 1.52 GB more batch.  With the default False nothing is allocated and
-    the launches, the graph and the results are what they were."""
+    the launches, the graph and the results are what they were.
+
+    metrics = True (batch_mode = "complete_episodes" only): `episodes.metrics()` gives the collect's line of RLlib's training result
+    (`episode_reward_mean` and the rest: train_hetero.py:285) from three more launches in the collect's graph; see EpisodeBatch."""
 
     def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes",
-                 record_logits=False):
-        """opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
+                 metrics=False, record_logits=False):
+        """metrics / record_logits: pass them by keyword (record_logits stays the last parameter, where its callers and its test expect it).
+        opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
         a `pilots.OpponentNets(world, skip_first=False)` (its bank bound, so that hh_step_begin lists the opponents' rows itself) or any
         callable(opp_obs f32 [N, 2, 30] on the device, None) -> int8 [N, 2, 4] that only enqueues work on the current stream"""
         if batch_mode not in ("truncate_episodes", "complete_episodes"):
             raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes: EpisodeBatch)")
         if batch_mode == "complete_episodes" and semantics == "masked":
             raise ValueError("batch_mode='complete_episodes' is defined for RLlib's trajectory view only (semantics='rllib')")
+        if metrics and batch_mode != "complete_episodes":
+            raise ValueError("metrics=True needs batch_mode='complete_episodes': the episode metrics are those of the whole-episode batch")
         from . import pilots
         assert world.cfg.env_kind == L.ENV_LOWLEVEL and world.n_agents == 2 and world.cfg.auto_reset, "PPORollout drives an auto-resetting LowLevelEnv world"
         if semantics not in ("rllib", "masked"):
@@ -323,7 +412,7 @@ class PPORollout:
         self.episodes = None
         if batch_mode == "complete_episodes":
             self.episodes = EpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done",)}, max(world.cfg.horizon - 1, 0),
-                                         self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None)
+                                         self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics))
         self.use_graph = use_graph
         self._graph = None
         self._started = False

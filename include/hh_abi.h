@@ -339,6 +339,65 @@ typedef struct hh_episode_aux {
  * that is not written is not written in any column); HH_E_ARG for aux_dim out of range, reserved0 != 0, a null or misaligned buffer. */
 int hh_episodes_emit_aux(const hh_episode_bufs *b, const hh_episode_aux *x, void *stream);
 
+/* Episode metrics of one emitted whole-episode batch (RLlib's per-iteration result: episode_reward_mean/min/max, episode_len_mean,
+ * episodes_this_iter, policy_reward_*, vf_explained_var, episodes_total, timesteps_total), computed on the device right behind
+ * hh_episodes_emit / hh_commander_episodes_emit from the batch's reward / vf / target columns and its episode table.  Three launches
+ * on `stream`, no host synchronisation, no allocation (graph-capturable).  The numbers of rows and episodes are READ FROM `counts`
+ * ON THE DEVICE (clamped to the capacities); rows and table entries beyond them are never read.
+ *   ep_return[e, a]  the sum of reward[ep_start[e] .. ep_start[e] + ep_len[e] - 1, a] in float64 (NaN for a table entry that does not lie
+ *                    inside the emitted rows: only after an emitter overflow, which counts[2] reports)
+ *   summary          f64 [HH_EP_METRICS], the slots below.  An episode's reward is the sum of its agents' returns (in agent order), as
+ *                    RLlib counts it; the per-agent slots [a] are RLlib's policy_reward_*, slots of agents >= n_agents are NaN.
+ *                    explained variance of agent a = max(-1, 1 - Var(target - vf) / Var(target)) over ALL emitted rows of that agent
+ *                    (ray/rllib/utils/torch_utils.py explained_variance; the two variances' common divisor cancels), from two-pass
+ *                    sums of squared deviations (no E[x^2] - E[x]^2): per tile of 1024 rows around the tile's own mean, the tiles
+ *                    combined around the global mean (sum M2_i + n_i (mean_i - mean)^2).
+ *   totals           i64 [2], accumulated: [0] episodes_total += episodes, [1] timesteps_total += rows.  timesteps_total counts
+ *                    ENVIRONMENT steps (one per emitted row, whatever n_agents), not agent steps.  The caller zeroes it.
+ * With 0 episodes: episodes = rows = 0, every other slot NaN, totals unchanged.
+ * Determinism: float64, no floating-point atomics; every sum has a fixed order that does not depend on the grid size (an episode: lane
+ * l of its wave adds rows l, l + 64, ... in order, then a butterfly over the 64 lanes; the row tiles: likewise per workgroup, partials
+ * into `scratch`; the last launch is one workgroup that folds episodes and tile partials in index order) — the same inputs give the
+ * same bytes on every run.
+ * HH_E_ARG, nothing enqueued: m = NULL, a NULL pointer, n_agents outside 1 .. HH_EP_METRICS_MAX_AGENTS, reserved0 != 0, row_cap
+ * outside 1 .. 2^31 - 1024 (tiles of 1024 rows are counted in 32 bits) or ep_cap outside 1 .. 2^31 - 1, reward / vf / target / ep_start /
+ * ep_len / counts not 4-byte aligned, ep_return / summary / totals / scratch not 8-byte aligned, scratch_bytes below
+ * hh_episodes_metrics_scratch_bytes(ep_cap, row_cap, n_agents). */
+#define HH_EP_METRICS_MAX_AGENTS 5
+#define HH_EPM_EPISODES 0          /* episodes of this batch (episodes_this_iter) */
+#define HH_EPM_ROWS 1              /* rows of this batch (environment steps) */
+#define HH_EPM_REWARD_MEAN 2       /* episode reward: mean, min, max over the batch's episodes */
+#define HH_EPM_REWARD_MIN 3
+#define HH_EPM_REWARD_MAX 4
+#define HH_EPM_LEN_MEAN 5          /* episode length in rows: mean, min, max */
+#define HH_EPM_LEN_MIN 6
+#define HH_EPM_LEN_MAX 7
+#define HH_EPM_AGENT_MEAN 8        /* [5] per agent: return mean, min, max over the batch's episodes */
+#define HH_EPM_AGENT_MIN 13
+#define HH_EPM_AGENT_MAX 18
+#define HH_EPM_AGENT_EXPLAINED_VAR 23 /* [5] per agent: vf_explained_var over the batch's rows */
+#define HH_EP_METRICS 28           /* length of the summary block */
+typedef struct hh_episode_metrics_bufs {
+    int32_t n_agents;         /* 1 .. HH_EP_METRICS_MAX_AGENTS */
+    int32_t reserved0;        /* must be 0 */
+    int64_t row_cap;          /* rows of the batch's columns */
+    int64_t ep_cap;           /* entries of the episode table */
+    const float *reward;      /* [dev] f32 [row_cap, n_agents]: the emitted batch's columns (o_reward, o_vf, o_target) */
+    const float *vf;
+    const float *target;
+    const int32_t *ep_start;  /* [dev] i32 [ep_cap] */
+    const int32_t *ep_len;    /* [dev] i32 [ep_cap] */
+    const int32_t *counts;    /* [dev] the emitter's counts: [0] rows, [1] episodes, [2] overflow flag */
+    double *ep_return;        /* [dev] f64 [ep_cap, n_agents] out */
+    double *summary;          /* [dev] f64 [HH_EP_METRICS] out */
+    int64_t *totals;          /* [dev] i64 [2] in/out: episodes_total, timesteps_total (accumulated) */
+    void *scratch;            /* [dev] scratch_bytes >= hh_episodes_metrics_scratch_bytes(...), 8-byte aligned */
+    int64_t scratch_bytes;
+} hh_episode_metrics_bufs;
+
+int hh_episodes_metrics_scratch_bytes(int64_t ep_cap, int64_t row_cap, int32_t n_agents, int64_t *bytes);
+int hh_episodes_metrics(const hh_episode_metrics_bufs *m, void *stream);
+
 /* Test probe: the shared math of include/hh_math.h / hh_geodesic.h evaluated ON THE DEVICE over arrays of operands, so that a
  * -m gpu test can compare the kernels' arithmetic with the CPU oracle's bit for bit (tests/test_gpu_math.py), not only through
  * trajectories.  fn: 0 sincos(a) -> o0, o1 | 1 atan2(a, b) | 2 acos(a) | 3 sincosd(a) -> o0, o1 | 4 atan2d(a, b) | 5 pymod(a, b) |

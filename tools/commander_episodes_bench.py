@@ -3,8 +3,11 @@ against today's fixed windows: two rollouts of the same world configuration (N a
 timed alternately with device events after a warm-up; the emission's share of a collect; the share of the collected rows that leave as
 whole episodes in steady state; and the bytes the emission moves per collect (for the bandwidth of a separate rocprofv3 --kernel-trace run).
 --logits adds both modes with record_logits=True (the sampler's logits as a batch column, 48 B more per row).
+--metrics adds complete_episodes with metrics=True (the episode metrics behind the emitter, hh_episodes_metrics): what the flag costs a
+collect against complete_episodes without it, next to the emission's own overhead, and the three metrics launches alone on the last
+batch; with it only those lines are written, APPENDED to --out.
     python tools/commander_episodes_bench.py [--arenas 8192] [--steps 16] [--horizon 500] [--warmup 8] [--collects 10] [--rounds 3]
-        [--logits] [--out profiles/commander_episodes.log]"""
+        [--logits] [--metrics] [--out profiles/commander_episodes.log]"""
 import argparse
 import math
 import os
@@ -19,6 +22,7 @@ from hhmarl_2d_amd import _lib as L  # noqa: E402
 from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weights  # noqa: E402
 from hhmarl_2d_amd.pilots import VariantNetPilot  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
+from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
 
 ROW_IN = 3 * 34 * 4 + 3 + 3 * 4 * 3 + 3          # obs, actions, logp / vf / reward, valid of one arena row
 ROW_OUT = ROW_IN + 3 * 4 * 2 + 1 + 3 * 4          # + adv / target, done, arena / episode / t
@@ -28,8 +32,8 @@ STATE = 3 * 2 * 200 * 4                          # the GRU states of one arena r
 def make(N, T, H, mode):
     w = World(make_config(n_arenas=N, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=1, auto_reset=True, horizon=H), device=0)
     net = CommanderNet(0, 3 * N).set_weights(random_weights(6))
-    rec = mode.endswith("+logits")
-    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode[:-len("+logits")] if rec else mode, record_logits=rec)
+    rec, met = mode.endswith("+logits"), mode.endswith("+metrics")
+    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode.split("+")[0], record_logits=rec, metrics=met)
 
 
 def ms_per_collect(ro, n):
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--collects", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
+    ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends only its lines to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_episodes.log"))
     a = ap.parse_args()
     N, T, H = a.arenas, a.steps, a.horizon
@@ -74,7 +79,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ())
+    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ()) + \
+        (("complete_episodes+metrics",) if a.metrics else ())
     runs = {m: make(N, T, H, m) for m in modes}
     ro = runs["complete_episodes"]
     ep = ro.episodes
@@ -93,6 +99,11 @@ def main():
     tr, ce = statistics.median(times["truncate_episodes"]), statistics.median(times["complete_episodes"])
     say(f"median ms per collect: truncate_episodes {tr:.3f} | complete_episodes {ce:.3f} | emission {ce - tr:.3f} ms = "
         f"{100 * (ce - tr) / ce:.2f} % of a complete_episodes collect (target: 0.5 ms)")
+    if a.metrics:
+        mlines = [f"# tools/commander_episodes_bench.py --metrics on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per collect, "
+                  f"horizon {H}, {a.collects} collects x {a.rounds} rounds after {a.warmup}"]
+        mlines += metrics_lines(runs["complete_episodes+metrics"].episodes, tr, ce, statistics.median(times["complete_episodes+metrics"]))
+        print("\n".join(mlines), flush=True)
     if a.logits:
         trl, cel = statistics.median(times["truncate_episodes+logits"]), statistics.median(times["complete_episodes+logits"])
         say(f"with the logits column: truncate_episodes+logits {trl:.3f} (the sampler's logits stores: {trl - tr:+.3f} ms) | complete_episodes+logits "
@@ -127,8 +138,8 @@ def main():
     say(f"hh_k_ep_emit (the commander's instance) moves {mb:.1f} MB per collect (row gather, sequence-start states, carry rewrite): at "
         f"6.3 TB/s that is {mb / 6.3e3 * 1e3:.1f} us; at the measured emission above {mb / max(ce - tr, 1e-9):.0f} GB/s over the whole emission")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    with open(a.out, "a" if a.metrics else "w") as f:       # --metrics: its own lines only, after what the log holds
+        f.write("\n".join(mlines if a.metrics else lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -6,7 +6,11 @@ collects.  Level 3 fight (horizon 300), random-init Fight1/Fight2 policies, one 
 gives what writing the logits costs the sampler, the complete pair what the emission costs with the column.  The bytes the emission moves
 per collect are counted from the batch and carry counts, so that a time (this tool's difference, or hh_k_ep_emit's in a separate
 rocprofv3 --kernel-trace run) becomes bytes/s.
-    python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]"""
+--metrics adds complete_episodes with metrics=True (the episode metrics behind the emitter, hh_episodes_metrics): what the flag costs a
+collect (against complete_episodes without it, whose launches are the ones from before the flag existed), next to the emission's own
+overhead, and the time of the three metrics launches alone on the last batch; those lines are appended to --out.
+    python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]
+        [--metrics [--out profiles/episode_emit.log]]"""
 import argparse
 import os
 import statistics
@@ -18,11 +22,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hhmarl_2d_amd import pilots  # noqa: E402
 from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
+from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
 
 
 def make(N, T, mode):
     w = World(make_config(n_arenas=N, level=3, seed=1, auto_reset=True), device=0)
     bank = pilots.PolicyBank.trainable_init(w.device, seed=0, max_rows=2 * N)
+    if mode.endswith("+metrics"):
+        return PPORollout(w, bank, T, batch_mode=mode[:-len("+metrics")], metrics=True)
     if mode.endswith("+logits"):
         return PPORollout(w, bank, T, batch_mode=mode[:-len("+logits")], record_logits=True)
     return PPORollout(w, bank, T, batch_mode=mode)
@@ -59,9 +66,12 @@ def main():
     ap.add_argument("--collects", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
+    ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends its lines to --out")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "episode_emit.log"))
     a = ap.parse_args()
     N, T = a.arenas, a.ticks
-    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ())
+    modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ()) + \
+        (("complete_episodes+metrics",) if a.metrics else ())
     runs = {m: make(N, T, m) for m in modes}
     ep = runs["complete_episodes"].episodes
     print(f"{N} arenas x {T} ticks per collect, level 3 fight, horizon {runs['complete_episodes'].w.cfg.horizon}; "
@@ -85,6 +95,13 @@ def main():
         print(f"with the logits column: truncate_episodes+logits {trl:.3f} (the sampler's logits stores: {trl - tr:+.3f} ms) | complete_episodes+logits "
               f"{cel:.3f} | emission overhead {cel - trl:.3f} ms = {100 * (cel - trl) / trl:.2f} % of a collect; {(cel - trl) / max(ce - tr, 1e-9):.2f} x the "
               f"emission without the column")
+    if a.metrics:
+        lines = [f"# tools/episode_emit_bench.py --metrics on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, "
+                 f"{a.collects} collects x {a.rounds} rounds after {a.warmup}"]
+        lines += metrics_lines(runs["complete_episodes+metrics"].episodes, tr, ce, statistics.median(times["complete_episodes+metrics"]))
+        print("\n".join(lines))
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
     for m, dt in over.items():      # the bytes the emission moves, over a few steady-state collects of that rollout
         r, e = runs[m], runs[m].episodes
         nb = []
