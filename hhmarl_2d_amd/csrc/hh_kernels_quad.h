@@ -359,6 +359,13 @@ __device__ __forceinline__ bool q_any(bool x) {
     return b != 0ULL;
 }
 
+/* arm_cannon(m) on the lanes where `cond` holds, as a select: the same field, the same value, no exec-mask region */
+__device__ __forceinline__ void arm_cannon_if(Unit &m, bool cond) {
+    const int b = HH_AC_BURST(m.ac_type);
+    const int armed = m.cannon_remain < b ? m.cannon_remain : b;
+    m.burst = cond ? armed : m.burst;
+}
+
 /* ordering point between LDS accesses of ONE wave (the LDS unit executes a wave's instructions in order, so this
  * only has to stop the compiler from moving them and to drain the counter); the two-wave kernel below cannot use
  * __syncthreads() inside the simulation wave — that would be a workgroup barrier the output wave does not take */
@@ -443,16 +450,19 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
      * read), the post-tick table on return: computed once per tick, straight-line on every lane, instead of once per reader */
     constexpr int A = 4;
     const int id = s + 1;
-    const bool running = active && !ar.done;
+    const bool running = active & (ar.done == 0); /* lane predicates are combined with &, not &&: a short-circuit is a branch */
     const bool agent = s < 2;
     out.reward = 0.0;
     out.valid = 0;
     out.kill_event = 0;
     uint32_t evm = 0;
-    if (OWT && HH_USUAL(pre.ok)) { /* wave-uniform: the key of this tick was computed by the output wave during the last one */
-        if (running) { ar.steps += 1; ar.tkey = pre.tkey; }
-    } else if (running) { ar.steps += 1; arena_rekey(ar); }
-    const bool snap = running && m.alive;
+    {
+        const int steps1 = ar.steps + 1;
+        ar.steps = running ? steps1 : ar.steps;
+        if (OWT && HH_USUAL(pre.ok)) ar.tkey = running ? pre.tkey : ar.tkey; /* wave-uniform: the key of this tick was computed by the output wave during the last one */
+        else if (running) arena_rekey(ar);
+    }
+    const bool snap = running & (m.alive != 0);
     const int amask0 = tb.amask; /* alive at tick start, by absolute slot */
     /* rocket_unit.py:25-35 speed profile of this slot's rocket (a launch in this tick starts at age 0).  Looked up
      * here, a whole phase before its use, so the table read is off the critical path. */
@@ -489,15 +499,18 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
 #ifdef HHQ_ABL_DECODE /* tuning builds only (tools/build_variant.sh): WRONG RESULTS on purpose, timing of what a piece costs */
             m.cmd_hdg = m.hdg; m.cmd_spd = 300.0;
 #else
-            double nh = hh_pymod360(m.hdg + (double)(((int)act[0] - 6) * 15));
-            if (nh >= 360.0 || nh < 0.0) nh = 0.0;
-            m.cmd_hdg = nh;
+            const double nh = hh_pymod360(m.hdg + (double)(((int)act[0] - 6) * 15));
+            const bool nh_out = (nh >= 360.0) | (nh < 0.0);
+            m.cmd_hdg = nh_out ? 0.0 : nh;
             double mx = HH_AC_MAX_SPEED(m.ac_type);
             m.cmd_spd = 100.0 + ((mx - 100.0) / 8.0) * (double)act[1];
 #endif
-            if (HH_USUAL(act[2] && m.cannon_remain > 0)) {
-                arm_cannon(m);
-                if (agent && c.agent_mode == HH_MODE_ESCAPE && m.cannon_remain < 90) out.reward -= 0.1;
+            { /* fire_cannon and the escape mode's ammunition penalty as selects */
+                const bool arm = (act[2] != 0) & (m.cannon_remain > 0);
+                arm_cannon_if(m, arm);
+                const double rw = out.reward - 0.1;
+                const bool pen = arm & agent & (c.agent_mode == HH_MODE_ESCAPE) & (m.cannon_remain < 90);
+                out.reward = pen ? rw : out.reward;
             }
             {
                 const bool gate = (m.ac_type == 1) & (act[3] != 0) & (t != 0) & (m.missile_remain > 0) & (m.has_missile == 0) & (m.missile_wait == 0);
@@ -591,19 +604,19 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
         }
     }
     } else { /* spec: apply what the output wave decided (same functions, same operands) */
-        if (HH_USUAL(running)) {
-            ar.escaping = (pre.sp_w >> 8) & 0xff;
-            ar.escaping_time = (int)(int8_t)((pre.sp_w >> 16) & 0xff);
-            if (HH_USUAL(snap && !agent)) {
-                const int opp = ((pre.sp_w >> 2) & 7) - 1;
-                m.cmd_hdg = pre.sp_hdg;
-                m.cmd_spd = pre.sp_spd;
-                if (pre.sp_w & 1) arm_cannon(m);
-                if ((pre.sp_w & 2) && opp >= 0 && !m.has_missile && m.missile_wait == 0 && m.ac_type == 1) {
-                    want_launch = 1; launch_tgt = opp; wait_after = 10;
-                }
-            }
-        }
+        /* one set of selects: the arena's words under `running`, the opponent's under ONE lane predicate */
+        const int esc_w = (pre.sp_w >> 8) & 0xff, esc_t_w = (int)(int8_t)((pre.sp_w >> 16) & 0xff);
+        ar.escaping = running ? esc_w : ar.escaping;
+        ar.escaping_time = running ? esc_t_w : ar.escaping_time;
+        const bool opl = snap & !agent;
+        const int opp = ((pre.sp_w >> 2) & 7) - 1;
+        m.cmd_hdg = opl ? pre.sp_hdg : m.cmd_hdg;
+        m.cmd_spd = opl ? pre.sp_spd : m.cmd_spd;
+        arm_cannon_if(m, opl & ((pre.sp_w & 1) != 0));
+        const bool lm = opl & ((pre.sp_w & 2) != 0) & (opp >= 0) & (m.has_missile == 0) & (m.missile_wait == 0) & (m.ac_type == 1);
+        want_launch = lm ? 1 : want_launch;
+        launch_tgt = lm ? opp : launch_tgt;
+        wait_after = lm ? 10 : wait_after;
     }
 
     HH_PROF(0);
@@ -612,8 +625,17 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
     bool fired = false;
     const int rk_pre = m.rk_alive;
     const int has_missile_pre = m.has_missile;
-    const bool try_launch = want_launch && !m.has_missile && m.missile_remain > 0; /* ac1.py:73 */
+    const bool try_launch = (want_launch != 0) & (m.has_missile == 0) & (m.missile_remain > 0); /* ac1.py:73 */
     double turn_deg = 0.0;
+    /* the guidance noise of this slot's rocket: read by the steering of a rocket in flight (below) and by a launch in this tick (the speculative
+     * move).  The mailbox's draw as a rule; the tick's own draw — the same site, the same key — is taken ONCE, in front of both uses, behind one
+     * wave-uniform test: while !a_ok, and only when some lane of the wave reads it */
+    const bool steer = snap & (m.has_missile != 0) & (m.rk_alive != 0);
+    double u_noise = u_noise_ahead;
+    if (HH_RARE(!a_ok)) { /* wave-uniform */
+        const bool rd = steer | (running & !rk_pre & try_launch);
+        if (q_any(rd)) if (rd) u_noise = d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0);
+    }
     if (HH_USUAL(snap)) {
         int t = m.ac_type;
         {
@@ -633,38 +655,39 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
             const double ns = hh_fabs(delta) <= max_delta ? m.cmd_spd : stepped;
             m.spd = m.spd != m.cmd_spd ? ns : m.spd;
         }
-        if (HH_USUAL(m.burst > 0)) {
-            fired = true;
-            m.burst = m.burst - 1 > 0 ? m.burst - 1 : 0;
-            m.cannon_remain = m.cannon_remain - 1 > 0 ? m.cannon_remain - 1 : 0;
+        { /* the cannon burst's countdown as selects */
+            const bool bt = m.burst > 0;
+            const int b1 = m.burst - 1 > 0 ? m.burst - 1 : 0, c1 = m.cannon_remain - 1 > 0 ? m.cannon_remain - 1 : 0;
+            fired = bt;
+            m.burst = bt ? b1 : m.burst;
+            m.cannon_remain = bt ? c1 : m.cannon_remain;
         }
         { /* ac1.py:117-128, rocket launched in an earlier step */
-            const bool steer = (m.has_missile != 0) & (m.rk_alive != 0);
-            if (HH_USUAL(steer)) {
-                double un = u_noise_ahead;
-                if (HH_RARE(!a_ok)) un = d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0); /* wave-uniform */
-                m.rk_cmd = hh_clip(m.rk_hdg * hh_rng_uniform(un, 0.95, 1.05), 0.0, 359.0);
-            }
+            const double cmd = hh_clip(m.rk_hdg * hh_rng_uniform(u_noise, 0.95, 1.05), 0.0, 359.0);
+            m.rk_cmd = steer ? cmd : m.rk_cmd;
             m.has_missile = ((m.has_missile != 0) & (m.rk_alive == 0)) ? 0 : m.has_missile;
         }
     }
     /* aircraft move + speculative move of this slot's rocket (in flight, or the one a pending launch creates) */
-    const bool rk_spec = running && (rk_pre ? m.rk_life <= HH_ROCKET_MAX_LIFE : try_launch);
+    const bool rk_life_ok = m.rk_life <= HH_ROCKET_MAX_LIFE;
+    const bool rk_spec = running & (rk_pre ? rk_life_ok : try_launch);
     double rk_nlat = 0.0, rk_nlon = 0.0, rk_nhdg = 0.0, rk_ncmd = 0.0;
     {
-        const bool mv_a = snap && m.spd > 0.0;
-        const bool any_rk = __ballot(rk_spec) != 0ULL;
+        const bool mv_a = snap & (m.spd > 0.0);
+        /* "a rocket in the wave" is ONE test, and none in the 8-arena form: there some lane of the wave has a rocket in flight or a launch pending on
+         * almost every tick, every value below selects cleanly (a lane without a rocket moves the dummy point and nobody reads the result), and
+         * at one wave per SIMD three uniform branches cost more than the instructions they skip.  The single-wave forms are VALU-bound and keep the test. */
+        const bool any_rk = DUAL || __ballot(rk_spec) != 0ULL;
         double r_lat = 5.0, r_lon = 7.0, r_hdg = 0.0;
         if (HH_USUAL(any_rk)) {
             r_lat = rk_pre ? m.rk_lat : lat_old; r_lon = rk_pre ? m.rk_lon : lon_old;
             r_hdg = rk_pre ? m.rk_hdg : hdg_old;
             rk_ncmd = m.rk_cmd;
-            if (HH_RARE(q_any(!rk_pre & rk_spec))) /* a launch in this tick: rare */
-                if (!rk_pre) {
-                    double un = u_noise_ahead;
-                    if (HH_RARE(!a_ok)) un = d_rng(ar, id, HH_SITE_ROCKET_NOISE, 0); /* wave-uniform */
-                    rk_ncmd = hh_clip(hdg_old * hh_rng_uniform(un, 0.95, 1.05), 0.0, 359.0);
-                }
+            const bool launch_new = !rk_pre & rk_spec;
+            if (HH_RARE(q_any(launch_new))) { /* a launch in this tick: rare */
+                const double cmd = hh_clip(hdg_old * hh_rng_uniform(u_noise, 0.95, 1.05), 0.0, 359.0);
+                rk_ncmd = launch_new ? cmd : rk_ncmd;
+            }
             {
                 const double delta = d_signed_heading_diff(r_hdg, rk_ncmd);
                 const double stepped = r_hdg + (delta >= 0.0 ? HH_ROCKET_TURN_RATE : -HH_ROCKET_TURN_RATE);
@@ -677,7 +700,7 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
             /* ONE chain per lane: the main lane moves the aircraft, its helper the rocket (d_geo_move2's two interleaved chains give
              * the same bits as d_geo_move of each argument set) */
             double x_lat = m.lat, x_lon = m.lon, x_hdg = m.hdg, x_s = mv_a ? m.spd * HH_KNOTS_TO_MS * 1.0 : 0.0;
-            if (HH_USUAL(any_rk)) {
+            {
                 const double h_lat = q_down_d(rk_spec ? r_lat : 5.0), h_lon = q_down_d(rk_spec ? r_lon : 7.0);
                 const double h_hdg = q_down_d(r_hdg), h_s = q_down_d(rk_speed0 * HH_KNOTS_TO_MS * 1.0);
                 x_lat = helper ? h_lat : x_lat; x_lon = helper ? h_lon : x_lon; x_hdg = helper ? h_hdg : x_hdg; x_s = helper ? h_s : x_s;
@@ -688,14 +711,14 @@ __device__ __forceinline__ void tick_quad(const DevCfg &c, Shared<4, 64> &sh, in
 #else
             d_geo_move(x_lat, x_lon, x_hdg, x_s, o_lat, o_lon);
 #endif
-            if (mv_a) { m.lat = o_lat; m.lon = o_lon; }
-            if (HH_USUAL(any_rk)) { rk_nlat = q_up_d(o_lat); rk_nlon = q_up_d(o_lon); }
+            m.lat = mv_a ? o_lat : m.lat; m.lon = mv_a ? o_lon : m.lon;
+            rk_nlat = q_up_d(o_lat); rk_nlon = q_up_d(o_lon);
         } else if (HH_USUAL(any_rk)) {
             const double r_spd = rk_speed0;
             double a_lat, a_lon;
             d_geo_move2(m.lat, m.lon, m.hdg, mv_a ? m.spd * HH_KNOTS_TO_MS * 1.0 : 0.0, a_lat, a_lon,
                         rk_spec ? r_lat : 5.0, rk_spec ? r_lon : 7.0, r_hdg, r_spd * HH_KNOTS_TO_MS * 1.0, rk_nlat, rk_nlon);
-            if (mv_a) { m.lat = a_lat; m.lon = a_lon; }
+            m.lat = mv_a ? a_lat : m.lat; m.lon = mv_a ? a_lon : m.lon;
         } else {
             if (mv_a) d_geo_move(m.lat, m.lon, m.hdg, m.spd * HH_KNOTS_TO_MS * 1.0, m.lat, m.lon);
         }
@@ -1407,6 +1430,10 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
     pre.ok = false; pre.spec = false; pre.sp_hdg = pre.sp_spd = 0.0; pre.sp_w = 0;
     pre.tkey = 0ULL; pre.sx = pre.sy = 0.0;
     pre.a_ok = false; pre.a_par = 0;
+    /* c.inv_diag as the block behind barrier Y multiplies by it, held in a vector register pair: as a scalar it is one of sixteen configuration words that
+     * are spilled to lanes as a group, and the whole group comes back (16 v_readlane) on every tick for this one product */
+    double inv_diag_v = c.inv_diag;
+    if constexpr (OWT) asm volatile("" : "+v"(inv_diag_v));
     bool noreset_prev = false; /* the tick before ran in this launch and reset nothing: with the same of this tick, what QAheadMail's validity asks */
     const size_t act_stride = (size_t)c.N * c.n_ctrl * 4;
     const int8_t *act_ptr = has_act ? actions + ((size_t)n * c.n_ctrl + s) * 4 : actions; /* lanes without a row re-read row 0, unused */
@@ -1484,21 +1511,28 @@ __global__ __launch_bounds__(TWO ? 128 : 64, W) __attribute__((amdgpu_waves_per_
             HH_PROF(9);
             __syncthreads(); /* barrier Y */
             HH_PROF(13);
+            /* the usual path's words are requested HERE, in front of the ballot and the branches that decide which of them count, so that the LDS
+             * latency runs under the tests: the mailbox is always readable, and on a reset tick (or behind a changed alive mask) the words are merely unused */
+            const unsigned long long m_tk = mbx.tab.tk[tid];
+            const double m_sx = mbx.tab.sx[tid], m_sy = mbx.tab.sy[tid], m_uc = mbx.tab.uc[tid], m_us = mbx.tab.us[tid];
+            const double m_sp_hdg = mbx.tab.sp_hdg[tid], m_sp_spd = mbx.tab.sp_spd[tid];
+            const int m_sp_w = mbx.tab.sp_w[tid], m_nbw = mbx.tab.nbw[tid];
+            const double m_nr0 = mbx.tab.nr0[tid], m_nfoc = mbx.tab.nfoc[tid], m_nfocr = mbx.tab.nfocr[tid];
             pre.ok = !reset_tick;
             pre.a_ok = !reset_tick && noreset_prev;
             noreset_prev = !reset_tick;
             pre.a_par = (t + 1) & 1;
             pre.spec = !reset_tick && !q_any(active && tb.amask != amask_before);
             if (HH_USUAL(!reset_tick)) { /* wave-uniform: take what the output wave built while this wave ran the envelope phases, and what it computed ahead */
-                pre.tkey = mbx.tab.tk[tid]; pre.sx = mbx.tab.sx[tid]; pre.sy = mbx.tab.sy[tid];
-                pub.uc = mbx.tab.uc[tid]; pub.us = mbx.tab.us[tid]; /* the exact heading vector (the tick carried a rotated one) */
-                pre.sp_hdg = mbx.tab.sp_hdg[tid]; pre.sp_spd = mbx.tab.sp_spd[tid]; pre.sp_w = mbx.tab.sp_w[tid];
+                pre.tkey = m_tk; pre.sx = m_sx; pre.sy = m_sy;
+                pub.uc = m_uc; pub.us = m_us; /* the exact heading vector (the tick carried a rotated one) */
+                pre.sp_hdg = m_sp_hdg; pre.sp_spd = m_sp_spd; pre.sp_w = m_sp_w;
                 if (HH_USUAL(pre.spec)) { /* wave-uniform: no alive mask of the wave changed — the output wave's _nearby_object and target entries are this tick's (QTgt) */
-                    const int w = mbx.tab.nbw[tid];
-                    const double r0 = mbx.tab.nr0[tid];
-                    tg.foc = mbx.tab.nfoc[tid]; tg.focr = mbx.tab.nfocr[tid]; tg.dist = r0;
+                    const int w = m_nbw;
+                    const double r0 = m_nr0;
+                    tg.foc = m_nfoc; tg.focr = m_nfocr; tg.dist = r0;
                     nbc.n = w & 3; nbc.j0 = (w >> 2) & 3; nbc.k0 = (w >> 4) & 3;
-                    nbc.r0 = r0; nbc.d0 = c.inv_diag * r0; /* quad_nearby's own product (r0 = 0 without a live opponent) */
+                    nbc.r0 = r0; nbc.d0 = inv_diag_v * r0; /* quad_nearby's own product (r0 = 0 without a live opponent) */
                     nbc.j1 = nbc.k1 = 0; nbc.d1 = nbc.r1 = 0.0; /* the second entry is read by escape-mode rows and the escape shaping only: never on this wave */
                 } else { /* somebody was removed: the table's distances with the new alive mask */
                     QTab tf = tb;
