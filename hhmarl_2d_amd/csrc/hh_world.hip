@@ -218,22 +218,82 @@ extern "C" int hh_trace_read(hh_world *w, float *rows, int32_t *count) {
 extern "C" int hh_obs_dim(const hh_world *w) { return w ? w->dc.D : HH_E_ARG; }
 extern "C" int hh_n_ctrl(const hh_world *w) { return w ? w->dc.n_ctrl : HH_E_ARG; }
 
+/* ---- which template instance a call launches: ONE decision per kernel family.  The launchers below, hh_rollout_kernel_name and
+ * hh_kernel_instance all read these three functions, so a name can never describe another kernel than the one that runs (the policy
+ * side does the same with hhp_choose_form, hh_policy_kernel.h). ---- */
+struct QuadForm {  /* LowLevelEnv rollouts / steps: hh_k_world_quad<two ? 2 : 1, pre, pair, half ? 8 : 16, dual, !noshape>, or hh_k_world<4, 64, two ? 2 : 1, false> */
+    bool quad;     /* the register-exchange kernel (hh_kernels_quad.h); false: the generic LDS-exchange kernel (HH_NO_QUAD=1, tracing) */
+    bool two;      /* more waves than SIMDs (or HH_FORCE_W=2): hold two per SIMD */
+    bool pair;     /* small worlds (every workgroup resident with a SIMD pair to itself): simulation wave + output wave per group */
+    bool half;     /* smaller still (the two-wave form of 8-arena groups fits one wave per SIMD): 8 arenas per simulation wave */
+    int pre;       /* the preset instance that runs — 1: level 3 fight, 2 / 3: levels 1 / 2 fight, 4: level 3 escape, 0: general (hh_kernels_quad.h) */
+    bool noshape;  /* a general two-wave instance without the escape distance shaping: the pair table goes to the output wave like in the presets (SHAPE = false) */
+    bool dual;     /* the 8-arena form with helper lanes */
+};
+static QuadForm hh_choose_quad(const hh_world *w) {
+    const DevCfg &c = w->dc;
+    QuadForm f;
+    const int waves = (c.N + 15) / 16, grid8 = (c.N + 7) / 8;   /* one wave per 16-arena workgroup */
+    f.quad = !w->no_quad && !w->P.trace; /* tracing runs on the generic kernel */
+    f.two = w->force_w == 2 || (w->force_w == 0 && waves > w->n_simd);
+    f.pair = f.quad && !f.two && !w->no_two && waves <= w->n_simd / 2; /* 128-thread groups at one wave per SIMD: two per CU resident */
+    f.half = f.pair && w->apw != 16 && 2 * grid8 <= w->n_simd;
+    f.pre = (!f.quad || w->no_spec) ? 0 : hh_cfg_preset(c);
+    if (f.pair && !f.half && f.pre != 1) f.pre = 0; /* 16 arenas per wave, two waves (4097..8192 arenas): the benchmark's preset only */
+    f.noshape = f.pair && f.pre == 0 && !w->no_owt && !(c.esc_dist_rew && c.agent_mode == HH_MODE_ESCAPE);
+    f.dual = f.half && !w->no_dual;
+    return f;
+}
+
+struct HierForm {  /* HighLevelEnv */
+    bool wide;     /* ten unit slots (more than three aircraft on a side): six ten-lane arenas per wave on the LDS-exchange kernels, W = 1 */
+    bool oct;      /* the register-exchange form (hh_kernels_oct.h): one arena per 8-lane group */
+    bool two;      /* two waves per SIMD: by the 8-arena grid in the register-exchange form, by the 10-arena grid in the LDS form */
+    bool half;     /* LDS macro step only: 8 arenas per wave while every workgroup still has a SIMD of its own */
+    bool hld;      /* macro step only: the instance compiled for the reference's default HighLevelEnv configuration */
+};
+/* the phase launches (hh_hl_begin / hh_hl_agents_act / hh_hl_tick / hh_hl_end; reset and refresh always run on the LDS form) */
+static HierForm hh_choose_hier(const hh_world *w, int phase) {
+    const DevCfg &c = w->dc;
+    HierForm f;
+    const int grid = (c.N + 9) / 10, grid8 = (c.N + 7) / 8;
+    f.wide = c.A == 10;
+    f.oct = !f.wide && !w->no_oct && phase <= HH_HL_END;
+    /* the W = 2 instance of the LDS form stages the pilot rows per SIDE (three slots each): n-vs-m arenas use its W = 1 instance */
+    f.two = f.wide ? false : f.oct ? (w->force_w == 2 || (w->force_w == 0 && grid8 > w->n_simd))
+                                   : ((w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd)) && c.nA == 3 && c.nO == 3);
+    f.half = false; f.hld = false;
+    return f;
+}
+/* hh_hl_rollout */
+static HierForm hh_choose_macro(const hh_world *w) {
+    const DevCfg &c = w->dc;
+    HierForm f;
+    const int grid = (c.N + 9) / 10, grid8 = (c.N + 7) / 8;
+    f.wide = c.A == 10;
+    f.oct = !f.wide && !w->no_oct;
+    f.two = f.wide ? false : w->force_w == 2 || (w->force_w == 0 && (f.oct ? grid8 : grid) > w->n_simd);
+    f.half = !f.wide && !f.oct && !f.two && w->apw != 16 && grid8 <= w->n_simd;
+    f.hld = !f.wide && !w->no_spec && hh_cfg_is_hl_default(c);
+    return f;
+}
+
 static int launch_hier(hh_world *w, int phase, const int8_t *cmd, const int8_t *actions, float *pilot_obs, uint8_t *pilot_mode,
                        float *obs, float *reward, uint8_t *valid, uint8_t *done, const uint8_t *mask, hipStream_t st) {
     const DevCfg &c = w->dc;
     if (w->cfg.env_kind != HH_ENV_HIGHLEVEL || (c.A != 6 && c.A != 10)) { g_err = "not a HighLevelEnv world"; return HH_E_ARG; }
     HH_GUARD(w);
-    if (c.A == 10) { /* more than three aircraft on a side: six ten-lane arenas per wave on the LDS-exchange kernel */
+    const HierForm f = hh_choose_hier(w, phase);
+    if (f.wide) {
         hipLaunchKernelGGL((hh_k_hier<10, HH_BLOCK, 1>), dim3((c.N + 5) / 6), dim3(HH_BLOCK), 0, st, w->P, c, phase, cmd, actions, pilot_obs, pilot_mode, obs,
                            reward, valid, done, w->counter, mask);
         HIPCHK(hipGetLastError());
         return HH_OK;
     }
-    if (!w->no_oct && phase <= HH_HL_END) { /* register-exchange form (hh_kernels_oct.h): one arena per 8-lane group */
+    if (f.oct) {
         const int grid8 = (c.N + 7) / 8;
-        const bool two8 = w->force_w == 2 || (w->force_w == 0 && grid8 > w->n_simd);
 #define HH_LAUNCH_OCT(W_, PH_) hipLaunchKernelGGL((hh_k_hier_oct<W_, PH_>), dim3(grid8), dim3(64), 0, st, w->P, c, cmd, actions, pilot_obs, pilot_mode, obs, reward, valid, done, w->counter)
-#define HH_LAUNCH_OCT_W(PH_) do { if (two8) HH_LAUNCH_OCT(2, PH_); else HH_LAUNCH_OCT(1, PH_); } while (0)
+#define HH_LAUNCH_OCT_W(PH_) do { if (f.two) HH_LAUNCH_OCT(2, PH_); else HH_LAUNCH_OCT(1, PH_); } while (0)
         switch (phase) {
         case HH_HL_BEGIN: HH_LAUNCH_OCT_W(HH_HL_BEGIN); break;
         case HH_HL_AGENTS_ACT: HH_LAUNCH_OCT_W(HH_HL_AGENTS_ACT); break;
@@ -246,10 +306,8 @@ static int launch_hier(hh_world *w, int phase, const int8_t *cmd, const int8_t *
         return HH_OK;
     }
     constexpr int B = HH_BLOCK, GPB = B / 6;
-    int grid = (c.N + GPB - 1) / GPB;
-    /* the W = 2 instance stages the pilot rows per SIDE (three slots each): n-vs-m arenas use the W = 1 instance */
-    const bool two = (w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd)) && c.nA == 3 && c.nO == 3;
-    if (two)
+    const int grid = (c.N + GPB - 1) / GPB;
+    if (f.two)
         hipLaunchKernelGGL((hh_k_hier<6, B, 2>), dim3(grid), dim3(B), 0, st, w->P, c, phase, cmd, actions, pilot_obs, pilot_mode, obs, reward,
                            valid, done, w->counter, mask);
     else
@@ -269,33 +327,24 @@ static int launch(hh_world *w, int run, int T, const int8_t *actions, const uint
     if (c.A != 4) { g_err = "LowLevelEnv worlds are 2-vs-2"; return HH_E_ARG; }
     HH_GUARD(w);
     constexpr int B = HH_BLOCK, GPB = B / 4;
-    const int grid = (c.N + GPB - 1) / GPB;
-    const int waves = grid * (B / 64);
-    const bool two = w->force_w == 2 || (w->force_w == 0 && waves > w->n_simd); /* more waves than SIMDs: hold two per SIMD */
-    if (run == HH_RUN_ROLLOUT && !w->no_quad && !w->P.trace) { /* tracing runs on the generic kernel */
-        static_assert(B == 64, "the register-exchange kernel is one wave per workgroup");
-        const int pre = w->no_spec ? 0 : hh_cfg_preset(c); /* 1: level 3 fight, 2 / 3: levels 1 / 2 fight, 4: level 3 escape (hh_kernels_quad.h) */
-        /* small worlds (every workgroup resident with a SIMD pair to itself): simulation wave + output wave per 16 arenas */
-        const bool pair = !two && !w->no_two && waves <= w->n_simd / 2; /* 128-thread groups at one wave per SIMD: two per CU resident */
-        /* smaller still (the two-wave form of 8-arena groups fits one wave per SIMD): 8 arenas per simulation wave, hh_kernels_quad.h */
-        const int grid8 = (c.N + 7) / 8;
-        const bool half = pair && w->apw != 16 && 2 * grid8 <= w->n_simd;
+    static_assert(B == 64 && GPB == 16, "the register-exchange kernel is one wave per workgroup; hh_choose_quad counts 16 arenas per wave");
+    const int grid = (c.N + GPB - 1) / GPB, grid8 = (c.N + 7) / 8;
+    const QuadForm f = hh_choose_quad(w);
+    if (run == HH_RUN_ROLLOUT && f.quad) {
 #define HH_QLAUNCH(Wv, Pv, TWOv) hipLaunchKernelGGL((hh_k_world_quad<Wv, Pv, TWOv>), dim3(grid), dim3(TWOv ? 128 : 64), 0, st, w->P, c, T, actions, obs, reward, valid, done)
-#define HH_QLAUNCH8(Pv) do { if (w->no_dual) hipLaunchKernelGGL((hh_k_world_quad<1, Pv, true, 8>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); \
-                            else hipLaunchKernelGGL((hh_k_world_quad<1, Pv, true, 8, true>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); } while (0)
-        /* general two-wave instances without the escape distance shaping: the pair table goes to the output wave like in the presets (hh_kernels_quad.h: SHAPE) */
-        const bool noshape = pre == 0 && !w->no_owt && !(c.esc_dist_rew && c.agent_mode == HH_MODE_ESCAPE);
-#define HH_QLAUNCH8_NS() do { if (w->no_dual) hipLaunchKernelGGL((hh_k_world_quad<1, 0, true, 8, false, false>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); \
-                              else hipLaunchKernelGGL((hh_k_world_quad<1, 0, true, 8, true, false>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); } while (0)
-#define HH_QPRE(LAUNCH) switch (pre) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; default: LAUNCH(0); }
+#define HH_QLAUNCH8(Pv) do { if (f.dual) hipLaunchKernelGGL((hh_k_world_quad<1, Pv, true, 8, true>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); \
+                            else hipLaunchKernelGGL((hh_k_world_quad<1, Pv, true, 8>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); } while (0)
+#define HH_QLAUNCH8_NS() do { if (f.dual) hipLaunchKernelGGL((hh_k_world_quad<1, 0, true, 8, true, false>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); \
+                              else hipLaunchKernelGGL((hh_k_world_quad<1, 0, true, 8, false, false>), dim3(grid8), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done); } while (0)
+#define HH_QPRE(LAUNCH) switch (f.pre) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; default: LAUNCH(0); }
 #define HH_Q2(Pv) HH_QLAUNCH(2, Pv, false)
 #define HH_Q1(Pv) HH_QLAUNCH(1, Pv, false)
-        if (two) { HH_QPRE(HH_Q2) }
-        else if (half && noshape) { HH_QLAUNCH8_NS(); }
-        else if (half) { HH_QPRE(HH_QLAUNCH8) }
-        else if (pair) { /* 4097..8192 arenas: the benchmark's preset only */
-            if (pre == 1) HH_QLAUNCH(1, 1, true);
-            else if (!w->no_owt && !(c.esc_dist_rew && c.agent_mode == HH_MODE_ESCAPE))
+        if (f.two) { HH_QPRE(HH_Q2) }
+        else if (f.half && f.noshape) { HH_QLAUNCH8_NS(); }
+        else if (f.half) { HH_QPRE(HH_QLAUNCH8) }
+        else if (f.pair) { /* hh_choose_quad: preset 1 or general */
+            if (f.pre == 1) HH_QLAUNCH(1, 1, true);
+            else if (f.noshape)
                 hipLaunchKernelGGL((hh_k_world_quad<1, 0, true, 16, false, false>), dim3(grid), dim3(128), 0, st, w->P, c, T, actions, obs, reward, valid, done);
             else HH_QLAUNCH(1, 0, true);
         }
@@ -308,7 +357,7 @@ static int launch(hh_world *w, int run, int T, const int8_t *actions, const uint
 #undef HH_QLAUNCH8_NS
     } else if (run >= HH_RUN_LL_BEGIN)
         hipLaunchKernelGGL((hh_k_world<4, B, 1, true>), dim3(grid), dim3(B), 0, st, w->P, c, run, T, actions, mask, obs, reward, valid, done);
-    else if (two)
+    else if (f.two)
         hipLaunchKernelGGL((hh_k_world<4, B, 2, false>), dim3(grid), dim3(B), 0, st, w->P, c, run, T, actions, mask, obs, reward, valid, done);
     else
         hipLaunchKernelGGL((hh_k_world<4, B, 1, false>), dim3(grid), dim3(B), 0, st, w->P, c, run, T, actions, mask, obs, reward, valid, done);
@@ -316,28 +365,23 @@ static int launch(hh_world *w, int run, int T, const int8_t *actions, const uint
     return HH_OK;
 }
 
-/* which instance hh_rollout / hh_step launches for this world on this device (bench.py and profiles name it) */
+/* which instance hh_rollout / hh_step (LowLevelEnv) or the hh_hl_* phase launches (HighLevelEnv) run for this world on this device
+ * (bench.py and profiles name it) */
 extern "C" int hh_rollout_kernel_name(hh_world *w, char *buf, int32_t len) {
     if (!w || !buf || len <= 0) return HH_E_ARG;
-    const DevCfg &c = w->dc;
     if (w->cfg.env_kind != HH_ENV_LOWLEVEL) {
-        const int grid = (c.N + 9) / 10;
-        const bool two = (w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd)) && c.nA == 3 && c.nO == 3;
-        if (c.A == 10) snprintf(buf, (size_t)len, "hh_k_hier<10,64,1>");
-        else snprintf(buf, (size_t)len, "hh_k_hier<6,64,%d>", two ? 2 : 1);
+        const HierForm f = hh_choose_hier(w, HH_HL_TICK);
+        if (f.wide) snprintf(buf, (size_t)len, "hh_k_hier<10,64,1>");
+        else if (f.oct) snprintf(buf, (size_t)len, "hh_k_hier_oct<%d,phase>", f.two ? 2 : 1);
+        else snprintf(buf, (size_t)len, "hh_k_hier<6,64,%d>", f.two ? 2 : 1);
         return HH_OK;
     }
-    const int waves = (c.N + 15) / 16;
-    const bool two = w->force_w == 2 || (w->force_w == 0 && waves > w->n_simd);
-    int pre = w->no_spec ? 0 : hh_cfg_preset(c);
-    const bool pair = !two && !w->no_two && waves <= w->n_simd / 2;
-    const bool half = pair && w->apw != 16 && 2 * ((c.N + 7) / 8) <= w->n_simd;
-    if (w->no_quad) snprintf(buf, (size_t)len, "hh_k_world<4,64,%d,false>", two ? 2 : 1);
+    const QuadForm f = hh_choose_quad(w);
+    if (!f.quad) snprintf(buf, (size_t)len, "hh_k_world<4,64,%d,false>", f.two ? 2 : 1);
     else {
-        if (pair && !half && pre != 1) pre = 0;
         static const char *names[5] = {"general", "L3 fight", "L1 fight", "L2 fight", "L3 escape"};
-        snprintf(buf, (size_t)len, "hh_k_world_quad<W=%d,preset=%s,%s%s>", two ? 2 : 1, names[pre],
-                 pair ? "simulation wave + output wave" : "single wave", half ? (w->no_dual ? ",8 arenas per wave" : ",8 arenas per wave + helper lanes") : "");
+        snprintf(buf, (size_t)len, "hh_k_world_quad<W=%d,preset=%s,%s%s>", f.two ? 2 : 1, names[f.pre],
+                 f.pair ? "simulation wave + output wave" : "single wave", f.half ? (f.dual ? ",8 arenas per wave + helper lanes" : ",8 arenas per wave") : "");
     }
     return HH_OK;
 }
@@ -346,44 +390,25 @@ extern "C" int hh_rollout_kernel_name(hh_world *w, char *buf, int32_t len) {
  * counter evidence against.  which = 0: hh_rollout / hh_step (LowLevelEnv) or the hh_hl_* phase launches; 1: hh_hl_rollout */
 extern "C" int hh_kernel_instance(hh_world *w, int32_t which, char *buf, int32_t len) {
     if (!w || !buf || len <= 0) return HH_E_ARG;
-    const DevCfg &c = w->dc;
     if (w->cfg.env_kind != HH_ENV_LOWLEVEL) {
-        const int grid = (c.N + 9) / 10, grid8 = (c.N + 7) / 8;
-        if (c.A == 10) {
-            snprintf(buf, (size_t)len, which == 0 ? "hh_k_hier<10, 64, 1>" : "hh_k_hier_macro<10, 64, 1, false, 6>");
-            return HH_OK;
-        }
         if (which == 0) {
-            const bool two = (w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd)) && c.nA == 3 && c.nO == 3;
-            if (!w->no_oct) snprintf(buf, (size_t)len, "hh_k_hier_oct<%d, phase>", (w->force_w == 2 || (w->force_w == 0 && grid8 > w->n_simd)) ? 2 : 1);
-            else snprintf(buf, (size_t)len, "hh_k_hier<6, 64, %d>", two ? 2 : 1);
+            const HierForm f = hh_choose_hier(w, HH_HL_TICK);
+            if (f.wide) snprintf(buf, (size_t)len, "hh_k_hier<10, 64, 1>");
+            else if (f.oct) snprintf(buf, (size_t)len, "hh_k_hier_oct<%d, phase>", f.two ? 2 : 1);
+            else snprintf(buf, (size_t)len, "hh_k_hier<6, 64, %d>", f.two ? 2 : 1);
             return HH_OK;
         }
-        const bool hld = !w->no_spec && hh_cfg_is_hl_default(c);
-        if (!w->no_oct) {
-            const bool two8 = w->force_w == 2 || (w->force_w == 0 && grid8 > w->n_simd);
-            snprintf(buf, (size_t)len, "hh_k_hier_macro_oct<%d, %s>", two8 ? 2 : 1, hld ? "true" : "false");
-            return HH_OK;
-        }
-        const bool two = w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd);
-        const bool half = !two && w->apw != 16 && grid8 <= w->n_simd;
-        snprintf(buf, (size_t)len, "hh_k_hier_macro<6, 64, %d, %s, %d>", two ? 2 : 1, hld ? "true" : "false", half ? 8 : 10);
+        const HierForm f = hh_choose_macro(w);
+        if (f.wide) snprintf(buf, (size_t)len, "hh_k_hier_macro<10, 64, 1, false, 6>");
+        else if (f.oct) snprintf(buf, (size_t)len, "hh_k_hier_macro_oct<%d, %s>", f.two ? 2 : 1, f.hld ? "true" : "false");
+        else snprintf(buf, (size_t)len, "hh_k_hier_macro<6, 64, %d, %s, %d>", f.two ? 2 : 1, f.hld ? "true" : "false", f.half ? 8 : 10);
         return HH_OK;
     }
-    const int waves = (c.N + 15) / 16;
-    const bool two = w->force_w == 2 || (w->force_w == 0 && waves > w->n_simd);
-    int pre = w->no_spec ? 0 : hh_cfg_preset(c);
-    const bool pair = !two && !w->no_two && waves <= w->n_simd / 2;
-    const bool half = pair && w->apw != 16 && 2 * ((c.N + 7) / 8) <= w->n_simd;
-    if (w->no_quad || w->P.trace) snprintf(buf, (size_t)len, "hh_k_world<4, 64, %d, false>", two ? 2 : 1);
-    else {
-        if (pair && !half && pre != 1) pre = 0;
-        const bool noshape = pair && pre == 0 && !w->no_owt && !(c.esc_dist_rew && c.agent_mode == HH_MODE_ESCAPE);
-        /* six template arguments, as a profiler prints the instance: W, PRE, TWO, APW, DUAL, SHAPE */
-        if (noshape) snprintf(buf, (size_t)len, "hh_k_world_quad<1, 0, true, %d, %s, false>", half ? 8 : 16, (half && !w->no_dual) ? "true" : "false");
-        else if (half && !w->no_dual) snprintf(buf, (size_t)len, "hh_k_world_quad<1, %d, true, 8, true, true>", pre);
-        else snprintf(buf, (size_t)len, "hh_k_world_quad<%d, %d, %s, %d, false, true>", two ? 2 : 1, pre, pair ? "true" : "false", half ? 8 : 16);
-    }
+    const QuadForm f = hh_choose_quad(w);
+    if (!f.quad) snprintf(buf, (size_t)len, "hh_k_world<4, 64, %d, false>", f.two ? 2 : 1);
+    else /* six template arguments, as a profiler prints the instance: W, PRE, TWO, APW, DUAL, SHAPE */
+        snprintf(buf, (size_t)len, "hh_k_world_quad<%d, %d, %s, %d, %s, %s>", f.two ? 2 : 1, f.pre, f.pair ? "true" : "false", f.half ? 8 : 16,
+                 f.dual ? "true" : "false", f.noshape ? "false" : "true");
     return HH_OK;
 }
 
@@ -719,33 +744,29 @@ extern "C" int hh_hl_rollout(hh_world *w, const int8_t *commander_actions, const
     const DevCfg &c = w->dc;
     if (w->cfg.env_kind != HH_ENV_HIGHLEVEL || (c.A != 6 && c.A != 10)) { g_err = "not a HighLevelEnv world"; return HH_E_ARG; }
     HH_GUARD(w);
-    if (c.A == 10) {
+    const HierForm f = hh_choose_macro(w);
+    if (f.wide) {
         hipLaunchKernelGGL((hh_k_hier_macro<10, HH_BLOCK, 1, false>), dim3((c.N + 5) / 6), dim3(HH_BLOCK), 0, (hipStream_t)stream, w->P, c, commander_actions,
                            pilot_tape, obs, reward, reward_valid, done, w->counter);
         HIPCHK(hipGetLastError());
         return HH_OK;
     }
     constexpr int B = HH_BLOCK, GPB = B / 6;
-    const int grid = (c.N + GPB - 1) / GPB;
-    const bool two = w->force_w == 2 || (w->force_w == 0 && grid > w->n_simd);
+    const int grid = (c.N + GPB - 1) / GPB, grid8 = (c.N + 7) / 8;
     hipStream_t st = (hipStream_t)stream;
-    const bool hld = !w->no_spec && hh_cfg_is_hl_default(c); /* the instance compiled for the reference's default HighLevelEnv configuration */
-    const int grid8 = (c.N + 7) / 8;
-    const bool half = !two && w->apw != 16 && grid8 <= w->n_simd; /* 8 arenas per wave while every workgroup still has a SIMD of its own */
-    if (!w->no_oct) { /* register-exchange form (hh_kernels_oct.h): one arena per 8-lane group */
-        const bool two8 = w->force_w == 2 || (w->force_w == 0 && grid8 > w->n_simd);
+    if (f.oct) {
 #define HH_OLAUNCH(Wv, Dv) hipLaunchKernelGGL((hh_k_hier_macro_oct<Wv, Dv>), dim3(grid8), dim3(64), 0, st, w->P, c, commander_actions, pilot_tape, obs, reward, reward_valid, done, w->counter)
-        if (two8) { if (hld) HH_OLAUNCH(2, true); else HH_OLAUNCH(2, false); }
-        else { if (hld) HH_OLAUNCH(1, true); else HH_OLAUNCH(1, false); }
+        if (f.two) { if (f.hld) HH_OLAUNCH(2, true); else HH_OLAUNCH(2, false); }
+        else { if (f.hld) HH_OLAUNCH(1, true); else HH_OLAUNCH(1, false); }
 #undef HH_OLAUNCH
         HIPCHK(hipGetLastError());
         return HH_OK;
     }
 #define HH_MLAUNCH(Wv, Dv) hipLaunchKernelGGL((hh_k_hier_macro<6, B, Wv, Dv>), dim3(grid), dim3(B), 0, st, w->P, c, commander_actions, pilot_tape, obs, reward, reward_valid, done, w->counter)
 #define HH_MLAUNCH8(Dv) hipLaunchKernelGGL((hh_k_hier_macro<6, B, 1, Dv, 8>), dim3(grid8), dim3(B), 0, st, w->P, c, commander_actions, pilot_tape, obs, reward, reward_valid, done, w->counter)
-    if (two) { if (hld) HH_MLAUNCH(2, true); else HH_MLAUNCH(2, false); }
-    else if (half) { if (hld) HH_MLAUNCH8(true); else HH_MLAUNCH8(false); }
-    else { if (hld) HH_MLAUNCH(1, true); else HH_MLAUNCH(1, false); }
+    if (f.two) { if (f.hld) HH_MLAUNCH(2, true); else HH_MLAUNCH(2, false); }
+    else if (f.half) { if (f.hld) HH_MLAUNCH8(true); else HH_MLAUNCH8(false); }
+    else { if (f.hld) HH_MLAUNCH(1, true); else HH_MLAUNCH(1, false); }
 #undef HH_MLAUNCH8
 #undef HH_MLAUNCH
     HIPCHK(hipGetLastError());

@@ -20,10 +20,11 @@ def _same_state(a, b, what):
 def test_macro_step_parity(oracle, kw):
     import torch
     from hhmarl_2d_amd.world import World, make_config
-    N = 170  # 10 arenas per 64-lane workgroup: 17 full groups; the partial-group case is covered by the traces (N = 1)
+    N = 170  # one arena per 8-lane group of the register-exchange kernels (hh_k_hier_oct<1, phase>): 21 full waves and one of two arenas
     base = dict(n_arenas=N, env_kind=1, seed=21, arena_offset=500, auto_reset=True)
     base.update(kw)
     g = World(make_config(**base))
+    assert g.kernel_instance() == "hh_k_hier_oct<1, phase>"
     o = oracle.OracleWorld(oracle.make_config(**base))
     assert np.array_equal(g.reset().cpu().numpy(), o.reset())
     _same_state(g.get_state(), o.get_state(), "reset")
@@ -68,18 +69,26 @@ def test_macro_step_parity(oracle, kw):
     assert int(tot[:, :3].sum()) > 0 and int(tot[:, 7].sum()) > 0 and int(g.eval_info()[1].sum()) == 0   # sums were cleared
 
 
-@pytest.mark.parametrize("N,force_w", [(8192, "0"), (12003, "0"), (173, "2")],
-                         ids=["configs3-8192-W1", "12003-auto-W2-partial-group", "173-forced-W2"])
-def test_macro_step_parity_at_size(oracle, monkeypatch, N, force_w):
-    """BASELINE configs[3] size (8192 arenas: hh_k_hier<6,64,1>) and the two-waves-per-SIMD instance hh_k_hier<6,64,2> that
-    the host picks above one workgroup per SIMD (N = 12003: 1201 workgroups, the last one partially filled; and forced at a
-    small size), >= 3 commander steps with every sub-step's pilot observations, outputs and the final state against the oracle"""
+@pytest.mark.parametrize("N,force_w,no_oct", [(8192, "0", "0"), (12003, "0", "0"), (173, "2", "0"), (8192, "0", "1"), (12003, "0", "1"), (173, "2", "1")],
+                         ids=["configs3-8192-W1", "12003-auto-W2-partial-group", "173-forced-W2",
+                              "configs3-8192-W1-lds", "12003-auto-W2-partial-group-lds", "173-forced-W2-lds"])
+def test_macro_step_parity_at_size(oracle, monkeypatch, N, force_w, no_oct):
+    """BASELINE configs[3] size (8192 arenas: one wave per SIMD) and the two-waves-per-SIMD instances that the host picks above one workgroup
+    per SIMD (N = 12003, the last workgroup partially filled; and forced at a small size), >= 3 commander steps with every sub-step's pilot
+    observations, outputs and the final state against the oracle.  The phase launches run the register-exchange kernels hh_k_hier_oct<W, phase>
+    (8 arenas per wave: W = 2 above 8 x SIMD count arenas); the "-lds" cases run the LDS-exchange kernels hh_k_hier<6, 64, 1> /
+    hh_k_hier<6, 64, 2> (HH_NO_OCT=1, 10 arenas per wave: W = 2 above 10 x SIMD count arenas, 12003 arenas = 1201 workgroups)"""
     import torch
     from hhmarl_2d_amd.world import World, make_config
     monkeypatch.setenv("HH_FORCE_W", force_w)
+    monkeypatch.setenv("HH_NO_OCT", no_oct)
     base = dict(n_arenas=N, env_kind=1, seed=77, arena_offset=3, auto_reset=True, horizon=40)   # short horizon: resets inside the run
     g = World(make_config(**base))
-    assert g.kernel_name() == ("hh_k_hier<6,64,2>" if (force_w == "2" or N > 10240) else "hh_k_hier<6,64,1>")
+    n_simd = torch.cuda.get_device_properties(0).multi_processor_count * 4
+    per_wave = 10 if no_oct == "1" else 8
+    two = force_w == "2" or (N + per_wave - 1) // per_wave > n_simd
+    assert g.kernel_instance() == (f"hh_k_hier<6, 64, {2 if two else 1}>" if no_oct == "1" else f"hh_k_hier_oct<{2 if two else 1}, phase>")
+    assert g.kernel_name() == g.kernel_instance().replace(", ", ",")
     o = oracle.OracleWorld(oracle.make_config(**base))
     assert np.array_equal(g.reset().cpu().numpy(), o.reset())
     rng = np.random.default_rng(N)
@@ -164,23 +173,40 @@ def test_n_vs_m_parity(oracle, nA, nO):
     assert dones > 0
 
 
-@pytest.mark.parametrize("N,force_w,horizon,apw", [(170, "0", 60, "0"), (8192, "0", 60, "0"), (12003, "0", 60, "0"), (333, "2", 60, "0"), (170, "0", 500, "0"),
-                                                   (8192, "0", 500, "0"), (333, "2", 500, "0"), (170, "0", 60, "16"), (190, "0", 500, "16")],
-                         ids=["170", "8192", "12003-W2", "333-forced-W2", "170-default-config", "configs3-8192-default-config", "333-forced-W2-default-config",
-                              "170-ten-arenas-per-wave", "190-default-config-ten-arenas-per-wave"])
-def test_persistent_macro_step_equals_phase_path(oracle, monkeypatch, N, force_w, horizon, apw):
+@pytest.mark.parametrize("N,force_w,horizon,apw,no_oct", [
+    (170, "0", 60, "0", "0"), (8192, "0", 60, "0", "0"), (12003, "0", 60, "0", "0"), (333, "2", 60, "0", "0"), (170, "0", 500, "0", "0"),
+    (8192, "0", 500, "0", "0"), (333, "2", 500, "0", "0"), (170, "0", 60, "16", "1"), (190, "0", 500, "16", "1"),
+    (170, "0", 60, "0", "1"), (12003, "0", 60, "0", "1"), (333, "2", 60, "0", "1"), (170, "0", 500, "0", "1"), (333, "2", 500, "0", "1")],
+    ids=["170", "8192", "12003-W2", "333-forced-W2", "170-default-config", "configs3-8192-default-config", "333-forced-W2-default-config",
+         "170-ten-arenas-per-wave", "190-default-config-ten-arenas-per-wave",
+         "170-lds", "12003-W2-lds", "333-forced-W2-lds", "170-default-config-lds", "333-forced-W2-default-config-lds"])
+def test_persistent_macro_step_equals_phase_path(oracle, monkeypatch, N, force_w, horizon, apw, no_oct):
     """hh_hl_rollout (one launch per commander step, actions from a resident tape) against the phase-by-phase path with the same
-    tape: outputs, final state, event masks, eval counters, episode statistics and tick counts bit for bit; at N = 170 also
+    tape: outputs, final state, event masks, eval counters, episode statistics and tick counts bit for bit; at N <= 200 also
     against the oracle.  horizon = 500 is the reference's default HighLevelEnv configuration, which runs the macro-step instance
-    compiled with that configuration as constants (hh_cfg_set_hl_default); any other horizon runs the general instance.  Worlds of up
-    to 8192 arenas run 8 arenas per wave unless HH_APW=16 keeps the 10 that fill a wave."""
+    compiled with that configuration as constants (hh_cfg_set_hl_default); any other horizon runs the general instance.  By default both
+    paths run the register-exchange kernels (hh_k_hier_macro_oct<W, HLD> against hh_k_hier_oct<W, phase>: 8 arenas per wave, W = 2 above
+    8 x SIMD count arenas or forced; HH_APW plays no part there).  The "-lds" and "ten-arenas-per-wave" cases set HH_NO_OCT=1 and run the
+    LDS-exchange kernels (hh_k_hier_macro<6, 64, W, HLD, APW> against hh_k_hier<6, 64, W>): worlds of up to 8 x SIMD count arenas run 8
+    arenas per wave in the macro step unless HH_APW=16 keeps the 10 that fill a wave; W = 2 above 10 x SIMD count arenas or forced."""
     import torch
     from hhmarl_2d_amd.env_hier import macro_step
     from hhmarl_2d_amd.world import World, make_config
     monkeypatch.setenv("HH_FORCE_W", force_w)
     monkeypatch.setenv("HH_APW", apw)
+    monkeypatch.setenv("HH_NO_OCT", no_oct)
     base = dict(n_arenas=N, env_kind=1, seed=8, arena_offset=11, auto_reset=True, horizon=horizon)
     a, b = World(make_config(**base)), World(make_config(**base))
+    n_simd = torch.cuda.get_device_properties(0).multi_processor_count * 4
+    hld = "true" if horizon == 500 else "false"
+    if no_oct == "0":
+        W = 2 if (force_w == "2" or (N + 7) // 8 > n_simd) else 1
+        want = (f"hh_k_hier_oct<{W}, phase>", f"hh_k_hier_macro_oct<{W}, {hld}>")
+    else:
+        W = 2 if (force_w == "2" or (N + 9) // 10 > n_simd) else 1
+        per_wave = 8 if (W == 1 and apw != "16" and (N + 7) // 8 <= n_simd) else 10
+        want = (f"hh_k_hier<6, 64, {W}>", f"hh_k_hier_macro<6, 64, {W}, {hld}, {per_wave}>")
+    assert (a.kernel_instance(0), b.kernel_instance(1)) == want
     o = oracle.OracleWorld(oracle.make_config(**base)) if N <= 200 else None
     assert torch.equal(a.reset(), b.reset())
     if o is not None:

@@ -3,7 +3,8 @@ move, and the mailbox reads behind barrier Y), and the CPU half of their test: t
 rewritten site is reached.  A fixture that never reaches a site would let the GPU test (test_gpu_quad_select_paths.py) pass on nothing, so
 a zero count fails HERE, on the CPU.
 
-Every fixture: 8 arenas (one full workgroup of the 8-arena form) or 9 (a one-arena tail), two launches of LAUNCH ticks, the keyed action tape.
+Every fixture: 8 arenas (one full workgroup of the 8-arena form), 9 (a one-arena tail) or 17 (one full wave of the 16-arena forms and a one-arena
+tail), two launches of LAUNCH ticks, the keyed action tape.
 The start is the state the oracle reached after WARM ticks of the same configuration, with these injections (set_state):
 
     arena 0   agent 0 has no cannon ammunition and no burst running, and the tape orders it to fire on ticks 0..3   (fire with no ammunition)
@@ -17,6 +18,9 @@ The start is the state the oracle reached after WARM ticks of the same configura
     every arena: step counters spread so that the horizon ends episodes inside both launches
 
 The fixture "l3-stay-done" runs without auto-reset: its arenas end one after the other and stay done beside the ones still running.
+The fixture "l3-escape-shaping" is "l3-escape" with the escape distance shaping (env_hetero.py:198-214), the one way into the general instances
+that keep the pair table on the simulation wave with the shaping term live: the site `shaping_live` counts the ticks whose rewards differ from
+those of "l3-escape", so the fixture cannot pass with the term dead.
 """
 import functools
 
@@ -36,8 +40,9 @@ CONFIGS = {
     "l3-escape": dict(level=3, agent_mode=MODE_ESCAPE, auto_reset=True, horizon=70),                    # preset 4
     "l3-general": dict(level=3, auto_reset=True, horizon=70, rew_scale=2.0, friendly_punish=True),      # no preset: PRE = 0
     "l3-stay-done": dict(level=3, auto_reset=False, horizon=70),                                        # arenas that are done and stay done
+    "l3-escape-shaping": dict(level=3, agent_mode=MODE_ESCAPE, esc_dist_rew=True, auto_reset=True, horizon=70),   # no preset, the shaping term live
 }
-SIZES = (8, 9)
+SIZES = (8, 9, 17)
 CASES = [(c, n) for c in CONFIGS for n in SIZES]
 STEPS0 = (5, 12, 20, 31, 44, 57, 67, 63, 50)   # arena 6: horizon - 3
 
@@ -45,6 +50,7 @@ STEPS0 = (5, 12, 20, 31, 44, 57, 67, 63, 50)   # arena 6: horizon - 3
 SITES = {
     "fire_no_ammo": None, "burst_ends": None, "burst_without_rounds": None, "steer_first_two_ticks": None, "steer_after_reset": ("auto",),
     "launch_tick": None, "dead_aircraft": None, "stationary": ("l1", "l2"), "done_stays": ("l3-stay-done",), "reset": ("auto",),
+    "shaping_live": ("l3-escape-shaping",),
 }
 
 
@@ -155,6 +161,11 @@ def oracle_run(cfg, N):
         n["done_stays"] += int((~ran).sum())
         n["reset"] += int((done & auto).sum())
         prev_done = done
+    if cfg == "l3-escape-shaping":   # the same run without the shaping term: same start, same tape, other rewards
+        plain = oracle_run("l3-escape", N)
+        for k in range(2):
+            assert np.array_equal(launches[k]["outs"][3], plain["launches"][k]["outs"][3]), "the shaping term changes rewards only"
+            n["shaping_live"] += int((launches[k]["outs"][1] != plain["launches"][k]["outs"][1]).any(axis=(1, 2)).sum())
     res["counts"] = n
     return res
 
@@ -173,5 +184,5 @@ def test_fixture_reaches_every_site(oracle, cfg, N):
         assert res["launches"][1]["outs"][3][-1].all(), "every arena ended its episode and stayed done"
         running_beside_done = n["done_stays"] < (2 * LAUNCH) * N
         assert running_beside_done
-    if N == 9:
-        assert res["launches"][0]["outs"][2][:, 8].any(), "the tail arena runs"
+    if N in (9, 17):
+        assert res["launches"][0]["outs"][2][:, N - 1].any(), "the tail arena runs"
