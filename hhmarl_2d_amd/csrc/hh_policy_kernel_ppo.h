@@ -50,6 +50,12 @@ struct HhpSampleArgs {
     float *logp, *vf, *logits_out;
 };
 
+/* The draw compares the running sum of the exponentials with (float) u * S.  A double u >= 1 - 2^-25 (one draw in 3.4e7) rounds to 1.0f: then no
+ * running sum exceeds S, and the "nothing found" fallback took the LAST index whatever its probability — an action of probability e^-200 with
+ * logp -200 when the mass sits on an earlier index.  u is held to the largest float below 1 instead: S (1 - 2^-24) rounds below S for every S,
+ * so the scan ends at the last index that carries mass, as the inverse CDF in double does. */
+#define HHP_U_BELOW_ONE 0x1.fffffep-1f
+
 /* LDS (bytes): Zh 32 KB | Zl 32 KB | Xh 5 KB | Xl 5 KB | rows 128 | norm partials 512 | biases (512 + 512 + 160 floats); the L3 partials
  * (36 KB) and the logits (4 KB at byte 40960) alias the activation tile once S is dead.  2 x 81152 B = 158.5 KB: two workgroups per CU. */
 #define HHPP_OFF_ZL 32768
@@ -321,7 +327,7 @@ __device__ __forceinline__ void hhp_ppo_tile(const HhpNet &N, const HhpNetH &H, 
                         u = hh_rng_u01(hh_rng_tick_key(hh_rng_arena_key(sa.seed, sa.arena_offset + (unsigned long long)n), (uint32_t)ap.y, (uint32_t)ap.x),
                                        (uint32_t)(s + 1), HH_SITE_POLICY_SAMPLE, (uint32_t)k);
                     }
-                    const float t = (float)u * S;
+                    const float t = fminf((float)u, HHP_U_BELOW_ONE) * S;
                     float cum = 0.0f;
                     a = hi - lo - 1;
                     bool found = false;

@@ -483,7 +483,7 @@ __device__ __forceinline__ void hhx_forward_tile(const HhpNet &N, const unsigned
                     u = hh_rng_u01(hh_rng_tick_key(hh_rng_arena_key(sa->seed, sa->arena_offset + (unsigned long long)n), (uint32_t)ap.y, (uint32_t)ap.x),
                                    (uint32_t)(sl_ + 1), HH_SITE_POLICY_SAMPLE, (uint32_t)k);
                 }
-                const float t = (float)u * S;
+                const float t = fminf((float)u, HHP_U_BELOW_ONE) * S;
                 float cum = 0.0f;
                 a = hi - lo - 1;
                 bool found = false;

@@ -144,8 +144,8 @@ int hh_policy_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w)
  *   logp      [dev] f32 [n_rows]      sum over the components of log softmax(logits_c)[a_c]   (nullable)
  *   vf        [dev] f32 [n_rows]      value_function()                                         (nullable: the critic tiles are skipped)
  *   logits    [dev] f32 [n_rows, 32]  optional, as hh_policy_act
- * Inverse CDF of a component with logits l[0..n): m = max l, e_i = exp(l_i - m), S = sum e_i in index order, t = (float)u * S, the action
- * is the first i whose running sum exceeds t (the last index if none does); logp_c = (l_a - m) - log S.  Rows without a network: action
+ * Inverse CDF of a component with logits l[0..n): m = max l, e_i = exp(l_i - m), S = sum e_i in index order, t = min((float)u, 1 - 2^-24) * S (a
+ * u that rounds to 1.0f must not fall off the end: t < S always), the action is the first i whose running sum exceeds t; logp_c = (l_a - m) - log S.  Rows without a network: action
  * 0, logp / vf untouched.  Everything is ordered on `stream`; no host synchronisation (HIP-graph capturable). */
 int hh_policy_sample(hh_policy *p, const float *obs, int32_t n_rows, int32_t obs_stride, const uint8_t *sel, struct hh_world *w,
                      const double *uniforms, const float *crit_act, int32_t greedy, int8_t *actions, float *logp, float *vf, float *logits,
