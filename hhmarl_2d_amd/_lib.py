@@ -126,7 +126,9 @@ COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commande
                      "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux"]  # include/hh_commander.h
 
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
-                   "hh_gru_seq_backward"]  # include/hh_learner.h
+                   "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
+                   "hh_residual_normalize_backward"]  # include/hh_learner.h
+ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
 
@@ -227,6 +229,10 @@ def lib():
         L.hh_gru_seq_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.hh_gru_seq_forward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
         L.hh_gru_seq_backward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
+        L.hh_chunk_attn_forward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
+        L.hh_chunk_attn_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.hh_residual_normalize_forward.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
+        L.hh_residual_normalize_backward.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -2,7 +2,9 @@
 `hh_ppo_loss` (include/hh_learner.h) behind a torch.autograd.Function, the four trainable networks as torch modules in TRAINING form, and
 `PPOLearner`, which turns the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")` into one PPO update of ac1_policy and
 ac2_policy and hands the new weights back to the sampler's `PolicyBank` — collect -> update -> publish -> collect on one GPU, the
-batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss and its gradient are one HIP pass.
+batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss and its gradient are one HIP pass.  Opt-in
+(`attention="fused"`): what the fight networks' two attention blocks do between and after their projections runs in HIP too
+(`chunk_attention`: hh_chunk_attn_*, `residual_normalize`: hh_residual_normalize_*); the default path is nn.MultiheadAttention.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -132,6 +134,105 @@ def ppo_loss_torch(logits, vf, batch, *, n_comp, clip_param=0.25, vf_clip_param=
     return total, stats
 
 
+# ------------------------------------------------------------------------------------------------------------------ the chunk attention
+ATTENTION_MODES = ("torch", "fused")
+
+
+def _need_gpu(who):
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"hhmarl_2d_amd.{who} needs a ROCm GPU (no CPU fallback)")
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class _ChunkAttn(torch.autograd.Function):
+    """forward: hh_chunk_attn_forward; backward: hh_chunk_attn_backward, the probabilities recomputed from the kept qkv"""
+
+    @staticmethod
+    def forward(ctx, qkv):
+        S, Lm, E3 = qkv.shape
+        out = torch.empty((S, Lm, E3 // 3), dtype=torch.float32, device=qkv.device)
+        L.check(L.lib().hh_chunk_attn_forward(S, Lm, E3 // 3, _p(qkv), _p(out), _stream(qkv.device)))
+        ctx.save_for_backward(qkv)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        qkv, = ctx.saved_tensors
+        S, Lm, E3 = qkv.shape
+        d_qkv = torch.empty_like(qkv)
+        L.check(L.lib().hh_chunk_attn_backward(S, Lm, E3 // 3, _p(qkv), _p(d_out.contiguous()), _p(d_qkv), _stream(qkv.device)))
+        return d_qkv
+
+
+class _ResidualNormalize(torch.autograd.Function):
+    """forward: hh_residual_normalize_forward; backward: hh_residual_normalize_backward from the kept y and norm, one gradient for both inputs"""
+
+    @staticmethod
+    def forward(ctx, x, a):
+        E = x.shape[-1]
+        R = x.numel() // E
+        y = torch.empty_like(x)
+        norm = torch.empty((R,), dtype=torch.float32, device=x.device)
+        L.check(L.lib().hh_residual_normalize_forward(R, E, _p(x), _p(a), _p(y), _p(norm), _stream(x.device)))
+        ctx.save_for_backward(y, norm)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_y):
+        y, norm = ctx.saved_tensors
+        d_s = torch.empty_like(y)
+        L.check(L.lib().hh_residual_normalize_backward(norm.numel(), y.shape[-1], _p(y), _p(norm), _p(d_y.contiguous()), _p(d_s), _stream(y.device)))
+        return d_s, d_s
+
+
+def _fused_input(who, t, what):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError(f"{who}: {what} is a contiguous float32 CUDA tensor (the torch-op form for other dtypes and devices is {who}_torch)")
+
+
+def chunk_attention(qkv):
+    """The core of nn.MultiheadAttention(E, 2, batch_first=True) between its in- and its out-projection, fused (hh_chunk_attn_forward /
+    hh_chunk_attn_backward, include/hh_learner.h): qkv f32 [S, L, 3E] = x W_in^T + b_in (columns q | k | v, two head slices of E / 2
+    each), contiguous, CUDA, E = 100 | 150, 1 <= L <= 32 -> ctx f32 [S, L, E] = softmax(Q K^T / sqrt(E / 2)) V per sequence and head,
+    heads concatenated; no mask.  Differentiable with respect to qkv (first order).  No host synchronisation; a missing library or
+    GPU is an error."""
+    _need_gpu("chunk_attention")
+    _fused_input("chunk_attention", qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[2] % 3 or qkv.shape[2] // 3 not in L.ATTN_WIDTHS or not 1 <= qkv.shape[1] <= L.ATTN_MAX_LEN:
+        raise ValueError(f"chunk_attention: qkv is [S, L, 3E] with E in {L.ATTN_WIDTHS} and 1 <= L <= {L.ATTN_MAX_LEN}, got {tuple(qkv.shape)}")
+    return _ChunkAttn.apply(qkv)
+
+
+def residual_normalize(x, a):
+    """F.normalize(x + a, dim=-1), fused (hh_residual_normalize_forward / _backward): x, a f32 [..., E] of one shape, contiguous, CUDA,
+    E = 100 | 150 -> f32 [..., E].  Differentiable with respect to both (first order).  No host synchronisation, no fallback."""
+    _need_gpu("residual_normalize")
+    _fused_input("residual_normalize", x, "x")
+    _fused_input("residual_normalize", a, "a")
+    if x.shape != a.shape or x.dim() < 1 or x.shape[-1] not in L.ATTN_WIDTHS or x.device != a.device:
+        raise ValueError(f"residual_normalize: x and a are [..., E] of one shape on one device with E in {L.ATTN_WIDTHS}, got {tuple(x.shape)} and {tuple(a.shape)}")
+    return _ResidualNormalize.apply(x, a)
+
+
+def chunk_attention_torch(qkv):
+    """chunk_attention with torch ops, any dtype and device (the A/B partner): [S, L, 3E] -> [S, L, E]"""
+    S, Lm, E3 = qkv.shape
+    d = E3 // (3 * L.ATTN_HEADS)
+    q, k, v = (t.reshape(S, Lm, L.ATTN_HEADS, d).transpose(1, 2) for t in qkv.split(E3 // 3, dim=-1))       # [S, heads, L, d]
+    p = torch.softmax((q @ k.transpose(-1, -2)) / d ** 0.5, dim=-1)
+    return (p @ v).transpose(1, 2).reshape(S, Lm, E3 // 3)
+
+
+def residual_normalize_torch(x, a):
+    """residual_normalize with torch ops, any dtype and device"""
+    return F.normalize(x + a, dim=-1)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the networks
 class _FC(nn.Module):
     """a linear layer under the reference's parameter names (RLlib's SlimFC keeps its nn.Linear in `_model.0`)"""
@@ -155,11 +256,20 @@ class TrainableNet(nn.Module):
                     normalize(x + att) per row.  2-D inputs [R, ...] are R chunks of length 1 — the sampler's forward.
                     -> logits [S, L, 26 | 24], value [S, L]
       escape kinds: rows [..., >= OBS_DIM], [..., 66] -> logits [..., 26 | 24], value [...]
-    critic_row is rollout.central_critic_rows' layout: [own act | friend's act | own obs | friend's obs]."""
+    critic_row is rollout.central_critic_rows' layout: [own act | friend's act | own obs | friend's obs].
 
-    def __init__(self, kind):
+    attention = "torch" (the default) runs att_act / att_val through nn.MultiheadAttention and F.normalize.  "fused" (fight kinds only,
+    float32 on the GPU) keeps the two projections as GEMMs and runs what lies between and after them through chunk_attention and
+    residual_normalize; the nn.MultiheadAttention objects stay the parameter holders, so state_dict() is the same either way."""
+
+    def __init__(self, kind, attention="torch"):
         super().__init__()
         self.kind = int(kind)
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"attention is one of {ATTENTION_MODES}, got {attention!r}")
+        if attention == "fused" and not PN.HAS_ATT[self.kind]:
+            raise ValueError(f'attention="fused": {PN.KIND_NAMES[self.kind]} has no attention')
+        self.attention = attention
         for i, (c0, c1, w) in enumerate(PN.INPUTS[kind]):
             setattr(self, f"inp{i + 1}", _FC(c1 - c0, w))
         self.shared_layer = _FC(500, 500)
@@ -173,6 +283,13 @@ class TrainableNet(nn.Module):
             self.inp1_val = _FC(d1 + a1 + d2 + a2, 500)
         self.val_out = _FC(500, 1)
 
+    @staticmethod
+    def _attend_fused(att, h):
+        """normalize(h + att(h, h, h)) with the in- and out-projection as GEMMs and the rest in two fused launches each way"""
+        qkv = F.linear(h, att.in_proj_weight, att.in_proj_bias)
+        out = F.linear(chunk_attention(qkv), att.out_proj.weight, att.out_proj.bias)
+        return residual_normalize(h, out)
+
     def forward(self, obs_own, critic_row):
         kind = self.kind
         d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
@@ -185,7 +302,11 @@ class TrainableNet(nn.Module):
         o_own, o_2 = critic_row[..., a1 + a2:a1 + a2 + d1], critic_row[..., a1 + a2 + d1:]
         v1, v2 = torch.cat((o_own, act_own), dim=-1), torch.cat((o_2, act_2), dim=-1)
         v3 = torch.cat((v1, v2), dim=-1)
-        if PN.HAS_ATT[kind]:
+        if PN.HAS_ATT[kind] and self.attention == "fused":
+            h[2] = self._attend_fused(self.att_act, h[2])
+            y = torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1)
+            y = torch.cat((y, self._attend_fused(self.att_val, torch.tanh(self.v3(v3)))), dim=-1)
+        elif PN.HAS_ATT[kind]:
             att, _ = self.att_act(h[2], h[2], h[2], need_weights=False)
             h[2] = F.normalize(h[2] + att, dim=-1)
             y = torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1)
@@ -313,15 +434,17 @@ class PPOLearner:
     when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
-                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True):
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch"):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
-        torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's."""
+        torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
+        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*)."""
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
-        self.modules = tie([TrainableNet(k).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+        self.attention = attention
+        self.modules = tie([TrainableNet(k, attention=attention).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
                             for k, sd in zip(self.kinds, state_dicts)])
         for m in self.modules:
             m.to(self.device)

@@ -1,7 +1,8 @@
 /*
  * hh_learner.h — C ABI of the learner side of train_hetero.py's and train_hier.py's PPO (part of libhh_world.so): the fused PPO loss,
  * forward and backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies and for the commander's Categorical,
- * and the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*, at the end of this file).
+ * the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*), and the fight networks' chunk attention without its
+ * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*, at the end of this file).
  *
  * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
  * predictions, per row that the mask keeps (n = number of such rows):
@@ -110,6 +111,31 @@ int hh_gru_seq_forward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_g
  * GEMM), db_hh = the column sums of d_gh, and everything upstream of gi. */
 int hh_gru_seq_backward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_gru_seq_io *io, const int32_t *seq_len, const void *scratch,
                         int64_t scratch_bytes, void *stream);
+
+/* ---- the fight networks' self-attention over RLlib's max_seq_len chunks, without its GEMMs (Fight1 / Fight2: att_act of width 100 and
+ * att_val of width 150, models/ac_models_hetero.py) ----
+ *
+ * What nn.MultiheadAttention(embed, 2, batch_first=True)(x, x, x) and F.normalize(x + att) compute between and after the in- and the
+ * out-projection, which stay GEMMs with the caller.  Everything is float32 and ordered on `stream`; no allocation, no host
+ * synchronisation, no floating-point atomics, HIP-graph capturable; the same inputs give the same bytes on every run.  All pointers are
+ * [dev], whole contiguous tensors (4-byte aligned for the core, 8-byte for normalize; norm 4-byte); an output may not overlap any other
+ * tensor of the call.  embed and width are 100 or 150 (compile-time instances), 1 <= len <= HH_ATTN_MAX_LEN, n_seq <= 2^24,
+ * n_rows <= 2^32; anything else is HH_E_ARG and launches nothing.  n_seq == 0 or n_rows == 0 succeeds without a launch.
+ * The exponentials are expf's, the softmax subtracts the row maximum, every sum runs in index order. */
+#define HH_ATTN_HEADS 2
+#define HH_ATTN_MAX_LEN 32
+/* qkv [n_seq, len, 3*embed] = x W_in^T + b_in, columns q | k | v, each split into HH_ATTN_HEADS contiguous head slices of d = embed/2;
+ * ctx [n_seq, len, embed]: per sequence and head softmax(Q K^T / sqrt(d)) V, heads concatenated (what nn.MultiheadAttention hands its
+ * out_proj).  No mask: all `len` rows of a sequence are keys, zero-padded rows included (the reference passes no key_padding_mask).
+ * With len == 1 ctx equals the v columns bit for bit. */
+int hh_chunk_attn_forward (int64_t n_seq, int32_t len, int32_t embed, const float *qkv, float *ctx, void *stream);
+/* P recomputed from qkv (nothing saved by the forward):  dV = P^T dO;  dP = dO V^T;  dS = P o (dP - rowsum(P o dP));
+ * dQ = dS K / sqrt(d);  dK = dS^T Q / sqrt(d);  d_qkv in qkv's layout, so the in-projection's backward stays ONE GEMM */
+int hh_chunk_attn_backward(int64_t n_seq, int32_t len, int32_t embed, const float *qkv, const float *d_ctx, float *d_qkv, void *stream);
+/* y = s / max(|s|_2, 1e-12), s = x + a, per row (F.normalize(x + att), p = 2, eps = 1e-12); norm [n_rows] = |s|_2 saved for the backward */
+int hh_residual_normalize_forward (int64_t n_rows, int32_t width, const float *x, const float *a, float *y, float *norm, void *stream);
+/* d_s (= d_x = d_a) = (d_y - y (y . d_y)) / norm where norm >= 1e-12, d_y / 1e-12 elsewhere (autograd of clamp_min and of norm at 0) */
+int hh_residual_normalize_backward(int64_t n_rows, int32_t width, const float *y, const float *norm, const float *d_y, float *d_s, void *stream);
 
 #ifdef __cplusplus
 }

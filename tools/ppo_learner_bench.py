@@ -12,6 +12,12 @@
           one of them with the logits column: at the default N = 16384, T = 64, H = 300 about 2.8 GB (rows and carry without the
           column) + 5.8 GB (with it: 2.8 GB of that the column's carry and batch, 0.27 GB its collect buffer), on top of the full
           run's own rollout when it runs at its end
+  attention  --attention runs this section alone and appends its lines to --out: the fight networks' chunk attention through
+          TrainableNet(attention="fused") (hh_chunk_attn_*, hh_residual_normalize_*) against the default nn.MultiheadAttention +
+          F.normalize path, both timed in the same run: (a) one attention block, forward + backward, E = 100 and 150 at 14 and 3560
+          chunks of 20; (b) the Fight1 minibatch step at 256 and 65536 rows; (c) the four kernels alone as bytes/s of their algorithmic
+          bytes (core: 16 E per row forward, 28 E backward; normalize: 12 E + 4 each way).  A difference is called a gain (or a loss)
+          only where the medians differ by more than the larger of the two (max - min) spreads
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -21,6 +27,8 @@ import sys
 import time
 
 import torch
+import torch.nn as nn
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -44,6 +52,7 @@ def main():
     ap.add_argument("--passes", type=int, default=1)
     ap.add_argument("--minibatch", type=int, default=65536)
     ap.add_argument("--old-logits-only", action="store_true", help="only the old_logits section; its lines are appended to --out")
+    ap.add_argument("--attention", action="store_true", help="only the chunk-attention section; its lines are appended to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -95,6 +104,88 @@ def main():
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines[1:]) + "\n")
+        return
+
+    def attention_section():
+        """attention="fused" against attention="torch": one block, the minibatch step, the kernels alone"""
+        import ctypes as C
+        from hhmarl_2d_amd import _lib as L
+        from hhmarl_2d_amd import policy_nets as PN
+        med = statistics.median
+
+        def verdict(t_torch, t_fused):
+            spread = max(max(t_torch) - min(t_torch), max(t_fused) - min(t_fused))
+            d = med(t_torch) - med(t_fused)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"torch / fused = {med(t_torch) / med(t_fused):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --attention on {torch.cuda.get_device_name(0)}: TrainableNet(attention=\"fused\") against the default "
+            f"attention=\"torch\", both in this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+        # (a) one block: in-projection, core, out-projection, residual + normalize; forward + backward
+        for E in (100, 150):
+            att = nn.MultiheadAttention(E, 2, batch_first=True).to(dev)
+            for S in (14, 3560):
+                g = torch.Generator().manual_seed(E + S)
+                h = torch.tanh(torch.randn((S, 20, E), generator=g)).to(dev).requires_grad_(True)
+                dy = torch.randn((S, 20, E), generator=g).to(dev)
+
+                def block(fused):
+                    h.grad = None
+                    att.zero_grad(set_to_none=True)
+                    if fused:
+                        y = LR.TrainableNet._attend_fused(att, h)
+                    else:
+                        o, _ = att(h, h, h, need_weights=False)
+                        y = F.normalize(h + o, dim=-1)
+                    y.backward(dy)
+                t_t, t_f = events(lambda: block(False)), events(lambda: block(True))
+                say(f"attention block (in-projection, core, out-projection, normalize(x + att); forward + backward), E = {E}, {S} chunks of 20: "
+                    f"torch {q(t_t)}; fused {q(t_f)}; {verdict(t_t, t_f)}")
+        # (c) the kernels alone
+        lib = L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        for E in (100, 150):
+            for S in (14, 3560):
+                R = S * 20
+                qkv, d_ctx = torch.randn((S, 20, 3 * E), device=dev), torch.randn((S, 20, E), device=dev)
+                ctx, d_qkv = torch.empty_like(d_ctx), torch.empty_like(qkv)
+                x, av = torch.randn((R, E), device=dev), torch.randn((R, E), device=dev)
+                y, d_s, norm = torch.empty_like(x), torch.empty_like(x), torch.empty((R,), device=dev)
+                runs = (("hh_chunk_attn_forward", 16 * E * R, lambda: L.check(lib.hh_chunk_attn_forward(S, 20, E, p(qkv), p(ctx), st))),
+                        ("hh_chunk_attn_backward", 28 * E * R, lambda: L.check(lib.hh_chunk_attn_backward(S, 20, E, p(qkv), p(d_ctx), p(d_qkv), st))),
+                        ("hh_residual_normalize_forward", (12 * E + 4) * R, lambda: L.check(lib.hh_residual_normalize_forward(R, E, p(x), p(av), p(y), p(norm), st))),
+                        ("hh_residual_normalize_backward", (12 * E + 4) * R, lambda: L.check(lib.hh_residual_normalize_backward(R, E, p(y), p(norm), p(d_ctx), p(d_s), st))))
+                for name, nbytes, fn in runs:
+                    t = events(fn)
+                    say(f"    {name} alone, E = {E}, {S} chunks of 20 ({R} rows): {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB "
+                        f"algorithmic bytes ({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+        # (b) the Fight1 minibatch step
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        learners = {att: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, attention=att) for att in ("torch", "fused")}
+        with torch.no_grad():
+            old = learners["torch"].old_logits(rows["obs"], bank, ro.episodes.N)
+            b = learners["torch"].policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            mb = {k: v[s0:s1] for k, v in b.items() if k != "seq_len"}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            t = {att: events(lambda: lr.minibatch_step(0, mb)) for att, lr in learners.items()}
+            say(f"minibatch step ({PN.KIND_NAMES[learners['torch'].kinds[0]]}, forward + loss + backward + Adam, fused loss), {int(seq_len[s0:s1].sum())} unpadded rows in "
+                f"{s1 - s0} chunks of 20: attention = torch {q(t['torch'])}; attention = fused {q(t['fused'])}; {verdict(t['torch'], t['fused'])}")
+
+    if a.attention:
+        lines.clear()
+        attention_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
         return
 
     # ---- errors against float64 (the GPU test's generator and bound: kernel <= 4 x e32 per quantity)
