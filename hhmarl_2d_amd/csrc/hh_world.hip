@@ -840,6 +840,9 @@ extern "C" int hh_gae_rllib(int32_t T, int32_t N, int32_t n_agents, const float 
 /* ---- the fight networks' chunk attention core and normalize(x + att), forward and backward (C ABI in include/hh_learner.h) ---- */
 #include "hh_chunk_attn.h"
 
+/* ---- the networks' input layers in front of shared_layer as one grouped stage, forward and backward (C ABI in include/hh_learner.h) ---- */
+#include "hh_input_stage.h"
+
 /* hh_math_eval: the shared math headers on the device (test probe, include/hh_abi.h) */
 __global__ void hh_k_math_eval(int fn, int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ o0, double *__restrict__ o1) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -5,6 +5,8 @@ ac2_policy and hands the new weights back to the sampler's `PolicyBank` — coll
 batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss and its gradient are one HIP pass.  Opt-in
 (`attention="fused"`): what the fight networks' two attention blocks do between and after their projections runs in HIP too
 (`chunk_attention`: hh_chunk_attn_*, `residual_normalize`: hh_residual_normalize_*); the default path is nn.MultiheadAttention.
+Opt-in as well (`inputs="fused"`, all five networks): the layers in front of shared_layer as one grouped launch per side
+(`input_stage`: hh_input_stage_*); the default path slices, concatenates and runs them one by one.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -233,6 +235,152 @@ def residual_normalize_torch(x, a):
     return F.normalize(x + a, dim=-1)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the input stage
+INPUT_MODES = ("torch", "fused")
+
+
+def _stage_layout(src_width, groups, packs):
+    """checks of input_stage / input_stage_torch that need no device -> (packs as a tuple of tuples, per group (pack, first column))"""
+    n = len(groups)
+    packs = (tuple(range(n)),) if packs is None else tuple(tuple(int(i) for i in p) for p in packs)
+    if sorted(i for p in packs for i in p) != list(range(n)) or not all(packs):
+        raise ValueError(f"input_stage: packs is a partition of the group indices 0..{n - 1}, got {packs}")
+    place = {}
+    for pi, p in enumerate(packs):
+        c = 0
+        for i in p:
+            place[i] = (pi, c)
+            c += groups[i][0].shape[0]
+    for w, b, segs in groups:
+        k = sum(ln for _, ln in segs)
+        if w.dim() != 2 or w.shape[1] != k or tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"input_stage: a group is (weight [n_out, K], bias [n_out], segments of K columns in all), got {tuple(w.shape)}, "
+                             f"{tuple(b.shape)} and K = {k}")
+        if any(c0 < 0 or ln < 1 or c0 + ln > src_width for c0, ln in segs):
+            raise ValueError(f"input_stage: a segment of {tuple(segs)} reaches outside the source's {src_width} columns")
+    return packs, place
+
+
+class _InputStage(torch.autograd.Function):
+    """forward: hh_input_stage_forward into the packs; backward: hh_input_stage_backward from the kept src and packs (d_w, d_b only)"""
+
+    @staticmethod
+    def forward(ctx, src, segments, packs, place, *wb):
+        n = len(segments)
+        ld = src.shape[-1]
+        R = src.numel() // ld
+        ws, bs = [t.detach().contiguous() for t in wb[:n]], [t.detach().contiguous() for t in wb[n:]]
+        widths = [sum(ws[i].shape[0] for i in p) for p in packs]
+        outs = [torch.empty(tuple(src.shape[:-1]) + (wd,), dtype=torch.float32, device=src.device) for wd in widths]
+        io = (L.HHInputGroup * n)()
+        for i, segs in enumerate(segments):
+            g, (pi, c) = io[i], place[i]
+            g.n_out, g.n_seg = ws[i].shape[0], len(segs)
+            for s, (c0, ln) in enumerate(segs):
+                g.seg_col[s], g.seg_len[s] = c0, ln
+            g.w, g.b = ws[i].data_ptr(), bs[i].data_ptr()
+            g.y, g.y_ld = outs[pi].data_ptr() + 4 * c, widths[pi]
+        L.check(L.lib().hh_input_stage_forward(R, _p(src), ld, ld, n, io, _stream(src.device)))
+        ctx.io, ctx.place, ctx.n_packs, ctx.shapes = io, place, len(packs), [(w.shape, w.device) for w in ws]
+        ctx.save_for_backward(src, *outs)
+        ctx.keep = (ws, bs)        # io holds their addresses
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *d_outs):
+        src, *outs = ctx.saved_tensors
+        n, io = len(ctx.shapes), ctx.io
+        ld = src.shape[-1]
+        R = src.numel() // ld
+        dev = src.device
+        d_outs = [torch.zeros_like(o) if d is None else d.contiguous() for d, o in zip(d_outs, outs)]
+        d_ws = [torch.empty(tuple(shp), dtype=torch.float32, device=dev) for shp, _ in ctx.shapes]
+        d_bs = [torch.empty((shp[0],), dtype=torch.float32, device=dev) for shp, _ in ctx.shapes]
+        for i in range(n):
+            pi, c = ctx.place[i]
+            io[i].y, io[i].y_ld = outs[pi].data_ptr() + 4 * c, outs[pi].shape[-1]
+            io[i].d_y, io[i].d_y_ld = d_outs[pi].data_ptr() + 4 * c, d_outs[pi].shape[-1]
+            io[i].d_w, io[i].d_b = d_ws[i].data_ptr(), d_bs[i].data_ptr()
+        nbytes = C.c_int64()
+        lib = L.lib()
+        L.check(lib.hh_input_stage_scratch_bytes(n, io, R, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value // 4,), dtype=torch.float32, device=dev)
+        L.check(lib.hh_input_stage_backward(R, _p(src), ld, ld, n, io, _p(scratch), nbytes.value, _stream(dev)))
+        return (None, None, None, None) + tuple(d_ws) + tuple(d_bs)
+
+
+def input_stage(src, groups, packs=None):
+    """What a network does in front of shared_layer, fused (hh_input_stage_forward / hh_input_stage_backward, include/hh_learner.h):
+    G <= 4 layers y_g = tanh(W_g gather_g(src) + b_g) from one source, one launch forward and two backward.
+    src f32 [..., ld], CUDA, contiguous (an observation or a critic row; no gradient flows into it).  groups: a sequence of
+    (weight [n_out, K], bias [n_out], segments), segments = ((first column, length), ...): the layer's input is these column runs of a
+    source row side by side, K columns in all.  packs: a partition of the group indices, each pack one output tensor
+    [..., sum of its groups' n_out] with its groups side by side in the order given; default one pack of all groups.
+    -> a tuple of tensors, one per pack.  Differentiable with respect to every weight and bias (first order).  No host
+    synchronisation; a missing library or GPU is an error."""
+    _need_gpu("input_stage")
+    _fused_input("input_stage", src, "src")
+    for w, b, _ in groups:
+        if not (w.is_cuda and b.is_cuda and w.dtype == torch.float32 and b.dtype == torch.float32 and w.device == src.device and b.device == src.device):
+            raise ValueError("input_stage: weights and biases are float32 CUDA tensors on the source's device (the torch-op form is input_stage_torch)")
+    if src.dim() < 1 or not 1 <= len(groups) <= L.INSTAGE_MAX_GROUPS:
+        raise ValueError(f"input_stage: src is [..., ld] and there are 1 .. {L.INSTAGE_MAX_GROUPS} groups")
+    segments = tuple(tuple((int(c0), int(ln)) for c0, ln in segs) for _, _, segs in groups)
+    packs, place = _stage_layout(src.shape[-1], [(w, b, sg) for (w, b, _), sg in zip(groups, segments)], packs)
+    if (any(not 1 <= len(sg) <= L.INSTAGE_MAX_SEGS or sum(ln for _, ln in sg) > L.INSTAGE_MAX_K for sg in segments)
+            or sum(w.shape[0] for w, _, _ in groups) > L.INSTAGE_MAX_OUT):
+        raise ValueError(f"input_stage: at most {L.INSTAGE_MAX_SEGS} segments and {L.INSTAGE_MAX_K} inputs per group, {L.INSTAGE_MAX_OUT} outputs in all")
+    return _InputStage.apply(src, segments, packs, place, *[w for w, _, _ in groups], *[b for _, b, _ in groups])
+
+
+def input_stage_torch(src, groups, packs=None):
+    """input_stage with torch ops, any dtype and device (the A/B partner, and the modules' own front restated): per group the column runs
+    sliced and concatenated, F.linear, tanh; per pack the results concatenated"""
+    packs, _ = _stage_layout(src.shape[-1], groups, packs)
+    ys = []
+    for w, b, segs in groups:
+        runs = [src[..., c0:c0 + ln] for c0, ln in segs]
+        ys.append(torch.tanh(F.linear(runs[0] if len(runs) == 1 else torch.cat(runs, dim=-1), w, b)))
+    return tuple(ys[p[0]] if len(p) == 1 else torch.cat([ys[i] for i in p], dim=-1) for p in packs)
+
+
+def stage_layers(kind):
+    """the modules of TrainableNet(kind) that hold the stages' parameters, in the order of stage_tables' groups"""
+    names = tuple(f"inp{i + 1}" for i in range(len(PN.INPUTS[kind])))
+    return {"actor": names, "critic": ("v1", "v2", "v3") if PN.HAS_ATT[kind] else ("inp1_val",)}
+
+
+COMMANDER_STAGE_LAYERS = {"actor": ("inp1", "inp2", "inp3", "inp4"), "critic": ("v1", "v2", "v3", "v4")}
+
+
+def stage_tables(kind):
+    """the input stages of TrainableNet(kind), derived from PN.INPUTS and PN.CRITIC_DIMS -> {"actor" | "critic": (segments per layer,
+    packs)}: the actor reads the own observation, the critic the [act_own | act_2 | o_own | o_2] row of central_critic_rows; the
+    layers are stage_layers(kind)'s"""
+    segs = tuple(((c0, c1 - c0),) for c0, c1, _ in PN.INPUTS[kind])
+    d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
+    own, other = ((a1 + a2, d1), (0, a1)), ((a1 + a2 + d1, d2), (a1, a2))      # [o_own | act_own], [o_2 | act_2]
+    if PN.HAS_ATT[kind]:
+        return {"actor": (segs, ((0, 1), (2,))), "critic": ((own, other, own + other), ((0, 1), (2,)))}
+    return {"actor": (segs, ((0, 1, 2),)), "critic": ((own + other,), ((0,),))}
+
+
+def commander_stage_tables():
+    """stage_tables for CommanderTrainable (layers: COMMANDER_STAGE_LAYERS): the actor reads the 34-wide observation, the critic
+    central_critic_rows_hl's [a_own, a_o1, a_o2 | obs_own | obs_o1 | obs_o2] row, v_k = [obs_k | a_k]"""
+    v = tuple(((3 + 34 * k, 34), (k, 1)) for k in range(3))
+    return {"actor": ((((0, 4),), ((4, 20),), ((24, 10),), ((0, 34),)), ((0, 1, 2), (3,))),
+            "critic": (v + (v[0] + v[1] + v[2],), ((0, 1, 2), (3,)))}
+
+
+def stage_groups(module, names, table):
+    """(groups, packs) for input_stage / input_stage_torch from a module's layers `names` and one of stage_tables' (segments, packs)"""
+    segs, packs = table
+    lin = [getattr(module, nm)._model[0] for nm in names]
+    return [(l.weight, l.bias, sg) for l, sg in zip(lin, segs)], packs
+
+
 # ------------------------------------------------------------------------------------------------------------------ the networks
 class _FC(nn.Module):
     """a linear layer under the reference's parameter names (RLlib's SlimFC keeps its nn.Linear in `_model.0`)"""
@@ -260,11 +408,18 @@ class TrainableNet(nn.Module):
 
     attention = "torch" (the default) runs att_act / att_val through nn.MultiheadAttention and F.normalize.  "fused" (fight kinds only,
     float32 on the GPU) keeps the two projections as GEMMs and runs what lies between and after them through chunk_attention and
-    residual_normalize; the nn.MultiheadAttention objects stay the parameter holders, so state_dict() is the same either way."""
+    residual_normalize; the nn.MultiheadAttention objects stay the parameter holders, so state_dict() is the same either way.
 
-    def __init__(self, kind, attention="torch"):
+    inputs = "torch" (the default) slices, concatenates and runs inp1..inp3 and v1..v3 / inp1_val one by one.  "fused" (any kind, float32
+    on the GPU) runs each side's layers as ONE input_stage that reads obs_own / critic_row as they are and writes the concatenated
+    activations (stage_tables(kind)); the _FC modules stay the parameter holders.  Independent of `attention`."""
+
+    def __init__(self, kind, attention="torch", inputs="torch"):
         super().__init__()
         self.kind = int(kind)
+        if inputs not in INPUT_MODES:
+            raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
+        self.inputs = inputs
         if attention not in ATTENTION_MODES:
             raise ValueError(f"attention is one of {ATTENTION_MODES}, got {attention!r}")
         if attention == "fused" and not PN.HAS_ATT[self.kind]:
@@ -290,32 +445,39 @@ class TrainableNet(nn.Module):
         out = F.linear(chunk_attention(qkv), att.out_proj.weight, att.out_proj.bias)
         return residual_normalize(h, out)
 
+    @staticmethod
+    def _attend_torch(att, h):
+        """normalize(h + att(h, h, h)) through nn.MultiheadAttention and F.normalize"""
+        a, _ = att(h, h, h, need_weights=False)
+        return F.normalize(h + a, dim=-1)
+
     def forward(self, obs_own, critic_row):
         kind = self.kind
-        d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
         flat = PN.HAS_ATT[kind] and obs_own.dim() == 2
         if flat:
             obs_own, critic_row = obs_own[:, None], critic_row[:, None]
-        x = obs_own[..., :PN.OBS_DIM[kind]]
-        h = [torch.tanh(getattr(self, f"inp{i + 1}")(x[..., c0:c1])) for i, (c0, c1, _) in enumerate(PN.INPUTS[kind])]
-        act_own, act_2 = critic_row[..., :a1], critic_row[..., a1:a1 + a2]
-        o_own, o_2 = critic_row[..., a1 + a2:a1 + a2 + d1], critic_row[..., a1 + a2 + d1:]
-        v1, v2 = torch.cat((o_own, act_own), dim=-1), torch.cat((o_2, act_2), dim=-1)
-        v3 = torch.cat((v1, v2), dim=-1)
-        if PN.HAS_ATT[kind] and self.attention == "fused":
-            h[2] = self._attend_fused(self.att_act, h[2])
-            y = torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1)
-            y = torch.cat((y, self._attend_fused(self.att_val, torch.tanh(self.v3(v3)))), dim=-1)
-        elif PN.HAS_ATT[kind]:
-            att, _ = self.att_act(h[2], h[2], h[2], need_weights=False)
-            h[2] = F.normalize(h[2] + att, dim=-1)
-            y = torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1)
-            yf = torch.tanh(self.v3(v3))
-            att, _ = self.att_val(yf, yf, yf, need_weights=False)
-            y = torch.cat((y, F.normalize(yf + att, dim=-1)), dim=-1)
+        # the front: h and y are the pieces that shared_layer sees side by side; a fight kind's last piece goes through its attention block first
+        if self.inputs == "fused":
+            tables, layers = stage_tables(kind), stage_layers(kind)
+            h = list(input_stage(obs_own.contiguous(), *stage_groups(self, layers["actor"], tables["actor"])))
+            y = list(input_stage(critic_row.contiguous(), *stage_groups(self, layers["critic"], tables["critic"])))
         else:
-            y = torch.tanh(self.inp1_val(v3))
-        logits = self.act_out(torch.tanh(self.shared_layer(torch.cat(h, dim=-1))))
+            d1, a1, d2, a2 = PN.CRITIC_DIMS[kind]
+            x = obs_own[..., :PN.OBS_DIM[kind]]
+            h = [torch.tanh(getattr(self, f"inp{i + 1}")(x[..., c0:c1])) for i, (c0, c1, _) in enumerate(PN.INPUTS[kind])]
+            act_own, act_2 = critic_row[..., :a1], critic_row[..., a1:a1 + a2]
+            o_own, o_2 = critic_row[..., a1 + a2:a1 + a2 + d1], critic_row[..., a1 + a2 + d1:]
+            v1, v2 = torch.cat((o_own, act_own), dim=-1), torch.cat((o_2, act_2), dim=-1)
+            v3 = torch.cat((v1, v2), dim=-1)
+            if PN.HAS_ATT[kind]:
+                y = [torch.cat((torch.tanh(self.v1(v1)), torch.tanh(self.v2(v2))), dim=-1), torch.tanh(self.v3(v3))]
+            else:
+                y = [torch.tanh(self.inp1_val(v3))]
+        if PN.HAS_ATT[kind]:
+            attend = self._attend_fused if self.attention == "fused" else self._attend_torch
+            h[-1], y[-1] = attend(self.att_act, h[-1]), attend(self.att_val, y[-1])
+        h, y = (t[0] if len(t) == 1 else torch.cat(t, dim=-1) for t in (h, y))
+        logits = self.act_out(torch.tanh(self.shared_layer(h)))
         value = self.val_out(torch.tanh(self.shared_layer(y))).squeeze(-1)
         if flat:
             logits, value = logits[:, 0], value[:, 0]
@@ -434,17 +596,18 @@ class PPOLearner:
     when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
-                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch"):
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch"):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
-        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*)."""
+        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
+        inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*)."""
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
-        self.attention = attention
-        self.modules = tie([TrainableNet(k, attention=attention).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+        self.attention, self.inputs = attention, inputs
+        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
                             for k, sd in zip(self.kinds, state_dicts)])
         for m in self.modules:
             m.to(self.device)
@@ -809,10 +972,15 @@ class CommanderTrainable(nn.Module):
     rnn_act / rnn_val start from.  critic_row is rollout.central_critic_rows_hl's layout [a_own, a_o1, a_o2 | obs_own | obs_o1 | obs_o2];
     v1..v3 see [obs_k | act_k], v4 all three.  The GRU outputs are 0 at padded steps, whose logits and values mean nothing.
     fused_gru=True runs both GRUs through gru_sequence_pair (CUDA, float32, seq_len int32); False steps the same cell with torch ops on
-    any device and dtype.  return_states=True appends (h_act, h_val) [S, 200] each: the states after each sequence's last step."""
+    any device and dtype.  return_states=True appends (h_act, h_val) [S, 200] each: the states after each sequence's last step.
+    inputs = "fused" (float32 on the GPU) runs inp1..inp4 and v1..v4 as one input_stage each (commander_stage_tables()) that read obs_own and
+    critic_row as they are; the default "torch" slices, concatenates and runs the eight layers one by one.  state_dict() is the same."""
 
-    def __init__(self):
+    def __init__(self, inputs="torch"):
         super().__init__()
+        if inputs not in INPUT_MODES:
+            raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
+        self.inputs = inputs
         self.shared_layer = _FC(500, 500)
         self.rnn_act, self.rnn_val = _GRUWeights(), _GRUWeights()
         self.inp1, self.inp2, self.inp3, self.inp4 = _FC(4, 50), _FC(20, 200), _FC(10, 50), _FC(34, 200)
@@ -821,14 +989,19 @@ class CommanderTrainable(nn.Module):
         self.val_out = _FC(500, 1)
 
     def forward(self, obs_own, critic_row, state_in, seq_len, fused_gru=True, return_states=False):
-        x = torch.cat((torch.tanh(self.inp1(obs_own[..., :4])), torch.tanh(self.inp2(obs_own[..., 4:24])),
-                       torch.tanh(self.inp3(obs_own[..., 24:]))), dim=-1)
-        x_full = torch.tanh(self.inp4(obs_own))
-        a = critic_row[..., :3]
-        o = [critic_row[..., 3 + 34 * k:3 + 34 * (k + 1)] for k in range(3)]
-        v = [torch.cat((o[k], a[..., k:k + 1]), dim=-1) for k in range(3)]
-        z = torch.cat([torch.tanh(m(vk)) for m, vk in zip((self.v1, self.v2, self.v3), v)], dim=-1)
-        z_full = torch.tanh(self.v4(torch.cat(v, dim=-1)))
+        if self.inputs == "fused":
+            tables = commander_stage_tables()
+            x, x_full = input_stage(obs_own.contiguous(), *stage_groups(self, COMMANDER_STAGE_LAYERS["actor"], tables["actor"]))
+            z, z_full = input_stage(critic_row.contiguous(), *stage_groups(self, COMMANDER_STAGE_LAYERS["critic"], tables["critic"]))
+        else:
+            x = torch.cat((torch.tanh(self.inp1(obs_own[..., :4])), torch.tanh(self.inp2(obs_own[..., 4:24])),
+                           torch.tanh(self.inp3(obs_own[..., 24:]))), dim=-1)
+            x_full = torch.tanh(self.inp4(obs_own))
+            a = critic_row[..., :3]
+            o = [critic_row[..., 3 + 34 * k:3 + 34 * (k + 1)] for k in range(3)]
+            v = [torch.cat((o[k], a[..., k:k + 1]), dim=-1) for k in range(3)]
+            z = torch.cat([torch.tanh(m(vk)) for m, vk in zip((self.v1, self.v2, self.v3), v)], dim=-1)
+            z_full = torch.tanh(self.v4(torch.cat(v, dim=-1)))
         ra, rv = self.rnn_act, self.rnn_val
         gi_a = x_full @ ra.weight_ih_l0.T + ra.bias_ih_l0
         gi_v = z_full @ rv.weight_ih_l0.T + rv.bias_ih_l0
@@ -893,12 +1066,14 @@ class CommanderLearner:
     (gru_sequence_torch) instead of hh_ppo_loss_categorical and hh_gru_seq_*; nothing else differs."""
 
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
-                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True):
-        """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys()"""
+                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch"):
+        """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys().  inputs: CommanderTrainable's argument
+        ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*)."""
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
-        self.module = CommanderTrainable().load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        self.inputs = inputs
+        self.module = CommanderTrainable(inputs=inputs).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
         self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)

@@ -2,7 +2,8 @@
  * hh_learner.h — C ABI of the learner side of train_hetero.py's and train_hier.py's PPO (part of libhh_world.so): the fused PPO loss,
  * forward and backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies and for the commander's Categorical,
  * the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*), and the fight networks' chunk attention without its
- * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*, at the end of this file).
+ * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*), and the networks' input layers as one grouped stage (hh_input_stage_*, at the end of
+ * this file).
  *
  * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
  * predictions, per row that the mask keeps (n = number of such rows):
@@ -136,6 +137,46 @@ int hh_chunk_attn_backward(int64_t n_seq, int32_t len, int32_t embed, const floa
 int hh_residual_normalize_forward (int64_t n_rows, int32_t width, const float *x, const float *a, float *y, float *norm, void *stream);
 /* d_s (= d_x = d_a) = (d_y - y (y . d_y)) / norm where norm >= 1e-12, d_y / 1e-12 elsewhere (autograd of clamp_min and of norm at 0) */
 int hh_residual_normalize_backward(int64_t n_rows, int32_t width, const float *y, const float *norm, const float *d_y, float *d_s, void *stream);
+
+/* ---- the input stage: what every trainable network does in front of shared_layer (inp1..inp4, v1..v4, inp1_val) ----
+ *
+ * n_groups <= HH_INSTAGE_MAX_GROUPS layers  y_g = tanh(W_g gather_g(src) + b_g)  from ONE source matrix src [n_rows, src_width] (row
+ * stride src_ld floats), each layer's input the concatenation of up to HH_INSTAGE_MAX_SEGS column runs of a source row, each output written
+ * to its own place: g->y is the first element of the group's columns in a wider (concatenated) tensor of row stride y_ld.
+ * Backward, from the saved y (no pre-activation is kept):
+ *     d_pre = d_y (1 - y^2);   d_b[n] = sum_r d_pre[r, n];   d_w[n, k] = sum_r d_pre[r, n] src[r, col_k]
+ * There is no gradient for src: observations and critic rows are data.
+ * All tensors are float32 and everything is ordered on `stream`; no allocation, no host synchronisation, HIP-graph capturable.  The
+ * forward is one launch, the backward two: per-workgroup partial sums over the rows into `scratch` (float32 products and sums for d_w;
+ * d_b's sum of d_pre runs in float64 and is stored as float32), then the partial sums of every element added in slot order in float64
+ * and rounded to float32 once — no floating-point atomics, the same inputs give the same bytes on every run.  The workgroups of the first backward launch walk the row tiles (32 rows)
+ * grid-stride, HH_INSTAGE_MAX_PARTS of them at most per column block, so hh_input_stage_scratch_bytes stops growing at
+ * HH_INSTAGE_MAX_PARTS * 32 = 2048 rows (it is then HH_INSTAGE_MAX_PARTS * sum_g n_out (K + 1) * 4 bytes).
+ * All pointers are [dev] and need 4-byte alignment only; an output may not overlap any other tensor of the call.  HH_E_ARG, with nothing
+ * launched: n_groups outside 1..HH_INSTAGE_MAX_GROUPS, n_seg outside 1..HH_INSTAGE_MAX_SEGS, K outside 1..HH_INSTAGE_MAX_K, n_out < 1,
+ * sum n_out > HH_INSTAGE_MAX_OUT, an empty segment or one that reaches outside [0, src_width), src_ld < src_width, y_ld < n_out (backward:
+ * d_y_ld < n_out too), n_rows < 0, a null pointer among those the call uses, a scratch that is too small.  n_rows == 0 succeeds without a
+ * launch.  The fields a call does not use are ignored. */
+#define HH_INSTAGE_MAX_GROUPS 4
+#define HH_INSTAGE_MAX_SEGS   6     /* commander v4: [o1|a1|o2|a2|o3|a3] */
+#define HH_INSTAGE_MAX_K      112   /* widest input: 105 */
+#define HH_INSTAGE_MAX_OUT    500   /* sum of n_out over the groups of one call */
+#define HH_INSTAGE_MAX_PARTS  64    /* the cap on the backward's partial sums per output element */
+
+typedef struct hh_input_group {     /* field order is ABI; host struct of device pointers, like hh_gru_seq_io */
+    int32_t n_out, n_seg;
+    int16_t seg_col[HH_INSTAGE_MAX_SEGS], seg_len[HH_INSTAGE_MAX_SEGS]; /* the layer's input = these column runs of a src row, in order; K = sum seg_len */
+    const float *w, *b;             /* [n_out, K] (nn.Linear layout), [n_out]                                   forward */
+    float *y;  int64_t y_ld;        /* forward out / backward in: first element of this group's columns, row stride in floats */
+    const float *d_y; int64_t d_y_ld; /* backward in: d loss / d y, placed like y */
+    float *d_w, *d_b;               /* backward out: [n_out, K], [n_out] */
+} hh_input_group;
+
+/* bytes of `scratch` that hh_input_stage_backward needs for these groups (n_out, n_seg and the segments are read) and n_rows rows */
+int hh_input_stage_scratch_bytes(int32_t n_groups, const hh_input_group *g, int64_t n_rows, int64_t *bytes);
+int hh_input_stage_forward (int64_t n_rows, const float *src, int64_t src_ld, int32_t src_width, int32_t n_groups, const hh_input_group *g, void *stream);
+int hh_input_stage_backward(int64_t n_rows, const float *src, int64_t src_ld, int32_t src_width, int32_t n_groups, const hh_input_group *g,
+                            void *scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,9 @@
           torch.nn.GRU (MIOpen) with the same weights, device events
   step    one minibatch step of CommanderLearner (forward, loss, backward, Adam), fused against unfused
   update  one whole update, fused against unfused, at N arenas and T commander steps per collect
+  inputs  --inputs: only the minibatch step with CommanderLearner(inputs="fused") (hh_input_stage_*) against the default inputs="torch",
+          both in one process, at 256 and 16384 rows; its lines are appended to --out.  A difference is called a gain (or a loss) only
+          where the medians differ by more than the larger of the two (max - min) spreads
 Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
 that fails or runs out of time ends the run, nothing is retried.
     python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
@@ -139,6 +142,32 @@ def step_step(a, say):
                 f"sequences: {q(t)}")
 
 
+def step_inputs(a, say):
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    ro, net = _rollout(a)
+    dev = torch.device("cuda", 0)
+    med = statistics.median
+    say(f"# tools/commander_learner_bench.py --inputs on {torch.cuda.get_device_name(0)}: CommanderLearner(inputs=\"fused\") against the default "
+        f"inputs=\"torch\", both in this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+    learners = {inp: LR.CommanderLearner.trainable_init(dev, seed=6, inputs=inp) for inp in ("torch", "fused")}
+    with torch.no_grad():
+        b = learners["torch"].policy_batch(ro.episodes.sequences())
+        b["old_logits"] = learners["torch"].old_logits(b)
+    seq_len = b["seq_len"].cpu().numpy()
+    for size in (256, 16384):
+        s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+        mb = {k: v[s0:s1] for k, v in b.items()}
+        mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+        t = {inp: events(lambda: lr.minibatch_step(mb), a.iters, a.warmup) for inp, lr in learners.items()}
+        spread = max(max(v) - min(v) for v in t.values())
+        d = med(t["torch"]) - med(t["fused"])
+        word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+        say(f"minibatch step (forward + loss + backward + Adam, fused GRU and loss), {int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} sequences: "
+            f"inputs = torch {q(t['torch'])}; inputs = fused {q(t['fused'])}; torch / fused = {med(t['torch']) / med(t['fused']):.2f}x, medians "
+            f"{d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}")
+
+
 def step_update(a, say):
     import torch
     from hhmarl_2d_amd import learner as LR
@@ -168,7 +197,8 @@ def main():
     ap.add_argument("--passes", type=int, default=1)
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_learner.log"))
-    ap.add_argument("--step", choices=[s for s, _ in STEPS], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--inputs", action="store_true", help="only the inputs=\"fused\" against inputs=\"torch\" minibatch step; appended to --out")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     if a.step:
         sys.path.insert(0, ROOT)
@@ -181,12 +211,14 @@ def main():
                     f.write(s + "\n")
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
-        {"gru": step_gru, "step": step_step, "update": step_update}[a.step](a, say)
+        {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs}[a.step](a, say)
         return
+    fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
+    if a.inputs:
+        sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step inputs {' '.join(fwd)}", shell=True))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         open(a.out, "w").close()
-    fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
     cmd = " && ".join(f"timeout -k 10 {limit} '{sys.executable}' '{os.path.abspath(__file__)}' --step {s} {' '.join(fwd)}" for s, limit in STEPS)
     sys.exit(subprocess.call(cmd, shell=True))
 

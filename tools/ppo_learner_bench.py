@@ -18,6 +18,11 @@
           chunks of 20; (b) the Fight1 minibatch step at 256 and 65536 rows; (c) the four kernels alone as bytes/s of their algorithmic
           bytes (core: 16 E per row forward, 28 E backward; normalize: 12 E + 4 each way).  A difference is called a gain (or a loss)
           only where the medians differ by more than the larger of the two (max - min) spreads
+  inputs  --inputs runs this section alone and appends its lines to --out: everything in front of shared_layer through
+          TrainableNet(inputs="fused") (hh_input_stage_*) against the default slices + cat + nn.Linear + tanh + cat, both timed in the
+          same run: (a) each Fight1 stage (actor, critic), forward + backward, at 14 and 3560 chunks of 20; (b) the stage kernels
+          alone as bytes/s of their algorithmic bytes (forward: the source row in, the activations out; backward: the source row, y
+          and d_y in); (c) the Fight1 minibatch step with attention="fused" at 256 and 65536 rows.  The same rule for gain / loss
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -53,6 +58,7 @@ def main():
     ap.add_argument("--minibatch", type=int, default=65536)
     ap.add_argument("--old-logits-only", action="store_true", help="only the old_logits section; its lines are appended to --out")
     ap.add_argument("--attention", action="store_true", help="only the chunk-attention section; its lines are appended to --out")
+    ap.add_argument("--inputs", action="store_true", help="only the input-stage section; its lines are appended to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -183,6 +189,98 @@ def main():
     if a.attention:
         lines.clear()
         attention_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def inputs_section():
+        """inputs="fused" against inputs="torch": each Fight1 stage, the stage kernels alone, the minibatch step"""
+        import ctypes as C
+        from hhmarl_2d_amd import _lib as L
+        from hhmarl_2d_amd import policy_nets as PN
+        med = statistics.median
+
+        def verdict(t_torch, t_fused):
+            spread = max(max(t_torch) - min(t_torch), max(t_fused) - min(t_fused))
+            d = med(t_torch) - med(t_fused)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"torch / fused = {med(t_torch) / med(t_fused):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --inputs on {torch.cuda.get_device_name(0)}: TrainableNet(inputs=\"fused\") against the default "
+            f"inputs=\"torch\", both in this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+        kind = PN.FIGHT1
+        net = LR.TrainableNet(kind).to(dev)
+        tables, layers = LR.stage_tables(kind), LR.stage_layers(kind)
+        lib = L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for side, width in (("actor", PN.OBS_DIM[kind]), ("critic", sum(PN.CRITIC_DIMS[kind]))):
+            groups, packs = LR.stage_groups(net, layers[side], tables[side])
+            for S in (14, 3560):
+                R = S * 20
+                g = torch.Generator().manual_seed(S + width)
+                src = torch.rand((S, 20, width), generator=g).to(dev)
+                d_out = [torch.randn((S, 20, sum(groups[i][0].shape[0] for i in p)), generator=g).to(dev) for p in packs]
+
+                def stage(fn):
+                    net.zero_grad(set_to_none=True)
+                    torch.autograd.backward(fn(src, groups, packs), d_out)
+                t_t, t_f = events(lambda: stage(LR.input_stage_torch)), events(lambda: stage(LR.input_stage))
+                say(f"input stage (Fight1 {side}: {' '.join(layers[side])} -> {[d.shape[-1] for d in d_out]}; forward + backward), {S} chunks of 20: "
+                    f"torch {q(t_t)}; fused {q(t_f)}; {verdict(t_t, t_f)}")
+                # the kernels alone, on buffers of their own
+                n = len(groups)
+                io = (L.HHInputGroup * n)()
+                outs = [torch.empty_like(d) for d in d_out]
+                d_ws, d_bs = [torch.empty_like(w) for w, _, _ in groups], [torch.empty_like(b) for _, b, _ in groups]
+                for pi, pk in enumerate(packs):
+                    col = 0
+                    for i in pk:
+                        w_, b_, segs = groups[i]
+                        io[i].n_out, io[i].n_seg = w_.shape[0], len(segs)
+                        for k, (c0, ln) in enumerate(segs):
+                            io[i].seg_col[k], io[i].seg_len[k] = c0, ln
+                        io[i].w, io[i].b = w_.data_ptr(), b_.data_ptr()
+                        io[i].y, io[i].y_ld = outs[pi].data_ptr() + 4 * col, outs[pi].shape[-1]
+                        io[i].d_y, io[i].d_y_ld = d_out[pi].data_ptr() + 4 * col, d_out[pi].shape[-1]
+                        io[i].d_w, io[i].d_b = d_ws[i].data_ptr(), d_bs[i].data_ptr()
+                        col += w_.shape[0]
+                nb = C.c_int64()
+                L.check(lib.hh_input_stage_scratch_bytes(n, io, R, C.byref(nb)))
+                scratch = torch.empty((nb.value // 4,), device=dev)
+                p = lambda t: C.c_void_p(t.data_ptr())
+                n_out = sum(w_.shape[0] for w_, _, _ in groups)
+                runs = (("hh_input_stage_forward", 4 * R * (width + n_out), lambda: L.check(lib.hh_input_stage_forward(R, p(src), width, width, n, io, st))),
+                        ("hh_input_stage_backward", 4 * R * (width + 2 * n_out),
+                         lambda: L.check(lib.hh_input_stage_backward(R, p(src), width, width, n, io, p(scratch), nb.value, st))))
+                for name, nbytes, fn in runs:
+                    t = events(fn)
+                    say(f"    {name} alone, Fight1 {side}, {S} chunks of 20 ({R} rows): {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB "
+                        f"algorithmic bytes ({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+        # the Fight1 minibatch step, attention = "fused" in both
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        learners = {inp: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, attention="fused", inputs=inp) for inp in ("torch", "fused")}
+        with torch.no_grad():
+            old = learners["torch"].old_logits(rows["obs"], bank, ro.episodes.N)
+            b = learners["torch"].policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            mb = {k: v[s0:s1] for k, v in b.items() if k != "seq_len"}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            t = {inp: events(lambda: lr.minibatch_step(0, mb)) for inp, lr in learners.items()}
+            say(f"minibatch step ({PN.KIND_NAMES[learners['torch'].kinds[0]]}, forward + loss + backward + Adam, fused loss, attention = fused), "
+                f"{int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} chunks of 20: inputs = torch {q(t['torch'])}; inputs = fused {q(t['fused'])}; "
+                f"{verdict(t['torch'], t['fused'])}")
+
+    if a.inputs:
+        lines.clear()
+        inputs_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
