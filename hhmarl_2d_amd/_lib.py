@@ -128,7 +128,7 @@ COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commande
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
                    "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
                    "hh_residual_normalize_backward", "hh_input_stage_scratch_bytes", "hh_input_stage_forward",
-                   "hh_input_stage_backward"]  # include/hh_learner.h
+                   "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward"]  # include/hh_learner.h
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
@@ -152,6 +152,14 @@ class HHInputGroup(C.Structure):
     _fields_ = [("n_out", C.c_int32), ("n_seg", C.c_int32), ("seg_col", C.c_int16 * INSTAGE_MAX_SEGS), ("seg_len", C.c_int16 * INSTAGE_MAX_SEGS),
                 ("w", C.c_void_p), ("b", C.c_void_p), ("y", C.c_void_p), ("y_ld", C.c_int64), ("d_y", C.c_void_p), ("d_y_ld", C.c_int64),
                 ("d_w", C.c_void_p), ("d_b", C.c_void_p)]
+
+
+DENSE_MAX_SRC, DENSE_MAX_DIM, DENSE_ROW_TILE, DENSE_MAX_PARTS, DENSE_FWD_SCRATCH_BYTES = 2, 512, 64, 32, 2048  # HH_DENSE_* (include/hh_learner.h)
+
+
+class HHDenseSrc(C.Structure):
+    """hh_dense_src (include/hh_learner.h): one row block of hh_dense_tanh_*, its row count, then device pointers; field order is ABI"""
+    _fields_ = [("n_rows", C.c_int64), ("x", C.c_void_p), ("ld", C.c_int64), ("y", C.c_void_p), ("d_y", C.c_void_p), ("d_x", C.c_void_p)]
 
 
 _lib = None
@@ -247,6 +255,9 @@ def lib():
         L.hh_input_stage_scratch_bytes.argtypes = [C.c_int32, C.POINTER(HHInputGroup), C.c_int64, C.POINTER(C.c_int64)]
         L.hh_input_stage_forward.argtypes = [C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HHInputGroup), vp]
         L.hh_input_stage_backward.argtypes = [C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HHInputGroup), vp, C.c_int64, vp]
+        L.hh_dense_tanh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), C.POINTER(C.c_int64)]
+        L.hh_dense_tanh_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), vp, vp, vp, C.c_int64, vp]
+        L.hh_dense_tanh_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), vp, vp, vp, vp, C.c_int64, vp]
         _lib = L
     return _lib
 

@@ -901,3 +901,7 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- the learner's weights into the policy bank and the commander on the device (C ABI in include/hh_policy.h, include/hh_commander.h) ---- */
 #include "hh_weight_refresh.h"
+
+/* ---- the learners' shared layer on the matrix cores, forward and backward (C ABI in include/hh_learner.h; after the policy kernels: it uses their
+ * fp16 split and fragment types) ---- */
+#include "hh_dense_tanh.h"

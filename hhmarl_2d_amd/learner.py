@@ -7,6 +7,8 @@ batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss a
 (`chunk_attention`: hh_chunk_attn_*, `residual_normalize`: hh_residual_normalize_*); the default path is nn.MultiheadAttention.
 Opt-in as well (`inputs="fused"`, all five networks): the layers in front of shared_layer as one grouped launch per side
 (`input_stage`: hh_input_stage_*); the default path slices, concatenates and runs them one by one.
+And (`trunk="fused"`, all five networks): shared_layer with its bias and tanh over the actor's and the critic's rows as ONE call
+on the matrix cores (`dense_tanh`: hh_dense_tanh_*, split-fp16 MFMA); the default path is two float32 GEMMs and two tanh.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -381,6 +383,106 @@ def stage_groups(module, names, table):
     return [(l.weight, l.bias, sg) for l, sg in zip(lin, segs)], packs
 
 
+# ------------------------------------------------------------------------------------------------------------------ the shared layer
+TRUNK_MODES = ("torch", "fused")
+
+
+def _dense_rows(x):
+    """x [..., K] -> (its rows as a 2-D tensor the kernels can read in place, the row stride in floats): a view where the last dimension is
+    contiguous and the leading ones collapse to one stride >= K (a column slice of a wider row is read where it lies), else a copy"""
+    K = x.shape[-1]
+    x2 = x.reshape(-1, K)
+    if (K > 1 and x2.stride(1) != 1) or (x2.shape[0] > 1 and x2.stride(0) < K):
+        x2 = x2.contiguous()
+    return x2, (x2.stride(0) if x2.shape[0] > 1 else K)
+
+
+class _DenseTanh(torch.autograd.Function):
+    """forward: hh_dense_tanh_forward over all row blocks; backward: hh_dense_tanh_backward from the kept inputs and outputs"""
+
+    @staticmethod
+    def forward(ctx, weight, bias, *xs):
+        N, K = weight.shape
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        flat = [_dense_rows(x.detach())[0] for x in xs]
+        ys = [torch.empty(tuple(x.shape[:-1]) + (N,), dtype=torch.float32, device=x.device) for x in xs]
+        io = (L.HHDenseSrc * len(xs))()
+        for i, (x2, y) in enumerate(zip(flat, ys)):
+            io[i].n_rows, io[i].x, io[i].ld, io[i].y = x2.shape[0], x2.data_ptr(), _dense_rows(x2)[1], y.data_ptr()
+        scratch = torch.empty((L.DENSE_FWD_SCRATCH_BYTES // 4,), dtype=torch.int32, device=w.device)
+        L.check(L.lib().hh_dense_tanh_forward(K, N, len(xs), io, _p(w), _p(b), _p(scratch), L.DENSE_FWD_SCRATCH_BYTES, _stream(w.device)))
+        ctx.save_for_backward(w, *flat, *ys)
+        ctx.n, ctx.x_shapes = len(xs), [tuple(x.shape) for x in xs]
+        return tuple(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *d_ys):
+        w, *rest = ctx.saved_tensors
+        n = ctx.n
+        flat, ys = rest[:n], rest[n:]
+        N, K = w.shape
+        dev = w.device
+        d_ys = [torch.zeros_like(y) if d is None else d.contiguous() for d, y in zip(d_ys, ys)]
+        d_xs = [torch.empty(shp, dtype=torch.float32, device=dev) for shp in ctx.x_shapes]
+        d_w, d_b = torch.empty_like(w), torch.empty((N,), dtype=torch.float32, device=dev)
+        io = (L.HHDenseSrc * n)()
+        for i in range(n):
+            x2 = flat[i]
+            io[i].n_rows, io[i].x, io[i].ld = x2.shape[0], x2.data_ptr(), _dense_rows(x2)[1]
+            io[i].y, io[i].d_y, io[i].d_x = ys[i].data_ptr(), d_ys[i].data_ptr(), d_xs[i].data_ptr()
+        if all(x2.shape[0] == 0 for x2 in flat):
+            return (torch.zeros_like(w), torch.zeros_like(d_b)) + tuple(d_xs)
+        nbytes = C.c_int64()
+        lib = L.lib()
+        L.check(lib.hh_dense_tanh_scratch_bytes(K, N, n, io, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value // 4,), dtype=torch.float32, device=dev)
+        L.check(lib.hh_dense_tanh_backward(K, N, n, io, _p(w), _p(d_w), _p(d_b), _p(scratch), nbytes.value, _stream(dev)))
+        return (d_w, d_b) + tuple(d_xs)
+
+
+def _dense_args(xs):
+    """one tensor or a sequence of them -> (list, whether a single tensor came in)"""
+    single = isinstance(xs, torch.Tensor)
+    return ([xs] if single else list(xs)), single
+
+
+def dense_tanh(xs, weight, bias):
+    """tanh(F.linear(x, weight, bias)) for one or two tensors x [..., K] that go through the same layer, fused and on the matrix cores
+    (hh_dense_tanh_forward / hh_dense_tanh_backward, include/hh_learner.h): split-fp16 MFMA with float32 accumulators, within
+    (4 * 2^-22 + (n + 2) * 2^-24) |A| |B| of float64 per product.  xs: a float32 CUDA tensor or a sequence of one or two (the actor's
+    and the critic's rows: one call serves both); the last dimension may be a column slice of a wider row.  weight f32 [N, K], bias f32
+    [N], 1 <= K, N <= 512, on the same device.  -> a tensor [..., N] per input (a single tensor for a single tensor).  Differentiable
+    with respect to every input, the weight and the bias (first order); the same inputs give the same bytes.  No host synchronisation;
+    a missing library or GPU is an error."""
+    _need_gpu("dense_tanh")
+    xs, single = _dense_args(xs)
+    if not 1 <= len(xs) <= L.DENSE_MAX_SRC:
+        raise ValueError(f"dense_tanh: one .. {L.DENSE_MAX_SRC} inputs, got {len(xs)}")
+    for what, t in [("x", x) for x in xs] + [("weight", weight), ("bias", bias)]:
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise ValueError(f"dense_tanh: {what} is a contiguous float32 CUDA tensor (the torch-op form for other dtypes and devices is dense_tanh_torch)")
+    if (weight.dim() != 2 or tuple(bias.shape) != (weight.shape[0],) or not all(1 <= d <= L.DENSE_MAX_DIM for d in weight.shape)
+            or any(x.dim() < 1 or x.shape[-1] != weight.shape[1] or x.device != weight.device for x in xs) or bias.device != weight.device):
+        raise ValueError(f"dense_tanh: weight [N, K], bias [N], inputs [..., K] on one device with 1 <= K, N <= {L.DENSE_MAX_DIM}, got "
+                         f"{tuple(weight.shape)}, {tuple(bias.shape)} and {[tuple(x.shape) for x in xs]}")
+    ys = _DenseTanh.apply(weight, bias, *xs)
+    return ys[0] if single else ys
+
+
+def dense_tanh_torch(xs, weight, bias):
+    """dense_tanh with torch ops, any dtype and device (the A/B partner): tanh(F.linear(x, weight, bias)) per input"""
+    xs, single = _dense_args(xs)
+    ys = tuple(torch.tanh(F.linear(x, weight, bias)) for x in xs)
+    return ys[0] if single else ys
+
+
+def _trunk_mode(trunk):
+    if trunk not in TRUNK_MODES:
+        raise ValueError(f"trunk is one of {TRUNK_MODES}, got {trunk!r}")
+    return trunk
+
+
 # ------------------------------------------------------------------------------------------------------------------ the networks
 class _FC(nn.Module):
     """a linear layer under the reference's parameter names (RLlib's SlimFC keeps its nn.Linear in `_model.0`)"""
@@ -412,11 +514,17 @@ class TrainableNet(nn.Module):
 
     inputs = "torch" (the default) slices, concatenates and runs inp1..inp3 and v1..v3 / inp1_val one by one.  "fused" (any kind, float32
     on the GPU) runs each side's layers as ONE input_stage that reads obs_own / critic_row as they are and writes the concatenated
-    activations (stage_tables(kind)); the _FC modules stay the parameter holders.  Independent of `attention`."""
+    activations (stage_tables(kind)); the _FC modules stay the parameter holders.  Independent of `attention`.
 
-    def __init__(self, kind, attention="torch", inputs="torch"):
+    trunk = "torch" (the default) applies shared_layer and tanh to the actor's and to the critic's rows one after the other.  "fused" (any
+    kind, float32 on the GPU) runs both through ONE dense_tanh (split-fp16 MFMA, bias and tanh in its epilogue); the _FC module stays
+    the parameter holder, so state_dict(), tie and publish are the same, and a tied layer receives gradients only from the module that
+    ran.  Independent of `attention` and `inputs`."""
+
+    def __init__(self, kind, attention="torch", inputs="torch", trunk="torch"):
         super().__init__()
         self.kind = int(kind)
+        self.trunk = _trunk_mode(trunk)
         if inputs not in INPUT_MODES:
             raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
         self.inputs = inputs
@@ -477,8 +585,13 @@ class TrainableNet(nn.Module):
             attend = self._attend_fused if self.attention == "fused" else self._attend_torch
             h[-1], y[-1] = attend(self.att_act, h[-1]), attend(self.att_val, y[-1])
         h, y = (t[0] if len(t) == 1 else torch.cat(t, dim=-1) for t in (h, y))
-        logits = self.act_out(torch.tanh(self.shared_layer(h)))
-        value = self.val_out(torch.tanh(self.shared_layer(y))).squeeze(-1)
+        if self.trunk == "fused":
+            lin = self.shared_layer._model[0]
+            h, y = dense_tanh((h, y), lin.weight, lin.bias)
+            logits, value = self.act_out(h), self.val_out(y).squeeze(-1)
+        else:
+            logits = self.act_out(torch.tanh(self.shared_layer(h)))
+            value = self.val_out(torch.tanh(self.shared_layer(y))).squeeze(-1)
         if flat:
             logits, value = logits[:, 0], value[:, 0]
         return logits, value
@@ -596,18 +709,19 @@ class PPOLearner:
     when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
-                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch"):
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch"):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
         argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
-        inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*)."""
+        inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*).
+        trunk: TrainableNet's argument too ("fused": shared_layer, bias and tanh of both sides through hh_dense_tanh_*)."""
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
-        self.attention, self.inputs = attention, inputs
-        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+        self.attention, self.inputs, self.trunk = attention, inputs, _trunk_mode(trunk)
+        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs, trunk=trunk).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
                             for k, sd in zip(self.kinds, state_dicts)])
         for m in self.modules:
             m.to(self.device)
@@ -974,10 +1088,13 @@ class CommanderTrainable(nn.Module):
     fused_gru=True runs both GRUs through gru_sequence_pair (CUDA, float32, seq_len int32); False steps the same cell with torch ops on
     any device and dtype.  return_states=True appends (h_act, h_val) [S, 200] each: the states after each sequence's last step.
     inputs = "fused" (float32 on the GPU) runs inp1..inp4 and v1..v4 as one input_stage each (commander_stage_tables()) that read obs_own and
-    critic_row as they are; the default "torch" slices, concatenates and runs the eight layers one by one.  state_dict() is the same."""
+    critic_row as they are; the default "torch" slices, concatenates and runs the eight layers one by one.  state_dict() is the same.
+    trunk = "fused" (float32 on the GPU) runs shared_layer, its bias and tanh over the actor's and the critic's rows as ONE dense_tanh; the
+    default "torch" applies the layer twice.  state_dict() is the same; independent of `inputs`."""
 
-    def __init__(self, inputs="torch"):
+    def __init__(self, inputs="torch", trunk="torch"):
         super().__init__()
+        self.trunk = _trunk_mode(trunk)
         if inputs not in INPUT_MODES:
             raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
         self.inputs = inputs
@@ -1013,8 +1130,13 @@ class CommanderTrainable(nn.Module):
             y_a, y_v = gru_sequence_torch(*act, seq_len), gru_sequence_torch(*val, seq_len)
         x_full = F.normalize(x_full + y_a, dim=-1)
         z_full = F.normalize(z_full + y_v, dim=-1)
-        logits = self.act_out(torch.tanh(self.shared_layer(torch.cat((x, x_full), dim=-1))))
-        value = self.val_out(torch.tanh(self.shared_layer(torch.cat((z, z_full), dim=-1)))).squeeze(-1)
+        if self.trunk == "fused":
+            lin = self.shared_layer._model[0]
+            h, y = dense_tanh((torch.cat((x, x_full), dim=-1), torch.cat((z, z_full), dim=-1)), lin.weight, lin.bias)
+            logits, value = self.act_out(h), self.val_out(y).squeeze(-1)
+        else:
+            logits = self.act_out(torch.tanh(self.shared_layer(torch.cat((x, x_full), dim=-1))))
+            value = self.val_out(torch.tanh(self.shared_layer(torch.cat((z, z_full), dim=-1)))).squeeze(-1)
         if not return_states:
             return logits, value
         last = (seq_len.long() - 1).clamp(min=0)[:, None, None].expand(-1, 1, GRU_H)
@@ -1066,14 +1188,14 @@ class CommanderLearner:
     (gru_sequence_torch) instead of hh_ppo_loss_categorical and hh_gru_seq_*; nothing else differs."""
 
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
-                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch"):
+                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch"):
         """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys().  inputs: CommanderTrainable's argument
-        ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*)."""
+        ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*); trunk: its argument too ("fused": shared_layer through hh_dense_tanh_*)."""
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
-        self.inputs = inputs
-        self.module = CommanderTrainable(inputs=inputs).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        self.inputs, self.trunk = inputs, _trunk_mode(trunk)
+        self.module = CommanderTrainable(inputs=inputs, trunk=trunk).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
         self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)

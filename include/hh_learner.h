@@ -2,8 +2,8 @@
  * hh_learner.h — C ABI of the learner side of train_hetero.py's and train_hier.py's PPO (part of libhh_world.so): the fused PPO loss,
  * forward and backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies and for the commander's Categorical,
  * the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*), and the fight networks' chunk attention without its
- * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*), and the networks' input layers as one grouped stage (hh_input_stage_*, at the end of
- * this file).
+ * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*), the networks' input layers as one grouped stage (hh_input_stage_*), and the
+ * layer they share on the matrix cores (hh_dense_tanh_*, at the end of this file).
  *
  * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
  * predictions, per row that the mask keeps (n = number of such rows):
@@ -177,6 +177,49 @@ int hh_input_stage_scratch_bytes(int32_t n_groups, const hh_input_group *g, int6
 int hh_input_stage_forward (int64_t n_rows, const float *src, int64_t src_ld, int32_t src_width, int32_t n_groups, const hh_input_group *g, void *stream);
 int hh_input_stage_backward(int64_t n_rows, const float *src, int64_t src_ld, int32_t src_width, int32_t n_groups, const hh_input_group *g,
                             void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- the shared layer: y = tanh(x W^T + b) on the matrix cores, for up to two row blocks that go through the same weights ----
+ *
+ * n_src <= HH_DENSE_MAX_SRC row blocks x_i [n_rows_i, K] (row stride ld_i >= K floats; the columns from K on are never read), ONE
+ * w [N, K] (nn.Linear's layout) and b [N]; y_i [n_rows_i, N] contiguous.  1 <= K, N <= HH_DENSE_MAX_DIM, any value in that range (the
+ * networks use 500 / 500); n_rows_i >= 0.  Backward, from the saved y_i (no pre-activation is kept):
+ *     d_pre_i = d_y_i (1 - y_i^2);  d_x_i = d_pre_i W  [n_rows_i, K] contiguous;  d_w = sum_i d_pre_i^T x_i;  d_b = sum_i column sums of d_pre_i
+ * Arithmetic: every product except d_b's sum is v_mfma_f32_16x16x32_f16 on an fp16 (hi, lo) split of both operands (hi hi + lo hi + hi lo,
+ * float32 accumulators).  Every operand is scaled by powers of two before the split (forward: x per row, w per row n; d_x: d_pre per
+ * row, w per column k; d_w: d_pre and x per row tile and column) and the scale is undone on the float32 result, so values of any
+ * magnitude a float32 holds as a normal number keep their 22 bits — d_y of order 1e-12 as well as weights of order 0.03.  Against float64, componentwise, with n the length of the sum:
+ *     |C - C64| <= (4 * 2^-22 + (n + 2) * 2^-24) (|A| |B|)      (tests/dense_tanh_ref.py)
+ * Everything is ordered on `stream`; no allocation, no host synchronisation, HIP-graph capturable.  The forward is two launches (the row scales of w into
+ * `scratch`; the layer), the backward four: the column scales of w; d_x; per-workgroup partial sums of d_w and d_b over the row tiles (HH_DENSE_ROW_TILE rows; the tiles of block 0, then
+ * those of block 1, walked grid-stride by min(HH_DENSE_MAX_PARTS, tiles) workgroups per 128 x 128 block of d_w) into `scratch`; the slots
+ * of every element added in slot order in float64 and rounded once (d_b: float64 sums inside a workgroup as well).  No floating-point
+ * atomics: the same inputs give the same bytes on every run.  hh_dense_tanh_scratch_bytes (what the backward needs) is HH_DENSE_FWD_SCRATCH_BYTES
+ * + min(HH_DENSE_MAX_PARTS, tiles) (N K + N) * 4 (w's scales, then the slots; the forward needs the first HH_DENSE_FWD_SCRATCH_BYTES only, and
+ * the two calls need not share a buffer) and stops growing at HH_DENSE_MAX_PARTS * HH_DENSE_ROW_TILE rows; no split copy of w is kept (every workgroup splits the chunks it reads).
+ * All pointers are [dev] and need 4-byte alignment only; an output may not overlap any other tensor of the call.  HH_E_ARG, with nothing
+ * launched: K or N outside 1..HH_DENSE_MAX_DIM, n_src outside 1..HH_DENSE_MAX_SRC, n_rows < 0, ld < K (forward, backward), a null pointer
+ * among those the call uses (the pointers of a block of 0 rows are not used), a scratch that is too small.  With every block at 0 rows the
+ * call succeeds without a launch.  The fields a call does not use are ignored. */
+#define HH_DENSE_MAX_SRC   2
+#define HH_DENSE_MAX_DIM   512
+#define HH_DENSE_ROW_TILE  64    /* rows per tile of the backward's partial sums (the forward and d_x take two such tiles per workgroup) */
+#define HH_DENSE_MAX_PARTS 32    /* the cap on the backward's partial sums per element of d_w and d_b */
+#define HH_DENSE_FWD_SCRATCH_BYTES 2048   /* the forward's `scratch`: HH_DENSE_MAX_DIM exponents */
+
+typedef struct hh_dense_src {     /* field order is ABI; host struct of device pointers, like hh_input_group */
+    int64_t n_rows;
+    const float *x; int64_t ld;   /* [n_rows, K], row stride in floats                      forward, backward */
+    float *y;                     /* [n_rows, N]                                            forward out, backward in */
+    const float *d_y;             /* [n_rows, N]  d loss / d y                              backward */
+    float *d_x;                   /* [n_rows, K]  d loss / d x                              backward out */
+} hh_dense_src;
+
+/* bytes of `scratch` that hh_dense_tanh_backward needs (n_rows of every block is read) */
+int hh_dense_tanh_scratch_bytes(int32_t K, int32_t N, int32_t n_src, const hh_dense_src *src, int64_t *bytes);
+int hh_dense_tanh_forward (int32_t K, int32_t N, int32_t n_src, const hh_dense_src *src, const float *w, const float *b,
+                           void *scratch, int64_t scratch_bytes, void *stream);
+int hh_dense_tanh_backward(int32_t K, int32_t N, int32_t n_src, const hh_dense_src *src, const float *w, float *d_w, float *d_b,
+                           void *scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,10 @@
   inputs  --inputs: only the minibatch step with CommanderLearner(inputs="fused") (hh_input_stage_*) against the default inputs="torch",
           both in one process, at 256 and 16384 rows; its lines are appended to --out.  A difference is called a gain (or a loss) only
           where the medians differ by more than the larger of the two (max - min) spreads
+  trunk   --trunk: shared_layer, bias and tanh over the actor's and the critic's rows through CommanderLearner(trunk="fused")
+          (hh_dense_tanh_*, split-fp16 MFMA) against the default two float32 GEMMs + tanh, both in one process: the layer alone (forward
+          + backward) and the two kernel calls alone (useful TFLOP/s, 2 R K N per product) at 2 x 262 and 2 x 16396 rows, and the
+          minibatch step with inputs="fused" at 256 and 16384 rows; its lines are appended to --out.  The same rule for gain / loss
 Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
 that fails or runs out of time ends the run, nothing is retried.
     python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
@@ -168,6 +172,73 @@ def step_inputs(a, say):
             f"{d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}")
 
 
+def step_trunk(a, say):
+    import ctypes as C
+
+    import torch
+    from hhmarl_2d_amd import _lib as L
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    med = statistics.median
+
+    def verdict(t_torch, t_fused):
+        spread = max(max(t_torch) - min(t_torch), max(t_fused) - min(t_fused))
+        d = med(t_torch) - med(t_fused)
+        word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+        return f"torch / fused = {med(t_torch) / med(t_fused):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+    say(f"# tools/commander_learner_bench.py --trunk on {torch.cuda.get_device_name(0)}: CommanderLearner(trunk=\"fused\") against the default "
+        f"trunk=\"torch\", both in this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+    lin = torch.nn.Linear(500, 500).to(dev)
+    lib = L.lib()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    for R in (262, 16396):
+        g = torch.Generator().manual_seed(R)
+        xs = [torch.tanh(torch.randn((R, 500), generator=g)).to(dev).requires_grad_(True) for _ in range(2)]
+        dys = [(torch.randn((R, 500), generator=g) / R).to(dev) for _ in range(2)]
+
+        def layer(fn):
+            lin.zero_grad(set_to_none=True)
+            for x in xs:
+                x.grad = None
+            torch.autograd.backward(fn(xs, lin.weight, lin.bias), dys)
+        t_t, t_f = events(lambda: layer(LR.dense_tanh_torch), a.iters, a.warmup), events(lambda: layer(LR.dense_tanh), a.iters, a.warmup)
+        say(f"shared layer (tanh(x W^T + b), 500 -> 500, the actor's and the critic's rows; forward + backward), 2 x {R} rows: "
+            f"torch {q(t_t)}; fused {q(t_f)}; {verdict(t_t, t_f)}")
+        io = (L.HHDenseSrc * 2)()
+        keep = []
+        for i in range(2):
+            y, dx = torch.empty((R, 500), device=dev), torch.empty((R, 500), device=dev)
+            keep += [y, dx]
+            io[i].n_rows, io[i].x, io[i].ld, io[i].y, io[i].d_y, io[i].d_x = R, xs[i].data_ptr(), 500, y.data_ptr(), dys[i].data_ptr(), dx.data_ptr()
+        nb = C.c_int64()
+        L.check(lib.hh_dense_tanh_scratch_bytes(500, 500, 2, io, C.byref(nb)))
+        scratch, d_w, d_b = torch.empty((nb.value // 4,), device=dev), torch.empty((500, 500), device=dev), torch.empty((500,), device=dev)
+        w_, b_ = lin.weight.detach(), lin.bias.detach()
+        flop = 2.0 * (2 * R) * 500 * 500
+        runs = (("hh_dense_tanh_forward", 1, lambda: L.check(lib.hh_dense_tanh_forward(500, 500, 2, io, p(w_), p(b_), p(scratch), nb.value, st))),
+                ("hh_dense_tanh_backward", 2, lambda: L.check(lib.hh_dense_tanh_backward(500, 500, 2, io, p(w_), p(d_w), p(d_b), p(scratch), nb.value, st))))
+        for name, products, fn in runs:
+            t = events(fn, a.iters, a.warmup)
+            tf = products * flop / med(t) / 1e9
+            say(f"    {name} alone, 2 x {R} rows: {q(t)} = {tf:.1f} useful TFLOP/s ({products} product(s) of 2 R K N = {flop / 1e9:.2f} GFLOP): "
+                f"{100 * tf / 155:.1f} % of the 155 TF float32 matrix rate, {100 * tf / (2500 / 3):.1f} % of 2.5 PF / 3")
+    ro, net = _rollout(a)
+    learners = {tr: LR.CommanderLearner.trainable_init(dev, seed=6, inputs="fused", trunk=tr) for tr in ("torch", "fused")}
+    with torch.no_grad():
+        b = learners["torch"].policy_batch(ro.episodes.sequences())
+        b["old_logits"] = learners["torch"].old_logits(b)
+    seq_len = b["seq_len"].cpu().numpy()
+    for size in (256, 16384):
+        s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+        mb = {k: v[s0:s1] for k, v in b.items()}
+        mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+        t = {tr: events(lambda: lr.minibatch_step(mb), a.iters, a.warmup) for tr, lr in learners.items()}
+        say(f"minibatch step (forward + loss + backward + Adam, fused GRU and loss, inputs = fused), {int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} "
+            f"sequences: trunk = torch {q(t['torch'])}; trunk = fused {q(t['fused'])}; {verdict(t['torch'], t['fused'])}")
+
+
 def step_update(a, say):
     import torch
     from hhmarl_2d_amd import learner as LR
@@ -198,7 +269,8 @@ def main():
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_learner.log"))
     ap.add_argument("--inputs", action="store_true", help="only the inputs=\"fused\" against inputs=\"torch\" minibatch step; appended to --out")
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--trunk", action="store_true", help="only the trunk=\"fused\" against trunk=\"torch\" section; appended to --out")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     if a.step:
         sys.path.insert(0, ROOT)
@@ -211,11 +283,13 @@ def main():
                     f.write(s + "\n")
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
-        {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs}[a.step](a, say)
+        {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
     if a.inputs:
         sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step inputs {' '.join(fwd)}", shell=True))
+    if a.trunk:
+        sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step trunk {' '.join(fwd)}", shell=True))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         open(a.out, "w").close()

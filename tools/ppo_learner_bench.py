@@ -23,6 +23,12 @@
           same run: (a) each Fight1 stage (actor, critic), forward + backward, at 14 and 3560 chunks of 20; (b) the stage kernels
           alone as bytes/s of their algorithmic bytes (forward: the source row in, the activations out; backward: the source row, y
           and d_y in); (c) the Fight1 minibatch step with attention="fused" at 256 and 65536 rows.  The same rule for gain / loss
+  trunk   --trunk runs this section alone and appends its lines to --out: shared_layer, its bias and tanh over the actor's and the critic's
+          rows through TrainableNet(trunk="fused") (hh_dense_tanh_*, split-fp16 MFMA) against the default two float32 GEMMs + tanh, both
+          timed in the same run: (a) the layer alone on both sides' rows, forward + backward, at 14 and 3560 chunks of 20; (b) the two
+          kernel calls alone as useful TFLOP/s (2 R K N per product: one forward, two backward), against the 155 TF float32 matrix
+          rate and against 2.5 PF / 3 (three fp16 products per float32 one); (c) the Fight1 minibatch step with attention="fused",
+          inputs="fused" at 256 and 65536 rows.  The same rule for gain / loss
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -59,6 +65,7 @@ def main():
     ap.add_argument("--old-logits-only", action="store_true", help="only the old_logits section; its lines are appended to --out")
     ap.add_argument("--attention", action="store_true", help="only the chunk-attention section; its lines are appended to --out")
     ap.add_argument("--inputs", action="store_true", help="only the input-stage section; its lines are appended to --out")
+    ap.add_argument("--trunk", action="store_true", help="only the shared-layer section; its lines are appended to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -281,6 +288,87 @@ def main():
     if a.inputs:
         lines.clear()
         inputs_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def trunk_section():
+        """trunk="fused" against trunk="torch": the layer alone, the two kernel calls alone, the minibatch step"""
+        import ctypes as C
+        from hhmarl_2d_amd import _lib as L
+        from hhmarl_2d_amd import policy_nets as PN
+        med = statistics.median
+
+        def verdict(t_torch, t_fused):
+            spread = max(max(t_torch) - min(t_torch), max(t_fused) - min(t_fused))
+            d = med(t_torch) - med(t_fused)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"torch / fused = {med(t_torch) / med(t_fused):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --trunk on {torch.cuda.get_device_name(0)}: TrainableNet(trunk=\"fused\") against the default "
+            f"trunk=\"torch\", both in this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+        lin = nn.Linear(500, 500).to(dev)
+        lib = L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        for S in (14, 3560):
+            R = S * 20
+            g = torch.Generator().manual_seed(S)
+            xs = [torch.tanh(torch.randn((S, 20, 500), generator=g)).to(dev).requires_grad_(True) for _ in range(2)]
+            dys = [(torch.randn((S, 20, 500), generator=g) / R).to(dev) for _ in range(2)]
+
+            def layer(fn):
+                lin.zero_grad(set_to_none=True)
+                for x in xs:
+                    x.grad = None
+                torch.autograd.backward(fn(xs, lin.weight, lin.bias), dys)
+            t_t, t_f = events(lambda: layer(LR.dense_tanh_torch)), events(lambda: layer(LR.dense_tanh))
+            say(f"shared layer (tanh(x W^T + b), 500 -> 500, the actor's and the critic's rows; forward + backward), 2 x {S} chunks of 20: "
+                f"torch {q(t_t)}; fused {q(t_f)}; {verdict(t_t, t_f)}")
+            # the kernel calls alone, on buffers of their own
+            io = (L.HHDenseSrc * 2)()
+            keep = []
+            for i in range(2):
+                y, dx = torch.empty((R, 500), device=dev), torch.empty((R, 500), device=dev)
+                keep += [y, dx]
+                io[i].n_rows, io[i].x, io[i].ld, io[i].y, io[i].d_y, io[i].d_x = R, xs[i].data_ptr(), 500, y.data_ptr(), dys[i].data_ptr(), dx.data_ptr()
+            nb = C.c_int64()
+            L.check(lib.hh_dense_tanh_scratch_bytes(500, 500, 2, io, C.byref(nb)))
+            scratch, d_w, d_b = torch.empty((nb.value // 4,), device=dev), torch.empty((500, 500), device=dev), torch.empty((500,), device=dev)
+            w_, b_ = lin.weight.detach(), lin.bias.detach()
+            flop = 2.0 * (2 * R) * 500 * 500
+            runs = (("hh_dense_tanh_forward", 1, lambda: L.check(lib.hh_dense_tanh_forward(500, 500, 2, io, p(w_), p(b_), p(scratch), nb.value, st))),
+                    ("hh_dense_tanh_backward", 2, lambda: L.check(lib.hh_dense_tanh_backward(500, 500, 2, io, p(w_), p(d_w), p(d_b), p(scratch), nb.value, st))))
+            for name, products, fn in runs:
+                t = events(fn)
+                tf = products * flop / med(t) / 1e9
+                say(f"    {name} alone, 2 x {R} rows: {q(t)} = {tf:.1f} useful TFLOP/s ({products} product(s) of 2 R K N = {flop / 1e9:.2f} GFLOP): "
+                    f"{100 * tf / 155:.1f} % of the 155 TF float32 matrix rate, {100 * tf / (2500 / 3):.1f} % of 2.5 PF / 3")
+        # the Fight1 minibatch step, attention = "fused" and inputs = "fused" in both
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        learners = {tr: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, attention="fused", inputs="fused", trunk=tr) for tr in ("torch", "fused")}
+        with torch.no_grad():
+            old = learners["torch"].old_logits(rows["obs"], bank, ro.episodes.N)
+            b = learners["torch"].policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            mb = {k: v[s0:s1] for k, v in b.items() if k != "seq_len"}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            t = {tr: events(lambda: lr.minibatch_step(0, mb)) for tr, lr in learners.items()}
+            say(f"minibatch step ({PN.KIND_NAMES[learners['torch'].kinds[0]]}, forward + loss + backward + Adam, fused loss, attention = fused, inputs = fused), "
+                f"{int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} chunks of 20: trunk = torch {q(t['torch'])}; trunk = fused {q(t['fused'])}; "
+                f"{verdict(t['torch'], t['fused'])}")
+
+    if a.trunk:
+        lines.clear()
+        trunk_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
