@@ -128,7 +128,8 @@ COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commande
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
                    "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
                    "hh_residual_normalize_backward", "hh_input_stage_scratch_bytes", "hh_input_stage_forward",
-                   "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward"]  # include/hh_learner.h
+                   "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward",
+                   "hh_adam_step", "hh_minibatch_stage", "hh_train_commit"]  # include/hh_learner.h
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
@@ -160,6 +161,19 @@ DENSE_MAX_SRC, DENSE_MAX_DIM, DENSE_ROW_TILE, DENSE_MAX_PARTS, DENSE_FWD_SCRATCH
 class HHDenseSrc(C.Structure):
     """hh_dense_src (include/hh_learner.h): one row block of hh_dense_tanh_*, its row count, then device pointers; field order is ABI"""
     _fields_ = [("n_rows", C.c_int64), ("x", C.c_void_p), ("ld", C.c_int64), ("y", C.c_void_p), ("d_y", C.c_void_p), ("d_x", C.c_void_p)]
+
+
+ADAM_MAX_TENSORS, STAGE_MAX_COLS = 64, 8  # HH_ADAM_MAX_TENSORS, HH_STAGE_MAX_COLS (include/hh_learner.h)
+
+
+class HHAdamTensor(C.Structure):
+    """hh_adam_tensor (include/hh_learner.h): one parameter tensor of hh_adam_step, device pointers, then the element count; field order is ABI"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+class HHStageCol(C.Structure):
+    """hh_stage_col (include/hh_learner.h): one column of hh_minibatch_stage; field order is ABI"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("chunk_bytes", C.c_int64)]
 
 
 _lib = None
@@ -258,6 +272,9 @@ def lib():
         L.hh_dense_tanh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), C.POINTER(C.c_int64)]
         L.hh_dense_tanh_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), vp, vp, vp, C.c_int64, vp]
         L.hh_dense_tanh_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), vp, vp, vp, vp, C.c_int64, vp]
+        L.hh_adam_step.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+        L.hh_minibatch_stage.argtypes = [C.c_int32, C.POINTER(HHStageCol), C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        L.hh_train_commit.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -905,3 +905,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 /* ---- the learners' shared layer on the matrix cores, forward and backward (C ABI in include/hh_learner.h; after the policy kernels: it uses their
  * fp16 split and fragment types) ---- */
 #include "hh_dense_tanh.h"
+
+/* ---- the learner's minibatch step as a replayable chain: staging by a device schedule, Adam on the device, the commit (C ABI in include/hh_learner.h) ---- */
+#include "hh_train_step.h"

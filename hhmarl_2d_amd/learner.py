@@ -9,6 +9,9 @@ Opt-in as well (`inputs="fused"`, all five networks): the layers in front of sha
 (`input_stage`: hh_input_stage_*); the default path slices, concatenates and runs them one by one.
 And (`trunk="fused"`, all five networks): shared_layer with its bias and tanh over the actor's and the critic's rows as ONE call
 on the matrix cores (`dense_tanh`: hh_dense_tanh_*, split-fp16 MFMA); the default path is two float32 GEMMs and two tanh.
+And (`PPOLearner(optimizer="fused", step="graph")`): Adam on the device (`adam_step`: hh_adam_step) and the whole minibatch step — the
+minibatch staged by a device schedule (`minibatch_stage`: hh_minibatch_stage), forward, loss, backward, Adam and the step's bookkeeping
+(`train_commit`: hh_train_commit) — replayed from ONE HIP graph per policy; the default is torch.optim.Adam and the eager step.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -675,6 +678,178 @@ def standardize(adv):
     return (adv - adv.mean()) / torch.clamp(adv.std(unbiased=False), min=1e-4)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the replayable step
+OPTIMIZER_MODES = ("torch", "fused")
+STEP_MODES = ("eager", "graph")
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8      # torch.optim.Adam's defaults, which the learners use
+
+
+def _optimizer_mode(optimizer):
+    if optimizer not in OPTIMIZER_MODES:
+        raise ValueError(f"optimizer is one of {OPTIMIZER_MODES}, got {optimizer!r}")
+    return optimizer
+
+
+def _step_mode(step, optimizer):
+    if step not in STEP_MODES:
+        raise ValueError(f"step is one of {STEP_MODES}, got {step!r}")
+    if step == "graph" and optimizer != "fused":
+        raise ValueError(f'step="graph" needs optimizer="fused" (torch.optim.Adam keeps its step count on the host), got optimizer={optimizer!r}')
+    return step
+
+
+def adam_step(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+    """One step of torch.optim.Adam (amsgrad = False, weight_decay = 0) on a list of tensors, on the device (hh_adam_step, include/hh_learner.h):
+    params, grads, ms, vs are lists of contiguous float32 CUDA tensors, shape by shape the same; t is an int32 [1] CUDA tensor holding the
+    number of steps taken so far (the step uses t + 1; train_commit advances it).  In place on params, ms and vs.  ceil(n / 64) launches,
+    no host synchronisation, HIP-graph capturable; a missing library or GPU is an error."""
+    _need_gpu("adam_step")
+    n = len(params)
+    if not (len(grads) == len(ms) == len(vs) == n):
+        raise ValueError("adam_step: params, grads, ms and vs are lists of one length")
+    if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
+        raise ValueError("adam_step: t is an int32 [1] CUDA tensor (the torch-op form is adam_step_torch)")
+    desc = (L.HHAdamTensor * max(n, 1))()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, ms, vs)):
+        for what, x in (("a parameter", p), ("a gradient", g), ("a first moment", m), ("a second moment", v)):
+            if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == p.shape and x.device == t.device):
+                raise ValueError(f"adam_step: {what} is a contiguous float32 CUDA tensor of its parameter's shape on t's device (the torch-op form "
+                                 "is adam_step_torch)")
+        desc[i].p, desc[i].g, desc[i].m, desc[i].v, desc[i].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    L.check(L.lib().hh_adam_step(n, desc, _p(t), float(lr), float(betas[0]), float(betas[1]), float(eps), _stream(t.device)))
+
+
+def adam_step_torch(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+    """adam_step with torch ops, any dtype and device (the A/B partner): t is the number of steps taken so far, a Python int or a
+    one-element tensor (read on the host); in place on params, ms and vs"""
+    step = int(t) + 1
+    b1, b2 = betas
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    with torch.no_grad():
+        for p, g, m, v in zip(params, grads, ms, vs):
+            m.mul_(b1).add_(g, alpha=1.0 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+            p.addcdiv_(m, v.sqrt() / bc2 ** 0.5 + eps, value=-(lr / bc1))
+
+
+def minibatch_schedule(parts, n_valid, num_sgd_iter, seed, update, policy):
+    """the minibatch steps of one policy's update as hh_minibatch_stage's table: per pass the parts of minibatch_partition in
+    minibatch_order's order -> int32 [num_sgd_iter * len(parts), 4] = (first chunk, last chunk + 1, unpadded rows, 0)"""
+    rows = [(parts[i][0], parts[i][1], int(n_valid[i]), 0) for sgd_pass in range(int(num_sgd_iter))
+            for i in minibatch_order(len(parts), seed, update, policy, sgd_pass)]
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+
+
+def minibatch_stage(cols, staged, chunk_len, schedule, cursor, n_valid, src_chunks=None):
+    """The minibatch that schedule[cursor] names, copied into fixed-address staging buffers in ONE launch (hh_minibatch_stage,
+    include/hh_learner.h).  cols: up to 8 contiguous CUDA tensors [S, ...] (chunks first; any dtype); staged: per column a contiguous
+    tensor [cap, ...] of the same dtype and trailing shape; schedule int32 [n_steps, 4] and cursor int32 [1] on the device; n_valid
+    int32 [1] receives the row's third entry.  Chunks beyond the minibatch's are zeroed in every staged tensor.  src_chunks: the chunks the
+    kernel may read of every column (default S).  The cursor is not written.  No host synchronisation, HIP-graph capturable."""
+    _need_gpu("minibatch_stage")
+    if len(cols) != len(staged) or len(cols) > L.STAGE_MAX_COLS:
+        raise ValueError(f"minibatch_stage: as many staging buffers as columns, at most {L.STAGE_MAX_COLS}")
+    dev = cursor.device
+    for what, x in (("schedule", schedule), ("cursor", cursor), ("n_valid", n_valid)):
+        if not (x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.device == dev):
+            raise ValueError(f"minibatch_stage: {what} is a contiguous int32 CUDA tensor (the torch-op form is minibatch_stage_torch)")
+    if schedule.dim() != 2 or schedule.shape[1] != 4 or cursor.numel() != 1 or n_valid.numel() != 1:
+        raise ValueError("minibatch_stage: schedule is [n_steps, 4], cursor and n_valid hold one element")
+    S = cols[0].shape[0] if cols else 0
+    cap = staged[0].shape[0] if staged else 1
+    desc = (L.HHStageCol * max(len(cols), 1))()
+    for i, (c, s) in enumerate(zip(cols, staged)):
+        if not (c.is_cuda and s.is_cuda and c.device == dev and s.device == dev and c.is_contiguous() and s.is_contiguous() and c.dtype == s.dtype
+                and c.shape[1:] == s.shape[1:] and c.shape[0] == S and s.shape[0] == cap and c.dim() >= 1):
+            raise ValueError("minibatch_stage: a column is a contiguous CUDA tensor [S, ...] and its staging buffer [cap, ...] has its dtype and trailing shape")
+        desc[i].src, desc[i].dst, desc[i].chunk_bytes = c.data_ptr(), s.data_ptr(), (c.numel() // S if S else s.numel() // cap) * c.element_size()
+    src_chunks = S if src_chunks is None else int(src_chunks)
+    if not 0 <= src_chunks <= S:
+        raise ValueError(f"minibatch_stage: src_chunks is within the columns' {S} chunks")
+    L.check(L.lib().hh_minibatch_stage(len(cols), desc, int(chunk_len), cap, src_chunks, _p(schedule), schedule.shape[0], _p(cursor), _p(n_valid), _stream(dev)))
+
+
+def minibatch_stage_torch(cols, cap, row):
+    """minibatch_stage with torch ops, any device: row = (first chunk, last chunk + 1, unpadded rows, 0) -> (per column a new tensor
+    [cap, ...]: the chunks, then zeros; n_valid)"""
+    s0, s1, nv = int(row[0]), int(row[1]), int(row[2])
+    out = []
+    for c in cols:
+        z = torch.zeros((int(cap),) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device)
+        z[:s1 - s0] = c[s0:s1]
+        out.append(z)
+    return out, nv
+
+
+def train_commit(stats, table, cursor, t):
+    """the step's bookkeeping in one one-thread launch (hh_train_commit): table[cursor] = stats (f64 [6] -> f64 [n, 6]), cursor += 1,
+    t += 1; cursor and t int32 [1], all CUDA.  The only writer of the two counters (include/hh_learner.h has the hazard)."""
+    _need_gpu("train_commit")
+    ok = (stats.is_cuda and table.is_cuda and stats.dtype == torch.float64 and table.dtype == torch.float64 and stats.is_contiguous()
+          and table.is_contiguous() and stats.numel() == len(L.PPO_STATS) and table.dim() == 2 and table.shape[1] == len(L.PPO_STATS)
+          and all(x.is_cuda and x.dtype == torch.int32 and x.numel() == 1 for x in (cursor, t)))
+    if not ok:
+        raise ValueError("train_commit: stats f64 [6], table f64 [n, 6], cursor and t int32 [1], all CUDA")
+    L.check(L.lib().hh_train_commit(_p(stats), _p(table), table.shape[0], _p(cursor), _p(t), _stream(table.device)))
+
+
+class DeviceAdam:
+    """torch.optim.Adam(params, lr) with its state on the device: m and v per parameter and the step count t (int32 [1]), stepped by
+    adam_step (hh_adam_step).  t is advanced by train_commit, not by step()."""
+
+    def __init__(self, params, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+        self.params = list(params)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.m = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.v = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.t = torch.zeros((1,), dtype=torch.int32, device=self.params[0].device)
+
+    def zero_grad(self, set_to_none=True):
+        for p in self.params:
+            p.grad = None
+
+    def step(self):
+        """one Adam step of every parameter that has a gradient (as torch.optim.Adam skips the others), from the current .grad pointers"""
+        live = [i for i, p in enumerate(self.params) if p.grad is not None]
+        adam_step([self.params[i].data for i in live], [self.params[i].grad for i in live], [self.m[i] for i in live], [self.v[i] for i in live],
+                  self.t, lr=self.lr, betas=self.betas, eps=self.eps)
+
+
+class _StepBook:
+    """what one policy's replayable step keeps on the device: the cursor, the statistics table, and for step="graph" the persistent copy
+    of the policy batch, the schedule, the staging buffers and the captured graph"""
+
+    def __init__(self, device):
+        self.device = device
+        self.cursor = torch.zeros((1,), dtype=torch.int32, device=device)
+        self.n_valid = torch.zeros((1,), dtype=torch.int32, device=device)
+        self.table = torch.zeros((0, len(L.PPO_STATS)), dtype=torch.float64, device=device)
+        self.schedule = torch.zeros((0, 4), dtype=torch.int32, device=device)
+        self.src, self.staged, self.graph, self.key, self.keep = {}, {}, None, None, None
+        self.captures = 0
+
+    @staticmethod
+    def _grown(t, n, shape, dtype, device):
+        """a zeroed tensor [>= n, *shape]: t itself while it is large enough (its address stays), else one of twice the need"""
+        if t is not None and t.shape[0] >= n and tuple(t.shape[1:]) == tuple(shape) and t.dtype == dtype:
+            return t
+        return torch.zeros((max(2 * n, 16),) + tuple(shape), dtype=dtype, device=device)
+
+    def begin(self, n_steps):
+        """room for n_steps rows of statistics, cursor = 0"""
+        self.table = self._grown(self.table, n_steps, (len(L.PPO_STATS),), torch.float64, self.device)
+        self.cursor.zero_()
+
+    def load(self, cols, schedule):
+        """the policy batch's columns and the schedule into the persistent buffers (the graph reads these addresses)"""
+        for k, c in cols.items():
+            self.src[k] = self._grown(self.src.get(k), c.shape[0], c.shape[1:], c.dtype, self.device)
+            self.src[k][:c.shape[0]].copy_(c)
+        sched = torch.from_numpy(np.ascontiguousarray(schedule, dtype=np.int32)).to(self.device)
+        self.schedule = self._grown(self.schedule, sched.shape[0], (4,), torch.int32, self.device)
+        self.schedule[:sched.shape[0]].copy_(sched)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the learner
 class PPOLearner:
     """One PPO update of train_hetero.py's two policies from the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")`:
@@ -709,12 +884,19 @@ class PPOLearner:
     when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
-                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch"):
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch",
+                 optimizer="torch", step="eager"):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
         argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
         inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*).
-        trunk: TrainableNet's argument too ("fused": shared_layer, bias and tanh of both sides through hh_dense_tanh_*)."""
+        trunk: TrainableNet's argument too ("fused": shared_layer, bias and tanh of both sides through hh_dense_tanh_*).
+        optimizer: "torch" (the default) steps with torch.optim.Adam; "fused" keeps each policy's m, v and step count on the device
+        (DeviceAdam: hh_adam_step) and gathers the steps' statistics in a device table (hh_train_commit).
+        step: "eager" (the default) issues every minibatch step's launches from Python; "graph" (needs optimizer="fused") captures
+        stage -> forward -> loss -> backward -> Adam -> commit once per policy as ONE HIP graph and replays it per step (graph_prepare)."""
+        self.optimizer = _optimizer_mode(optimizer)
+        self.step = _step_mode(step, optimizer)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -726,7 +908,8 @@ class PPOLearner:
         for m in self.modules:
             m.to(self.device)
         tie(self.modules)
-        self.optimizers = [torch.optim.Adam(m.parameters(), lr=lr) for m in self.modules]
+        self.optimizers = [(DeviceAdam if self.optimizer == "fused" else torch.optim.Adam)(m.parameters(), lr=lr) for m in self.modules]
+        self._books = [_StepBook(self.device) for _ in self.modules] if self.optimizer == "fused" else None
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
         self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
         self.use_kl = kl_coeff > 0.0            # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
@@ -810,7 +993,96 @@ class PPOLearner:
         opt.zero_grad(set_to_none=True)
         total.backward()
         opt.step()
+        if self.optimizer == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
+            book = self._books[agent]
+            train_commit(stats, book.table, book.cursor, opt.t)
         return stats
+
+    # ---- the step as one HIP graph (step="graph")
+    def graph_prepare(self, agent, b, cap=None):
+        """Everything one policy's pass needs before its first replay: the schedule of policy_batch `b` (minibatch_partition, then
+        minibatch_order per pass) and the batch's columns uploaded into persistent device buffers, the cursor set to 0, and the graph of ONE
+        minibatch step captured — stage, forward, loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only —
+        unless the graph of an earlier call still fits: it is kept while cap, kl_coeff (which travels by value in hh_ppo_loss_params) and the
+        buffers' addresses are what they were.  cap: the staging capacity in chunks (escape: rows); default and minimum: the largest
+        minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)"""
+        if self.step != "graph":
+            raise ValueError('graph_prepare needs PPOLearner(step="graph")')
+        book = self._books[agent]
+        cols = {k: v.contiguous() for k, v in b.items() if k != "seq_len"}
+        S = cols["obs"].shape[0]
+        if self.recurrent:
+            seq_len = b["seq_len"].cpu().numpy()
+        else:
+            seq_len = np.ones(S, dtype=np.int64)
+            cols["mask"] = torch.ones((S,), dtype=torch.uint8, device=self.device)      # padding rows of the staging buffers need one
+        cols["mask"] = cols["mask"].to(torch.uint8)
+        parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+        csum = np.concatenate([[0], np.cumsum(seq_len)])
+        sched = minibatch_schedule(parts, [csum[s1] - csum[s0] for s0, s1 in parts], self.num_sgd_iter, self.seed, self.updates, agent)
+        need = max(s1 - s0 for s0, s1 in parts)
+        cap = need if cap is None else int(cap)
+        if cap < need:
+            raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} chunks)")
+        book.begin(len(sched))
+        book.load(cols, sched)
+        book.n_steps, book.cap = len(sched), cap
+        src_chunks = min(t.shape[0] for t in book.src.values())
+        names = tuple(cols)
+        kl = self.kl_coeff[agent] if self.use_kl else 0.0
+        key = (cap, kl, names, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(), book.table.shape[0]) + tuple(
+            book.src[k].data_ptr() for k in names)
+        if book.graph is None or book.key != key:
+            self._capture(agent, book, names, src_chunks)
+            book.key = key
+        return len(sched), int(seq_len.sum())
+
+    def _capture(self, agent, book, names, src_chunks):
+        opt, module, dev = self.optimizers[agent], self.modules[agent], self.device
+        if book.staged.get("obs") is None or book.staged["obs"].shape[0] != book.cap or tuple(book.staged) != names:
+            book.staged = {k: torch.zeros((book.cap,) + tuple(book.src[k].shape[1:]), dtype=book.src[k].dtype, device=dev) for k in names}
+        srcs, staged = [book.src[k][:src_chunks] for k in names], [book.staged[k] for k in names]
+        mb = dict(book.staged, n_valid=book.n_valid)
+        Lc = self.max_seq_len if self.recurrent else 1
+
+        def stage():
+            minibatch_stage(srcs, staged, Lc, book.schedule, book.cursor, book.n_valid)
+
+        def forward_backward():
+            logits, vf = module(mb["obs"], mb["critic"])
+            total, stats = self.loss(agent, logits, vf, mb)
+            total.backward()
+            return stats
+        # the warm-up: forward and backward only (rocBLAS and autograd initialise), on a side stream as torch's capture recipe has it;
+        # it reads schedule[0] through the cursor and writes nothing but the staging buffers and gradients that are thrown away
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            stage()
+            for _ in range(2):
+                opt.zero_grad(set_to_none=True)
+                forward_backward()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        opt.zero_grad(set_to_none=True)     # backward inside the capture assigns the gradients from the graph's pool: their addresses are fixed
+        book.graph = None
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            stage()
+            stats = forward_backward()
+            opt.step()
+            train_commit(stats, book.table, book.cursor, opt.t)
+        book.graph, book.keep = graph, stats
+        book.captures += 1
+
+    def graph_replay(self, agent, n=1):
+        """n minibatch steps of policy `agent` from its captured graph, no host work between them"""
+        graph = self._books[agent].graph
+        for _ in range(int(n)):
+            graph.replay()
+
+    def graph_stats(self, agent, n):
+        """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
+        return self._books[agent].table[:int(n)]
 
     # ---- one update
     def update(self, episodes, bank=None):
@@ -826,6 +1098,15 @@ class PPOLearner:
             old = self.batch_old_logits(rows, bank, episodes.N)
             batches = [self.policy_batch(rows, old, a) for a in range(2)]
         for agent, b in enumerate(batches):
+            if self.step == "graph":
+                n_steps, n_rows = self.graph_prepare(agent, b)
+                self.graph_replay(agent, n_steps)
+                m = self.graph_stats(agent, n_steps).mean(dim=0).tolist()
+                if self.use_kl:
+                    self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
+                out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
+                                steps=n_steps, rows=n_rows))
+                continue
             if self.recurrent:
                 seq_len = b["seq_len"].cpu().numpy()
             else:
@@ -835,6 +1116,8 @@ class PPOLearner:
             n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
             cols = [k for k in b if k != "seq_len"]
             all_stats = []
+            if self.optimizer == "fused":
+                self._books[agent].begin(self.num_sgd_iter * len(parts))
             for sgd_pass in range(self.num_sgd_iter):
                 for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
                     s0, s1 = parts[i]

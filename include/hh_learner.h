@@ -221,6 +221,52 @@ int hh_dense_tanh_forward (int32_t K, int32_t N, int32_t n_src, const hh_dense_s
 int hh_dense_tanh_backward(int32_t K, int32_t N, int32_t n_src, const hh_dense_src *src, const float *w, float *d_w, float *d_b,
                            void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the minibatch step as a fixed chain of launches: staging by a device schedule, Adam on the device, the step's bookkeeping ----
+ *
+ * What lets PPOLearner(step="graph") replay  stage -> forward -> loss -> backward -> adam -> commit  from ONE HIP graph with no host work
+ * between the steps.  Two device counters steer a step: `cursor` (which row of the schedule the stage reads and which row of the
+ * statistics table the commit fills) and `step` (Adam's t: the number of steps taken).  No launch reads a counter that a thread of the
+ * same launch writes: hh_minibatch_stage and hh_adam_step only READ them, hh_train_commit — one launch of one thread, ordered by the
+ * stream after the Adam launch — is the only writer.  All three are ordered on `stream`: no atomics, no allocation, no host
+ * synchronisation, HIP-graph capturable; the same inputs give the same bytes on every run.  HH_E_ARG, with nothing enqueued: a null
+ * pointer, a negative count, cap < 1, chunk_len < 1.  An empty tensor / column list succeeds without a launch. */
+#define HH_ADAM_MAX_TENSORS 64   /* descriptors per launch: 64 x 48 bytes by value, inside the 4 KiB of kernel arguments; longer lists take more launches */
+#define HH_STAGE_MAX_COLS   8    /* columns of one hh_minibatch_stage call */
+
+typedef struct hh_adam_tensor {  /* field order is ABI; host struct of device pointers */
+    float *p; const float *g; float *m; float *v;   /* parameter, gradient, first and second moment: f32 [n], 4-byte aligned */
+    int64_t n;
+} hh_adam_tensor;
+
+/* One step of torch.optim.Adam (amsgrad = False, weight_decay = 0, maximize = False) on every tensor of t[n_tensors] (host array), float32:
+ *     m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * with t = step[0] + 1 read from the device ([dev] i32 [1]: the steps taken so far; hh_train_commit advances it).  The bias corrections
+ * are computed once per workgroup in float64.  Every element is stepped in float64 from its float32 inputs and each stored value is rounded
+ * to float32 once: m and v are the correctly rounded updates of the stored state, p moves by the float64 step from the stored m and v
+ * (the kernel moves 28 bytes per element and stays memory-bound).  A gradient of 0 on fresh state leaves p bit for bit.  A tensor
+ * whose four pointers are 16-byte aligned is stepped in float4s with a scalar tail of n % 4 elements; any other tensor element by element
+ * (the same arithmetic).  ceil(n_tensors / HH_ADAM_MAX_TENSORS) launches, the descriptors by value.  Tensors may not overlap. */
+int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, double lr, double beta1, double beta2, double eps, void *stream);
+
+typedef struct hh_stage_col {    /* field order is ABI; host struct of device pointers */
+    const void *src;             /* the policy batch's column: [src_chunks] chunks of chunk_bytes bytes */
+    void *dst;                   /* its staging buffer: [cap] chunks */
+    int64_t chunk_bytes;         /* bytes of one chunk (chunk_len rows): a positive multiple of chunk_len */
+} hh_stage_col;
+
+/* ONE launch: with (s0, s1, nv, 0) = schedule[cursor[0]] ([dev] i32 [sched_rows, 4]: first chunk, last chunk + 1, unpadded rows) every column's
+ * chunks s0 .. s1-1 go byte for byte to the front of its staging buffer, chunks s1-s0 .. cap-1 of every staging buffer become zero (on
+ * every call: a previous, larger minibatch leaves nothing behind), and n_valid[0] = nv.  The copy unit of a column is the widest of 16, 8,
+ * 4, 2, 1 bytes that src, dst and chunk_bytes are all multiples of.  chunk_len is the rows per chunk (20 for the fight networks, 1 for rows).
+ * The kernel clamps what it reads from the table to 0 <= s0 <= s1 <= src_chunks and s1 - s0 <= cap, and a cursor outside
+ * [0, sched_rows) stages an empty minibatch, so no table content makes it touch memory outside the columns.  cursor is not written. */
+int hh_minibatch_stage(int32_t n_cols, const hh_stage_col *cols, int32_t chunk_len, int32_t cap, int64_t src_chunks, const int32_t *schedule,
+                       int32_t sched_rows, const int32_t *cursor, int32_t *n_valid, void *stream);
+
+/* The step's bookkeeping, one thread: table[cursor[0]] = stats (f64 [HH_PPO_STATS], hh_ppo_loss's; skipped when cursor[0] is outside
+ * [0, table_rows)), cursor[0] += 1, step[0] += 1.  All pointers [dev]. */
+int hh_train_commit(const double *stats, double *table, int32_t table_rows, int32_t *cursor, int32_t *step, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,16 @@
           kernel calls alone as useful TFLOP/s (2 R K N per product: one forward, two backward), against the 155 TF float32 matrix
           rate and against 2.5 PF / 3 (three fp16 products per float32 one); (c) the Fight1 minibatch step with attention="fused",
           inputs="fused" at 256 and 65536 rows.  The same rule for gain / loss
+  step    --step runs this section alone and appends its lines to --out: the minibatch step as PPOLearner(optimizer="fused",
+          step="graph") replays it from one HIP graph (hh_minibatch_stage, hh_adam_step, hh_train_commit) against the eager step, all in
+          the same run: (a) hh_adam_step on a Fight1 module's tensors and on one 64 Mi-element tensor, hh_minibatch_stage on a Fight1 batch
+          at 14 and 3560 chunks, as bytes/s of their algorithmic bytes (Adam: 16 B in, 12 B out per element; stage: every staged byte
+          read and written once); (b) the Fight1 minibatch step with attention="fused", inputs="fused", trunk="torch" at 256 and 65536
+          rows in three configurations — eager + torch.optim.Adam, eager + the device Adam, graph — one step per timing and 50 steps
+          back to back, and what a capture costs; (c) one whole update at --step-minibatch (default 256) rows and --passes passes, eager
+          against graph.  The same rule for gain / loss.  --step-launches eager|graph (with --step-count K) only runs K steps of that
+          kind at 256 rows, for a kernel count under rocprofv3 --kernel-trace --stats in a run of its own (two values of K: the
+          difference is the steps' share)
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -66,6 +76,10 @@ def main():
     ap.add_argument("--attention", action="store_true", help="only the chunk-attention section; its lines are appended to --out")
     ap.add_argument("--inputs", action="store_true", help="only the input-stage section; its lines are appended to --out")
     ap.add_argument("--trunk", action="store_true", help="only the shared-layer section; its lines are appended to --out")
+    ap.add_argument("--step", action="store_true", help="only the graph-step section; its lines are appended to --out")
+    ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
+    ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
+    ap.add_argument("--step-count", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_learner.log"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -370,6 +384,139 @@ def main():
         lines.clear()
         trunk_section()
         if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def step_section():
+        """step="graph" and optimizer="fused" against the eager step with torch.optim.Adam: the two kernels alone, the minibatch step, one update"""
+        from hhmarl_2d_amd import policy_nets as PN
+        med = statistics.median
+
+        def verdict(t_base, t_new):
+            spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+            d = med(t_base) - med(t_new)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"eager+torch / this = {med(t_base) / med(t_new):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        FUSED = dict(attention="fused", inputs="fused", trunk="torch")
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        base = make()
+        with torch.no_grad():
+            old = base.old_logits(rows["obs"], bank, ro.episodes.N)
+            b = base.policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+
+        def one_minibatch(size):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+            mb = {k: v for k, v in sub.items() if k != "seq_len"}
+            mb["n_valid"] = torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=dev)
+            return sub, mb, s1 - s0, int(seq_len[s0:s1].sum())
+
+        def graph_learner(sub, n_steps):
+            """a graph learner whose one pass is n_steps visits of the single minibatch `sub` -> (learner, milliseconds graph_prepare took)"""
+            lr = make(optimizer="fused", step="graph", num_sgd_iter=n_steps, sgd_minibatch_size=1 << 30)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lr.graph_prepare(0, sub)
+            torch.cuda.synchronize()
+            return lr, (time.perf_counter() - t0) * 1e3
+
+        if a.step_launches:
+            sub, mb, _, _ = one_minibatch(256)
+            if a.step_launches == "graph":
+                lr, _ = graph_learner(sub, a.step_count)
+                lr.graph_replay(0, a.step_count)
+            else:
+                for _ in range(a.step_count):
+                    base.minibatch_step(0, mb)
+            torch.cuda.synchronize()
+            print(f"{a.step_count} {a.step_launches} steps done")
+            return
+
+        say(f"# tools/ppo_learner_bench.py --step on {torch.cuda.get_device_name(0)}: PPOLearner(optimizer=\"fused\", step=\"graph\") against the eager step "
+            f"with torch.optim.Adam, all in this run; attention = fused, inputs = fused, trunk = torch; {a.iters} timed iterations after {a.warmup} "
+            f"warm-up, device events (a later run, appended):")
+        # (a) the kernels alone
+        mod = base.modules[0]
+        params = [p.detach().clone() for p in mod.parameters()]
+        for label, ps in ((f"a Fight1 module's {len(params)} tensors", params), ("one tensor of 64 Mi elements", [torch.zeros((1 << 26,), device=dev)])):
+            gs, ms, vs = [torch.randn_like(p) for p in ps], [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+            t_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
+            n = sum(p.numel() for p in ps)
+            t = events(lambda: LR.adam_step(ps, gs, ms, vs, t_dev, lr=1e-4))
+            say(f"    hh_adam_step alone, {label} ({n} elements): {q(t)} = {28 * n / med(t) / 1e6:.1f} GB/s of {28 * n / 1e6:.2f} MB algorithmic bytes "
+                f"({100 * 28 * n / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+            del gs, ms, vs
+        names = [k for k in b if k != "seq_len"]
+        for S in (14, 3560):
+            srcs = [b[k][:S].contiguous() for k in names]
+            staged = [torch.zeros_like(c) for c in srcs]
+            sched = torch.tensor([(0, S, 0, 0)], dtype=torch.int32, device=dev)
+            cur, nv = torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+            nbytes = 2 * sum(c.numel() * c.element_size() for c in srcs)
+            t = events(lambda: LR.minibatch_stage(srcs, staged, 20, sched, cur, nv))
+            say(f"    hh_minibatch_stage alone, the {len(names)} columns of a Fight1 batch, {S} chunks of 20: {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of "
+                f"{nbytes / 1e6:.2f} MB algorithmic bytes ({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+        # (b) the minibatch step
+        K = 50
+        dev_adam = make(optimizer="fused")
+
+        def burst(fn):
+            """K steps back to back, no host synchronisation between them -> milliseconds per step, three times"""
+            out = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                out.append((e0.elapsed_time(e1) / K, (time.perf_counter() - t0) * 1e3 / K))
+            return "; ".join(f"{d:.3f} device / {h:.3f} host" for d, h in out)
+
+        for size in (256, 65536):
+            sub, mb, n_chunks, n_rows = one_minibatch(size)
+            n_total = 4 * (a.iters + a.warmup) + 4 * K + 8
+            dev_adam._books[0].begin(n_total)
+            graph, t_cap = graph_learner(sub, n_total)
+            t_e = events(lambda: base.minibatch_step(0, mb))
+            t_f = events(lambda: dev_adam.minibatch_step(0, mb))
+            t_g = events(lambda: graph.graph_replay(0, 1))
+            say(f"minibatch step (Fight1, forward + loss + backward + Adam, fused loss), {n_rows} unpadded rows in {n_chunks} chunks of 20: eager + torch Adam "
+                f"{q(t_e)}; eager + device Adam {q(t_f)} [{verdict(t_e, t_f)}]; graph {q(t_g)} [{verdict(t_e, t_g)}]")
+            say(f"    {K} steps back to back, ms per step, three runs: eager + torch Adam {burst(lambda: [base.minibatch_step(0, mb) for _ in range(K)])} | "
+                f"eager + device Adam {burst(lambda: [dev_adam.minibatch_step(0, mb) for _ in range(K)])} | graph {burst(lambda: graph.graph_replay(0, K))}")
+            say(f"    graph_prepare (upload, warm-up, capture) of this step: {t_cap:.1f} ms on the host clock")
+            del graph
+        # (c) one whole update
+        res = {}
+        for label, kw in (("eager + torch Adam", {}), ("graph", dict(optimizer="fused", step="graph"))):
+            lr = make(num_sgd_iter=a.passes, sgd_minibatch_size=a.step_minibatch, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = lr.update(ro.episodes, bank)
+            torch.cuda.synchronize()
+            res[label] = ((time.perf_counter() - t0) * 1e3, st)
+        (t_e, st_e), (t_g, st_g) = res["eager + torch Adam"], res["graph"]
+        say(f"one update of both policies ({a.passes} pass(es), minibatches of >= {a.step_minibatch} rows: {st_e[0]['steps']} + {st_e[1]['steps']} steps over "
+            f"{st_e[0]['rows']} rows each), host clock to a synchronise, first update of a new learner (the graph's includes its two captures): "
+            f"eager + torch Adam {t_e:.1f} ms; graph {t_g:.1f} ms; eager / graph = {t_e / t_g:.2f}x")
+        say(f"    mean statistics, eager: {[{k: round(v, 6) for k, v in s.items()} for s in st_e]}")
+        say(f"    mean statistics, graph: {[{k: round(v, 6) for k, v in s.items()} for s in st_g]}")
+
+    if a.step or a.step_launches:
+        lines.clear()
+        step_section()
+        if a.out and a.step:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
         return
