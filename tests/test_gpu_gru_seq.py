@@ -14,18 +14,38 @@ import commander_ref as REF
 
 pytestmark = pytest.mark.gpu
 LEN, H = 20, 200
+MAX_LEN = 32                                     # HH_GRU_MAX_LEN
 TILE = 16                                        # HHG_TILE
 SIZES = (1, TILE - 1, TILE, TILE + 1, 1000)
 NAMES = ("y", "d_gi", "d_h0", "d_w_hh", "d_b_hh")
 
 
-def _inputs(S, seed):
+def _inputs(S, seed, max_len=LEN):
     g = torch.Generator().manual_seed(seed)
-    seq_len = torch.randint(1, LEN + 1, (S,), generator=g).to(torch.int32)
-    seq_len[0] = LEN if S > 1 else 13
-    return dict(gi=torch.randn((S, LEN, 3 * H), generator=g), h0=0.5 * torch.randn((S, H), generator=g),
+    seq_len = torch.randint(1, max_len + 1, (S,), generator=g).to(torch.int32)
+    seq_len[0] = max_len if S > 1 else min(13, max_len)
+    return dict(gi=torch.randn((S, max_len, 3 * H), generator=g), h0=0.5 * torch.randn((S, H), generator=g),
                 w_hh=torch.randn((3 * H, H), generator=g) / H ** 0.5, b_hh=0.1 * torch.randn((3 * H,), generator=g),
-                wy=torch.randn((S, LEN, H), generator=g), seq_len=seq_len)
+                wy=torch.randn((S, max_len, H), generator=g), seq_len=seq_len)
+
+
+def _pattern(name, S, max_len, seq_len):
+    """the length patterns a tile of 16 sequences can meet, written over the random lengths `seq_len` [S] of S = 2 TILE + 1 sequences"""
+    out = seq_len.clone()
+    if name == "all-one":                        # no tile runs past step 0
+        out[:] = 1
+    elif name == "all-full":                     # no padding anywhere
+        out[:] = max_len
+    elif name == "short-tile-then-full-tile":    # the first tile stops at step 3 at the latest, the second runs all max_len steps with every lane on
+        out[:TILE] = 1 + torch.arange(TILE, dtype=torch.int32) % 3
+        out[TILE:2 * TILE] = max_len
+    elif name == "one-full-among-ones":          # the second tile runs max_len steps for one sequence; its other 15 stopped after step 0
+        out[TILE:] = 1
+        out[TILE + 5] = max_len
+    else:
+        raise KeyError(name)
+    assert S == 2 * TILE + 1 and int(out.min()) >= 1 and int(out.max()) <= max_len
+    return out
 
 
 def _cell_path(inp, dtype, device):
@@ -35,7 +55,7 @@ def _cell_path(inp, dtype, device):
           "g.weight_hh_l0": t["w_hh"], "g.bias_hh_l0": t["b_hh"]}
     seq_len = inp["seq_len"].to(device)
     h, ys = t["h0"], []
-    for s in range(LEN):
+    for s in range(inp["gi"].shape[1]):
         on = (seq_len > s)[:, None]
         hn = REF._gru(sd, "g", t["gi"][:, s], h)
         h = torch.where(on, hn, h)
@@ -59,7 +79,28 @@ def _kernel_path(inps):
 @pytest.mark.parametrize("n_gru", (1, 2))
 @pytest.mark.parametrize("S", SIZES)
 def test_forward_and_gradients_against_float64(S, n_gru):
-    inps = [_inputs(S, 100 * g + S) for g in range(n_gru)]
+    _check_against_float64(S, n_gru, LEN)
+
+
+@pytest.mark.parametrize("n_gru", (1, 2))
+@pytest.mark.parametrize("S", (TILE - 1, TILE + 1))
+@pytest.mark.parametrize("max_len", (1, MAX_LEN))
+def test_forward_and_gradients_at_the_shortest_and_the_longest_max_len(max_len, S, n_gru):
+    """hh_gru_seq_* accept 1 <= max_len <= 32: one step only (every sequence has length 1, dW_hh sees h0 alone) and all 32"""
+    _check_against_float64(S, n_gru, max_len)
+
+
+@pytest.mark.parametrize("n_gru", (1, 2))
+@pytest.mark.parametrize("pattern", ("all-one", "all-full", "short-tile-then-full-tile", "one-full-among-ones"))
+def test_forward_and_gradients_at_length_patterns(pattern, n_gru):
+    """a tile runs to the longest of ITS sequences: tiles whose longest sequence is short of max_len beside tiles that run all of it"""
+    _check_against_float64(2 * TILE + 1, n_gru, LEN, pattern)
+
+
+def _check_against_float64(S, n_gru, max_len, pattern=None):
+    inps = [_inputs(S, 100 * g + S, max_len) for g in range(n_gru)]
+    if pattern is not None:
+        inps[0]["seq_len"] = _pattern(pattern, S, max_len, inps[0]["seq_len"])
     for inp in inps[1:]:
         inp["seq_len"] = inps[0]["seq_len"]
     got = _kernel_path(inps)
@@ -67,21 +108,21 @@ def test_forward_and_gradients_against_float64(S, n_gru):
     for g, inp in enumerate(inps):
         want = _cell_path(inp, torch.float64, "cpu")
         t32 = _cell_path(inp, torch.float32, "cuda")
-        pad = ~(torch.arange(LEN)[None, :] < inp["seq_len"][:, None])
+        pad = ~(torch.arange(max_len)[None, :] < inp["seq_len"][:, None])
         for name, k, c, w in zip(NAMES, got[g], t32, want):
             k, c = k.double().cpu(), c.double().cpu()
             assert torch.isfinite(k).all()
             scale = w.abs().max().item()
             e_k, e_32 = (k - w).abs().max().item() / scale, (c - w).abs().max().item() / scale
-            print(f"S={S} n_gru={n_gru} gru {g} {name}: max |ref| {scale:.3e}; relative error of the float32 torch-op cell {e_32:.3e}, of the kernel {e_k:.3e}")
+            print(f"S={S} L={max_len}{'' if pattern is None else ' ' + pattern} n_gru={n_gru} gru {g} {name}: max |ref| {scale:.3e}; relative error of the float32 torch-op cell {e_32:.3e}, of the kernel {e_k:.3e}")
             assert e_k <= 4.0 * e_32, f"{name}: kernel error {e_k:.3e} above 4 x {e_32:.3e}"
             if name in ("y", "d_gi") and pad.any():
                 assert torch.equal(k[pad], torch.zeros_like(k[pad])), f"{name}: not exactly zero past seq_len"
 
 
-def _raw(S, n_gru, seed=7):
+def _raw(S, n_gru, seed=7, max_len=LEN):
     from hhmarl_2d_amd import learner as LR
-    inps = [_inputs(S, seed + g) for g in range(n_gru)]
+    inps = [_inputs(S, seed + g, max_len) for g in range(n_gru)]
     seq_len = inps[0]["seq_len"].cuda()
     parts = [tuple(inp[k].cuda().contiguous() for k in ("gi", "h0", "w_hh", "b_hh")) for inp in inps]
     dys = [inp["wy"].cuda().contiguous() for inp in inps]
@@ -106,6 +147,19 @@ def test_padding_is_exactly_zero_and_two_runs_give_the_same_bytes(S, n_gru):
             assert torch.equal(t[pad], torch.zeros_like(t[pad])), name
             assert t[~pad].abs().max().item() > 0
         assert torch.isfinite(d_h0).all()
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(first, second))
+
+
+@pytest.mark.parametrize("max_len,S,n_gru", [(1, TILE + 1, 2), (MAX_LEN, TILE + 1, 1)])
+def test_two_runs_give_the_same_bytes_at_the_shortest_and_the_longest_max_len(max_len, S, n_gru):
+    run, seq_len, _, _ = _raw(S, n_gru, max_len=max_len)
+    first, second = run(), run()
+    pad = (~(torch.arange(max_len)[None, :] < seq_len[:, None])).cuda()
+    assert bool(pad.any()) == (max_len > 1)
+    for g in range(n_gru):
+        for name, t in zip(("y", "d_gi", "d_gh"), first[4 * g:4 * g + 3]):
+            assert torch.equal(t[pad], torch.zeros_like(t[pad])), name
+            assert torch.isfinite(t).all() and t[~pad].abs().max().item() > 0
     assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(first, second))
 
 
