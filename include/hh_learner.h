@@ -47,9 +47,13 @@ int hh_ppo_loss_scratch_bytes(int64_t n_rows, int64_t *bytes);
  *   old_logits  [dev] f32 [n_rows, 32]   the sampler's logits (HH_POLICY_LOGITS rows: hh_policy_act / hh_policy_sample)
  *   actions     [dev] i8  [n_rows, 4]    the sampled action (components outside their range are clamped into it)
  *   old_logp, adv, vf, target [dev] f32 [n_rows]    ACTION_LOGP, standardised advantages, the learner's value predictions, VALUE_TARGETS
- *   mask        [dev] u8  [n_rows]       rows with mask != 0 count (the unpadded rows of RLlib's sequence chunks); NULL = all rows
+ *   mask        [dev] u8  [n_rows]       rows with mask != 0 count (the unpadded rows of RLlib's sequence chunks); NULL = all rows.  A row
+ *                                        with mask == 0 may hold anything in every other input, NaN included: nothing of it reaches an output
  *   n_valid     [dev] i32 [1]            the number of rows with mask != 0 (n_rows with mask == NULL): the divisor, known before the pass, which
- *                                        is what makes every row's gradient local
+ *                                        is what makes every row's gradient local.  It is taken as given (stats[5] reports it).  With
+ *                                        n_valid = 0 (every row masked) the gradients are all 0.0f, stats[5] is 0 and the means are 0 / 0:
+ *                                        total_loss, mean_policy_loss, mean_vf_loss and mean_entropy are NaN, mean_kl is NaN with
+ *                                        kl_coeff > 0 and 0.0 otherwise
  *   stats       [dev] f64 [HH_PPO_STATS]
  *   d_logits    [dev] f32 [n_rows, ld]   d total / d logits; exactly 0.0f in masked rows and in the columns beyond the policy's logits
  *   d_vf        [dev] f32 [n_rows]       d total / d vf; exactly 0.0f in masked rows
