@@ -129,7 +129,8 @@ LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_cate
                    "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
                    "hh_residual_normalize_backward", "hh_input_stage_scratch_bytes", "hh_input_stage_forward",
                    "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward",
-                   "hh_adam_step", "hh_minibatch_stage", "hh_train_commit"]  # include/hh_learner.h
+                   "hh_adam_step", "hh_minibatch_stage", "hh_train_commit", "hh_gru_seq_tile"]  # include/hh_learner.h
+GRU_TILES = (16, 8, 4)  # the compiled instances of hh_k_gru_seq_fwd / _bwd (HH_GRU_TILE forces one; hh_gru_seq_tile tells which a call uses)
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
@@ -262,6 +263,7 @@ def lib():
         L.hh_gru_seq_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.hh_gru_seq_forward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
         L.hh_gru_seq_backward.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(HHGruSeqIO), vp, vp, C.c_int64, vp]
+        L.hh_gru_seq_tile.argtypes = [C.c_int64]
         L.hh_chunk_attn_forward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
         L.hh_chunk_attn_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.hh_residual_normalize_forward.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp]

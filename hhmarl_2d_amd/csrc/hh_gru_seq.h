@@ -2,10 +2,12 @@
  * hh_gru_seq.h — the learner's GRU over whole sequences, forward and backward, one launch each for up to two GRUs (rnn_act and rnn_val
  * of CommanderGru) over all L <= 32 steps (C ABI and the arithmetic: include/hh_learner.h).
  *
- * Shape.  A workgroup of 256 lanes owns a tile of HHG_TILE = 16 sequences of one GRU for all steps (blockIdx.x = tile, blockIdx.y = GRU).
- * Lane j < 200 owns hidden unit j of all 16 sequences: its h (forward) or its dh carry (backward) lives in registers for the whole
- * launch, and the three gates of a unit meet in one lane, so the gate arithmetic needs no exchange.  The h tile (forward) or the d_gh tile
- * (backward) is kept in LDS unit-major ([unit][16]), so the contraction reads it as four 16-byte broadcasts per k.
+ * Shape.  A workgroup of 256 lanes owns a tile of TILE sequences of one GRU for all steps (blockIdx.x = tile, blockIdx.y = GRU); TILE is
+ * a template parameter, instantiated at 16, 8 and 4 (hhg_pick_tile chooses).  Lane j < 200 owns hidden unit j of
+ * all TILE sequences: its h (forward) or its dh carry (backward) lives in registers for the whole launch, and the three gates of a unit
+ * meet in one lane, so the gate arithmetic needs no exchange.  The h tile (forward) or the d_gh tile (backward) is kept in LDS unit-major
+ * ([unit][TILE]), so the contraction reads it as TILE / 4 16-byte broadcasts per k.  A sequence's arithmetic is its own fmaf chain in k
+ * order whatever the tile, and the save buffer is indexed by sequence, so every instance writes the same bytes.
  *
  * Arithmetic: plain float32 fmaf chains in k order, one per output (no split-fp16 MFMA: see DESIGN.md — the result is what a float32
  * GEMM gives, and the test's bound, 4 x the error of the float32 torch-op cell, is met with room instead of depending on a dropped
@@ -16,11 +18,14 @@
  * minibatch step, so this runs in front of every forward (480 KB per GRU, L2 resident afterwards).  The backward contraction
  * dh[s, k] = sum_c d_gh[s, c] W_hh[c, k] reads W_hh as nn.GRU holds it.  Either way a lane streams its weights from L2 eight k (or c)
  * ahead of the fmaf chain that uses them; a tile of 16 instead of the sampler's 32 halves the accumulators (48 per lane) so that two
- * workgroups fit a CU and twice as many CUs are busy at the learner's sizes (13 sequences at 256 rows, ~820 at 16384).
+ * workgroups fit a CU and twice as many CUs are busy at the learner's sizes (13 sequences at 256 rows, ~820 at 16384).  The narrow
+ * instances (8, 4) shorten the per-k chain further (24, 12 accumulators forward) and hand a small minibatch to more workgroups.
  *
  * Tail padding: a tile runs to the longest of its sequences; steps t >= seq_len[s] write exact zeros and leave the sequence's state alone
  * (backward: such a step loads row 0 of dy, of the save buffer and of h0 in place of its own and drops what it loaded, so nothing past
- * seq_len reaches a result).  Fixed summation order, no atomics: the same bytes on every run.
+ * seq_len reaches a result).  A sequence of length 0 is all tail: exact zeros in y, d_gi, d_gh and d_h0, its h0 never read, and a tile
+ * made of such sequences only runs no step at all.  Row 0 is what ended sequences read, so sequence 0 has at least one step (the contract
+ * in hh_learner.h).  Fixed summation order, no atomics: the same bytes on every run.
  */
 #ifndef HH_GRU_SEQ_H
 #define HH_GRU_SEQ_H
@@ -32,7 +37,7 @@
 
 #define HHG_H HH_GRU_HIDDEN      /* 200 */
 #define HHG_G3 (3 * HH_GRU_HIDDEN) /* 600 gate rows r | z | n */
-#define HHG_TILE 16              /* sequences per workgroup */
+#define HHG_TILE_WIDE 16         /* sequences per workgroup: the widest instance (8 and 4 are the narrow ones) */
 #define HHG_THREADS 256
 #define HHG_KB 8                 /* weights in flight per lane and gate */
 #define HHG_SAVE 4               /* floats kept per (sequence, step, unit): r, z, n, W_hn h + b_hn */
@@ -65,52 +70,54 @@ __global__ __launch_bounds__(256) void hh_k_gru_pack(hhg_dev_io io, float *__res
 
 __device__ __forceinline__ float hhg_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+template <int TILE>
 __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_fwd(hhg_dev_io io, int64_t S, int L, const int32_t *__restrict__ seq_len,
                                                                 const float *__restrict__ wt_all, float *__restrict__ save_all) {
-    __shared__ float4 s_h[HHG_H][HHG_TILE / 4];
-    __shared__ int s_len[HHG_TILE];
+    static_assert(TILE == 4 || TILE == 8 || TILE == 16, "a tile is whole float4s of sequences");
+    __shared__ float4 s_h[HHG_H][TILE / 4];
+    __shared__ int s_len[TILE];
     const int g = blockIdx.y, j = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * HHG_TILE;
+    const int64_t s0 = (int64_t)blockIdx.x * TILE;
     const float *__restrict__ gi = io.gi[g];
     const float *__restrict__ wt = wt_all + (int64_t)g * HHG_G3 * HHG_H;
     float *__restrict__ y = io.y[g];
     float *__restrict__ save = save_all + (int64_t)g * S * L * (HHG_SAVE * HHG_H);
-    if (j < HHG_TILE) {
+    if (j < TILE) {
         int n = s0 + j < S ? seq_len[s0 + j] : 0;
-        s_len[j] = n < 0 ? 0 : (n > L ? L : n);     /* the entry point documents 1..L; a stray value cannot take a lane out of bounds */
+        s_len[j] = n < 0 ? 0 : (n > L ? L : n);     /* the entry point documents 0..L; a stray value cannot take a lane out of bounds */
     }
     __syncthreads();
-    int len[HHG_TILE], t_max = 0;
+    int len[TILE], t_max = 0;
 #pragma unroll
-    for (int s = 0; s < HHG_TILE; s++) {
+    for (int s = 0; s < TILE; s++) {
         len[s] = s_len[s];
         t_max = len[s] > t_max ? len[s] : t_max;
     }
     const bool unit = j < HHG_H;
-    float h[HHG_TILE];
+    float h[TILE];
     float br = 0.0f, bz = 0.0f, bn = 0.0f;
     if (unit) {
         br = io.b_hh[g][j]; bz = io.b_hh[g][HHG_H + j]; bn = io.b_hh[g][2 * HHG_H + j];
 #pragma unroll
-        for (int s = 0; s < HHG_TILE; s++) h[s] = len[s] > 0 ? io.h0[g][(s0 + s) * HHG_H + j] : 0.0f;
+        for (int s = 0; s < TILE; s++) h[s] = len[s] > 0 ? io.h0[g][(s0 + s) * HHG_H + j] : 0.0f;
 #pragma unroll
-        for (int q = 0; q < HHG_TILE / 4; q++) s_h[j][q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
+        for (int q = 0; q < TILE / 4; q++) s_h[j][q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
     }
     __syncthreads();
 
     for (int t = 0; t < t_max; t++) {
         if (unit) {
             /* this step's gi, in flight under the contraction (a sequence that has ended reads row 0 of the tensor and drops it) */
-            float xr[HHG_TILE], xz[HHG_TILE], xn[HHG_TILE];
+            float xr[TILE], xz[TILE], xn[TILE];
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) {
+            for (int s = 0; s < TILE; s++) {
                 const int64_t row = t < len[s] ? (s0 + s) * L + t : 0;
                 const float *gp = gi + row * HHG_G3 + j;
                 xr[s] = gp[0]; xz[s] = gp[HHG_H]; xn[s] = gp[2 * HHG_H];
             }
-            float ar[HHG_TILE], az[HHG_TILE], an[HHG_TILE];
+            float ar[TILE], az[TILE], an[TILE];
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) { ar[s] = br; az[s] = bz; an[s] = bn; }
+            for (int s = 0; s < TILE; s++) { ar[s] = br; az[s] = bz; an[s] = bn; }
             float wr[HHG_KB], wz[HHG_KB], wn[HHG_KB];
 #pragma unroll
             for (int u = 0; u < HHG_KB; u++) {
@@ -130,7 +137,7 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_fwd(hhg_dev_io io, i
 #pragma unroll
                 for (int u = 0; u < HHG_KB; u++) {
 #pragma unroll
-                    for (int q = 0; q < HHG_TILE / 4; q++) {
+                    for (int q = 0; q < TILE / 4; q++) {
                         const float4 hv = s_h[k0 + u][q];
                         const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
 #pragma unroll
@@ -143,7 +150,7 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_fwd(hhg_dev_io io, i
                 }
             }
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) {
+            for (int s = 0; s < TILE; s++) {
                 if (t < len[s]) {
                     const int64_t row = (s0 + s) * L + t;
                     const float r = hhg_sigmoid(xr[s] + ar[s]);
@@ -159,54 +166,56 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_fwd(hhg_dev_io io, i
         __syncthreads();   /* every lane has read this step's h tile */
         if (unit) {
 #pragma unroll
-            for (int q = 0; q < HHG_TILE / 4; q++) s_h[j][q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
+            for (int q = 0; q < TILE / 4; q++) s_h[j][q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
         }
         __syncthreads();
     }
     /* the padded tail: exact zeros */
     if (unit) {
 #pragma unroll
-        for (int s = 0; s < HHG_TILE; s++)
+        for (int s = 0; s < TILE; s++)
             if (s0 + s < S)
                 for (int t = len[s]; t < L; t++) y[((s0 + s) * L + t) * HHG_H + j] = 0.0f;
     }
 }
 
+template <int TILE>
 __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_bwd(hhg_dev_io io, int64_t S, int L, const int32_t *__restrict__ seq_len,
                                                                 const float *__restrict__ save_all) {
-    __shared__ float4 s_d[HHG_G3][HHG_TILE / 4];
-    __shared__ int s_len[HHG_TILE];
+    static_assert(TILE == 4 || TILE == 8 || TILE == 16, "a tile is whole float4s of sequences");
+    __shared__ float4 s_d[HHG_G3][TILE / 4];
+    __shared__ int s_len[TILE];
     const int g = blockIdx.y, j = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * HHG_TILE;
+    const int64_t s0 = (int64_t)blockIdx.x * TILE;
     const float *__restrict__ w = io.w[g];
     const float *__restrict__ dy = io.dy[g];
     const float *__restrict__ y = io.y[g];
     const float *__restrict__ save = save_all + (int64_t)g * S * L * (HHG_SAVE * HHG_H);
     float *__restrict__ d_gi = io.d_gi[g];
     float *__restrict__ d_gh = io.d_gh[g];
-    if (j < HHG_TILE) {
+    if (j < TILE) {
         int n = s0 + j < S ? seq_len[s0 + j] : 0;
         s_len[j] = n < 0 ? 0 : (n > L ? L : n);
     }
     __syncthreads();
-    int len[HHG_TILE], t_max = 0;
+    int len[TILE], t_max = 0;
 #pragma unroll
-    for (int s = 0; s < HHG_TILE; s++) {
+    for (int s = 0; s < TILE; s++) {
         len[s] = s_len[s];
         t_max = len[s] > t_max ? len[s] : t_max;
     }
     const bool unit = j < HHG_H;
-    float dh[HHG_TILE];
+    float dh[TILE];
 #pragma unroll
-    for (int s = 0; s < HHG_TILE; s++) dh[s] = 0.0f;
+    for (int s = 0; s < TILE; s++) dh[s] = 0.0f;
 
     for (int t = t_max - 1; t >= 0; t--) {
-        float keep[HHG_TILE];    /* dh_total z: the part of the carry that does not go through the gates */
+        float keep[TILE];    /* dh_total z: the part of the carry that does not go through the gates */
         if (unit) {
-            float gr[HHG_TILE], gz[HHG_TILE], gn[HHG_TILE];
+            float gr[TILE], gz[TILE], gn[TILE];
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) {
-                /* unconditional loads, so that all 16 sequences' are in flight together; a sequence that has ended reads row 0 of dy, of the
+            for (int s = 0; s < TILE; s++) {
+                /* unconditional loads, so that all the tile's sequences' are in flight together; a sequence that has ended reads row 0 of dy, of the
                  * save buffer and of h0 and drops it.  Row 0 is in bounds and, with seq_len[0] >= 1 as the contract asks, written by the
                  * forward; were a stray seq_len[0] clamped to 0, the save row would be read unwritten and still dropped */
                 const bool on = t < len[s];
@@ -230,7 +239,7 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_bwd(hhg_dev_io io, i
                 }
             }
 #pragma unroll
-            for (int q = 0; q < HHG_TILE / 4; q++) {
+            for (int q = 0; q < TILE / 4; q++) {
                 s_d[j][q] = make_float4(gr[4 * q], gr[4 * q + 1], gr[4 * q + 2], gr[4 * q + 3]);
                 s_d[HHG_H + j][q] = make_float4(gz[4 * q], gz[4 * q + 1], gz[4 * q + 2], gz[4 * q + 3]);
                 s_d[2 * HHG_H + j][q] = make_float4(gn[4 * q], gn[4 * q + 1], gn[4 * q + 2], gn[4 * q + 3]);
@@ -238,9 +247,9 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_bwd(hhg_dev_io io, i
         }
         __syncthreads();
         if (unit) {
-            float acc[HHG_TILE];
+            float acc[TILE];
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) acc[s] = 0.0f;
+            for (int s = 0; s < TILE; s++) acc[s] = 0.0f;
             float wv[HHG_KB];
 #pragma unroll
             for (int u = 0; u < HHG_KB; u++) wv[u] = w[u * HHG_H + j];
@@ -255,7 +264,7 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_bwd(hhg_dev_io io, i
 #pragma unroll
                 for (int u = 0; u < HHG_KB; u++) {
 #pragma unroll
-                    for (int q = 0; q < HHG_TILE / 4; q++) {
+                    for (int q = 0; q < TILE / 4; q++) {
                         const float4 dv = s_d[c0 + u][q];
                         acc[4 * q] = fmaf(cv[u], dv.x, acc[4 * q]);
                         acc[4 * q + 1] = fmaf(cv[u], dv.y, acc[4 * q + 1]);
@@ -265,13 +274,13 @@ __global__ __launch_bounds__(HHG_THREADS) void hh_k_gru_seq_bwd(hhg_dev_io io, i
                 }
             }
 #pragma unroll
-            for (int s = 0; s < HHG_TILE; s++) dh[s] = t < len[s] ? keep[s] + acc[s] : 0.0f;
+            for (int s = 0; s < TILE; s++) dh[s] = t < len[s] ? keep[s] + acc[s] : 0.0f;
         }
         __syncthreads();   /* every lane has read this step's d_gh tile */
     }
     if (unit) {
 #pragma unroll
-        for (int s = 0; s < HHG_TILE; s++) {
+        for (int s = 0; s < TILE; s++) {
             if (s0 + s < S) {
                 io.d_h0[g][(s0 + s) * HHG_H + j] = dh[s];
                 for (int t = len[s]; t < L; t++) {
@@ -298,6 +307,48 @@ static int hhg_check_shape(const char *who, int32_t G, int64_t S, int32_t L) {
         return HH_E_ARG;
     }
     return HH_OK;
+}
+
+/* The tile of a call over n_seq sequences: HH_GRU_TILE (read at every call; 16 | 8 | 4, for A/B runs) or, without it, the rule measured
+ * in DESIGN.md section 19: each narrow tile up to the largest measured n_seq at which it still beat tile 16 by more than both runs' spread.
+ * While the workgroups fit the device side by side the launch lasts as long as one workgroup's dependent chain, which the narrow tile
+ * shortens (3.0 x at 13 sequences, 1.6 x at 1708); once they queue, the narrow tiles' extra passes over W_hh cost more than they save
+ * (tile 4 loses from 6832 sequences on).  Forward and backward of a pair see the same n_seq and so the same tile. */
+#define HHG_TILE4_MAX_SEQ 1708
+#define HHG_TILE8_MAX_SEQ 3416
+
+static int hhg_pick_tile(const char *who, int64_t n_seq, int *tile) {
+    const char *e = getenv("HH_GRU_TILE");
+    if (e && *e) {
+        const int v = atoi(e);
+        if (v != 16 && v != 8 && v != 4) {
+            g_err = std::string(who) + ": HH_GRU_TILE is one of the instantiated tiles 16, 8, 4, got \"" + e + "\"";
+            return HH_E_ARG;
+        }
+        *tile = v;
+        return HH_OK;
+    }
+    *tile = n_seq <= HHG_TILE4_MAX_SEQ ? 4 : (n_seq <= HHG_TILE8_MAX_SEQ ? 8 : HHG_TILE_WIDE);
+    return HH_OK;
+}
+
+extern "C" int hh_gru_seq_tile(int64_t n_seq) {
+    int tile = 0;
+    if (int rc = hhg_pick_tile("hh_gru_seq_tile", n_seq, &tile)) return rc;
+    return tile;
+}
+
+template <int TILE>
+static void hhg_launch_fwd(const hhg_dev_io &d, int64_t n_seq, int n_gru, int max_len, const int32_t *seq_len, const float *wt, float *save,
+                           hipStream_t st) {
+    const unsigned tiles = (unsigned)((n_seq + TILE - 1) / TILE);
+    hipLaunchKernelGGL(hh_k_gru_seq_fwd<TILE>, dim3(tiles, n_gru), dim3(HHG_THREADS), 0, st, d, n_seq, max_len, seq_len, wt, save);
+}
+
+template <int TILE>
+static void hhg_launch_bwd(const hhg_dev_io &d, int64_t n_seq, int n_gru, int max_len, const int32_t *seq_len, const float *save, hipStream_t st) {
+    const unsigned tiles = (unsigned)((n_seq + TILE - 1) / TILE);
+    hipLaunchKernelGGL(hh_k_gru_seq_bwd<TILE>, dim3(tiles, n_gru), dim3(HHG_THREADS), 0, st, d, n_seq, max_len, seq_len, save);
 }
 
 extern "C" int hh_gru_seq_scratch_bytes(int32_t n_gru, int64_t n_seq, int32_t max_len, int64_t *bytes) {
@@ -349,13 +400,16 @@ extern "C" int hh_gru_seq_forward(int32_t n_gru, int64_t n_seq, int32_t max_len,
         d.gi[g] = io[g].gi; d.h0[g] = io[g].h0; d.w[g] = io[g].w_hh; d.b_hh[g] = io[g].b_hh; d.y[g] = io[g].y;
     }
     if (int rc = hhg_check_spans("hh_gru_seq_forward", sp, n)) return rc;
+    int tile = 0;
+    if (int rc = hhg_pick_tile("hh_gru_seq_forward", n_seq, &tile)) return rc;
     hipStream_t st = (hipStream_t)stream;
     float *wt = static_cast<float *>(scratch);
     float *save = wt + hhg_pack_floats(n_gru);
     hipLaunchKernelGGL(hh_k_gru_pack, dim3((HHG_H + 31) / 32, (HHG_G3 + 31) / 32, n_gru), dim3(256), 0, st, d, wt);
     HIPCHK(hipGetLastError());
-    const unsigned tiles = (unsigned)((n_seq + HHG_TILE - 1) / HHG_TILE);
-    hipLaunchKernelGGL(hh_k_gru_seq_fwd, dim3(tiles, n_gru), dim3(HHG_THREADS), 0, st, d, n_seq, (int)max_len, seq_len, (const float *)wt, save);
+    if (tile == 4) hhg_launch_fwd<4>(d, n_seq, n_gru, max_len, seq_len, wt, save, st);
+    else if (tile == 8) hhg_launch_fwd<8>(d, n_seq, n_gru, max_len, seq_len, wt, save, st);
+    else hhg_launch_fwd<16>(d, n_seq, n_gru, max_len, seq_len, wt, save, st);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }
@@ -385,10 +439,13 @@ extern "C" int hh_gru_seq_backward(int32_t n_gru, int64_t n_seq, int32_t max_len
         d.d_gi[g] = io[g].d_gi; d.d_gh[g] = io[g].d_gh; d.d_h0[g] = io[g].d_h0;
     }
     if (int rc = hhg_check_spans("hh_gru_seq_backward", sp, n)) return rc;
+    int tile = 0;
+    if (int rc = hhg_pick_tile("hh_gru_seq_backward", n_seq, &tile)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float *save = static_cast<const float *>(scratch) + hhg_pack_floats(n_gru);
-    const unsigned tiles = (unsigned)((n_seq + HHG_TILE - 1) / HHG_TILE);
-    hipLaunchKernelGGL(hh_k_gru_seq_bwd, dim3(tiles, n_gru), dim3(HHG_THREADS), 0, st, d, n_seq, (int)max_len, seq_len, save);
+    if (tile == 4) hhg_launch_bwd<4>(d, n_seq, n_gru, max_len, seq_len, save, st);
+    else if (tile == 8) hhg_launch_bwd<8>(d, n_seq, n_gru, max_len, seq_len, save, st);
+    else hhg_launch_bwd<16>(d, n_seq, n_gru, max_len, seq_len, save, st);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }

@@ -740,6 +740,15 @@ def minibatch_schedule(parts, n_valid, num_sgd_iter, seed, update, policy):
     return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
 
 
+def sequence_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, policy):
+    """the minibatch steps of one update over sequences of these lengths (host integers [S]): minibatch_partition's parts and their
+    minibatch_schedule — per pass minibatch_order's order, what the eager path visits -> (parts, int32 [num_sgd_iter * len(parts), 4])"""
+    seq_len = np.asarray(seq_len, dtype=np.int64)
+    parts = minibatch_partition(seq_len, sgd_minibatch_size)
+    csum = np.concatenate([[0], np.cumsum(seq_len)])
+    return parts, minibatch_schedule(parts, [csum[s1] - csum[s0] for s0, s1 in parts], num_sgd_iter, seed, update, policy)
+
+
 def minibatch_stage(cols, staged, chunk_len, schedule, cursor, n_valid, src_chunks=None):
     """The minibatch that schedule[cursor] names, copied into fixed-address staging buffers in ONE launch (hh_minibatch_stage,
     include/hh_learner.h).  cols: up to 8 contiguous CUDA tensors [S, ...] (chunks first; any dtype); staged: per column a contiguous
@@ -1140,6 +1149,8 @@ class PPOLearner:
 # =================================================================================================================== the commander
 CMD_LD = 4      # HH_CMD_LOGITS: row width of hh_commander_sample's logits and of hh_ppo_loss_categorical's
 GRU_H = 200     # HH_GRU_HIDDEN
+# what CommanderLearner(step="graph") stages per minibatch: eight columns [S, L, ...] per step, then two per sequence
+COMMANDER_STAGE_COLS = ("obs", "critic", "actions", "old_logp", "adv", "target", "mask", "old_logits", "state_in", "seq_len")
 
 
 # ------------------------------------------------------------------------------------------------------------------ the GRU
@@ -1151,6 +1162,14 @@ def _gru_scratch_bytes(G, S, Lm):
     nbytes = C.c_int64()
     L.check(L.lib().hh_gru_seq_scratch_bytes(G, S, Lm, C.byref(nbytes)))
     return nbytes.value
+
+
+def gru_seq_tile(n_seq):
+    """the sequences per workgroup (one of _lib.GRU_TILES) that hh_gru_seq_forward / _backward use for n_seq sequences: what the
+    environment variable HH_GRU_TILE forces (read at every call; another value is an error), else the rule of DESIGN.md section 19"""
+    tile = L.lib().hh_gru_seq_tile(int(n_seq))
+    L.check(min(tile, 0))
+    return tile
 
 
 def gru_seq_forward(parts, seq_len):
@@ -1226,8 +1245,10 @@ def _check_gru(gi, h0, w_hh, b_hh, seq_len):
 def gru_sequence(gi, h0, w_hh, b_hh, seq_len):
     """One nn.GRU(200, 200) layer over S padded sequences with the input projection already applied, fused (hh_gru_seq_forward /
     hh_gru_seq_backward, include/hh_learner.h): gi f32 [S, L, 600] = x W_ih^T + b_ih, h0 f32 [S, 200], w_hh f32 [600, 200], b_hh f32 [600]
-    (gate rows r | z | n), seq_len i32 [S] with 1 <= seq_len <= L <= 32, all CUDA -> y f32 [S, L, 200], exactly 0 at steps t >= seq_len;
-    differentiable with respect to gi, h0, w_hh and b_hh.  No host synchronisation; a missing library or GPU is an error."""
+    (gate rows r | z | n), seq_len i32 [S] with 0 <= seq_len[s] <= L <= 32 and seq_len[0] >= 1, all CUDA -> y f32 [S, L, 200], exactly 0 at
+    steps t >= seq_len; differentiable with respect to gi, h0, w_hh and b_hh.  A sequence of length 0 (a padding slot of a staged
+    minibatch) gives exact zeros in y and in the gradients of its gi and h0 and changes no other sequence's bytes.  The sequences per
+    workgroup (gru_seq_tile) do not change the result.  No host synchronisation; a missing library or GPU is an error."""
     _check_gru(gi, h0, w_hh, b_hh, seq_len)
     return _GruSeq.apply(seq_len.contiguous(), gi, h0, w_hh, b_hh)[0]
 
@@ -1468,19 +1489,29 @@ class CommanderLearner:
         sgd_minibatch_size unpadded rows (minibatch_partition), visited in the order of minibatch_order(seed, update count, 0, pass);
       * after the passes KLCoeffMixin.update_kl (kl_coeff_update) on the mean of the minibatches' mean_kl.
     fused = False computes the loss with torch ops (ppo_loss_categorical_torch) and steps the GRU cell with torch ops
-    (gru_sequence_torch) instead of hh_ppo_loss_categorical and hh_gru_seq_*; nothing else differs."""
+    (gru_sequence_torch) instead of hh_ppo_loss_categorical and hh_gru_seq_*; nothing else differs.
+    optimizer="fused", step="graph" replays every minibatch step from one captured HIP graph, as PPOLearner's do (graph_prepare;
+    DESIGN.md section 19): the same minibatches in the same order, no Python, autograd dispatch or torch.optim.Adam between launches."""
 
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
-                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch"):
+                 entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch",
+                 optimizer="torch", step="eager"):
         """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys().  inputs: CommanderTrainable's argument
-        ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*); trunk: its argument too ("fused": shared_layer through hh_dense_tanh_*)."""
+        ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*); trunk: its argument too ("fused": shared_layer through hh_dense_tanh_*).
+        optimizer, step: PPOLearner's arguments, with its values, defaults and validation.  optimizer="fused" makes `self.optimizer` a
+        DeviceAdam (m, v and the step count on the device: hh_adam_step) and gathers the steps' statistics in a device table
+        (hh_train_commit); step="graph" (needs optimizer="fused") captures stage -> stage -> forward -> loss -> backward -> Adam -> commit
+        once as ONE HIP graph and replays it per minibatch step (graph_prepare).  The modes are kept in `optimizer_mode` and `step`."""
+        self.optimizer_mode = _optimizer_mode(optimizer)
+        self.step = _step_mode(step, optimizer)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.inputs, self.trunk = inputs, _trunk_mode(trunk)
         self.module = CommanderTrainable(inputs=inputs, trunk=trunk).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
-        self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
+        self.optimizer = (DeviceAdam if self.optimizer_mode == "fused" else torch.optim.Adam)(self.module.parameters(), lr=lr)
+        self._book = _StepBook(self.device) if self.optimizer_mode == "fused" else None
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
         self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
         self.use_kl = kl_coeff > 0.0
@@ -1548,7 +1579,95 @@ class CommanderLearner:
         self.optimizer.zero_grad(set_to_none=True)
         total.backward()
         self.optimizer.step()
+        if self.optimizer_mode == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
+            train_commit(stats, self._book.table, self._book.cursor, self.optimizer.t)
         return stats
+
+    # ---- the step as one HIP graph (step="graph")
+    def graph_prepare(self, b, cap=None):
+        """Everything one update needs before its first replay: the schedule of policy_batch `b` (with old_logits) and the batch's ten
+        columns — COMMANDER_STAGE_COLS: eight per step, then state_in and seq_len per sequence — uploaded into persistent device buffers,
+        the cursor set to 0, and the graph of ONE minibatch step captured — stage (per-step columns), stage (per-sequence columns), forward,
+        loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only — unless the graph of an earlier call still
+        fits: it is kept while cap, kl_coeff (by value in hh_ppo_loss_params), the columns and the buffers' addresses are what they were.
+        cap: the staging capacity in sequences; default and minimum: the largest minibatch.  The sequences of the staging buffers beyond a
+        minibatch's are zero in every column: sequences of length 0 (hh_gru_seq_*'s contract) whose rows the mask drops.  Weights, m, v, t
+        are left bit for bit as they were.  -> (n_steps, rows)"""
+        if self.step != "graph":
+            raise ValueError('graph_prepare needs CommanderLearner(step="graph")')
+        missing = [k for k in COMMANDER_STAGE_COLS if k not in b]
+        if missing:
+            raise ValueError(f"graph_prepare: the policy batch lacks {missing} (policy_batch, then old_logits from batch_old_logits)")
+        book = self._book
+        cols = {k: b[k].contiguous() for k in COMMANDER_STAGE_COLS}
+        cols["mask"], cols["seq_len"] = cols["mask"].to(torch.uint8), cols["seq_len"].to(torch.int32)
+        seq_len = cols["seq_len"].cpu().numpy()
+        parts, sched = sequence_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
+        need = max(s1 - s0 for s0, s1 in parts)
+        cap = need if cap is None else int(cap)
+        if cap < need:
+            raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} sequences)")
+        book.begin(len(sched))
+        book.load(cols, sched)
+        book.n_steps, book.cap = len(sched), cap
+        src_chunks = min(t.shape[0] for t in book.src.values())
+        kl = self.kl_coeff if self.use_kl else 0.0
+        key = (cap, kl, COMMANDER_STAGE_COLS, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(),
+               book.table.shape[0]) + tuple(book.src[k].data_ptr() for k in COMMANDER_STAGE_COLS)
+        if book.graph is None or book.key != key:
+            self._capture(book, src_chunks)
+            book.key = key
+        return len(sched), int(seq_len.sum())
+
+    def _capture(self, book, src_chunks):
+        opt, dev, names = self.optimizer, self.device, COMMANDER_STAGE_COLS
+        if book.staged.get("obs") is None or book.staged["obs"].shape[0] != book.cap or tuple(book.staged) != names:
+            book.staged = {k: torch.zeros((book.cap,) + tuple(book.src[k].shape[1:]), dtype=book.src[k].dtype, device=dev) for k in names}
+        mb = dict(book.staged, n_valid=book.n_valid)
+        # hh_minibatch_stage takes 8 columns: the per-step columns (chunks of max_seq_len rows) in one call, the per-sequence ones (state_in,
+        # seq_len: chunks of one row) in a second.  Both only read the cursor and the schedule and write the same n_valid.
+        groups = [(names[:L.STAGE_MAX_COLS], self.max_seq_len), (names[L.STAGE_MAX_COLS:], 1)]
+
+        def stage():
+            for ks, chunk_len in groups:
+                minibatch_stage([book.src[k][:src_chunks] for k in ks], [book.staged[k] for k in ks], chunk_len, book.schedule, book.cursor,
+                                book.n_valid)
+
+        def forward_backward():
+            logits, vf = self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused)
+            total, stats = self.loss(logits, vf, mb)
+            total.backward()
+            return stats
+        # the warm-up: forward and backward only (rocBLAS and autograd initialise), on a side stream as torch's capture recipe has it;
+        # it reads schedule[0] through the cursor and writes nothing but the staging buffers and gradients that are thrown away
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            stage()
+            for _ in range(2):
+                opt.zero_grad(set_to_none=True)
+                forward_backward()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        opt.zero_grad(set_to_none=True)     # backward inside the capture assigns the gradients from the graph's pool: their addresses are fixed
+        book.graph = None
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):       # the GRU's scratch and y (torch.empty in _GruSeq.forward) come from the graph's pool as well
+            stage()
+            stats = forward_backward()
+            opt.step()
+            train_commit(stats, book.table, book.cursor, opt.t)
+        book.graph, book.keep = graph, stats
+        book.captures += 1
+
+    def graph_replay(self, n=1):
+        """n minibatch steps from the captured graph, no host work between them"""
+        graph = self._book.graph
+        for _ in range(int(n)):
+            graph.replay()
+
+    def graph_stats(self, n):
+        """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
+        return self._book.table[:int(n)]
 
     # ---- one update
     def update(self, episodes, net=None):
@@ -1566,11 +1685,21 @@ class CommanderLearner:
         with torch.no_grad():
             b = self.policy_batch(seqs)
             b["old_logits"] = self.batch_old_logits(seqs, b)
+        if self.step == "graph":
+            n_steps, n_rows = self.graph_prepare(b)
+            self.graph_replay(n_steps)
+            m = self.graph_stats(n_steps).mean(dim=0).tolist()
+            if self.use_kl:
+                self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
+            self.updates += 1
+            return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=n_steps, rows=n_rows)
         seq_len = b["seq_len"].cpu().numpy()
         parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
         csum = np.concatenate([[0], np.cumsum(seq_len)])
         n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
         all_stats = []
+        if self.optimizer_mode == "fused":
+            self._book.begin(self.num_sgd_iter * len(parts))
         for sgd_pass in range(self.num_sgd_iter):
             for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
                 s0, s1 = parts[i]

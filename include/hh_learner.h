@@ -81,7 +81,10 @@ int hh_ppo_loss_categorical(int64_t n_rows, const float *logits, const float *ol
 /* ---- the learner's GRU over whole sequences (CommanderGru's rnn_act and rnn_val under RLlib's max_seq_len chunks) ----
  *
  * n_gru = 1 | 2 GRUs of width HH_GRU_HIDDEN = 200 (two: the actor's and the critic's in one launch, over the same sequences), n_seq
- * sequences of max_len <= HH_GRU_MAX_LEN steps, sequence s holding seq_len[s] steps (1..max_len) followed by padding.  Per step,
+ * sequences of max_len <= HH_GRU_MAX_LEN steps, sequence s holding seq_len[s] steps followed by padding: 0 <= seq_len[s] <= max_len, and
+ * seq_len[0] >= 1 (row 0 of every tensor is what a sequence that has ended loads and drops).  A sequence of length 0 — a padding slot of a
+ * staged minibatch — gives exact zeros in all of y, d_gi, d_gh and d_h0, its gi, h0 and dy are not read, and it changes no other
+ * sequence's bytes.  Per step,
  * torch.nn.GRU's cell with the input projection taken out (it is time-parallel: one GEMM in front):
  *     gh = W_hh h + b_hh;  r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r gh_n);  h' = (1 - z) n + z h
  * Everything is float32 and ordered on `stream`; no allocation, no host synchronisation, no floating-point atomics, HIP-graph capturable;
@@ -116,6 +119,12 @@ int hh_gru_seq_forward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_g
  * GEMM), db_hh = the column sums of d_gh, and everything upstream of gi. */
 int hh_gru_seq_backward(int32_t n_gru, int64_t n_seq, int32_t max_len, const hh_gru_seq_io *io, const int32_t *seq_len, const void *scratch,
                         int64_t scratch_bytes, void *stream);
+
+/* The sequences per workgroup (16, 8 or 4: the compiled instances) that hh_gru_seq_forward / _backward use for n_seq sequences; every
+ * instance writes the same bytes, and `scratch` does not depend on it.  The environment variable HH_GRU_TILE, read at every call, forces
+ * an instance (for A/B runs); any other value of it is HH_E_ARG, here and in the two entry points, with nothing enqueued.  Without it the
+ * tile follows from n_seq alone, so the forward and the backward of one pair always agree.  Host only. */
+int hh_gru_seq_tile(int64_t n_seq);
 
 /* ---- the fight networks' self-attention over RLlib's max_seq_len chunks, without its GEMMs (Fight1 / Fight2: att_act of width 100 and
  * att_val of width 150, models/ac_models_hetero.py) ----

@@ -11,6 +11,14 @@
           (hh_dense_tanh_*, split-fp16 MFMA) against the default two float32 GEMMs + tanh, both in one process: the layer alone (forward
           + backward) and the two kernel calls alone (useful TFLOP/s, 2 R K N per product) at 2 x 262 and 2 x 16396 rows, and the
           minibatch step with inputs="fused" at 256 and 16384 rows; its lines are appended to --out.  The same rule for gain / loss
+  graph   --graph: CommanderLearner(optimizer="fused", step="graph") with inputs="fused" against the eager step, all in one process: one
+          minibatch step at 256 and 16384 rows as eager + torch Adam, eager + device Adam and graph replay, 50 steps back to back, one
+          whole update at sgd_minibatch_size = 256 eager against graph (captures included) and the cost of one capture; its lines are
+          appended to --out.  The same rule for gain / loss, with eager + torch Adam as the base.  `--step graph --launches eager|graph`
+          runs nothing but --launch-count steps of that form after the set-up: the program of a kernel trace that counts launches
+  tile    --tile: the compiled tiles of hh_k_gru_seq_fwd / _bwd, each forced through HH_GRU_TILE in a child process of its own: both GRUs'
+          forward + backward kernels alone at --tile-seqs sequence counts (13 ... 854) and the graph step at 256 rows; then every narrow
+          tile against tile 16 by the same rule; appended to --out
 Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
 that fails or runs out of time ends the run, nothing is retried.
     python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
@@ -239,6 +247,189 @@ def step_trunk(a, say):
             f"sequences: trunk = torch {q(t['torch'])}; trunk = fused {q(t['fused'])}; {verdict(t['torch'], t['fused'])}")
 
 
+GRAPH = dict(optimizer="fused", step="graph")
+
+
+def verdict(t_base, t_new, base="base"):
+    """the spread rule: a difference counts only where the medians differ by more than the larger of the two (max - min) spreads"""
+    med = statistics.median
+    spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+    d = med(t_base) - med(t_new)
+    word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+    return f"{base} / this = {med(t_base) / med(t_new):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+
+def _policy_batch(a, **kw):
+    """the rollout's batch as a learner's policy batch with old_logits -> (rollout, net, batch, host seq_len)"""
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    ro, net = _rollout(a)
+    base = LR.CommanderLearner.trainable_init(torch.device("cuda", 0), seed=6, **kw)
+    with torch.no_grad():
+        b = base.policy_batch(ro.episodes.sequences())
+        b["old_logits"] = base.old_logits(b)
+    return ro, net, b, b["seq_len"].cpu().numpy()
+
+
+def _one_minibatch(b, seq_len, size):
+    """the first minibatch of >= size rows -> (its slice of the batch, the same with n_valid, sequences, unpadded rows)"""
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+    sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+    mb = dict(sub, n_valid=torch.tensor([int(seq_len[s0:s1].sum())], dtype=torch.int32, device=b["obs"].device))
+    return sub, mb, s1 - s0, int(seq_len[s0:s1].sum())
+
+
+def _graph_learner(sub, n_steps, **kw):
+    """a graph learner whose one update is n_steps visits of the single minibatch `sub` -> (learner, milliseconds graph_prepare took)"""
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    lr = LR.CommanderLearner.trainable_init(torch.device("cuda", 0), seed=6, num_sgd_iter=n_steps, sgd_minibatch_size=1 << 30, **GRAPH, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    lr.graph_prepare(sub)
+    torch.cuda.synchronize()
+    return lr, (time.perf_counter() - t0) * 1e3
+
+
+def step_graph(a, say):
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    FUSED = dict(inputs="fused")
+    make = lambda **kw: LR.CommanderLearner.trainable_init(dev, seed=6, **FUSED, **kw)
+    ro, net, b, seq_len = _policy_batch(a, **FUSED)
+    if a.launches:       # for a kernel trace: nothing but launch_count steps of one form after the set-up
+        sub, mb, _, _ = _one_minibatch(b, seq_len, 256)
+        if a.launches == "graph":
+            lr, _ = _graph_learner(sub, a.launch_count, **FUSED)
+            lr.graph_replay(a.launch_count)
+        else:
+            lr = make()
+            for _ in range(a.launch_count):
+                lr.minibatch_step(mb)
+        torch.cuda.synchronize()
+        print(f"{a.launch_count} {a.launches} steps done", flush=True)
+        return
+    say(f"# tools/commander_learner_bench.py --graph on {torch.cuda.get_device_name(0)}: CommanderLearner(optimizer=\"fused\", step=\"graph\") against the "
+        f"eager step with torch.optim.Adam, all in this run; inputs = fused, GRU tile {LR.gru_seq_tile(13)} at 13 sequences and {LR.gru_seq_tile(854)} at "
+        f"854; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+    K = 50
+
+    def burst(fn):
+        """K steps back to back, no host synchronisation between them -> milliseconds per step, three times"""
+        out = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append((e0.elapsed_time(e1) / K, (time.perf_counter() - t0) * 1e3 / K))
+        return "; ".join(f"{d:.3f} device / {h:.3f} host" for d, h in out)
+
+    base, dev_adam = make(), make(optimizer="fused")
+    for size in (256, 16384):
+        sub, mb, n_seq, n_rows = _one_minibatch(b, seq_len, size)
+        n_total = 4 * (a.iters + a.warmup) + 4 * K + 8
+        dev_adam._book.begin(n_total)
+        graph, t_cap = _graph_learner(sub, n_total, **FUSED)
+        t_e = events(lambda: base.minibatch_step(mb), a.iters, a.warmup)
+        t_f = events(lambda: dev_adam.minibatch_step(mb), a.iters, a.warmup)
+        t_g = events(lambda: graph.graph_replay(1), a.iters, a.warmup)
+        say(f"minibatch step (forward + loss + backward + Adam, fused GRU and loss), {n_rows} unpadded rows in {n_seq} sequences: eager + torch Adam "
+            f"{q(t_e)}; eager + device Adam {q(t_f)} [{verdict(t_e, t_f, 'eager+torch')}]; graph {q(t_g)} [{verdict(t_e, t_g, 'eager+torch')}]")
+        say(f"    {K} steps back to back, ms per step, three runs: eager + torch Adam {burst(lambda: [base.minibatch_step(mb) for _ in range(K)])} | "
+            f"eager + device Adam {burst(lambda: [dev_adam.minibatch_step(mb) for _ in range(K)])} | graph {burst(lambda: graph.graph_replay(K))}")
+        say(f"    graph_prepare (upload, warm-up, capture) of this step: {t_cap:.1f} ms on the host clock")
+        del graph
+    res = {}
+    for label, kw in (("eager + torch Adam", {}), ("graph", GRAPH)):
+        lr = make(num_sgd_iter=a.passes, sgd_minibatch_size=256, **kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = lr.update(ro.episodes, net)
+        torch.cuda.synchronize()
+        res[label] = ((time.perf_counter() - t0) * 1e3, st, lr)
+    (t_e, st_e, _), (t_g, st_g, lr_g) = res["eager + torch Adam"], res["graph"]
+    say(f"one update at {a.arenas} arenas, T = {a.T} ({a.passes} pass(es), minibatches of >= 256 rows: {st_e['steps']} steps over {st_e['rows']} rows), "
+        f"host clock to a synchronise, first update of a new learner (the graph's includes its {lr_g._book.captures} capture(s)): eager + torch Adam "
+        f"{t_e:.1f} ms; graph {t_g:.1f} ms; eager / graph = {t_e / t_g:.2f}x")
+    say(f"    mean statistics, eager: { {k: round(v, 6) for k, v in st_e.items()} }")
+    say(f"    mean statistics, graph: { {k: round(v, 6) for k, v in st_g.items()} }")
+
+
+def tile_lengths(n_seq, L, seed, device):
+    """n_seq ragged lengths drawn as `sequences` draws them (nine in ten full), the first one full"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    full = torch.rand((n_seq,), generator=g) < 0.9
+    n = torch.where(full, torch.full((n_seq,), L), torch.randint(1, L + 1, (n_seq,), generator=g))
+    n[0] = L
+    return n.to(torch.int32).to(device)
+
+
+def step_tile(a, say):
+    """one tile (HH_GRU_TILE, set by the parent): both GRUs' forward + backward kernels alone at each sequence count, then the graph step"""
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    tile = LR.gru_seq_tile(13)
+    assert str(tile) == os.environ.get("HH_GRU_TILE"), "the parent sets HH_GRU_TILE"
+    if tile == 16:
+        say(f"# tools/commander_learner_bench.py --tile on {torch.cuda.get_device_name(0)}: the compiled instances of hh_k_gru_seq_fwd / _bwd, each forced "
+            f"through HH_GRU_TILE in a process of its own; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+    Lm, H = 20, 200
+    for S in a.tile_seqs:
+        seq_len = tile_lengths(S, Lm, 1, dev)
+        g = torch.Generator().manual_seed(2)
+        mk = lambda *shape, s=1.0: (s * torch.randn(shape, generator=g)).to(dev)
+        parts = [(mk(S, Lm, 3 * H), mk(S, H, s=0.5), mk(3 * H, H, s=H ** -0.5), mk(3 * H, s=0.1)) for _ in range(2)]
+        dys = [mk(S, Lm, H) for _ in range(2)]
+
+        def both():
+            ys, scratch = LR.gru_seq_forward(parts, seq_len)
+            LR.gru_seq_backward(parts, ys, dys, seq_len, scratch)
+        t = events(both, a.iters, a.warmup)
+        say(f"tile {tile:2d}: hh_gru_seq_forward + hh_gru_seq_backward alone, both GRUs, {S} sequences of <= {Lm} steps ({int(seq_len.sum())} rows, "
+            f"{2 * ((S + tile - 1) // tile)} workgroups per launch): {q(t)}")
+        print("@tile", tile, f"gru{S}", " ".join(f"{x:.6f}" for x in t), flush=True)
+    ro, net, b, seq_len = _policy_batch(a, inputs="fused")
+    sub, _, n_seq, n_rows = _one_minibatch(b, seq_len, 256)
+    graph, _ = _graph_learner(sub, 2 * (a.iters + a.warmup) + 8, inputs="fused")
+    t = events(lambda: graph.graph_replay(1), a.iters, a.warmup)
+    say(f"tile {tile:2d}: graph minibatch step (inputs = fused), {n_rows} unpadded rows in {n_seq} sequences (cap {graph._book.cap}): {q(t)}")
+    print("@tile", tile, "graph", " ".join(f"{x:.6f}" for x in t), flush=True)
+
+
+def run_tiles(a, fwd):
+    """--tile: one child per compiled tile, then every narrow tile against tile 16 by the spread rule"""
+    sys.path.insert(0, ROOT)
+    from hhmarl_2d_amd import _lib
+    got = {}
+    for tile in _lib.GRU_TILES:
+        cmd = f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step tile {' '.join(fwd)}"
+        p = subprocess.run(cmd, shell=True, env=dict(os.environ, HH_GRU_TILE=str(tile)), stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(p.stdout)
+        if p.returncode:
+            return p.returncode         # the first child that fails or runs out of time ends the run
+        for line in p.stdout.splitlines():
+            if line.startswith("@tile "):
+                _, t, key, *xs = line.split()
+                got[(int(t), key)] = [float(x) for x in xs]
+    with open(a.out, "a") as f:
+        for (tile, key), t in sorted(got.items()):
+            if tile != 16:
+                what = "graph step" if key == "graph" else f"GRUs alone at {key[3:]} sequences"
+                s = f"tile {tile:2d} against tile 16, {what}: {verdict(got[(16, key)], t, 'tile 16')}"
+                print(s)
+                f.write(s + "\n")
+    return 0
+
+
 def step_update(a, say):
     import torch
     from hhmarl_2d_amd import learner as LR
@@ -270,8 +461,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_learner.log"))
     ap.add_argument("--inputs", action="store_true", help="only the inputs=\"fused\" against inputs=\"torch\" minibatch step; appended to --out")
     ap.add_argument("--trunk", action="store_true", help="only the trunk=\"fused\" against trunk=\"torch\" section; appended to --out")
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--graph", action="store_true", help="only the step=\"graph\" against the eager step section; appended to --out")
+    ap.add_argument("--tile", action="store_true", help="only the GRU tile instances, each through HH_GRU_TILE in a child; appended to --out")
+    ap.add_argument("--tile-seqs", default="13,26,52,104,208,416,854", help="the sequence counts of --tile's GRUs-alone timing")
+    ap.add_argument("--launches", choices=["eager", "graph"], help="with --step graph: only --launch-count steps of this form (for a kernel trace)")
+    ap.add_argument("--launch-count", type=int, default=20)
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
+    a.tile_seqs = [int(x) for x in a.tile_seqs.split(",")]
     if a.step:
         sys.path.insert(0, ROOT)
         import torch
@@ -283,9 +480,15 @@ def main():
                     f.write(s + "\n")
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
-        {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk}[a.step](a, say)
+        {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk, "graph": step_graph,
+         "tile": step_tile}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
+    if a.graph:
+        sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step graph {' '.join(fwd)}", shell=True))
+    if a.tile:
+        fwd.append("--tile-seqs " + ",".join(str(s) for s in a.tile_seqs))
+        sys.exit(run_tiles(a, fwd))
     if a.inputs:
         sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step inputs {' '.join(fwd)}", shell=True))
     if a.trunk:
