@@ -1218,6 +1218,7 @@ API int hho_set_state(void *h, const hh_state_view *v) {
         int ag, op;
         count_alive(w, a, &ag, &op);
         a->done = ag <= 0 || op <= 0 || a->steps >= w->cfg.horizon;
+        a->ep_ret = 0.0; /* an injected state starts the episode's return afresh, as hh_set_state does on the device */
         if (w->cfg.env_kind == HH_ENV_HIGHLEVEL) hl_state(w, a); else ll_state(w, a);
     }
     return HH_OK;
