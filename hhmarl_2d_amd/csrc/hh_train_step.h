@@ -98,8 +98,10 @@ __global__ __launch_bounds__(HTS_THREADS) void hh_k_adam_step(const hts_adam_arg
     }
 }
 
-extern "C" int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, double lr, double beta1, double beta2, double eps,
-                            void *stream) {
+/* the host side of an Adam step: the arguments checked, then the list packed into launches of at most HH_ADAM_MAX_TENSORS descriptors;
+ * launch(blocks, args) enqueues one of them (hh_k_adam_step here, hh_k_adam_step_clipped in hh_grad_clip.h) */
+template <typename Launch>
+static int hts_adam_run(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, double lr, double beta1, double beta2, double eps, Launch launch) {
     if (n_tensors < 0 || !step || (n_tensors > 0 && !t)) { g_err = "hh_adam_step: null argument or negative count"; return HH_E_ARG; }
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0)) {
         g_err = "hh_adam_step: need lr >= 0, 0 <= beta < 1, eps >= 0"; return HH_E_ARG;
@@ -110,7 +112,6 @@ extern "C" int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const in
                             reinterpret_cast<uintptr_t>(t[i].v)) & 3)) { g_err = "hh_adam_step: every tensor must be 4-byte aligned"; return HH_E_ARG; }
         if (t[i].n > ((int64_t)1 << 40)) { g_err = "hh_adam_step: a tensor of more than 2^40 elements"; return HH_E_ARG; }
     }
-    hipStream_t st = (hipStream_t)stream;
     int32_t i = 0;
     while (i < n_tensors) {
         hts_adam_args a;
@@ -134,10 +135,17 @@ extern "C" int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const in
         }
         if (k == 0) continue;
         a.n_tensors = k; a.n_blocks = (int32_t)blocks;
-        hipLaunchKernelGGL(hh_k_adam_step, dim3((unsigned)blocks), dim3(HTS_THREADS), 0, st, a, step);
+        launch((unsigned)blocks, a);
         HIPCHK(hipGetLastError());
     }
     return HH_OK;
+}
+
+extern "C" int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, double lr, double beta1, double beta2, double eps,
+                            void *stream) {
+    return hts_adam_run(n_tensors, t, step, lr, beta1, beta2, eps, [=](unsigned blocks, const hts_adam_args &a) {
+        hipLaunchKernelGGL(hh_k_adam_step, dim3(blocks), dim3(HTS_THREADS), 0, (hipStream_t)stream, a, step);
+    });
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ the stage */

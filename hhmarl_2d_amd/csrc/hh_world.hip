@@ -908,3 +908,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- the learner's minibatch step as a replayable chain: staging by a device schedule, Adam on the device, the commit (C ABI in include/hh_learner.h) ---- */
 #include "hh_train_step.h"
+
+/* ---- gradient clipping by global norm inside that chain: the norm of a module's gradients, the Adam step scaled from device memory (C ABI in include/hh_learner.h) ---- */
+#include "hh_grad_clip.h"

@@ -29,6 +29,7 @@ The commander half (train_hier.py with models/ac_models_hier.py:CommanderGru) is
 `ppo_loss_categorical` (hh_ppo_loss_categorical), `CommanderTrainable` and `CommanderLearner`, which does for
 `commander.CommanderRollout(batch_mode="complete_episodes")` what `PPOLearner` does for `PPORollout`."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -698,34 +699,118 @@ def _step_mode(step, optimizer):
     return step
 
 
-def adam_step(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+def _grad_clip(grad_clip):
+    """RLlib's grad_clip: None (no clipping) or a finite float > 0, the largest global L2 norm of one optimizer's gradients"""
+    if grad_clip is None:
+        return None
+    if isinstance(grad_clip, bool) or not isinstance(grad_clip, (int, float)) or not (math.isfinite(grad_clip) and grad_clip > 0):
+        raise ValueError(f"grad_clip is None or a finite float > 0, got {grad_clip!r}")
+    return float(grad_clip)
+
+
+def _adam_desc(who, params, grads, ms, vs, dev):
+    desc = (L.HHAdamTensor * max(len(params), 1))()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, ms, vs)):
+        for what, x in (("a parameter", p), ("a gradient", g), ("a first moment", m), ("a second moment", v)):
+            if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == p.shape and x.device == dev):
+                raise ValueError(f"{who}: {what} is a contiguous float32 CUDA tensor of its parameter's shape on t's device (the torch-op form "
+                                 f"is {who}_torch)")
+        desc[i].p, desc[i].g, desc[i].m, desc[i].v, desc[i].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return desc
+
+
+def _is_clip(clip, dev):
+    return (isinstance(clip, torch.Tensor) and clip.is_cuda and clip.dtype == torch.float64 and clip.is_contiguous()
+            and clip.numel() == L.CLIP_OUT and clip.device == dev)
+
+
+def grad_norm_scratch(grads):
+    """the scratch of grad_norm for these gradients (or tensors of their shapes): float64 [tiles], one slot per tensor and 4096 elements"""
+    tiles = sum((g.numel() + 4095) // 4096 for g in grads)
+    return torch.empty((max(tiles, 1),), dtype=torch.float64, device=grads[0].device if len(grads) else "cuda")
+
+
+def grad_norm(grads, max_norm, clip=None, cursor=None, table=None, scratch=None):
+    """The global L2 norm of a list of gradients and torch.nn.utils.clip_grad_norm_'s coefficient for it, on the device (hh_grad_norm,
+    include/hh_learner.h): grads is a list of contiguous float32 CUDA tensors, max_norm a finite float > 0
+    -> clip f64 [2] = (norm, min(1, max_norm / (norm + 1e-6))), the tensor given or a new one.  With cursor (int32 [1]) and table (f64 [n])
+    the norm also goes to table[cursor] (skipped outside the table; the cursor is only read).  scratch: grad_norm_scratch's (allocated
+    when not given).  Float64 sums in a fixed order: the same bytes on every run.  The gradients are not changed: adam_step(clip=...)
+    scales them as it reads them.  ceil(n / 64) + 1 launches, no host synchronisation, HIP-graph capturable; a missing library or GPU
+    is an error."""
+    _need_gpu("grad_norm")
+    grads = list(grads)
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not (math.isfinite(max_norm) and max_norm > 0):
+        raise ValueError(f"grad_norm: max_norm is a finite float > 0, got {max_norm!r}")
+    dev = clip.device if clip is not None else (grads[0].device if grads else torch.device("cuda", torch.cuda.current_device()))
+    if clip is None:
+        clip = torch.empty((L.CLIP_OUT,), dtype=torch.float64, device=dev)
+    if not _is_clip(clip, dev):
+        raise ValueError("grad_norm: clip is a contiguous float64 [2] CUDA tensor")
+    if (cursor is None) != (table is None):
+        raise ValueError("grad_norm: cursor and table come together")
+    if cursor is not None and not (cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1 and cursor.device == dev and table.is_cuda
+                                   and table.dtype == torch.float64 and table.dim() == 1 and table.is_contiguous() and table.device == dev):
+        raise ValueError("grad_norm: cursor is an int32 [1] and table a contiguous float64 [n] CUDA tensor on clip's device")
+    desc = (L.HHAdamTensor * max(len(grads), 1))()
+    for i, g in enumerate(grads):
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == dev):
+            raise ValueError("grad_norm: a gradient is a contiguous float32 CUDA tensor on one device (the torch-op form is grad_norm_torch)")
+        desc[i].g, desc[i].n = g.data_ptr(), g.numel()
+    nbytes = C.c_int64()
+    L.check(L.lib().hh_grad_norm_scratch_bytes(len(grads), desc, C.byref(nbytes)))
+    if scratch is None:
+        scratch = torch.empty((max(nbytes.value // 8, 1),), dtype=torch.float64, device=dev)
+    if not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.device == dev and scratch.numel() * 8 >= nbytes.value):
+        raise ValueError(f"grad_norm: scratch is a contiguous float64 CUDA tensor of at least {nbytes.value // 8} elements (grad_norm_scratch)")
+    L.check(L.lib().hh_grad_norm(len(grads), desc, float(max_norm), _p(clip), None if cursor is None else _p(cursor), None if table is None else _p(table),
+                                 0 if table is None else table.shape[0], _p(scratch), scratch.numel() * 8, _stream(dev)))
+    return clip
+
+
+def grad_norm_torch(grads, max_norm):
+    """grad_norm with torch ops, any dtype and device (the A/B partner): float64 throughout -> (norm, coef), two 0-d float64 tensors"""
+    grads = list(grads)
+    dev = grads[0].device if grads else "cpu"
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    for g in grads:
+        total = total + g.detach().double().square().sum()
+    norm = total.sqrt()
+    return norm, torch.clamp(float(max_norm) / (norm + 1e-6), max=1.0)
+
+
+def adam_step(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS, clip=None):
     """One step of torch.optim.Adam (amsgrad = False, weight_decay = 0) on a list of tensors, on the device (hh_adam_step, include/hh_learner.h):
     params, grads, ms, vs are lists of contiguous float32 CUDA tensors, shape by shape the same; t is an int32 [1] CUDA tensor holding the
     number of steps taken so far (the step uses t + 1; train_commit advances it).  In place on params, ms and vs.  ceil(n / 64) launches,
-    no host synchronisation, HIP-graph capturable; a missing library or GPU is an error."""
+    no host synchronisation, HIP-graph capturable; a missing library or GPU is an error.
+    clip: grad_norm's float64 [2] CUDA tensor; with it every gradient is read as float32(float64(g) * clip[1]) (hh_adam_step_clipped) — the
+    step of clip_grad_norm_ followed by Adam, except that the gradient tensors keep their unscaled values."""
     _need_gpu("adam_step")
     n = len(params)
     if not (len(grads) == len(ms) == len(vs) == n):
         raise ValueError("adam_step: params, grads, ms and vs are lists of one length")
     if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
         raise ValueError("adam_step: t is an int32 [1] CUDA tensor (the torch-op form is adam_step_torch)")
-    desc = (L.HHAdamTensor * max(n, 1))()
-    for i, (p, g, m, v) in enumerate(zip(params, grads, ms, vs)):
-        for what, x in (("a parameter", p), ("a gradient", g), ("a first moment", m), ("a second moment", v)):
-            if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == p.shape and x.device == t.device):
-                raise ValueError(f"adam_step: {what} is a contiguous float32 CUDA tensor of its parameter's shape on t's device (the torch-op form "
-                                 "is adam_step_torch)")
-        desc[i].p, desc[i].g, desc[i].m, desc[i].v, desc[i].n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-    L.check(L.lib().hh_adam_step(n, desc, _p(t), float(lr), float(betas[0]), float(betas[1]), float(eps), _stream(t.device)))
+    desc = _adam_desc("adam_step", params, grads, ms, vs, t.device)
+    if clip is None:
+        L.check(L.lib().hh_adam_step(n, desc, _p(t), float(lr), float(betas[0]), float(betas[1]), float(eps), _stream(t.device)))
+        return
+    if not _is_clip(clip, t.device):
+        raise ValueError("adam_step: clip is grad_norm's contiguous float64 [2] CUDA tensor on t's device")
+    L.check(L.lib().hh_adam_step_clipped(n, desc, _p(t), _p(clip), float(lr), float(betas[0]), float(betas[1]), float(eps), _stream(t.device)))
 
 
-def adam_step_torch(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+def adam_step_torch(params, grads, ms, vs, t, *, lr, betas=ADAM_BETAS, eps=ADAM_EPS, clip=None):
     """adam_step with torch ops, any dtype and device (the A/B partner): t is the number of steps taken so far, a Python int or a
-    one-element tensor (read on the host); in place on params, ms and vs"""
+    one-element tensor (read on the host); in place on params, ms and vs.  clip: (norm, coef) as grad_norm_torch returns them or a
+    two-element tensor; every gradient is read as (float64(g) * coef) rounded to its own dtype, and left as it is"""
     step = int(t) + 1
     b1, b2 = betas
     bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
     with torch.no_grad():
+        if clip is not None:
+            grads = [(g.double() * clip[1]).to(g.dtype) for g in grads]
         for p, g, m, v in zip(params, grads, ms, vs):
             m.mul_(b1).add_(g, alpha=1.0 - b1)
             v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
@@ -804,11 +889,20 @@ def train_commit(stats, table, cursor, t):
 
 class DeviceAdam:
     """torch.optim.Adam(params, lr) with its state on the device: m and v per parameter and the step count t (int32 [1]), stepped by
-    adam_step (hh_adam_step).  t is advanced by train_commit, not by step()."""
+    adam_step (hh_adam_step).  t is advanced by train_commit, not by step().
+    max_norm: clip the gradients by their global L2 norm over all of params (torch.nn.utils.clip_grad_norm_(params, max_norm)) inside
+    step(): grad_norm (hh_grad_norm) into `clip` f64 [2] = (the norm before clipping, the coefficient), then the clipped adam_step
+    (hh_adam_step_clipped).  Unlike torch's in-place scaling, .grad KEEPS THE UNSCALED GRADIENT: the step scales what it reads.
+    record(cursor, table) makes every step also write its norm to table[cursor] (the learners' per-step record)."""
 
-    def __init__(self, params, lr, betas=ADAM_BETAS, eps=ADAM_EPS):
+    def __init__(self, params, lr, betas=ADAM_BETAS, eps=ADAM_EPS, max_norm=None):
         self.params = list(params)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_norm = _grad_clip(max_norm)
+        self.cursor = self.table = self.clip = self.scratch = None
+        if self.max_norm is not None:
+            self.clip = torch.zeros((L.CLIP_OUT,), dtype=torch.float64, device=self.params[0].device)
+            self.scratch = grad_norm_scratch(self.params)       # room for every parameter: a step over fewer needs fewer slots
         self.m = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.v = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.t = torch.zeros((1,), dtype=torch.int32, device=self.params[0].device)
@@ -817,19 +911,28 @@ class DeviceAdam:
         for p in self.params:
             p.grad = None
 
+    def record(self, cursor, table):
+        """from now on step() writes the norm before clipping to table[cursor] as well (int32 [1], f64 [n]; None, None: no record)"""
+        self.cursor, self.table = cursor, table
+
     def step(self):
-        """one Adam step of every parameter that has a gradient (as torch.optim.Adam skips the others), from the current .grad pointers"""
+        """one Adam step of every parameter that has a gradient (as torch.optim.Adam skips the others), from the current .grad pointers;
+        with max_norm the norm over those gradients first, then the clipped step"""
         live = [i for i, p in enumerate(self.params) if p.grad is not None]
-        adam_step([self.params[i].data for i in live], [self.params[i].grad for i in live], [self.m[i] for i in live], [self.v[i] for i in live],
-                  self.t, lr=self.lr, betas=self.betas, eps=self.eps)
+        grads = [self.params[i].grad for i in live]
+        if self.max_norm is not None:
+            grad_norm(grads, self.max_norm, self.clip, self.cursor, self.table, self.scratch)
+        adam_step([self.params[i].data for i in live], grads, [self.m[i] for i in live], [self.v[i] for i in live],
+                  self.t, lr=self.lr, betas=self.betas, eps=self.eps, clip=self.clip)
 
 
 class _StepBook:
     """what one policy's replayable step keeps on the device: the cursor, the statistics table, and for step="graph" the persistent copy
     of the policy batch, the schedule, the staging buffers and the captured graph"""
 
-    def __init__(self, device):
+    def __init__(self, device, gnorm=False):
         self.device = device
+        self.gnorm = torch.zeros((0,), dtype=torch.float64, device=device) if gnorm else None      # grad_clip: the norm before clipping per step
         self.cursor = torch.zeros((1,), dtype=torch.int32, device=device)
         self.n_valid = torch.zeros((1,), dtype=torch.int32, device=device)
         self.table = torch.zeros((0, len(L.PPO_STATS)), dtype=torch.float64, device=device)
@@ -844,9 +947,13 @@ class _StepBook:
             return t
         return torch.zeros((max(2 * n, 16),) + tuple(shape), dtype=dtype, device=device)
 
-    def begin(self, n_steps):
-        """room for n_steps rows of statistics, cursor = 0"""
+    def begin(self, n_steps, opt=None):
+        """room for n_steps rows of statistics, cursor = 0; with a gnorm table, room in it too (grown with `table`), and `opt` (the
+        DeviceAdam) is handed the cursor and that table"""
         self.table = self._grown(self.table, n_steps, (len(L.PPO_STATS),), torch.float64, self.device)
+        if self.gnorm is not None:
+            self.gnorm = self._grown(self.gnorm, self.table.shape[0], (), torch.float64, self.device)
+            opt.record(self.cursor, self.gnorm)
         self.cursor.zero_()
 
     def load(self, cols, schedule):
@@ -894,7 +1001,7 @@ class PPOLearner:
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
                  vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch",
-                 optimizer="torch", step="eager"):
+                 optimizer="torch", step="eager", grad_clip=None):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
         argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
@@ -903,9 +1010,17 @@ class PPOLearner:
         optimizer: "torch" (the default) steps with torch.optim.Adam; "fused" keeps each policy's m, v and step count on the device
         (DeviceAdam: hh_adam_step) and gathers the steps' statistics in a device table (hh_train_commit).
         step: "eager" (the default) issues every minibatch step's launches from Python; "graph" (needs optimizer="fused") captures
-        stage -> forward -> loss -> backward -> Adam -> commit once per policy as ONE HIP graph and replays it per step (graph_prepare)."""
+        stage -> forward -> loss -> backward -> Adam -> commit once per policy as ONE HIP graph and replays it per step (graph_prepare).
+        grad_clip: RLlib's grad_clip.  None (the default, and the reference's value): nothing is clipped and nothing changes.  A finite float
+        > 0: in every minibatch step the gradients of ONE optimizer — one policy's parameter list, the tied shared layer in it, as RLlib's
+        apply_grad_clipping takes one optimizer's param groups — are scaled so that their global L2 norm does not exceed it, and every dict
+        of update() also has grad_gnorm, the mean over the update's steps of the norm BEFORE clipping (RLlib reports it under the same
+        condition).  optimizer="torch" calls torch.nn.utils.clip_grad_norm_ (float32 norm, scales .grad in place); "fused" computes the
+        norm in float64 on the device and scales inside the Adam step (DeviceAdam(max_norm=...): .grad keeps the unscaled gradient), and
+        the graph's chain becomes stage -> forward -> loss -> backward -> norm -> clipped Adam -> commit."""
         self.optimizer = _optimizer_mode(optimizer)
         self.step = _step_mode(step, optimizer)
+        self.grad_clip = _grad_clip(grad_clip)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -917,8 +1032,12 @@ class PPOLearner:
         for m in self.modules:
             m.to(self.device)
         tie(self.modules)
-        self.optimizers = [(DeviceAdam if self.optimizer == "fused" else torch.optim.Adam)(m.parameters(), lr=lr) for m in self.modules]
-        self._books = [_StepBook(self.device) for _ in self.modules] if self.optimizer == "fused" else None
+        if self.optimizer == "fused":
+            self.optimizers = [DeviceAdam(m.parameters(), lr=lr, max_norm=self.grad_clip) for m in self.modules]
+        else:
+            self.optimizers = [torch.optim.Adam(m.parameters(), lr=lr) for m in self.modules]
+        self._books = [_StepBook(self.device, gnorm=self.grad_clip is not None) for _ in self.modules] if self.optimizer == "fused" else None
+        self._gnorms = [[], []]                 # optimizer="torch" with grad_clip: clip_grad_norm_'s norms of the running update, per policy
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
         self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
         self.use_kl = kl_coeff > 0.0            # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
@@ -1001,6 +1120,8 @@ class PPOLearner:
         total, stats = self.loss(agent, logits, vf, mb)
         opt.zero_grad(set_to_none=True)
         total.backward()
+        if self.grad_clip is not None and self.optimizer == "torch":      # "fused": inside opt.step()
+            self._gnorms[agent].append(torch.nn.utils.clip_grad_norm_(self.modules[agent].parameters(), self.grad_clip))
         opt.step()
         if self.optimizer == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
             book = self._books[agent]
@@ -1013,7 +1134,7 @@ class PPOLearner:
         minibatch_order per pass) and the batch's columns uploaded into persistent device buffers, the cursor set to 0, and the graph of ONE
         minibatch step captured — stage, forward, loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only —
         unless the graph of an earlier call still fits: it is kept while cap, kl_coeff (which travels by value in hh_ppo_loss_params) and the
-        buffers' addresses are what they were.  cap: the staging capacity in chunks (escape: rows); default and minimum: the largest
+        buffers' addresses are what they were (with grad_clip also its value, which travels by value, and the norm table's address).  cap: the staging capacity in chunks (escape: rows); default and minimum: the largest
         minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)"""
         if self.step != "graph":
             raise ValueError('graph_prepare needs PPOLearner(step="graph")')
@@ -1033,7 +1154,7 @@ class PPOLearner:
         cap = need if cap is None else int(cap)
         if cap < need:
             raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} chunks)")
-        book.begin(len(sched))
+        book.begin(len(sched), self.optimizers[agent])
         book.load(cols, sched)
         book.n_steps, book.cap = len(sched), cap
         src_chunks = min(t.shape[0] for t in book.src.values())
@@ -1041,6 +1162,8 @@ class PPOLearner:
         kl = self.kl_coeff[agent] if self.use_kl else 0.0
         key = (cap, kl, names, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(), book.table.shape[0]) + tuple(
             book.src[k].data_ptr() for k in names)
+        if self.grad_clip is not None:
+            key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
         if book.graph is None or book.key != key:
             self._capture(agent, book, names, src_chunks)
             book.key = key
@@ -1093,16 +1216,25 @@ class PPOLearner:
         """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
         return self._books[agent].table[:int(n)]
 
+    def grad_gnorm(self, agent, n):
+        """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
+        if n == 0:
+            return float("nan")
+        if self.optimizer == "fused":
+            return float(self._books[agent].gnorm[:int(n)].mean())
+        return float(torch.stack(self._gnorms[agent][:int(n)]).double().mean())
+
     # ---- one update
     def update(self, episodes, bank=None):
         """one PPO update of both policies from episodes (an EpisodeBatch after a collect) -> per policy a dict: total_loss, policy_loss,
         vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows.
-        `bank` is read only when the batch has no `logits` column (batch_old_logits)."""
+        `bank` is read only when the batch has no `logits` column (batch_old_logits).  With grad_clip also grad_gnorm."""
         rows = episodes.rows()
         out = []
+        clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
         if rows["obs"].shape[0] == 0:
             return [dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
-                         kl_coeff=self.kl_coeff[a], steps=0, rows=0) for a in range(2)]
+                         kl_coeff=self.kl_coeff[a], steps=0, rows=0, **clipped) for a in range(2)]
         with torch.no_grad():
             old = self.batch_old_logits(rows, bank, episodes.N)
             batches = [self.policy_batch(rows, old, a) for a in range(2)]
@@ -1113,8 +1245,10 @@ class PPOLearner:
                 m = self.graph_stats(agent, n_steps).mean(dim=0).tolist()
                 if self.use_kl:
                     self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
+                if self.grad_clip is not None:
+                    clipped = dict(grad_gnorm=self.grad_gnorm(agent, n_steps))
                 out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
-                                steps=n_steps, rows=n_rows))
+                                steps=n_steps, rows=n_rows, **clipped))
                 continue
             if self.recurrent:
                 seq_len = b["seq_len"].cpu().numpy()
@@ -1126,7 +1260,8 @@ class PPOLearner:
             cols = [k for k in b if k != "seq_len"]
             all_stats = []
             if self.optimizer == "fused":
-                self._books[agent].begin(self.num_sgd_iter * len(parts))
+                self._books[agent].begin(self.num_sgd_iter * len(parts), self.optimizers[agent])
+            self._gnorms[agent] = []
             for sgd_pass in range(self.num_sgd_iter):
                 for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
                     s0, s1 = parts[i]
@@ -1136,8 +1271,10 @@ class PPOLearner:
             m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
             if self.use_kl and all_stats:
                 self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
+            if self.grad_clip is not None:
+                clipped = dict(grad_gnorm=self.grad_gnorm(agent, len(all_stats)))
             out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
-                            steps=len(all_stats), rows=int(seq_len.sum())))
+                            steps=len(all_stats), rows=int(seq_len.sum()), **clipped))
         self.updates += 1
         return out
 
@@ -1495,23 +1632,30 @@ class CommanderLearner:
 
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
                  entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch",
-                 optimizer="torch", step="eager"):
+                 optimizer="torch", step="eager", grad_clip=None):
         """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys().  inputs: CommanderTrainable's argument
         ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*); trunk: its argument too ("fused": shared_layer through hh_dense_tanh_*).
         optimizer, step: PPOLearner's arguments, with its values, defaults and validation.  optimizer="fused" makes `self.optimizer` a
         DeviceAdam (m, v and the step count on the device: hh_adam_step) and gathers the steps' statistics in a device table
         (hh_train_commit); step="graph" (needs optimizer="fused") captures stage -> stage -> forward -> loss -> backward -> Adam -> commit
-        once as ONE HIP graph and replays it per minibatch step (graph_prepare).  The modes are kept in `optimizer_mode` and `step`."""
+        once as ONE HIP graph and replays it per minibatch step (graph_prepare).  The modes are kept in `optimizer_mode` and `step`.
+        grad_clip: PPOLearner's argument (None: nothing changes; else the global L2 norm of the module's gradients is clipped to it in every
+        step — norm -> clipped Adam in the fused modes and in the graph — and update() also returns grad_gnorm)."""
         self.optimizer_mode = _optimizer_mode(optimizer)
         self.step = _step_mode(step, optimizer)
+        self.grad_clip = _grad_clip(grad_clip)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.inputs, self.trunk = inputs, _trunk_mode(trunk)
         self.module = CommanderTrainable(inputs=inputs, trunk=trunk).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
-        self.optimizer = (DeviceAdam if self.optimizer_mode == "fused" else torch.optim.Adam)(self.module.parameters(), lr=lr)
-        self._book = _StepBook(self.device) if self.optimizer_mode == "fused" else None
+        if self.optimizer_mode == "fused":
+            self.optimizer = DeviceAdam(self.module.parameters(), lr=lr, max_norm=self.grad_clip)
+        else:
+            self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
+        self._book = _StepBook(self.device, gnorm=self.grad_clip is not None) if self.optimizer_mode == "fused" else None
+        self._gnorms = []                       # optimizer="torch" with grad_clip: clip_grad_norm_'s norms of the running update
         self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
         self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
         self.use_kl = kl_coeff > 0.0
@@ -1578,6 +1722,8 @@ class CommanderLearner:
         total, stats = self.loss(logits, vf, mb)
         self.optimizer.zero_grad(set_to_none=True)
         total.backward()
+        if self.grad_clip is not None and self.optimizer_mode == "torch":      # "fused": inside optimizer.step()
+            self._gnorms.append(torch.nn.utils.clip_grad_norm_(self.module.parameters(), self.grad_clip))
         self.optimizer.step()
         if self.optimizer_mode == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
             train_commit(stats, self._book.table, self._book.cursor, self.optimizer.t)
@@ -1589,7 +1735,8 @@ class CommanderLearner:
         columns — COMMANDER_STAGE_COLS: eight per step, then state_in and seq_len per sequence — uploaded into persistent device buffers,
         the cursor set to 0, and the graph of ONE minibatch step captured — stage (per-step columns), stage (per-sequence columns), forward,
         loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only — unless the graph of an earlier call still
-        fits: it is kept while cap, kl_coeff (by value in hh_ppo_loss_params), the columns and the buffers' addresses are what they were.
+        fits: it is kept while cap, kl_coeff (by value in hh_ppo_loss_params), the columns and the buffers' addresses are what they were
+        (with grad_clip also its value, which travels by value, and the norm table's address).
         cap: the staging capacity in sequences; default and minimum: the largest minibatch.  The sequences of the staging buffers beyond a
         minibatch's are zero in every column: sequences of length 0 (hh_gru_seq_*'s contract) whose rows the mask drops.  Weights, m, v, t
         are left bit for bit as they were.  -> (n_steps, rows)"""
@@ -1607,13 +1754,15 @@ class CommanderLearner:
         cap = need if cap is None else int(cap)
         if cap < need:
             raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} sequences)")
-        book.begin(len(sched))
+        book.begin(len(sched), self.optimizer)
         book.load(cols, sched)
         book.n_steps, book.cap = len(sched), cap
         src_chunks = min(t.shape[0] for t in book.src.values())
         kl = self.kl_coeff if self.use_kl else 0.0
         key = (cap, kl, COMMANDER_STAGE_COLS, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(),
                book.table.shape[0]) + tuple(book.src[k].data_ptr() for k in COMMANDER_STAGE_COLS)
+        if self.grad_clip is not None:
+            key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
         if book.graph is None or book.key != key:
             self._capture(book, src_chunks)
             book.key = key
@@ -1669,19 +1818,29 @@ class CommanderLearner:
         """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
         return self._book.table[:int(n)]
 
+    def grad_gnorm(self, n):
+        """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
+        if n == 0:
+            return float("nan")
+        if self.optimizer_mode == "fused":
+            return float(self._book.gnorm[:int(n)].mean())
+        return float(torch.stack(self._gnorms[:int(n)]).double().mean())
+
     # ---- one update
     def update(self, episodes, net=None):
         """one PPO update of commander_policy from episodes (a CommanderEpisodeBatch after a collect) -> dict: total_loss, policy_loss,
         vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows (unpadded,
         all three agents).  `net` (the sampler's CommanderNet) is not read: the old logits are the batch's own `logits` column or, without
-        one, come from the module, which holds the weights the sampler was given at the last publish (batch_old_logits)."""
+        one, come from the module, which holds the weights the sampler was given at the last publish (batch_old_logits).  With grad_clip
+        also grad_gnorm."""
         seqs = episodes.sequences()
+        clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
         if seqs["obs"].shape[1] != self.max_seq_len:
             raise ValueError(f"CommanderLearner(max_seq_len={self.max_seq_len}) was given sequences of {seqs['obs'].shape[1]} steps: the rollout "
                              "cuts them, so both take the same max_seq_len")
         if seqs["obs"].shape[0] == 0:
             return dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
-                        kl_coeff=self.kl_coeff, steps=0, rows=0)
+                        kl_coeff=self.kl_coeff, steps=0, rows=0, **clipped)
         with torch.no_grad():
             b = self.policy_batch(seqs)
             b["old_logits"] = self.batch_old_logits(seqs, b)
@@ -1692,14 +1851,18 @@ class CommanderLearner:
             if self.use_kl:
                 self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
             self.updates += 1
-            return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=n_steps, rows=n_rows)
+            if self.grad_clip is not None:
+                clipped = dict(grad_gnorm=self.grad_gnorm(n_steps))
+            return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=n_steps, rows=n_rows,
+                        **clipped)
         seq_len = b["seq_len"].cpu().numpy()
         parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
         csum = np.concatenate([[0], np.cumsum(seq_len)])
         n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
         all_stats = []
         if self.optimizer_mode == "fused":
-            self._book.begin(self.num_sgd_iter * len(parts))
+            self._book.begin(self.num_sgd_iter * len(parts), self.optimizer)
+        self._gnorms = []
         for sgd_pass in range(self.num_sgd_iter):
             for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
                 s0, s1 = parts[i]
@@ -1710,8 +1873,10 @@ class CommanderLearner:
         if self.use_kl and all_stats:
             self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
         self.updates += 1
+        if self.grad_clip is not None:
+            clipped = dict(grad_gnorm=self.grad_gnorm(len(all_stats)))
         return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=len(all_stats),
-                    rows=int(seq_len.sum()))
+                    rows=int(seq_len.sum()), **clipped)
 
     def publish(self, net):
         """the new weights into the sampler's CommanderNet on the current stream (refresh_weights): captured collects replay with them"""

@@ -261,6 +261,35 @@ typedef struct hh_adam_tensor {  /* field order is ABI; host struct of device po
  * (the same arithmetic).  ceil(n_tensors / HH_ADAM_MAX_TENSORS) launches, the descriptors by value.  Tensors may not overlap. */
 int hh_adam_step(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, double lr, double beta1, double beta2, double eps, void *stream);
 
+/* Gradient clipping by global norm (RLlib's grad_clip, torch.nn.utils.clip_grad_norm_ with norm_type 2) as two more links of the chain:
+ * stage -> forward -> loss -> backward -> norm -> clipped Adam -> commit.
+ *
+ * The norm, over EVERY element of EVERY tensor of t[n_tensors] (only g and n are read; p, m, v may be NULL), in float64:
+ *     norm = sqrt(sum (double)g * (double)g);   coef = min(1.0, max_norm / (norm + 1e-6))
+ *     clip[0] = norm;  clip[1] = coef;  and, where cursor and table are given, table[cursor[0]] = norm
+ * ([dev] clip f64 [HH_CLIP_OUT], cursor i32 [1], table f64 [table_rows]; the row is skipped when cursor[0] is outside [0, table_rows); the
+ * cursor is only read).  No atomics and a fixed order of additions: one float64 partial per tensor and HTS_ADAM_TILE (4096) elements, in list
+ * order, goes into scratch ([dev], 8-byte aligned, at least the bytes the _scratch_bytes query returns = 8 x tiles) — per workgroup thread
+ * k sums elements 4k .. 4k+3 of each 1024-element row of its tile in ascending order, a 64-lane shuffle tree folds each wave, the waves are
+ * added in order through LDS — and ONE final launch of one workgroup adds the slots the same way (thread k: slots k, k + 256, ..).  The
+ * same inputs give the same bytes on every run, whatever g's alignment (float4 loads where g is 16-byte aligned, four float loads
+ * otherwise: the same elements in the same order).  The squares are exact in float64, so the norm is within n x 2^-53 (relative) of the
+ * exact one for n elements, for gradients whose float32 squares would overflow or vanish as well.  Launches: one per HH_ADAM_MAX_TENSORS
+ * non-empty tensors, then the final one — which is also enqueued for an empty list or all n == 0: clip = (0.0, 1.0) for max_norm >= 1e-6.
+ * Non-finite gradients give what IEEE arithmetic gives (a NaN norm gives a NaN coefficient), as clip_grad_norm_(error_if_nonfinite=False).
+ * HH_E_ARG, with nothing enqueued: a null clip, a negative count, max_norm not finite or not > 0, exactly one of cursor / table,
+ * table_rows < 0, a scratch that is too small, a tensor that hh_adam_step would refuse for its g or n. */
+#define HH_CLIP_OUT 2   /* clip f64 [2]: the norm before clipping, the coefficient */
+int hh_grad_norm_scratch_bytes(int32_t n_tensors, const hh_adam_tensor *t, int64_t *bytes);
+int hh_grad_norm(int32_t n_tensors, const hh_adam_tensor *t, double max_norm, double *clip, const int32_t *cursor,
+                 double *table, int32_t table_rows, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* hh_adam_step with every gradient read as g' = (float)((double)g * clip[1]) ([dev] clip f64 [HH_CLIP_OUT], hh_grad_norm's): the product is
+ * rounded to float32 once, then the step is hh_adam_step's, so clip[1] == 1.0 writes exactly its bytes.  The gradients are not written
+ * back (g keeps the unscaled values); the same 28 bytes per element move.  Arguments, launches and refusals as hh_adam_step, and a null clip. */
+int hh_adam_step_clipped(int32_t n_tensors, const hh_adam_tensor *t, const int32_t *step, const double *clip,
+                         double lr, double beta1, double beta2, double eps, void *stream);
+
 typedef struct hh_stage_col {    /* field order is ABI; host struct of device pointers */
     const void *src;             /* the policy batch's column: [src_chunks] chunks of chunk_bytes bytes */
     void *dst;                   /* its staging buffer: [cap] chunks */

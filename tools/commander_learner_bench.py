@@ -362,6 +362,63 @@ def step_graph(a, say):
     say(f"    mean statistics, graph: { {k: round(v, 6) for k, v in st_g.items()} }")
 
 
+def step_clip(a, say):
+    """CommanderLearner(grad_clip=...) against grad_clip = None (the step as it was), both in this run: hh_grad_norm on the module's
+    tensors, then the graph step at 256 and 16384 rows, one replay per timing and 50 back to back.  Reported as a cost."""
+    import torch
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    med = statistics.median
+    FUSED = dict(inputs="fused")
+    ro, net, b, seq_len = _policy_batch(a, **FUSED)
+    say(f"# tools/commander_learner_bench.py --clip on {torch.cuda.get_device_name(0)}: CommanderLearner(grad_clip=...) against grad_clip = None, both in "
+        f"this run; inputs = fused, graph step; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+
+    def cost(t_base, t_new):
+        spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+        d = med(t_new) - med(t_base)
+        word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+        return f"without -> with: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+    module = LR.CommanderLearner.trainable_init(dev, seed=6, **FUSED).module
+    gs = [torch.randn_like(p) for p in module.parameters()]
+    n = sum(g.numel() for g in gs)
+    clip, scratch = torch.zeros((2,), dtype=torch.float64, device=dev), LR.grad_norm_scratch(gs)
+    t = events(lambda: LR.grad_norm(gs, 1.0, clip, scratch=scratch), a.iters, a.warmup)
+    say(f"    hh_grad_norm alone ({(len(gs) + 63) // 64} partial launch(es) + the final one), the module's {len(gs)} tensors ({n} elements, {scratch.numel()} "
+        f"tiles): {q(t)} = {4 * n / med(t) / 1e6:.1f} GB/s of {4 * n / 1e6:.2f} MB algorithmic bytes")
+    K = 50
+    for size in (256, 16384):
+        sub, _, n_seq, n_rows = _one_minibatch(b, seq_len, size)
+        n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+        probe, _ = _graph_learner(sub, 1, grad_clip=1e30, **FUSED)
+        probe.graph_replay(1)
+        n0 = float(probe._book.gnorm[0].item())
+        ts, bursts = {}, {}
+        for label, gc in (("without", None), ("with", n0 / 2.0)):
+            lr, _ = _graph_learner(sub, n_total, grad_clip=gc, **FUSED)
+            ts[label] = events(lambda: lr.graph_replay(1), a.iters, a.warmup)
+            out = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lr.graph_replay(K)
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / K)
+            bursts[label] = out
+            if gc is not None:
+                used = int(lr._book.cursor.item())
+                say(f"    grad_clip = N0 / 2 = {gc:.4e}: mean norm before clipping over {used} steps {float(lr._book.gnorm[:used].mean()):.4e}, last "
+                    f"coefficient {lr.optimizer.clip[1].item():.4f}")
+            del lr
+        say(f"graph step (2 stages + forward + loss + backward + [norm, 2 launches] + Adam + commit), {n_rows} unpadded rows in {n_seq} sequences: "
+            f"grad_clip = None {q(ts['without'])}; grad_clip set {q(ts['with'])}; {cost(ts['without'], ts['with'])}")
+        say(f"    {K} replays back to back, ms per step, three runs: grad_clip = None {', '.join(f'{x:.4f}' for x in bursts['without'])} | grad_clip set "
+            f"{', '.join(f'{x:.4f}' for x in bursts['with'])}")
+
+
 def tile_lengths(n_seq, L, seed, device):
     """n_seq ragged lengths drawn as `sequences` draws them (nine in ten full), the first one full"""
     import torch
@@ -462,11 +519,12 @@ def main():
     ap.add_argument("--inputs", action="store_true", help="only the inputs=\"fused\" against inputs=\"torch\" minibatch step; appended to --out")
     ap.add_argument("--trunk", action="store_true", help="only the trunk=\"fused\" against trunk=\"torch\" section; appended to --out")
     ap.add_argument("--graph", action="store_true", help="only the step=\"graph\" against the eager step section; appended to --out")
+    ap.add_argument("--clip", action="store_true", help="only the grad_clip against grad_clip = None section; appended to --out")
     ap.add_argument("--tile", action="store_true", help="only the GRU tile instances, each through HH_GRU_TILE in a child; appended to --out")
     ap.add_argument("--tile-seqs", default="13,26,52,104,208,416,854", help="the sequence counts of --tile's GRUs-alone timing")
     ap.add_argument("--launches", choices=["eager", "graph"], help="with --step graph: only --launch-count steps of this form (for a kernel trace)")
     ap.add_argument("--launch-count", type=int, default=20)
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     a.tile_seqs = [int(x) for x in a.tile_seqs.split(",")]
     if a.step:
@@ -481,11 +539,13 @@ def main():
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
         {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk, "graph": step_graph,
-         "tile": step_tile}[a.step](a, say)
+         "tile": step_tile, "clip": step_clip}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
     if a.graph:
         sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step graph {' '.join(fwd)}", shell=True))
+    if a.clip:
+        sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step clip {' '.join(fwd)}", shell=True))
     if a.tile:
         fwd.append("--tile-seqs " + ",".join(str(s) for s in a.tile_seqs))
         sys.exit(run_tiles(a, fwd))

@@ -39,6 +39,12 @@
           against graph.  The same rule for gain / loss.  --step-launches eager|graph (with --step-count K) only runs K steps of that
           kind at 256 rows, for a kernel count under rocprofv3 --kernel-trace --stats in a run of its own (two values of K: the
           difference is the steps' share)
+  clip    --clip runs this section alone and appends its lines to --out: gradient clipping by global norm (PPOLearner(grad_clip=...):
+          hh_grad_norm, hh_adam_step_clipped) as a COST next to the grad_clip = None path of the same run: (a) hh_grad_norm on a Fight1
+          module's tensors and on one 64 Mi-element tensor as bytes/s of the 4 B per element it reads, hh_adam_step_clipped against
+          hh_adam_step at 64 Mi elements (the same 28 B per element); (b) the Fight1 graph step with attention="fused", inputs="fused"
+          at 256 and 65536 rows with and without grad_clip (a threshold that binds), one replay per timing and 50 back to back.  A step
+          with grad_clip has two launches more: the norm's partials and its final.  The same rule for gain / loss
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -77,6 +83,7 @@ def main():
     ap.add_argument("--inputs", action="store_true", help="only the input-stage section; its lines are appended to --out")
     ap.add_argument("--trunk", action="store_true", help="only the shared-layer section; its lines are appended to --out")
     ap.add_argument("--step", action="store_true", help="only the graph-step section; its lines are appended to --out")
+    ap.add_argument("--clip", action="store_true", help="only the gradient-clipping section; its lines are appended to --out")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
     ap.add_argument("--step-count", type=int, default=16)
@@ -517,6 +524,93 @@ def main():
         lines.clear()
         step_section()
         if a.out and a.step:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def clip_section():
+        """grad_clip against grad_clip = None: the two kernels alone, the graph step"""
+        med = statistics.median
+
+        def verdict(t_base, t_new, base="without"):
+            spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+            d = med(t_new) - med(t_base)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+            return f"{base} -> with: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --clip on {torch.cuda.get_device_name(0)}: PPOLearner(grad_clip=...) against grad_clip = None (the step as it "
+            f"was), both in this run; attention = fused, inputs = fused, trunk = torch; {a.iters} timed iterations after {a.warmup} warm-up, device "
+            f"events (a later run, appended):")
+        FUSED = dict(attention="fused", inputs="fused", trunk="torch")
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
+        base = make()
+        # (a) the kernels alone
+        params = [p.detach().clone() for p in base.modules[0].parameters()]
+        for label, ps in ((f"a Fight1 module's {len(params)} tensors", params), ("one tensor of 64 Mi elements", [torch.zeros((1 << 26,), device=dev)])):
+            gs = [torch.randn_like(p) for p in ps]
+            n = sum(p.numel() for p in ps)
+            clip, scratch = torch.zeros((2,), dtype=torch.float64, device=dev), LR.grad_norm_scratch(gs)
+            t = events(lambda: LR.grad_norm(gs, 1.0, clip, scratch=scratch))
+            say(f"    hh_grad_norm alone ({(len(ps) + 63) // 64} partial launch(es) + the final one), {label} ({n} elements, {scratch.numel()} tiles): {q(t)} = "
+                f"{4 * n / med(t) / 1e6:.1f} GB/s of {4 * n / 1e6:.2f} MB algorithmic bytes ({100 * 4 * n / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 "
+                f"copy reaches)")
+        ps = [torch.zeros((1 << 26,), device=dev)]
+        ms, vs, t_dev = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps], torch.zeros((1,), dtype=torch.int32, device=dev)
+        n = ps[0].numel()
+        t_p = events(lambda: LR.adam_step(ps, gs, ms, vs, t_dev, lr=1e-4))
+        t_c = events(lambda: LR.adam_step(ps, gs, ms, vs, t_dev, lr=1e-4, clip=clip))
+        say(f"    hh_adam_step alone, 64 Mi elements: {q(t_p)} = {28 * n / med(t_p) / 1e6:.1f} GB/s; hh_adam_step_clipped (coefficient {clip[1].item():.3e}): "
+            f"{q(t_c)} = {28 * n / med(t_c) / 1e6:.1f} GB/s of the same {28 * n / 1e6:.0f} MB; {verdict(t_p, t_c, 'unclipped')}")
+        del ps, gs, ms, vs
+        # (b) the graph step
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        with torch.no_grad():
+            old = base.old_logits(rows["obs"], bank, ro.episodes.N)
+            b = base.policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        K = 50
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+            n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+            probe = make(optimizer="fused", step="graph", num_sgd_iter=1, sgd_minibatch_size=1 << 30, grad_clip=1e30)
+            probe.graph_prepare(0, sub)
+            probe.graph_replay(0, 1)
+            n0 = float(probe._books[0].gnorm[0].item())
+            ts, bursts = {}, {}
+            for label, gc in (("without", None), ("with", n0 / 2.0)):
+                lr = make(optimizer="fused", step="graph", num_sgd_iter=n_total, sgd_minibatch_size=1 << 30, grad_clip=gc)
+                lr.graph_prepare(0, sub)
+                ts[label] = events(lambda: lr.graph_replay(0, 1))
+                out = []
+                for _ in range(3):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    lr.graph_replay(0, K)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    out.append(e0.elapsed_time(e1) / K)
+                bursts[label] = out
+                if gc is not None:
+                    used = int(lr._books[0].cursor.item())
+                    say(f"    grad_clip = N0 / 2 = {gc:.4e}: mean norm before clipping over {used} steps {float(lr._books[0].gnorm[:used].mean()):.4e}, last "
+                        f"coefficient {lr.optimizers[0].clip[1].item():.4f}")
+                del lr
+            say(f"graph step (Fight1, stage + forward + loss + backward + [norm, 2 launches] + Adam + commit), {int(seq_len[s0:s1].sum())} unpadded rows in "
+                f"{s1 - s0} chunks of 20: grad_clip = None {q(ts['without'])}; grad_clip set {q(ts['with'])}; {verdict(ts['without'], ts['with'])}")
+            say(f"    {K} replays back to back, ms per step, three runs: grad_clip = None {', '.join(f'{x:.4f}' for x in bursts['without'])} | grad_clip set "
+                f"{', '.join(f'{x:.4f}' for x in bursts['with'])}")
+
+    if a.clip:
+        lines.clear()
+        clip_section()
+        if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
         return
