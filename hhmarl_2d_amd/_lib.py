@@ -105,6 +105,8 @@ class HHEpisodeMetricsBufs(C.Structure):
 
 
 EP_METRICS_MAX_AGENTS = 5  # HH_EP_METRICS_MAX_AGENTS
+# hh_episodes_emit_append's accumulator i32 [HH_EP_ACC], in slot order (slot 7 is reserved and stays 0)
+EP_ACC = ("rows", "episodes", "overflow", "sequences", "complete", "collects", "batches", "reserved")
 # slot names of hh_episodes_metrics's summary f64 [HH_EP_METRICS], in slot order (HH_EPM_*: the per-agent blocks hold 5 slots each)
 EP_METRICS = ("episodes", "rows", "episode_reward_mean", "episode_reward_min", "episode_reward_max",
               "episode_len_mean", "episode_len_min", "episode_len_max") + tuple(
@@ -120,10 +122,11 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux",
-           "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics"]
+           "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics", "hh_episodes_emit_append"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
-                     "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux"]  # include/hh_commander.h
+                     "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux",
+                     "hh_commander_episodes_emit_append"]  # include/hh_commander.h
 
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
                    "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
@@ -227,6 +230,7 @@ def lib():
         L.hh_gae_rllib.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
         L.hh_episodes_emit.argtypes = [C.POINTER(HHEpisodeBufs), vp]
         L.hh_episodes_emit_aux.argtypes = [C.POINTER(HHEpisodeBufs), C.POINTER(HHEpisodeAux), vp]
+        L.hh_episodes_emit_append.argtypes = [C.POINTER(HHEpisodeBufs), C.POINTER(HHEpisodeAux), C.c_int64, vp, vp, vp]
         L.hh_episodes_metrics_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.hh_episodes_metrics.argtypes = [C.POINTER(HHEpisodeMetricsBufs), vp]
         L.hh_math_eval.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
@@ -255,6 +259,7 @@ def lib():
         L.hh_commander_kernel_name.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32]
         L.hh_commander_episodes_emit.argtypes = [C.POINTER(HHCommanderEpisodeBufs), vp]
         L.hh_commander_episodes_emit_aux.argtypes = [C.POINTER(HHCommanderEpisodeBufs), C.POINTER(HHEpisodeAux), vp]
+        L.hh_commander_episodes_emit_append.argtypes = [C.POINTER(HHCommanderEpisodeBufs), C.POINTER(HHEpisodeAux), C.c_int64, vp, vp, vp]
         L.hh_commander_refresh_weights.argtypes = [vp, C.POINTER(HHCommanderWeights), vp]
         L.hh_commander_copy_packed.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
         L.hh_commander_act_chain.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]

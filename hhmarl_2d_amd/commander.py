@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from . import policy_nets as PN
-from .rollout import EpisodeBatch, central_critic_rows_hl
+from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
 
@@ -233,30 +233,64 @@ class CommanderEpisodeBatch(EpisodeBatch):
     aux = (name, f32 [T, N, 3, d]): EpisodeBatch's optional column (hh_commander_episodes_emit_aux) — `name` f32 [R, 3, d] in `rows()`
     and, zero padded like the other columns, [S, L, 3, d] in `sequences()`.  CommanderRollout(record_logits=True) puts the sampler's
     logits there (d = 4): 48 B per row on top of 450 (carry) / 487 (batch) — at N = 8192, T = 16, C = 47: 18 MB more carry, 25 MB more
-    batch."""
+    batch.
+
+    train_batch_size = B: EpisodeBatch's accumulation (hh_commander_episodes_emit_append) — the collects are appended on the device
+    until the batch holds at least B rows; ep_start, seq_start and seq_ep are positions in the accumulated batch, `sequences()` and
+    `n_sequences` describe it.  Capacities: R = B - 1 + N (C + T) rows, E = B - 1 + N T episodes and by default S = B - 1 +
+    N (T + C // L) sequences, all below 2^31.  That S is safe for one-row episodes (a sequence each), and a sequence costs 4812 B:
+    seq_cap = S overrides it (at least N (T + C // L); with fewer than the batch needs the sticky flag is set and `rows()` raises).
+    Bytes: 487 per row, 12 per episode, 4812 per sequence — B = 4 collects' worth of rows at N = 8192, T = 16 (B = 524288) is 255 MB
+    of rows, 6 MB of episode table and 2.52 GB of sequences more than without; seq_cap = B // 4 + N (T + C // L) (enough while a batch
+    averages four rows or more per sequence) brings the sequences to 0.63 GB."""
 
     SEQ_TABLE = ("seq_start", "seq_len", "seq_ep")
     _EMIT, _SCRATCH, _N_COUNTS = "hh_commander_episodes_emit", (10, 4), 4
     _critic_rows = staticmethod(central_critic_rows_hl)
     AGENT_KEYS = (1, 2, 3)   # metrics(): the three agents of the one commander policy, by agent id
 
-    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam, aux=None, metrics=False):
+    @classmethod
+    def capacities(cls, N, T, carry_cap, train_batch_size=None, max_seq_len=None, seq_cap=None):
+        """-> EpisodeBatch.capacities' (R, E), and with max_seq_len = L (R, E, S sequences): N (T + carry_cap // L), with
+        train_batch_size = B another B - 1, or seq_cap where given (an int of at least N (T + carry_cap // L), train_batch_size only);
+        ValueError for capacities that reach 2^31"""
+        R, E = super().capacities(N, T, carry_cap, train_batch_size)
+        if max_seq_len is None:
+            return R, E
+        floor = int(N) * (int(T) + int(carry_cap) // int(max_seq_len))
+        S = floor + (0 if train_batch_size is None else train_batch_size - 1)
+        if seq_cap is not None:
+            if train_batch_size is None:
+                raise ValueError("seq_cap: only with train_batch_size (without it the sequence table is N (T + carry_cap // max_seq_len))")
+            if isinstance(seq_cap, bool) or not isinstance(seq_cap, int) or seq_cap < floor:
+                raise ValueError(f"seq_cap: an int of at least N (T + carry_cap // max_seq_len) = {floor}, got {seq_cap!r}")
+            S = seq_cap
+        if train_batch_size is not None and S >= 2 ** 31:
+            raise ValueError(f"train_batch_size = {train_batch_size}: the sequence capacity ({S}) must stay below 2^31")
+        return R, E, S
+
+    def __init__(self, collect, max_seq_len, carry_cap, gamma, lam, aux=None, metrics=False, train_batch_size=None, seq_cap=None):
         """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS, done and state_in) that every emission reads; aux: None or
-        (name, f32 [T, N, 3, d]) as EpisodeBatch takes it; metrics: EpisodeBatch's episode metrics (per-agent entries keyed 1..3)"""
-        self.L = int(max_seq_len)
-        super().__init__(collect, carry_cap, gamma, lam, aux=aux, metrics=metrics)
+        (name, f32 [T, N, 3, d]) as EpisodeBatch takes it; metrics: EpisodeBatch's episode metrics (per-agent entries keyed 1..3);
+        train_batch_size / seq_cap: accumulate to at least that many rows, with that many sequence entries (see the class)"""
+        self.L, self._seq_cap = int(max_seq_len), seq_cap
+        super().__init__(collect, carry_cap, gamma, lam, aux=aux, metrics=metrics, train_batch_size=train_batch_size)
         S, sc = self._bufs.seq_cap, max(-(-self.carry_cap // self.L), 1)
         z = lambda shape: torch.zeros(shape, dtype=torch.int32, device=self._device)
         self.seq_start, self.seq_len, self.seq_ep = z((S,)), z((S,)), z((S,))
         state = tuple(collect["state_in"].shape[2:])
         self.state_in = torch.zeros((S,) + state, dtype=torch.float32, device=self._device)
         self._carry["state"] = torch.zeros((self.N, sc) + state, dtype=torch.float32, device=self._device)
-        self.n_sequences = self._counts[3]
+        self.n_sequences = self._size[3]
         self._bind(collect, {"state": self._carry["state"]}, ("state_in",), ("state_in",), self.SEQ_TABLE)
+
+    def _capacities(self):
+        R, E, self._S = self.capacities(self.N, self.T, self.carry_cap, self.train_batch_size, self.L, self._seq_cap)
+        return R, E
 
     def _struct(self, R, E, gamma, lam):
         return L.HHCommanderEpisodeBufs(T=self.T, N=self.N, max_seq_len=self.L, carry_cap=self.carry_cap, row_cap=R, ep_cap=E,
-                                        seq_cap=self.N * (self.T + self.carry_cap // self.L), gamma=gamma, lam=lam)
+                                        seq_cap=self._S, gamma=gamma, lam=lam)
 
     def _parts(self):
         return super()._parts() + ((self.SEQ_TABLE + ("state_in",), 3),)   # rows() also holds the sequence table and state_in [S, 3, 2, 200]
@@ -310,17 +344,26 @@ class CommanderRollout:
 
     metrics = True (batch_mode = "complete_episodes" only): `episodes.metrics()` gives the collect's line of RLlib's training result
     (`episode_reward_mean` and the rest, train_hier.py's print) from three more launches behind the emitter; the per-agent entries are
-    keyed by agent id 1..3 (the three agents share the one commander policy); see EpisodeBatch."""
+    keyed by agent id 1..3 (the three agents share the one commander policy); see EpisodeBatch.
+
+    train_batch_size = B (batch_mode = "complete_episodes" only; train_hier.py's `train_batch_size=args.batch_size`): `episodes`
+    accumulates the collects on the device until it holds at least B rows (commander steps of an arena) — whole collects, nothing
+    trimmed — with the same launches per collect.  `collect_batch()` collects until `episodes.ready()`; the collect after a complete
+    batch starts the next one.  See CommanderEpisodeBatch for the capacities (its seq_cap is a keyword of the batch, not of the
+    rollout: the rollout takes the safe default)."""
 
     def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
-                 carry_cap=None, metrics=False, record_logits=False):
+                 carry_cap=None, metrics=False, train_batch_size=None, record_logits=False):
         """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world); metrics /
-        record_logits: pass them by keyword (record_logits stays the last parameter)"""
+        train_batch_size / record_logits: pass them by keyword (record_logits stays the last parameter)"""
         if batch_mode not in ("truncate_episodes", "complete_episodes"):
             raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes cut into GRU "
                              "sequences: CommanderEpisodeBatch)")
         if metrics and batch_mode != "complete_episodes":
             raise ValueError("metrics=True needs batch_mode='complete_episodes': the episode metrics are those of the whole-episode batch")
+        if train_batch_size is not None and batch_mode != "complete_episodes":
+            raise ValueError("train_batch_size needs batch_mode='complete_episodes': it is the whole-episode batch that accumulates")
+        train_batch_size = EpisodeBatch.check_train_batch_size(train_batch_size)
         if int(max_seq_len) < 1:
             raise ValueError("max_seq_len must be at least 1")
         if carry_cap is not None and int(carry_cap) < 0:
@@ -354,7 +397,8 @@ class CommanderRollout:
             cap = default_carry_cap(world.cfg.horizon, world.cfg.n_agents, world.cfg.n_opps) if carry_cap is None else int(carry_cap)
             self.episodes = CommanderEpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done", "state_in")},
                                                   self.max_seq_len, cap, self.gamma, self.lam,
-                                                  aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics))
+                                                  aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
+                                                  train_batch_size=train_batch_size)
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -430,6 +474,12 @@ class CommanderRollout:
             torch.cuda.current_stream(dev).wait_stream(side)
             self._graph, self._graph_gen = graph, gen
         self._graph.replay()
+        return self
+
+    def collect_batch(self, max_collects=None):
+        """train_batch_size only: collect() until `episodes.ready()` (one small synchronising read per collect), at most max_collects
+        times (None: no limit; `episodes.ready()` tells afterwards whether the batch is complete) -> self"""
+        collect_until_ready(self, max_collects)
         return self
 
     def critic_rows(self, agent):

@@ -26,6 +26,13 @@
  * Every order (rows, episodes, sequences) is fixed by the scans and the arrangement, never by scheduling: graph and eager runs give
  * identical batches.
  *
+ * hh_episodes_emit_append / hh_commander_episodes_emit_append accumulate consecutive calls into one batch (RLlib's train_batch_size: whole
+ * collects are concatenated until at least train_rows rows are there).  The same four launches; only the ACC instances of the scan and of
+ * the GAE differ: the scan starts its three exclusive scans from the device-side bases acc[0] / acc[1] / acc[3] (0 when the previous
+ * call completed a batch: acc[4]), so every offset the emit kernel reads — and with it ep_start, seq_start and seq_ep — is an absolute
+ * position in the accumulated batch and hh_k_ep_emit runs unchanged; the GAE walks the episodes this call appended only.  The order is
+ * collect-major, then arena, episode, time.
+ *
  * Host part: needs g_err / HIPCHK of the including translation unit (hh_world.hip).
  */
 #ifndef HH_EPISODES_H
@@ -84,6 +91,11 @@ struct hh_ep_desc {
     const float *aux;
     float *c_aux, *o_aux;
     int32_t aux_dim;
+    /* the _append entry points' accumulator (i32 [HH_EP_ACC]), batch size in rows and optional running totals (i64 [2]); read by the ACC
+       instances of hh_k_ep_scan / hh_k_ep_gae only */
+    int32_t *acc;
+    int64_t *totals;
+    int64_t train_rows;
 };
 
 template <bool SEQ>
@@ -114,12 +126,18 @@ __global__ __launch_bounds__(256) void hh_k_ep_count(hh_ep_desc b) {
 
 /* one workgroup: thread i sums a contiguous run of arenas, the 1024 sums are scanned (wave shuffles, then the 16 wave totals), and
  * every thread writes the exclusive offsets of its run; rows, episodes and (SEQ) sequences side by side.  Totals fit in int:
- * N (carry_cap + T) < 2^31 is checked at the entry points (and bounds the sequences) */
-template <bool SEQ>
+ * N (carry_cap + T) < 2^31 is checked at the entry points (and bounds the sequences).
+ * ACC (the _append entry points): the scans start from the accumulator's bases — thread 0 reads acc before the barrier and hands the bases
+ * out through LDS (w_tot[q][16]), and rewrites acc after it, so no thread reads what thread 0 has already advanced.  A base is taken
+ * into [0, capacity] whatever acc holds (acc is written clamped), so base + total stays below 2^32: the offsets are added as unsigned
+ * and saturate at INT32_MAX — at or beyond every capacity, where the emit kernel writes nothing — and the sums that decide the
+ * accumulator are taken in 64 bits */
+template <bool SEQ, bool ACC = false>
 __global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_ep_desc b) {
     constexpr int Q = SEQ ? 3 : 2;
     constexpr int in[3] = {HH_EP_S_ROWS, HH_EP_S_EPS, HH_EP_S_SEQ}, out[3] = {HH_EP_S_ROW_OFF, HH_EP_S_EP_OFF, HH_EP_S_SEQ_OFF};
-    __shared__ int w_tot[Q][16];
+    constexpr int slot[3] = {0, 1, 3};
+    __shared__ int w_tot[Q][ACC ? 17 : 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = b.N;
     int32_t *s = b.scratch;
     const int per = (N + 1023) / 1024, n0 = tid * per < N ? tid * per : N, n1 = n0 + per < N ? n0 + per : N;
@@ -142,6 +160,18 @@ __global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_ep_desc b) {
     if (lane == 63)
 #pragma unroll
         for (int q = 0; q < Q; q++) w_tot[q][wave] = x[q];
+    bool fresh = false;   // (ACC, thread 0) the previous call completed a batch: this one starts the next
+    if constexpr (ACC) {
+        if (tid == 0) {
+            fresh = b.acc[4] != 0;
+            const int64_t cap[3] = {b.row_cap, b.ep_cap, b.seq_cap};
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int a = b.acc[slot[q]];
+                w_tot[q][16] = fresh || a < 0 ? 0 : (a < cap[q] ? a : (int)cap[q]);
+            }
+        }
+    }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < Q; q++) { pre[q] = x[q] - sum[q]; tot[q] = 0; }
@@ -152,23 +182,55 @@ __global__ __launch_bounds__(1024) void hh_k_ep_scan(hh_ep_desc b) {
             if (w < wave) pre[q] += w_tot[q][w];
             tot[q] += w_tot[q][w];
         }
+    if constexpr (!ACC) {
 #pragma unroll 8
-    for (int n = n0; n < n1; n++)
+        for (int n = n0; n < n1; n++)
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            s[out[q] * N + n] = pre[q];
-            pre[q] += s[in[q] * N + n];
-        }
+            for (int q = 0; q < Q; q++) {
+                s[out[q] * N + n] = pre[q];
+                pre[q] += s[in[q] * N + n];
+            }
+    } else {
+        unsigned upre[Q];   // base + exclusive offset, below 2^32
+#pragma unroll
+        for (int q = 0; q < Q; q++) upre[q] = (unsigned)pre[q] + (unsigned)w_tot[q][16];
+#pragma unroll 8
+        for (int n = n0; n < n1; n++)
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                s[out[q] * N + n] = upre[q] < (unsigned)INT32_MAX ? (int)upre[q] : INT32_MAX;
+                upre[q] += (unsigned)s[in[q] * N + n];
+            }
+    }
     if (tid == 0) {
         const int64_t cap[3] = {b.row_cap, b.ep_cap, b.seq_cap};
-        constexpr int slot[3] = {0, 1, 3};
-        bool over = false;
+        if constexpr (!ACC) {
+            bool over = false;
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            b.counts[slot[q]] = tot[q] < cap[q] ? tot[q] : (int)cap[q];
-            over |= tot[q] > cap[q];
+            for (int q = 0; q < Q; q++) {
+                b.counts[slot[q]] = tot[q] < cap[q] ? tot[q] : (int)cap[q];
+                over |= tot[q] > cap[q];
+            }
+            if (over) b.counts[2] = 1;   // sticky: never cleared by a kernel
+        } else {
+            bool over = b.counts[2] != 0;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int base = w_tot[q][16];
+                const int64_t end = (int64_t)base + tot[q], endc = end < cap[q] ? end : cap[q];
+                b.acc[slot[q]] = (int)endc;
+                b.counts[slot[q]] = (int)(endc - base);   // written by this call; base <= cap
+                over |= end > cap[q];
+            }
+            if (over) { b.counts[2] = 1; b.acc[2] = 1; }   // both sticky
+            b.acc[4] = b.acc[0] >= b.train_rows;
+            b.acc[5] = (fresh ? 0 : b.acc[5]) + 1;
+            if (fresh) b.acc[6] += 1;
+            if (b.totals) {   // every episode and row once, whatever the metrics are taken over
+                b.totals[0] += b.counts[1];
+                b.totals[1] += b.counts[0];
+            }
         }
-        if (over) b.counts[2] = 1;   // sticky: never cleared by a kernel
     }
 }
 
@@ -363,12 +425,14 @@ __global__ __launch_bounds__(256) void hh_k_ep_emit(hh_ep_desc b) {
  * a < n_agents walks agent a backwards on the LDS copy (the chain is sequential: bit-exactness fixes its order), and the results leave
  * with coalesced stores.  Episodes longer than a chunk are walked chunk by chunk from the end, the recursion carried in registers. */
 #define HH_EP_GAE_LDS 512   /* floats per staged column */
+/* ACC: the episodes this call appended, [acc[1] - counts[1], acc[1]) — the adv / target bytes of the batch's earlier episodes stay */
+template <bool ACC = false>
 __global__ __launch_bounds__(64) void hh_k_ep_gae(hh_ep_desc b) {
     __shared__ float l_r[HH_EP_GAE_LDS], l_v[HH_EP_GAE_LDS];
     const int nA = b.n_agents, tid = threadIdx.x, chunk = HH_EP_GAE_LDS / nA;
-    const int n_eps = b.counts[1];
+    const int n_eps = ACC ? b.acc[1] : b.counts[1], e0 = ACC ? n_eps - b.counts[1] : 0;
     const double gamma = b.gamma, gl = b.gamma * b.lam;
-    for (int e = blockIdx.x; e < n_eps; e += gridDim.x) {
+    for (int e = e0 + blockIdx.x; e < n_eps; e += gridDim.x) {
         const int start = b.ep_start[e], len = b.ep_len[e];
         if (start < 0 || len <= 0 || (long long)start + len > b.row_cap) continue;   // only after an overflow (flagged)
         double a_next = 0.0;
@@ -449,11 +513,14 @@ static int hh_ep_launch(const hh_ep_desc &d, size_t lds, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(hh_k_ep_count<SEQ>, dim3((d.N + 255) / 256), dim3(256), 0, st, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hh_k_ep_scan<SEQ>, dim3(1), dim3(1024), 0, st, d);
+    if (d.acc) hipLaunchKernelGGL((hh_k_ep_scan<SEQ, true>), dim3(1), dim3(1024), 0, st, d);
+    else hipLaunchKernelGGL((hh_k_ep_scan<SEQ, false>), dim3(1), dim3(1024), 0, st, d);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL((hh_k_ep_emit<OBS, ACT, SEQ, AUX>), dim3(d.N), dim3(256), lds, st, d);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hh_k_ep_gae, dim3(d.ep_cap < 8192 ? (int)d.ep_cap : 8192), dim3(64), 0, st, d);
+    const dim3 gae_grid(d.ep_cap < 8192 ? (int)d.ep_cap : 8192);
+    if (d.acc) hipLaunchKernelGGL(hh_k_ep_gae<true>, gae_grid, dim3(64), 0, st, d);
+    else hipLaunchKernelGGL(hh_k_ep_gae<false>, gae_grid, dim3(64), 0, st, d);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }
@@ -476,7 +543,23 @@ static int hh_ep_check_aux(const char *fn, const hh_episode_aux *x, hh_ep_desc &
     return HH_OK;
 }
 
-static int hh_ep_emit_any(const char *fn, const hh_episode_bufs *b, const hh_episode_aux *x, void *stream) {
+/* the _append entry points' own argument checks, made after the struct's; fills the descriptor's accumulator fields */
+struct hh_ep_append {
+    int64_t train_rows;
+    int32_t *acc;
+    int64_t *totals;
+};
+
+static int hh_ep_check_append(const char *fn, const hh_ep_append *a, hh_ep_desc &d) {
+    if (a->train_rows < 1) return hh_ep_fail(fn, "train_rows must be at least 1");
+    if (!a->acc) return hh_ep_fail(fn, "null acc");
+    if ((uintptr_t)a->acc & 3) return hh_ep_fail(fn, "acc must be 4-byte aligned");
+    if ((uintptr_t)a->totals & 7) return hh_ep_fail(fn, "totals must be 8-byte aligned");
+    d.acc = a->acc; d.totals = a->totals; d.train_rows = a->train_rows;
+    return HH_OK;
+}
+
+static int hh_ep_emit_any(const char *fn, const hh_episode_bufs *b, const hh_episode_aux *x, void *stream, const hh_ep_append *a = NULL) {
     if (!b) return hh_ep_fail(fn, "bad sizes");
     hh_ep_desc d = hh_ep_common(b);
     d.n_agents = b->n_agents; d.obs_dim = b->obs_dim;
@@ -486,6 +569,7 @@ static int hh_ep_emit_any(const char *fn, const hh_episode_bufs *b, const hh_epi
     const bool obs4 = (b->n_agents * b->obs_dim) % 4 == 0;   // an obs row is 2 D floats = 16 B aligned for D = 26 | 30: dwordx4
     if (obs4 && (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 15)) return hh_ep_fail(fn, "obs buffers must be 16-byte aligned");
     if ((((uintptr_t)b->actions | (uintptr_t)b->c_actions | (uintptr_t)b->o_actions) & 3)) return hh_ep_fail(fn, "action buffers must be 4-byte aligned");
+    if (a && (rc = hh_ep_check_append(fn, a, d)) != HH_OK) return rc;
     if (x && (rc = hh_ep_check_aux(fn, x, d)) != HH_OK) return rc;
     const size_t lds = 3 * (size_t)b->T * sizeof(int);
     return obs4 ? hh_ep_launch_aux<float4, uint32_t, false>(d, lds, stream) : hh_ep_launch_aux<float, uint32_t, false>(d, lds, stream);
@@ -497,7 +581,14 @@ extern "C" int hh_episodes_emit_aux(const hh_episode_bufs *b, const hh_episode_a
     return hh_ep_emit_any("hh_episodes_emit_aux", b, x, stream);
 }
 
-static int hh_cep_emit_any(const char *fn, const hh_commander_episode_bufs *b, const hh_episode_aux *x, void *stream) {
+extern "C" int hh_episodes_emit_append(const hh_episode_bufs *b, const hh_episode_aux *x, int64_t train_rows, int32_t *acc, int64_t *totals,
+                                       void *stream) {
+    const hh_ep_append a = {train_rows, acc, totals};
+    return hh_ep_emit_any("hh_episodes_emit_append", b, x, stream, &a);
+}
+
+static int hh_cep_emit_any(const char *fn, const hh_commander_episode_bufs *b, const hh_episode_aux *x, void *stream,
+                           const hh_ep_append *a = NULL) {
     if (!b) return hh_ep_fail(fn, "bad sizes");
     hh_ep_desc d = hh_ep_common(b);
     d.n_agents = HH_CMD_AGENTS; d.obs_dim = HH_CMD_OBS; d.max_seq_len = b->max_seq_len; d.seq_cap = b->seq_cap;
@@ -513,6 +604,7 @@ static int hh_cep_emit_any(const char *fn, const hh_commander_episode_bufs *b, c
     if ((rc = hh_ep_check_ptrs(fn, d)) != HH_OK) return rc;
     if (((uintptr_t)b->state_in | (uintptr_t)b->c_state | (uintptr_t)b->o_state_in) & 15) return hh_ep_fail(fn, "state buffers must be 16-byte aligned");
     if (((uintptr_t)b->obs | (uintptr_t)b->c_obs | (uintptr_t)b->o_obs) & 7) return hh_ep_fail(fn, "obs buffers must be 8-byte aligned");
+    if (a && (rc = hh_ep_check_append(fn, a, d)) != HH_OK) return rc;
     if (x && (rc = hh_ep_check_aux(fn, x, d)) != HH_OK) return rc;
     return hh_ep_launch_aux<float2, uint8_t, true>(d, (size_t)lds, stream);
 }
@@ -523,6 +615,12 @@ extern "C" int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, vo
 
 extern "C" int hh_commander_episodes_emit_aux(const hh_commander_episode_bufs *b, const hh_episode_aux *x, void *stream) {
     return hh_cep_emit_any("hh_commander_episodes_emit_aux", b, x, stream);
+}
+
+extern "C" int hh_commander_episodes_emit_append(const hh_commander_episode_bufs *b, const hh_episode_aux *x, int64_t train_rows,
+                                                 int32_t *acc, int64_t *totals, void *stream) {
+    const hh_ep_append a = {train_rows, acc, totals};
+    return hh_cep_emit_any("hh_commander_episodes_emit_append", b, x, stream, &a);
 }
 
 #endif /* HH_EPISODES_H */

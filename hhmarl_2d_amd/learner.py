@@ -1228,7 +1228,9 @@ class PPOLearner:
     def update(self, episodes, bank=None):
         """one PPO update of both policies from episodes (an EpisodeBatch after a collect) -> per policy a dict: total_loss, policy_loss,
         vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows.
-        `bank` is read only when the batch has no `logits` column (batch_old_logits).  With grad_clip also grad_gnorm."""
+        `bank` is read only when the batch has no `logits` column (batch_old_logits).  With grad_clip also grad_gnorm.
+        An EpisodeBatch built with train_batch_size hands over its accumulated batch (RLlib's train_batch_size: update once
+        `episodes.ready()`, e.g. after `PPORollout.collect_batch()`); nothing else changes here."""
         rows = episodes.rows()
         out = []
         clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
@@ -1832,7 +1834,8 @@ class CommanderLearner:
         vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows (unpadded,
         all three agents).  `net` (the sampler's CommanderNet) is not read: the old logits are the batch's own `logits` column or, without
         one, come from the module, which holds the weights the sampler was given at the last publish (batch_old_logits).  With grad_clip
-        also grad_gnorm."""
+        also grad_gnorm.  A CommanderEpisodeBatch built with train_batch_size hands over its accumulated batch (update once
+        `episodes.ready()`, e.g. after `CommanderRollout.collect_batch()`); nothing else changes here."""
         seqs = episodes.sequences()
         clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
         if seqs["obs"].shape[1] != self.max_seq_len:

@@ -1,6 +1,7 @@
 """Rollout post-processing next to the environment: the centralised-critic input
 packing of train_hetero.py:113-181 and GAE (train_hetero.py:216) on device tensors."""
 import ctypes as C
+import numbers
 
 import torch
 
@@ -93,6 +94,20 @@ def episode_segments(done):
     return seg, seg < n_done
 
 
+def collect_until_ready(rollout, max_collects=None):
+    """what the rollouts' collect_batch() does: rollout.collect() until rollout.episodes.ready(), at most max_collects times"""
+    if rollout.episodes is None or rollout.episodes.train_batch_size is None:
+        raise RuntimeError(f"{type(rollout).__name__}.collect_batch(): built without train_batch_size")
+    if max_collects is not None and int(max_collects) < 1:
+        raise ValueError("max_collects: None or at least 1")
+    n = 0
+    while True:
+        rollout.collect()
+        n += 1
+        if rollout.episodes.ready() or (max_collects is not None and n >= int(max_collects)):
+            return n
+
+
 class EpisodeBatch:
     """The whole-episode batch of a `PPORollout(..., batch_mode="complete_episodes")` (train_hetero.py:212): after every collect, the rows
     of every episode that ENDED in it, from its reset row to its done row, in one flat batch — the episode's earlier rows come from a
@@ -126,7 +141,21 @@ class EpisodeBatch:
     without a finished episode reports nan), and `vf_explained_var` is that of the sampler's VF_PREDS (the `vf` column: zero action
     inputs) against the value targets, not of the learner's re-evaluation with the actions filled in.  `timesteps_total` counts
     environment steps (rows), not agent steps.  With the default False nothing is allocated and the launches, the graph and `rows()`
-    are what they were."""
+    are what they were.
+
+    train_batch_size = B (an int >= 1; RLlib's knob of that name, train_hetero.py:216 `args.batch_size`): the collects are no longer
+    overwritten but ACCUMULATED on the device until the batch holds at least B rows (environment steps) — whole collects, nothing
+    trimmed, as RLlib's training_step concatenates whole sample batches.  hh_episodes_emit_append (include/hh_abi.h) appends in place:
+    the same four launches in the collect's graph, no copy, no second batch, no host synchronisation; the order is collect-major, then
+    arena, episode, time, and ep_start (the commander's seq_start / seq_ep too) are positions in the accumulated batch.  `rows()`,
+    `critic_rows()`, `n_rows`, `n_episodes` describe the batch so far; `ready()` tells whether it has reached B, `batch_info()` its
+    counts; the collect after a complete batch starts the next one by itself (read `rows()` before it), `clear()` discards a partial
+    one.  With metrics=True, `metrics()` is RLlib's line for the iteration's batch so far (episodes_this_iter and the means over
+    every episode accumulated), while episodes_total / timesteps_total count every episode and row once.
+    Capacity: a batch was below B before its last collect, so R = B - 1 + N (H - 1 + T) rows and E = B - 1 + N T episodes (both must
+    stay below 2^31); the carry is unchanged.  For two agents 8 D + 47 bytes per row and 12 per episode (with the logits 256 more per
+    row): B = 4 collects' worth of rows at N = 16384, T = 64, fight D = 26 (B = 4194304) is 1.07 GB of rows and 50 MB of episode table
+    more than without.  With the default None everything is what it was: the same entry point, allocations and graph."""
 
     COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
     TABLES = ("ep_start", "ep_len", "ep_arena")
@@ -150,11 +179,33 @@ class EpisodeBatch:
             raise ValueError(f"aux: {name} must be [T, N, n_agents, d] = [{T}, {N}, {n_agents}, 1 .. {L.EP_AUX_MAX_DIM}], got {tuple(t.shape)}")
         return name, t
 
-    def __init__(self, collect, carry_cap, gamma, lam, aux=None, metrics=False):
+    @staticmethod
+    def check_train_batch_size(train_batch_size):
+        """train_batch_size as the constructors take it -> None or the int, or ValueError"""
+        B = train_batch_size
+        if B is None:
+            return None
+        if isinstance(B, bool) or not isinstance(B, numbers.Integral) or B < 1:
+            raise ValueError(f"train_batch_size: None (every collect is its own batch) or an int >= 1 (rows to accumulate), got {B!r}")
+        return int(B)
+
+    @classmethod
+    def capacities(cls, N, T, carry_cap, train_batch_size=None):
+        """-> (R rows, E episodes) of the batch buffers: N (carry_cap + T) and N T, with train_batch_size = B each B - 1 more (a batch was
+        below B before its last collect); ValueError for a B whose capacities reach 2^31"""
+        B = cls.check_train_batch_size(train_batch_size)
+        more = 0 if B is None else B - 1
+        R, E = more + int(N) * (int(carry_cap) + int(T)), more + int(N) * int(T)
+        if B is not None and max(R, E) >= 2 ** 31:
+            raise ValueError(f"train_batch_size = {B}: the capacities ({R} rows, {E} episodes) must stay below 2^31")
+        return R, E
+
+    def __init__(self, collect, carry_cap, gamma, lam, aux=None, metrics=False, train_batch_size=None):
         """collect: the rollout's [T(+1), N, ...] buffers (ROW_INPUTS and done) that every emission reads; every row column of the batch and
         of the carry takes its per-row shape and dtype from the collect's.  carry_cap: rows the carry holds per arena (horizon - 1).
         aux: None, or (name, f32 [T, N, n_agents, d]) — one more column that travels with the rows (see the class).
-        metrics: also compute the episode metrics of every emitted batch on the device (see the class)."""
+        metrics: also compute the episode metrics of every emitted batch on the device (see the class).
+        train_batch_size: None, or the rows to accumulate before a batch is complete (see the class)."""
         T, N = collect["done"].shape
         self.N, self.T, self.carry_cap = int(N), int(T), int(carry_cap)
         self.n_agents, self.D = int(collect["obs"].shape[2]), int(collect["obs"].shape[-1])
@@ -162,8 +213,9 @@ class EpisodeBatch:
         self.aux_name, self._aux = None, None
         if aux is not None:
             self.aux_name, aux_t = self.check_aux(aux, self.T, self.N, self.n_agents, self._device)
+        self.train_batch_size = self.check_train_batch_size(train_batch_size)
         N, T, cap = self.N, self.T, max(self.carry_cap, 1)
-        R, E = N * (self.carry_cap + T), N * T
+        R, E = self._capacities()
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self._device)
         i32 = torch.int32
         self._carry = {}
@@ -179,7 +231,10 @@ class EpisodeBatch:
         self._finished = z((N,), i32)            # episodes finished per arena since start()
         self._scratch = z((self._SCRATCH[0] * N + self._SCRATCH[1],), i32)
         self._counts = z((self._N_COUNTS,), i32)  # rows, episodes of the last collect; overflow flag (sticky)[; sequences of the last collect]
-        self.n_rows, self.n_episodes = self._counts[0], self._counts[1]
+        # train_batch_size: the accumulator of hh_episodes_emit_append (_lib.EP_ACC: the counts' slots describe the batch so far)
+        self._acc = z((len(L.EP_ACC),), i32) if self.train_batch_size is not None else None
+        self._size = self._counts if self._acc is None else self._acc   # what rows() is cut to
+        self.n_rows, self.n_episodes = self._size[0], self._size[1]
         b = self._struct(R, E, float(gamma), float(lam))
         self._bufs, self._collect = b, collect   # the struct holds raw pointers: keep the tensors alive
         self._bind(collect, self._carry, ("done",) + self.ROW_INPUTS, self.COLUMNS, self.TABLES)
@@ -202,12 +257,19 @@ class EpisodeBatch:
             self._summary[:2] = 0.0                  # no collect yet: what a collect without a finished episode leaves
             self._totals = z((2,), torch.int64)      # episodes_total, timesteps_total since start() / reset()
             self._m_scratch = z((nbytes.value // 8,), torch.float64)
-            self._m_host = None                      # pinned host copies (summary, totals, counts), made by the first metrics()
+            self._m_host = None                      # pinned host copies (summary, totals, counts[, acc]), made by the first metrics()
+            # accumulating: the metrics are taken over the batch so far (acc in place of the counts) and would count its earlier collects
+            # again — their totals go to a throwaway, the real ones come from the emitter, every episode and row once
+            self._m_totals = self._totals if self._acc is None else z((2,), torch.int64)
             self._metrics = L.HHEpisodeMetricsBufs(
                 n_agents=self.n_agents, reserved0=0, row_cap=R, ep_cap=E, reward=self.reward.data_ptr(), vf=self.vf.data_ptr(),
-                target=self.target.data_ptr(), ep_start=self.ep_start.data_ptr(), ep_len=self.ep_len.data_ptr(), counts=self._counts.data_ptr(),
-                ep_return=self.ep_return.data_ptr(), summary=self._summary.data_ptr(), totals=self._totals.data_ptr(),
+                target=self.target.data_ptr(), ep_start=self.ep_start.data_ptr(), ep_len=self.ep_len.data_ptr(), counts=self._size.data_ptr(),
+                ep_return=self.ep_return.data_ptr(), summary=self._summary.data_ptr(), totals=self._m_totals.data_ptr(),
                 scratch=self._m_scratch.data_ptr(), scratch_bytes=nbytes.value)
+
+    def _capacities(self):
+        """(R, E) of this batch; a subclass checks its own capacities here as well"""
+        return self.capacities(self.N, self.T, self.carry_cap, self.train_batch_size)
 
     def _struct(self, R, E, gamma, lam):
         return L.HHEpisodeBufs(T=self.T, N=self.N, n_agents=self.n_agents, obs_dim=self.D, carry_cap=self.carry_cap, reserved0=0, row_cap=R,
@@ -233,7 +295,8 @@ class EpisodeBatch:
     def reset(self):
         """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays); with metrics, the
         running totals start
-        again and the summary is that of a collect without a finished episode (0 episodes, 0 rows, nan) until the next collect"""
+        again and the summary is that of a collect without a finished episode (0 episodes, 0 rows, nan) until the next collect; with
+        train_batch_size, the batch accumulated so far is discarded as well (the accumulator is zeroed)"""
         if self._metrics is not None:
             self._totals.zero_()
             self._summary.fill_(float("nan"))    # no collect since the reset: what a collect without a finished episode leaves
@@ -242,18 +305,52 @@ class EpisodeBatch:
         self._finished.zero_()
         self._counts[:2].zero_()
         self._counts[3:].zero_()
+        if self._acc is not None:
+            self._acc.zero_()
+
+    def _accumulating(self, what):
+        if self._acc is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: built without train_batch_size")
+
+    def ready(self):
+        """train_batch_size only: has the batch reached train_batch_size rows?  One small synchronising read.  The next collect after a
+        True starts the next batch: take `rows()` before it."""
+        self._accumulating("ready()")
+        return bool(self._acc[4].item())
+
+    def batch_info(self):
+        """train_batch_size only; synchronises -> dict of ints: rows, episodes, sequences (0 without a sequence table) of the batch so far,
+        collects accumulated in it, batches completed before it (since reset() / clear())"""
+        self._accumulating("batch_info()")
+        a = dict(zip(L.EP_ACC, self._acc.tolist()))
+        return {k: a[k] for k in ("rows", "episodes", "sequences", "collects", "batches")}
+
+    def clear(self):
+        """train_batch_size only: discard the batch so far, complete or not (a zeroing of the accumulator in the order of the current
+        stream, no synchronisation): the next collect starts a batch at row 0.  The carry, the per-arena episode counters and the
+        running totals are untouched — the running episodes go on, none of their rows is lost."""
+        self._accumulating("clear()")
+        self._acc.zero_()
+        if self._metrics is not None:
+            self._summary.fill_(float("nan"))    # an empty batch: what a collect without a finished episode leaves
+            self._summary[:2] = 0.0
 
     def emit(self, stream):
-        if self._aux is None:
+        aux = None if self._aux is None else C.byref(self._aux)
+        if self._acc is not None:
+            totals = self._totals.data_ptr() if self._metrics is not None else None
+            L.check(getattr(L.lib(), self._EMIT + "_append")(C.byref(self._bufs), aux, self.train_batch_size, self._acc.data_ptr(), totals, stream))
+        elif aux is None:
             L.check(getattr(L.lib(), self._EMIT)(C.byref(self._bufs), stream))
         else:
-            L.check(getattr(L.lib(), self._EMIT + "_aux")(C.byref(self._bufs), C.byref(self._aux), stream))
+            L.check(getattr(L.lib(), self._EMIT + "_aux")(C.byref(self._bufs), aux, stream))
         if self._metrics is not None:
             self.enqueue_metrics(stream)
 
     def enqueue_metrics(self, stream):
         """hh_episodes_metrics over the batch as it stands, on `stream` (what emit() does right behind the emitter; a second call adds the
-        batch to the totals again: tools/episode_metrics_timing.py times the launches with it and puts the totals back)"""
+        batch to the totals again: tools/episode_metrics_timing.py times the launches with it and puts the totals back).  With
+        train_batch_size the batch is the accumulated one and the totals are the emitter's: this call leaves them alone."""
         if self._metrics is None:
             raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
         L.check(L.lib().hh_episodes_metrics(C.byref(self._metrics), stream))
@@ -271,21 +368,23 @@ class EpisodeBatch:
         return {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return}
 
     def metrics(self):
-        """-> the last collect's metrics under RLlib's result names (see the class for the two differences); copies the summary, the totals
-        and the counts to the host: one synchronisation of the current stream.  Raises like `rows()` after an overflow.
+        """-> the last collect's metrics (with train_batch_size: the accumulated batch's so far) under RLlib's result names (see the class
+        for the two differences); copies the summary, the totals and the counts to the host: one synchronisation of the current stream.
+        Raises like `rows()` after an overflow.
         Keys: episode_reward_mean / _min / _max, episode_len_mean, episodes_this_iter, policy_reward_mean / _min / _max, vf_explained_var,
         episodes_total, timesteps_total (RLlib's), and from the same summary episode_len_min / _max and timesteps_this_iter (the batch's
         rows).  The per-agent entries (policy_reward_*, vf_explained_var) are dicts keyed by AGENT_KEYS.  After reset() / start() and
         before the next collect: 0 episodes, nan, totals 0."""
         if self._metrics is None:
             raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
+        src = (self._summary, self._totals, self._counts) + (() if self._acc is None else (self._acc,))
         if self._m_host is None:
-            self._m_host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in (self._summary, self._totals, self._counts))
-        for h, d in zip(self._m_host, (self._summary, self._totals, self._counts)):
+            self._m_host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in src)
+        for h, d in zip(self._m_host, src):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream(self._device).synchronize()
-        s, totals, counts = (h.tolist() for h in self._m_host)
-        if counts[2]:
+        s, totals, *flags = (h.tolist() for h in self._m_host)
+        if any(f[2] for f in flags):
             raise self._overflow()
         slot = L.EP_METRICS_SLOT
         per_agent = lambda name: {k: s[slot[name + "_0"] + a] for a, k in enumerate(self.AGENT_KEYS)}
@@ -298,11 +397,11 @@ class EpisodeBatch:
         return out
 
     def rows(self):
-        """synchronises; -> dict of views cut to the last collect: the columns (COLUMNS), the episode table (TABLES) and a subclass's own
-        parts (_parts)"""
+        """synchronises; -> dict of views cut to the last collect (with train_batch_size: to the accumulated batch so far): the columns
+        (COLUMNS), the episode table (TABLES) and a subclass's own parts (_parts)"""
         torch.cuda.synchronize(self._device)
-        counts = self._counts.tolist()
-        if counts[2]:
+        counts = self._size.tolist()
+        if counts[2] or (self._acc is not None and int(self._counts[2])):
             raise self._overflow()
         return {k: getattr(self, k)[:counts[i]] for names, i in self._parts() for k in names}
 
@@ -357,11 +456,17 @@ class PPORollout:
     the launches, the graph and the results are what they were.
 
     metrics = True (batch_mode = "complete_episodes" only): `episodes.metrics()` gives the collect's line of RLlib's training result
-    (`episode_reward_mean` and the rest: train_hetero.py:285) from three more launches in the collect's graph; see EpisodeBatch."""
+    (`episode_reward_mean` and the rest: train_hetero.py:285) from three more launches in the collect's graph; see EpisodeBatch.
+
+    train_batch_size = B (batch_mode = "complete_episodes" only; train_hetero.py:216 `train_batch_size=args.batch_size`): `episodes`
+    accumulates the collects on the device until it holds at least B rows — whole collects, nothing trimmed — instead of being
+    overwritten by each; the launches of a collect and its graph stay the same.  `collect_batch()` collects until `episodes.ready()`;
+    the collect after a complete batch starts the next one.  See EpisodeBatch for the capacities."""
 
     def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes",
-                 metrics=False, record_logits=False):
-        """metrics / record_logits: pass them by keyword (record_logits stays the last parameter, where its callers and its test expect it).
+                 metrics=False, train_batch_size=None, record_logits=False):
+        """metrics / train_batch_size / record_logits: pass them by keyword (record_logits stays the last parameter, where its callers and
+        its test expect it).
         opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
         a `pilots.OpponentNets(world, skip_first=False)` (its bank bound, so that hh_step_begin lists the opponents' rows itself) or any
         callable(opp_obs f32 [N, 2, 30] on the device, None) -> int8 [N, 2, 4] that only enqueues work on the current stream"""
@@ -371,6 +476,9 @@ class PPORollout:
             raise ValueError("batch_mode='complete_episodes' is defined for RLlib's trajectory view only (semantics='rllib')")
         if metrics and batch_mode != "complete_episodes":
             raise ValueError("metrics=True needs batch_mode='complete_episodes': the episode metrics are those of the whole-episode batch")
+        if train_batch_size is not None and batch_mode != "complete_episodes":
+            raise ValueError("train_batch_size needs batch_mode='complete_episodes': it is the whole-episode batch that accumulates")
+        train_batch_size = EpisodeBatch.check_train_batch_size(train_batch_size)
         from . import pilots
         assert world.cfg.env_kind == L.ENV_LOWLEVEL and world.n_agents == 2 and world.cfg.auto_reset, "PPORollout drives an auto-resetting LowLevelEnv world"
         if semantics not in ("rllib", "masked"):
@@ -412,7 +520,8 @@ class PPORollout:
         self.episodes = None
         if batch_mode == "complete_episodes":
             self.episodes = EpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done",)}, max(world.cfg.horizon - 1, 0),
-                                         self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics))
+                                         self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
+                                         train_batch_size=train_batch_size)
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -465,6 +574,12 @@ class PPORollout:
                 with torch.cuda.graph(self._graph):
                     self._run()
             self._graph.replay()
+        return self
+
+    def collect_batch(self, max_collects=None):
+        """train_batch_size only: collect() until `episodes.ready()` (one small synchronising read per collect), at most max_collects
+        times (None: no limit; `episodes.ready()` tells afterwards whether the batch is complete) -> self"""
+        collect_until_ready(self, max_collects)
         return self
 
     @property

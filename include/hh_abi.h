@@ -339,6 +339,31 @@ typedef struct hh_episode_aux {
  * that is not written is not written in any column); HH_E_ARG for aux_dim out of range, reserved0 != 0, a null or misaligned buffer. */
 int hh_episodes_emit_aux(const hh_episode_bufs *b, const hh_episode_aux *x, void *stream);
 
+/* Accumulated batches (RLlib's train_batch_size: training_step concatenates whole sample batches until at least that many environment
+ * steps are there, trims nothing, then runs one update).  hh_episodes_emit_append is hh_episodes_emit_aux (x = NULL: no aux column)
+ * that APPENDS to the batch in place: the same four launches, no host synchronisation, no allocation, graph-capturable.  Its scan
+ * starts from the device-side accumulator `acc` instead of 0:
+ *   - acc[4] set (the previous call completed a batch): this call starts the next one — base rows, episodes and sequences are 0,
+ *     acc[5] restarts at 0 and acc[6] goes up by one; otherwise the bases are acc[0], acc[1], acc[3];
+ *   - every arena's row, episode and sequence offset is base + its exclusive scan, so ep_start (and the commander's seq_start / seq_ep)
+ *     are absolute positions in the accumulated batch; the order is collect-major, then arena, episode, time;
+ *   - afterwards acc[0], acc[1], acc[3] = base + this call's totals (clamped to the capacities), acc[4] = acc[0] >= train_rows,
+ *     acc[5] += 1; acc[2] (sticky, like counts[2], which is set with it) is set if base + totals exceeds a capacity or counts[2] was
+ *     already set; counts[0], counts[1], counts[3] keep meaning "written by this call";
+ *   - GAE runs over the episodes this call appended only, [acc[1] - counts[1], acc[1]): adv / target of earlier episodes are not
+ *     rewritten;
+ *   - totals (NULL, or [dev] i64 [2], 8-byte aligned): totals[0] += counts[1], totals[1] += counts[0] — every episode and row once.
+ * row_cap / ep_cap (/ seq_cap) are the capacities of the ACCUMULATED batch: a batch was below train_rows before its last call, so
+ * row_cap = train_rows - 1 + N (carry_cap + T), ep_cap = train_rows - 1 + N T never overflow.  With train_rows = 1 and a zeroed acc
+ * every call writes exactly the bytes of hh_episodes_emit_aux (a batch with any row is complete: the next call starts at 0).  The
+ * caller zeroes acc before the first call; zeroing it later discards a partial batch (the carry is untouched).
+ * HH_E_ARG, nothing launched: train_rows < 1, acc NULL or not 4-byte aligned, totals not 8-byte aligned, and whatever
+ * hh_episodes_emit_aux refuses. */
+#define HH_EP_ACC 8   /* i32 [8] on the device: [0] rows, [1] episodes, [2] overflow (sticky), [3] sequences, [4] batch complete
+                         (rows >= train_rows), [5] collects in this batch, [6] batches completed, [7] 0 */
+int hh_episodes_emit_append(const hh_episode_bufs *b, const hh_episode_aux *x, int64_t train_rows, int32_t *acc, int64_t *totals,
+                            void *stream);
+
 /* Episode metrics of one emitted whole-episode batch (RLlib's per-iteration result: episode_reward_mean/min/max, episode_len_mean,
  * episodes_this_iter, policy_reward_*, vf_explained_var, episodes_total, timesteps_total), computed on the device right behind
  * hh_episodes_emit / hh_commander_episodes_emit from the batch's reward / vf / target columns and its episode table.  Three launches

@@ -179,6 +179,13 @@ int hh_commander_episodes_emit(const hh_commander_episode_bufs *b, void *stream)
 struct hh_episode_aux;
 int hh_commander_episodes_emit_aux(const hh_commander_episode_bufs *b, const struct hh_episode_aux *x, void *stream);
 
+/* hh_commander_episodes_emit_aux (x = NULL: no aux column) that appends to the batch in place until it holds at least train_rows rows:
+ * hh_episodes_emit_append of hh_abi.h (acc i32 [HH_EP_ACC], totals NULL or i64 [2]; the same rules and errors), with the sequences:
+ * acc[3] is the sequence base, seq_start / seq_ep are absolute positions in the accumulated batch, and seq_cap is the accumulated
+ * batch's capacity (train_rows - 1 + N (T + carry_cap / L) never overflows: one-row episodes cost a sequence each). */
+int hh_commander_episodes_emit_append(const hh_commander_episode_bufs *b, const struct hh_episode_aux *x, int64_t train_rows,
+                                      int32_t *acc, int64_t *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

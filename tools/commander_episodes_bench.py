@@ -6,8 +6,11 @@ whole episodes in steady state; and the bytes the emission moves per collect (fo
 --metrics adds complete_episodes with metrics=True (the episode metrics behind the emitter, hh_episodes_metrics): what the flag costs a
 collect against complete_episodes without it, next to the emission's own overhead, and the three metrics launches alone on the last
 batch; with it only those lines are written, APPENDED to --out.
+--accumulate measures only what train_batch_size costs a collect: complete_episodes overwriting its batch against complete_episodes
+appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_timing.py: medians of 20 after 3 warm-up, the spread
+rule); its lines are APPENDED to --out.
     python tools/commander_episodes_bench.py [--arenas 8192] [--steps 16] [--horizon 500] [--warmup 8] [--collects 10] [--rounds 3]
-        [--logits] [--metrics] [--out profiles/commander_episodes.log]"""
+        [--logits] [--metrics] [--accumulate] [--out profiles/commander_episodes.log]"""
 import argparse
 import math
 import os
@@ -22,6 +25,7 @@ from hhmarl_2d_amd import _lib as L  # noqa: E402
 from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weights  # noqa: E402
 from hhmarl_2d_amd.pilots import VariantNetPilot  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
+from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
 from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
 
 ROW_IN = 3 * 34 * 4 + 3 + 3 * 4 * 3 + 3          # obs, actions, logp / vf / reward, valid of one arena row
@@ -29,11 +33,12 @@ ROW_OUT = ROW_IN + 3 * 4 * 2 + 1 + 3 * 4          # + adv / target, done, arena 
 STATE = 3 * 2 * 200 * 4                          # the GRU states of one arena row
 
 
-def make(N, T, H, mode):
+def make(N, T, H, mode, train_batch_size=None):
     w = World(make_config(n_arenas=N, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=1, auto_reset=True, horizon=H), device=0)
     net = CommanderNet(0, 3 * N).set_weights(random_weights(6))
     rec, met = mode.endswith("+logits"), mode.endswith("+metrics")
-    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode.split("+")[0], record_logits=rec, metrics=met)
+    return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode.split("+")[0], metrics=met, train_batch_size=train_batch_size,
+                            record_logits=rec)
 
 
 def ms_per_collect(ro, n):
@@ -71,8 +76,17 @@ def main():
     ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
     ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends only its lines to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_episodes.log"))
+    ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
     a = ap.parse_args()
     N, T, H = a.arenas, a.steps, a.horizon
+    if a.accumulate:
+        alines = [f"# tools/commander_episodes_bench.py --accumulate on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per "
+                  f"collect, VariantNetPilot, horizon {H}"]
+        alines += accumulate_lines(make(N, T, H, "complete_episodes"), make(N, T, H, "complete_episodes", train_batch_size=4 * N * T))
+        print("\n".join(alines), flush=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(alines) + "\n")
+        return
     lines = []
 
     def say(s):

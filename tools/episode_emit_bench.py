@@ -9,8 +9,11 @@ rocprofv3 --kernel-trace run) becomes bytes/s.
 --metrics adds complete_episodes with metrics=True (the episode metrics behind the emitter, hh_episodes_metrics): what the flag costs a
 collect (against complete_episodes without it, whose launches are the ones from before the flag existed), next to the emission's own
 overhead, and the time of the three metrics launches alone on the last batch; those lines are appended to --out.
+--accumulate measures only what train_batch_size costs a collect: complete_episodes overwriting its batch against complete_episodes
+appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_timing.py: medians of 20 after 3 warm-up, the spread
+rule); its lines are appended to --out.
     python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]
-        [--metrics [--out profiles/episode_emit.log]]"""
+        [--metrics [--out profiles/episode_emit.log]] | --accumulate [--arenas 16384] [--ticks 64] [--out ...]"""
 import argparse
 import os
 import statistics
@@ -22,12 +25,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hhmarl_2d_amd import pilots  # noqa: E402
 from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
+from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
 from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
 
 
-def make(N, T, mode):
+def make(N, T, mode, train_batch_size=None):
     w = World(make_config(n_arenas=N, level=3, seed=1, auto_reset=True), device=0)
     bank = pilots.PolicyBank.trainable_init(w.device, seed=0, max_rows=2 * N)
+    if train_batch_size is not None:
+        return PPORollout(w, bank, T, batch_mode=mode, train_batch_size=train_batch_size)
     if mode.endswith("+metrics"):
         return PPORollout(w, bank, T, batch_mode=mode[:-len("+metrics")], metrics=True)
     if mode.endswith("+logits"):
@@ -68,8 +74,16 @@ def main():
     ap.add_argument("--logits", action="store_true", help="also time both modes with record_logits=True")
     ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends its lines to --out")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "episode_emit.log"))
+    ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
     a = ap.parse_args()
     N, T = a.arenas, a.ticks
+    if a.accumulate:
+        lines = [f"# tools/episode_emit_bench.py --accumulate on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, level 3 fight"]
+        lines += accumulate_lines(make(N, T, "complete_episodes"), make(N, T, "complete_episodes", train_batch_size=4 * N * T))
+        print("\n".join(lines))
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     modes = ("truncate_episodes", "complete_episodes") + (("truncate_episodes+logits", "complete_episodes+logits") if a.logits else ()) + \
         (("complete_episodes+metrics",) if a.metrics else ())
     runs = {m: make(N, T, m) for m in modes}
