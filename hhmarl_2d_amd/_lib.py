@@ -133,7 +133,7 @@ LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_cate
                    "hh_residual_normalize_backward", "hh_input_stage_scratch_bytes", "hh_input_stage_forward",
                    "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward",
                    "hh_adam_step", "hh_minibatch_stage", "hh_train_commit", "hh_gru_seq_tile",
-                   "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped"]  # include/hh_learner.h
+                   "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped", "hh_minibatch_stage_gather"]  # include/hh_learner.h
 GRU_TILES = (16, 8, 4)  # the compiled instances of hh_k_gru_seq_fwd / _bwd (HH_GRU_TILE forces one; hh_gru_seq_tile tells which a call uses)
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
@@ -283,6 +283,7 @@ def lib():
         L.hh_dense_tanh_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HHDenseSrc), vp, vp, vp, vp, C.c_int64, vp]
         L.hh_adam_step.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]
         L.hh_minibatch_stage.argtypes = [C.c_int32, C.POINTER(HHStageCol), C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        L.hh_minibatch_stage_gather.argtypes = [C.c_int32, C.POINTER(HHStageCol), C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
         L.hh_train_commit.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
         L.hh_grad_norm_scratch_bytes.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), C.POINTER(C.c_int64)]
         L.hh_grad_norm.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), C.c_double, vp, vp, vp, C.c_int32, vp, C.c_int64, vp]

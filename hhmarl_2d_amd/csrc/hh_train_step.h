@@ -1,8 +1,8 @@
 /*
  * hh_train_step.h — what turns the PPO learner's minibatch step into a fixed chain of launches that a HIP graph can replay (C ABI at the
  * end of include/hh_learner.h): the Adam step of a whole module on the device (hh_adam_step), the minibatch's columns copied into
- * fixed-address staging buffers by a schedule table and a cursor that live on the device (hh_minibatch_stage), and the step's
- * bookkeeping (hh_train_commit).  Included from hh_world.hip (g_err, HIPCHK).
+ * fixed-address staging buffers by a schedule table and a cursor that live on the device (hh_minibatch_stage; through an order table,
+ * for shuffled minibatches: hh_minibatch_stage_gather), and the step's bookkeeping (hh_train_commit).  Included from hh_world.hip (g_err, HIPCHK).
  *
  * The counter hazard.  Two device counters steer a replayed step: the CURSOR (which schedule row the stage reads, which row of the
  * statistics table the commit fills) and Adam's T (the number of steps taken, from which the bias corrections follow).  Both change once
@@ -226,6 +226,109 @@ extern "C" int hh_minibatch_stage(int32_t n_cols, const hh_stage_col *cols, int3
     if (bx < 1) bx = 1;
     if (bx > HTS_STAGE_MAX_BLOCKS) bx = HTS_STAGE_MAX_BLOCKS;
     hipLaunchKernelGGL(hh_k_minibatch_stage, dim3((unsigned)bx, (unsigned)n_cols), dim3(HTS_THREADS), 0, (hipStream_t)stream, a, schedule, cursor, n_valid);
+    HIPCHK(hipGetLastError());
+    return HH_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------------------------ the gather stage
+ * hh_minibatch_stage with the chunks named by an order table: staged chunk i = source chunk order[o0 + i].  The unit of work is a SLOT (one
+ * staged chunk), and a group of G = 2^grp_log2 neighbouring lanes (1 .. 64, so a group never leaves its wave) copies it: lane l of the group
+ * moves units l, l + G, l + 2 G, ..  of the chunk, so the lanes of a group read and write consecutive units.  The host picks G per column so that a
+ * lane moves about four units: G = 1 for the one-unit chunks of the escape kinds (a lane per row), G = 64 for the fight kinds' chunks of
+ * hundreds of units (a wave per chunk).  Every lane of a group loads the slot's order entry itself — one address per group, once per slot,
+ * not per unit — and no division is needed: slot and lane come from shifts of the thread index.  Slots stride over the grid. */
+struct hts_gather_args {
+    hts_stage_col c[HH_STAGE_MAX_COLS];       /* `pad` holds grp_log2 here */
+    int32_t cap, sched_rows;
+    int64_t src_chunks, order_len;
+};
+
+template <typename T>
+__device__ __forceinline__ void hts_gather_slots(const hts_stage_col &c, const int32_t *__restrict__ order, int64_t o0, int32_t n, int32_t cap,
+                                                 int64_t src_chunks) {
+    const int g = c.pad;
+    const int32_t G = 1 << g, lane = (int32_t)threadIdx.x & (G - 1);
+    const int32_t upc = (int32_t)(c.chunk_bytes >> c.unit_log2);                     /* units per chunk: chunk_bytes <= 2^30 */
+    const int64_t groups = ((int64_t)gridDim.x * HTS_THREADS) >> g;
+    const T zero{};
+    for (int64_t slot = ((int64_t)blockIdx.x * HTS_THREADS + threadIdx.x) >> g; slot < cap; slot += groups) {
+        T *d = reinterpret_cast<T *>(c.dst + slot * c.chunk_bytes);
+        int64_t chunk = -1;
+        if (slot < n) chunk = order[o0 + slot];                                     /* o0 + slot < o1 <= order_len */
+        int32_t u = lane;
+        if (chunk >= 0 && chunk < src_chunks) {
+            const T *s = reinterpret_cast<const T *>(c.src + chunk * c.chunk_bytes);
+            for (; u + 3 * G < upc; u += 4 * G) {                                   /* four loads in flight per lane, as hts_copy_zero */
+                const T a = s[u], b = s[u + G], e = s[u + 2 * G], f = s[u + 3 * G];
+                d[u] = a; d[u + G] = b; d[u + 2 * G] = e; d[u + 3 * G] = f;
+            }
+            for (; u < upc; u += G) d[u] = s[u];
+        } else {
+            for (; u < upc; u += G) d[u] = zero;                                    /* behind the minibatch, or an entry that names no chunk */
+        }
+    }
+}
+
+__global__ __launch_bounds__(HTS_THREADS) void hh_k_minibatch_stage_gather(const hts_gather_args a, const int32_t *__restrict__ order,
+                                                                           const int32_t *__restrict__ schedule,
+                                                                           const int32_t *__restrict__ cursor, int32_t *__restrict__ n_valid) {
+    const int cur = cursor[0];
+    int64_t o0 = 0, o1 = 0;
+    int32_t nv = 0;
+    if (cur >= 0 && cur < a.sched_rows) {       /* a cursor beyond the table stages an empty minibatch: zeros everywhere, n_valid = 0 */
+        o0 = schedule[4 * (int64_t)cur]; o1 = schedule[4 * (int64_t)cur + 1]; nv = schedule[4 * (int64_t)cur + 2];
+    }
+    /* whatever the tables hold, nothing outside the order table, the source or the staging buffers is touched */
+    if (o0 < 0) o0 = 0;
+    if (o1 > a.order_len) o1 = a.order_len;
+    if (o1 < o0) o1 = o0;
+    if (o1 - o0 > a.cap) o1 = o0 + a.cap;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) n_valid[0] = nv;
+    const hts_stage_col c = a.c[blockIdx.y];
+    const int32_t n = (int32_t)(o1 - o0);
+    switch (c.unit_log2) {
+        case 4: hts_gather_slots<uint4>(c, order, o0, n, a.cap, a.src_chunks); break;
+        case 3: hts_gather_slots<uint2>(c, order, o0, n, a.cap, a.src_chunks); break;
+        case 2: hts_gather_slots<uint32_t>(c, order, o0, n, a.cap, a.src_chunks); break;
+        case 1: hts_gather_slots<uint16_t>(c, order, o0, n, a.cap, a.src_chunks); break;
+        default: hts_gather_slots<unsigned char>(c, order, o0, n, a.cap, a.src_chunks); break;
+    }
+}
+
+extern "C" int hh_minibatch_stage_gather(int32_t n_cols, const hh_stage_col *cols, int32_t chunk_len, int32_t cap, int64_t src_chunks,
+                                         const int32_t *order, int64_t order_len, const int32_t *schedule, int32_t sched_rows,
+                                         const int32_t *cursor, int32_t *n_valid, void *stream) {
+    if (n_cols < 0 || n_cols > HH_STAGE_MAX_COLS || cap < 1 || chunk_len < 1 || src_chunks < 0 || sched_rows < 0 || order_len < 0 || !order ||
+        !schedule || !cursor || !n_valid || (n_cols > 0 && !cols)) {
+        g_err = "hh_minibatch_stage_gather: need 0 <= n_cols <= 8, cap >= 1, chunk_len >= 1, src_chunks >= 0, sched_rows >= 0, order_len >= 0 and no null pointer";
+        return HH_E_ARG;
+    }
+    hts_gather_args a;
+    memset(&a, 0, sizeof(a));
+    a.cap = cap; a.sched_rows = sched_rows; a.src_chunks = src_chunks; a.order_len = order_len;
+    int64_t most = 0;
+    for (int32_t i = 0; i < n_cols; i++) {
+        const int64_t cb = cols[i].chunk_bytes;
+        if (!cols[i].src || !cols[i].dst || cb < 1 || cb % chunk_len || cb > ((int64_t)1 << 30)) {
+            g_err = "hh_minibatch_stage_gather: a column with a null pointer, or chunk_bytes that is not a positive multiple of chunk_len (at most 2^30)"; return HH_E_ARG;
+        }
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(cols[i].src) | reinterpret_cast<uintptr_t>(cols[i].dst) | (uintptr_t)cb;
+        int lg = 4;
+        while (lg > 0 && (bits & (((uintptr_t)1 << lg) - 1))) lg--;
+        const int64_t upc = cb >> lg;
+        int g = 0;
+        while (g < 6 && ((int64_t)4 << g) < upc) g++;          /* the smallest group, up to a wave, whose lanes move at most four units each */
+        a.c[i].src = (const unsigned char *)cols[i].src; a.c[i].dst = (unsigned char *)cols[i].dst; a.c[i].chunk_bytes = cb; a.c[i].unit_log2 = lg;
+        a.c[i].pad = g;
+        const int64_t threads = (int64_t)cap << g;
+        if (threads > most) most = threads;
+    }
+    if (n_cols == 0) return HH_OK;
+    int64_t bx = (most + HTS_THREADS - 1) / HTS_THREADS;        /* a group per slot of the widest column, grid-stride beyond the cap */
+    if (bx < 1) bx = 1;
+    if (bx > HTS_STAGE_MAX_BLOCKS) bx = HTS_STAGE_MAX_BLOCKS;
+    hipLaunchKernelGGL(hh_k_minibatch_stage_gather, dim3((unsigned)bx, (unsigned)n_cols), dim3(HTS_THREADS), 0, (hipStream_t)stream, a, order, schedule,
+                       cursor, n_valid);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }

@@ -665,6 +665,40 @@ def minibatch_order(n, seed, update, policy, sgd_pass):
     return np.random.default_rng([int(seed), int(update), int(policy), int(sgd_pass)]).permutation(int(n))
 
 
+def sequence_order(n, seed, update, policy, sgd_pass):
+    """shuffle_sequences: the order of one pass's n chunks (escape: rows), a permutation keyed by (seed, update count, policy, pass) and a
+    fifth entry 1 that keeps it a different stream from minibatch_order's -> int64 [n]"""
+    return np.random.default_rng([int(seed), int(update), int(policy), int(sgd_pass), 1]).permutation(int(n))
+
+
+def shuffled_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, policy):
+    """shuffle_sequences: the minibatch steps of one update over S chunks of these lengths (host integers [S]) as hh_minibatch_stage_gather's
+    two tables -> (order int32 [num_sgd_iter * S], sched int32 [n_steps, 4]).  Pass p owns order[p S:(p + 1) S] = sequence_order(S, seed,
+    update, policy, p); its minibatches are minibatch_partition's of the lengths in that order — consecutive runs of at least
+    sgd_minibatch_size unpadded rows, the last one what is left — visited in position order.  A schedule row is (o0, o1, unpadded rows, 0)
+    with o0, o1 absolute positions in order; the passes may differ in their number of steps."""
+    seq_len = np.asarray(seq_len, dtype=np.int64).reshape(-1)
+    S, passes = len(seq_len), int(num_sgd_iter)
+    if passes * S > np.iinfo(np.int32).max:
+        raise ValueError(f"shuffled_schedule: the order table of {passes} passes over {S} chunks does not fit int32 positions")
+    order = np.empty((max(passes, 0) * S,), dtype=np.int32)
+    rows = []
+    for p in range(passes):
+        perm = sequence_order(S, seed, update, policy, p)
+        order[p * S:(p + 1) * S] = perm
+        lens = seq_len[perm]
+        csum = np.concatenate([[0], np.cumsum(lens)])
+        rows += [(p * S + s0, p * S + s1, int(csum[s1] - csum[s0]), 0) for s0, s1 in minibatch_partition(lens, sgd_minibatch_size)]
+    return order, np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+
+
+def _shuffle_flag(shuffle_sequences):
+    """RLlib's shuffle_sequences: a bool and nothing else (1, "yes" and None are refused)"""
+    if not isinstance(shuffle_sequences, bool):
+        raise ValueError(f"shuffle_sequences is True or False, got {shuffle_sequences!r}")
+    return shuffle_sequences
+
+
 def kl_coeff_update(kl_coeff, sampled_kl, kl_target):
     """KLCoeffMixin.update_kl (ray/rllib/policy/torch_mixins.py): above 2 x target the coefficient grows by 1.5, below 0.5 x target it halves"""
     if sampled_kl > 2.0 * kl_target:
@@ -841,26 +875,66 @@ def minibatch_stage(cols, staged, chunk_len, schedule, cursor, n_valid, src_chun
     int32 [1] receives the row's third entry.  Chunks beyond the minibatch's are zeroed in every staged tensor.  src_chunks: the chunks the
     kernel may read of every column (default S).  The cursor is not written.  No host synchronisation, HIP-graph capturable."""
     _need_gpu("minibatch_stage")
+    dev, desc, cap, src_chunks = _stage_desc("minibatch_stage", cols, staged, (("schedule", schedule), ("cursor", cursor), ("n_valid", n_valid)), src_chunks)
+    L.check(L.lib().hh_minibatch_stage(len(cols), desc, int(chunk_len), cap, src_chunks, _p(schedule), schedule.shape[0], _p(cursor), _p(n_valid), _stream(dev)))
+
+
+def _stage_desc(who, cols, staged, tables, src_chunks):
+    """the checks that minibatch_stage and minibatch_stage_gather share -> (device, hh_stage_col array, cap, src_chunks); tables: (name,
+    tensor) pairs that end with schedule, cursor and n_valid"""
     if len(cols) != len(staged) or len(cols) > L.STAGE_MAX_COLS:
-        raise ValueError(f"minibatch_stage: as many staging buffers as columns, at most {L.STAGE_MAX_COLS}")
+        raise ValueError(f"{who}: as many staging buffers as columns, at most {L.STAGE_MAX_COLS}")
+    (_, schedule), (_, cursor), (_, n_valid) = tables[-3:]
     dev = cursor.device
-    for what, x in (("schedule", schedule), ("cursor", cursor), ("n_valid", n_valid)):
+    for what, x in tables:
         if not (x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.device == dev):
-            raise ValueError(f"minibatch_stage: {what} is a contiguous int32 CUDA tensor (the torch-op form is minibatch_stage_torch)")
+            raise ValueError(f"{who}: {what} is a contiguous int32 CUDA tensor (the torch-op form is {who}_torch)")
     if schedule.dim() != 2 or schedule.shape[1] != 4 or cursor.numel() != 1 or n_valid.numel() != 1:
-        raise ValueError("minibatch_stage: schedule is [n_steps, 4], cursor and n_valid hold one element")
+        raise ValueError(f"{who}: schedule is [n_steps, 4], cursor and n_valid hold one element")
     S = cols[0].shape[0] if cols else 0
     cap = staged[0].shape[0] if staged else 1
     desc = (L.HHStageCol * max(len(cols), 1))()
     for i, (c, s) in enumerate(zip(cols, staged)):
         if not (c.is_cuda and s.is_cuda and c.device == dev and s.device == dev and c.is_contiguous() and s.is_contiguous() and c.dtype == s.dtype
                 and c.shape[1:] == s.shape[1:] and c.shape[0] == S and s.shape[0] == cap and c.dim() >= 1):
-            raise ValueError("minibatch_stage: a column is a contiguous CUDA tensor [S, ...] and its staging buffer [cap, ...] has its dtype and trailing shape")
+            raise ValueError(f"{who}: a column is a contiguous CUDA tensor [S, ...] and its staging buffer [cap, ...] has its dtype and trailing shape")
         desc[i].src, desc[i].dst, desc[i].chunk_bytes = c.data_ptr(), s.data_ptr(), (c.numel() // S if S else s.numel() // cap) * c.element_size()
     src_chunks = S if src_chunks is None else int(src_chunks)
     if not 0 <= src_chunks <= S:
-        raise ValueError(f"minibatch_stage: src_chunks is within the columns' {S} chunks")
-    L.check(L.lib().hh_minibatch_stage(len(cols), desc, int(chunk_len), cap, src_chunks, _p(schedule), schedule.shape[0], _p(cursor), _p(n_valid), _stream(dev)))
+        raise ValueError(f"{who}: src_chunks is within the columns' {S} chunks")
+    return dev, desc, cap, src_chunks
+
+
+def minibatch_stage_gather(cols, staged, chunk_len, order, schedule, cursor, n_valid, src_chunks=None):
+    """minibatch_stage through an order table (hh_minibatch_stage_gather, include/hh_learner.h): schedule[cursor] = (o0, o1, unpadded rows, 0)
+    names positions of `order` (a contiguous int32 [n] CUDA tensor on the same device), and staged chunk i becomes chunk order[o0 + i] of
+    every column — zero where that entry names no chunk of [0, src_chunks) and behind the minibatch.  Everything else is minibatch_stage's:
+    ONE launch, the tables only read, no host synchronisation, HIP-graph capturable."""
+    _need_gpu("minibatch_stage_gather")
+    dev, desc, cap, src_chunks = _stage_desc("minibatch_stage_gather", cols, staged,
+                                             (("order", order), ("schedule", schedule), ("cursor", cursor), ("n_valid", n_valid)), src_chunks)
+    if order.dim() != 1 or order.numel() == 0:
+        raise ValueError("minibatch_stage_gather: order is [n], n >= 1 (an empty tensor has no address to hand over)")
+    L.check(L.lib().hh_minibatch_stage_gather(len(cols), desc, int(chunk_len), cap, src_chunks, C.c_void_p(order.data_ptr()), order.shape[0], _p(schedule),
+                                              schedule.shape[0], _p(cursor), _p(n_valid), _stream(dev)))
+
+
+def minibatch_stage_gather_torch(cols, cap, idx):
+    """minibatch_stage_gather with torch ops, any device: idx = the minibatch's order entries (integers [n], n <= cap) -> per column a new
+    tensor [cap, ...]: chunk idx[i] at place i (index_select), zero where idx[i] names no chunk of the column, zeros behind"""
+    out = []
+    for c in cols:
+        ix = torch.as_tensor(np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64), device=c.device).reshape(-1)
+        if ix.numel() > int(cap):
+            raise ValueError(f"minibatch_stage_gather_torch: {ix.numel()} chunks do not fit cap = {int(cap)}")
+        ok = (ix >= 0) & (ix < c.shape[0])
+        z = torch.zeros((int(cap),) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device)
+        if c.shape[0] and ix.numel():
+            got = c.index_select(0, torch.where(ok, ix, torch.zeros_like(ix)))
+            got[~ok] = 0
+            z[:ix.numel()] = got
+        out.append(z)
+    return out
 
 
 def minibatch_stage_torch(cols, cap, row):
@@ -938,6 +1012,7 @@ class _StepBook:
         self.table = torch.zeros((0, len(L.PPO_STATS)), dtype=torch.float64, device=device)
         self.schedule = torch.zeros((0, 4), dtype=torch.int32, device=device)
         self.src, self.staged, self.graph, self.key, self.keep = {}, {}, None, None, None
+        self.order = None       # shuffle_sequences: the order table int32 [>= num_sgd_iter * S] (load_order); never allocated without it
         self.captures = 0
 
     @staticmethod
@@ -964,6 +1039,13 @@ class _StepBook:
         sched = torch.from_numpy(np.ascontiguousarray(schedule, dtype=np.int32)).to(self.device)
         self.schedule = self._grown(self.schedule, sched.shape[0], (4,), torch.int32, self.device)
         self.schedule[:sched.shape[0]].copy_(sched)
+
+    def load_order(self, order):
+        """shuffle_sequences: the update's order table into its persistent buffer (grown like the schedule; 4 bytes per pass and chunk)"""
+        order = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(self.device)
+        self.order = self._grown(self.order, order.shape[0], (), torch.int32, self.device)
+        self.order[:order.shape[0]].copy_(order)
+        self.order_len = order.shape[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the learner
@@ -993,7 +1075,8 @@ class PPOLearner:
       * fight kinds: each episode cut into chunks of max_seq_len, zero-padded, mask = the unpadded rows;
       * num_sgd_iter passes; in each the chunks (escape: rows), in batch order, are split into consecutive minibatches of at least
         sgd_minibatch_size unpadded rows, visited in the order of minibatch_order(seed, update count, policy, pass).  RLlib's own
-        order is drawn from an unseeded generator and shuffles the chunks themselves; this one is reproducible by construction;
+        order is drawn from an unseeded generator and shuffles the chunks themselves; this one is reproducible by construction, and
+        shuffle_sequences=True shuffles the chunks themselves as well, per pass, from a seeded stream of its own (shuffled_schedule);
       * after the passes KLCoeffMixin.update_kl on the mean of the minibatches' mean_kl.
     fused = False computes the loss with torch ops (ppo_loss_torch) instead of hh_ppo_loss; nothing else differs.
     Inside a minibatch step nothing synchronises with the host (beyond what torch.optim.Adam does by itself); `update` itself synchronises
@@ -1001,7 +1084,7 @@ class PPOLearner:
 
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
                  vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch",
-                 optimizer="torch", step="eager", grad_clip=None):
+                 optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
         argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
@@ -1017,10 +1100,19 @@ class PPOLearner:
         of update() also has grad_gnorm, the mean over the update's steps of the norm BEFORE clipping (RLlib reports it under the same
         condition).  optimizer="torch" calls torch.nn.utils.clip_grad_norm_ (float32 norm, scales .grad in place); "fused" computes the
         norm in float64 on the device and scales inside the Adam step (DeviceAdam(max_norm=...): .grad keeps the unscaled gradient), and
-        the graph's chain becomes stage -> forward -> loss -> backward -> norm -> clipped Adam -> commit."""
+        the graph's chain becomes stage -> forward -> loss -> backward -> norm -> clipped Adam -> commit.
+        shuffle_sequences: RLlib's shuffle_sequences (its default is True; here False, and then nothing changes).  True: every pass draws
+        its own order of the chunks (escape: rows), sequence_order(seed, update count, policy, pass), and cuts THAT order into consecutive
+        minibatches of at least sgd_minibatch_size unpadded rows (shuffled_schedule), visited in position order: the minibatches hold
+        different chunks in every pass, and a pass may take one step more or fewer than another.  The eager modes gather each minibatch with
+        index_select; step="graph" stages through hh_minibatch_stage_gather from an order table uploaded once per update into a persistent
+        device buffer of 4 * num_sgd_iter * S bytes for S chunks, grown to twice the need so that its address outlives batches of varying
+        size (30 passes: about 6.6 MB for 1.09 M fight rows in chunks of 20, about 131 MB for the same rows as escape rows).  RLlib's own
+        permutation is unseeded, so equality with it is not claimed; what shuffling does to learning curves has not been measured here."""
         self.optimizer = _optimizer_mode(optimizer)
         self.step = _step_mode(step, optimizer)
         self.grad_clip = _grad_clip(grad_clip)
+        self.shuffle_sequences = _shuffle_flag(shuffle_sequences)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -1135,7 +1227,10 @@ class PPOLearner:
         minibatch step captured — stage, forward, loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only —
         unless the graph of an earlier call still fits: it is kept while cap, kl_coeff (which travels by value in hh_ppo_loss_params) and the
         buffers' addresses are what they were (with grad_clip also its value, which travels by value, and the norm table's address).  cap: the staging capacity in chunks (escape: rows); default and minimum: the largest
-        minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)"""
+        minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)
+        With shuffle_sequences the schedule is shuffled_schedule's, its order table is uploaded beside it (4 bytes per pass and chunk), the
+        stage is minibatch_stage_gather, cap defaults to the largest minibatch over all passes, and the key also holds the flag and the
+        order buffer's address and length."""
         if self.step != "graph":
             raise ValueError('graph_prepare needs PPOLearner(step="graph")')
         book = self._books[agent]
@@ -1147,15 +1242,22 @@ class PPOLearner:
             seq_len = np.ones(S, dtype=np.int64)
             cols["mask"] = torch.ones((S,), dtype=torch.uint8, device=self.device)      # padding rows of the staging buffers need one
         cols["mask"] = cols["mask"].to(torch.uint8)
-        parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-        csum = np.concatenate([[0], np.cumsum(seq_len)])
-        sched = minibatch_schedule(parts, [csum[s1] - csum[s0] for s0, s1 in parts], self.num_sgd_iter, self.seed, self.updates, agent)
-        need = max(s1 - s0 for s0, s1 in parts)
+        order = None
+        if self.shuffle_sequences:      # per pass its own order of the chunks and that order's partition; the stage gathers through the table
+            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, agent)
+            need = int((sched[:, 1] - sched[:, 0]).max()) if len(sched) else 1
+        else:
+            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+            csum = np.concatenate([[0], np.cumsum(seq_len)])
+            sched = minibatch_schedule(parts, [csum[s1] - csum[s0] for s0, s1 in parts], self.num_sgd_iter, self.seed, self.updates, agent)
+            need = max(s1 - s0 for s0, s1 in parts)
         cap = need if cap is None else int(cap)
         if cap < need:
             raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} chunks)")
         book.begin(len(sched), self.optimizers[agent])
         book.load(cols, sched)
+        if order is not None:
+            book.load_order(order)
         book.n_steps, book.cap = len(sched), cap
         src_chunks = min(t.shape[0] for t in book.src.values())
         names = tuple(cols)
@@ -1164,6 +1266,8 @@ class PPOLearner:
             book.src[k].data_ptr() for k in names)
         if self.grad_clip is not None:
             key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
+        if self.shuffle_sequences:
+            key += (True, book.order.data_ptr(), book.order.shape[0])
         if book.graph is None or book.key != key:
             self._capture(agent, book, names, src_chunks)
             book.key = key
@@ -1178,7 +1282,10 @@ class PPOLearner:
         Lc = self.max_seq_len if self.recurrent else 1
 
         def stage():
-            minibatch_stage(srcs, staged, Lc, book.schedule, book.cursor, book.n_valid)
+            if self.shuffle_sequences:
+                minibatch_stage_gather(srcs, staged, Lc, book.order, book.schedule, book.cursor, book.n_valid)
+            else:
+                minibatch_stage(srcs, staged, Lc, book.schedule, book.cursor, book.n_valid)
 
         def forward_backward():
             logits, vf = module(mb["obs"], mb["critic"])
@@ -1256,20 +1363,32 @@ class PPOLearner:
                 seq_len = b["seq_len"].cpu().numpy()
             else:
                 seq_len = np.ones(b["obs"].shape[0], dtype=np.int64)
-            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-            csum = np.concatenate([[0], np.cumsum(seq_len)])
-            n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
             cols = [k for k in b if k != "seq_len"]
             all_stats = []
-            if self.optimizer == "fused":
-                self._books[agent].begin(self.num_sgd_iter * len(parts), self.optimizers[agent])
             self._gnorms[agent] = []
-            for sgd_pass in range(self.num_sgd_iter):
-                for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
-                    s0, s1 = parts[i]
-                    mb = {k: b[k][s0:s1] for k in cols}
+            if self.shuffle_sequences:      # shuffled_schedule's steps in its order, each minibatch gathered by its order entries
+                order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, agent)
+                order = torch.from_numpy(order).to(b["obs"].device).long()
+                n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(b["obs"].device)
+                if self.optimizer == "fused":
+                    self._books[agent].begin(len(sched), self.optimizers[agent])
+                for i, (o0, o1) in enumerate(sched[:, :2].tolist()):
+                    idx = order[o0:o1]
+                    mb = {k: b[k].index_select(0, idx) for k in cols}
                     mb["n_valid"] = n_valid[i:i + 1]
                     all_stats.append(self.minibatch_step(agent, mb))
+            else:
+                parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+                csum = np.concatenate([[0], np.cumsum(seq_len)])
+                n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
+                if self.optimizer == "fused":
+                    self._books[agent].begin(self.num_sgd_iter * len(parts), self.optimizers[agent])
+                for sgd_pass in range(self.num_sgd_iter):
+                    for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
+                        s0, s1 = parts[i]
+                        mb = {k: b[k][s0:s1] for k in cols}
+                        mb["n_valid"] = n_valid[i:i + 1]
+                        all_stats.append(self.minibatch_step(agent, mb))
             m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
             if self.use_kl and all_stats:
                 self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
@@ -1634,7 +1753,7 @@ class CommanderLearner:
 
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
                  entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch",
-                 optimizer="torch", step="eager", grad_clip=None):
+                 optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
         """state_dict: CommanderGru's tensors (numpy or torch), keyed like commander.state_keys().  inputs: CommanderTrainable's argument
         ("fused": inp1..inp4 and v1..v4 through hh_input_stage_*); trunk: its argument too ("fused": shared_layer through hh_dense_tanh_*).
         optimizer, step: PPOLearner's arguments, with its values, defaults and validation.  optimizer="fused" makes `self.optimizer` a
@@ -1642,10 +1761,17 @@ class CommanderLearner:
         (hh_train_commit); step="graph" (needs optimizer="fused") captures stage -> stage -> forward -> loss -> backward -> Adam -> commit
         once as ONE HIP graph and replays it per minibatch step (graph_prepare).  The modes are kept in `optimizer_mode` and `step`.
         grad_clip: PPOLearner's argument (None: nothing changes; else the global L2 norm of the module's gradients is clipped to it in every
-        step — norm -> clipped Adam in the fused modes and in the graph — and update() also returns grad_gnorm)."""
+        step — norm -> clipped Adam in the fused modes and in the graph — and update() also returns grad_gnorm).
+        shuffle_sequences: PPOLearner's argument (False, the default: nothing changes).  True: every pass draws its own order of the 3 S
+        sequences, sequence_order(seed, update count, 0, pass), and cuts that order into minibatches (shuffled_schedule); state_in and
+        seq_len travel with their sequences.  The eager modes gather with index_select; the graph's two stage launches become
+        hh_minibatch_stage_gather through one order table of 4 * num_sgd_iter * 3 S bytes, uploaded once per update into a persistent
+        buffer (grown to twice the need).  Slot 0 of a staged minibatch is a real sequence, so seq_len[0] >= 1 holds as before.  What
+        shuffling does to learning curves has not been measured here."""
         self.optimizer_mode = _optimizer_mode(optimizer)
         self.step = _step_mode(step, optimizer)
         self.grad_clip = _grad_clip(grad_clip)
+        self.shuffle_sequences = _shuffle_flag(shuffle_sequences)
         if not torch.cuda.is_available():
             raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -1741,7 +1867,9 @@ class CommanderLearner:
         (with grad_clip also its value, which travels by value, and the norm table's address).
         cap: the staging capacity in sequences; default and minimum: the largest minibatch.  The sequences of the staging buffers beyond a
         minibatch's are zero in every column: sequences of length 0 (hh_gru_seq_*'s contract) whose rows the mask drops.  Weights, m, v, t
-        are left bit for bit as they were.  -> (n_steps, rows)"""
+        are left bit for bit as they were.  -> (n_steps, rows)
+        With shuffle_sequences the schedule is shuffled_schedule's, its order table is uploaded beside it, both stages are
+        minibatch_stage_gather, and the key also holds the flag and the order buffer's address and length."""
         if self.step != "graph":
             raise ValueError('graph_prepare needs CommanderLearner(step="graph")')
         missing = [k for k in COMMANDER_STAGE_COLS if k not in b]
@@ -1751,13 +1879,20 @@ class CommanderLearner:
         cols = {k: b[k].contiguous() for k in COMMANDER_STAGE_COLS}
         cols["mask"], cols["seq_len"] = cols["mask"].to(torch.uint8), cols["seq_len"].to(torch.int32)
         seq_len = cols["seq_len"].cpu().numpy()
-        parts, sched = sequence_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
-        need = max(s1 - s0 for s0, s1 in parts)
+        order = None
+        if self.shuffle_sequences:      # per pass its own order of the sequences and that order's partition; both stages gather through the table
+            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
+            need = int((sched[:, 1] - sched[:, 0]).max()) if len(sched) else 1
+        else:
+            parts, sched = sequence_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
+            need = max(s1 - s0 for s0, s1 in parts)
         cap = need if cap is None else int(cap)
         if cap < need:
             raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} sequences)")
         book.begin(len(sched), self.optimizer)
         book.load(cols, sched)
+        if order is not None:
+            book.load_order(order)
         book.n_steps, book.cap = len(sched), cap
         src_chunks = min(t.shape[0] for t in book.src.values())
         kl = self.kl_coeff if self.use_kl else 0.0
@@ -1765,6 +1900,8 @@ class CommanderLearner:
                book.table.shape[0]) + tuple(book.src[k].data_ptr() for k in COMMANDER_STAGE_COLS)
         if self.grad_clip is not None:
             key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
+        if self.shuffle_sequences:
+            key += (True, book.order.data_ptr(), book.order.shape[0])
         if book.graph is None or book.key != key:
             self._capture(book, src_chunks)
             book.key = key
@@ -1781,8 +1918,11 @@ class CommanderLearner:
 
         def stage():
             for ks, chunk_len in groups:
-                minibatch_stage([book.src[k][:src_chunks] for k in ks], [book.staged[k] for k in ks], chunk_len, book.schedule, book.cursor,
-                                book.n_valid)
+                srcs, staged = [book.src[k][:src_chunks] for k in ks], [book.staged[k] for k in ks]
+                if self.shuffle_sequences:
+                    minibatch_stage_gather(srcs, staged, chunk_len, book.order, book.schedule, book.cursor, book.n_valid)
+                else:
+                    minibatch_stage(srcs, staged, chunk_len, book.schedule, book.cursor, book.n_valid)
 
         def forward_backward():
             logits, vf = self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused)
@@ -1859,19 +1999,31 @@ class CommanderLearner:
             return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=n_steps, rows=n_rows,
                         **clipped)
         seq_len = b["seq_len"].cpu().numpy()
-        parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-        csum = np.concatenate([[0], np.cumsum(seq_len)])
-        n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
         all_stats = []
-        if self.optimizer_mode == "fused":
-            self._book.begin(self.num_sgd_iter * len(parts), self.optimizer)
         self._gnorms = []
-        for sgd_pass in range(self.num_sgd_iter):
-            for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
-                s0, s1 = parts[i]
-                mb = {k: v[s0:s1] for k, v in b.items()}
+        if self.shuffle_sequences:      # shuffled_schedule's steps in its order, every column (state_in and seq_len too) gathered by the order entries
+            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
+            order = torch.from_numpy(order).to(b["obs"].device).long()
+            n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(b["obs"].device)
+            if self.optimizer_mode == "fused":
+                self._book.begin(len(sched), self.optimizer)
+            for i, (o0, o1) in enumerate(sched[:, :2].tolist()):
+                idx = order[o0:o1]
+                mb = {k: v.index_select(0, idx) for k, v in b.items()}
                 mb["n_valid"] = n_valid[i:i + 1]
                 all_stats.append(self.minibatch_step(mb))
+        else:
+            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
+            csum = np.concatenate([[0], np.cumsum(seq_len)])
+            n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
+            if self.optimizer_mode == "fused":
+                self._book.begin(self.num_sgd_iter * len(parts), self.optimizer)
+            for sgd_pass in range(self.num_sgd_iter):
+                for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
+                    s0, s1 = parts[i]
+                    mb = {k: v[s0:s1] for k, v in b.items()}
+                    mb["n_valid"] = n_valid[i:i + 1]
+                    all_stats.append(self.minibatch_step(mb))
         m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
         if self.use_kl and all_stats:
             self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)

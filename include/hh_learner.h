@@ -305,6 +305,18 @@ typedef struct hh_stage_col {    /* field order is ABI; host struct of device po
 int hh_minibatch_stage(int32_t n_cols, const hh_stage_col *cols, int32_t chunk_len, int32_t cap, int64_t src_chunks, const int32_t *schedule,
                        int32_t sched_rows, const int32_t *cursor, int32_t *n_valid, void *stream);
 
+/* hh_minibatch_stage with the chunks named by an ORDER TABLE, so that a minibatch may hold any chunks of the batch in any order (the
+ * learners' shuffle_sequences).  ONE launch: with (o0, o1, nv, 0) = schedule[cursor[0]] — o0, o1 positions in order ([dev] i32 [order_len]) —
+ * clamped to 0 <= o0 <= o1 <= order_len and o1 - o0 <= cap, staged chunk i < o1 - o0 of every column is its source chunk c = order[o0 + i],
+ * byte for byte, where 0 <= c < src_chunks, and zero for any other c; chunks o1-o0 .. cap-1 of every staging buffer become zero (on every
+ * call), and n_valid[0] = nv.  A cursor outside [0, sched_rows) stages an empty minibatch.  cursor, order and schedule are only read, and no
+ * content of either table makes the kernel touch memory outside the tables, the columns and the staging buffers.  Arguments, refusals, copy
+ * units and the column limit are hh_minibatch_stage's, and HH_E_ARG also for a null order or order_len < 0.  A group of 1 .. 64 lanes
+ * copies one staged chunk (about four copy units per lane) and reads its order entry once.  The same inputs give the same bytes. */
+int hh_minibatch_stage_gather(int32_t n_cols, const hh_stage_col *cols, int32_t chunk_len, int32_t cap, int64_t src_chunks,
+                              const int32_t *order, int64_t order_len, const int32_t *schedule, int32_t sched_rows,
+                              const int32_t *cursor, int32_t *n_valid, void *stream);
+
 /* The step's bookkeeping, one thread: table[cursor[0]] = stats (f64 [HH_PPO_STATS], hh_ppo_loss's; skipped when cursor[0] is outside
  * [0, table_rows)), cursor[0] += 1, step[0] += 1.  All pointers [dev]. */
 int hh_train_commit(const double *stats, double *table, int32_t table_rows, int32_t *cursor, int32_t *step, void *stream);

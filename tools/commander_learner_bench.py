@@ -19,6 +19,10 @@
   tile    --tile: the compiled tiles of hh_k_gru_seq_fwd / _bwd, each forced through HH_GRU_TILE in a child process of its own: both GRUs'
           forward + backward kernels alone at --tile-seqs sequence counts (13 ... 854) and the graph step at 256 rows; then every narrow
           tile against tile 16 by the same rule; appended to --out
+  shuffle --shuffle: CommanderLearner(shuffle_sequences=True) against shuffle_sequences=False as a COST, both in one process: the two stage
+          launches alone (hh_minibatch_stage against hh_minibatch_stage_gather drawing from the whole batch), the graph step at 256 and
+          16384 rows, one whole update at sgd_minibatch_size = 256 (medians of --iters updates), the host time of shuffled_schedule and
+          the order table's bytes; appended to --out.  The same spread rule, worded cost / gain / no difference
 Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
 that fails or runs out of time ends the run, nothing is retried.
     python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
@@ -419,6 +423,108 @@ def step_clip(a, say):
             f"{', '.join(f'{x:.4f}' for x in bursts['with'])}")
 
 
+def step_shuffle(a, say):
+    """CommanderLearner(shuffle_sequences=True) against shuffle_sequences=False (the step as it was), both in this run, as a cost: the two
+    stage launches alone (contiguous against gathered from the whole batch), the graph step at 256 and 16384 rows, one whole update at
+    sgd_minibatch_size = 256, the host time of shuffled_schedule and the order table's bytes."""
+    import numpy as np
+    import torch
+    from hhmarl_2d_amd import _lib as L
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    med = statistics.median
+    FUSED = dict(inputs="fused")
+    ro, net, b, seq_len = _policy_batch(a, **FUSED)
+    S = len(seq_len)
+    say(f"# tools/commander_learner_bench.py --shuffle on {torch.cuda.get_device_name(0)}: CommanderLearner(shuffle_sequences=True) against "
+        f"shuffle_sequences=False, both in this run; {a.arenas} arenas, T = {a.T}: {S} sequences, {int(seq_len.sum())} rows; inputs = fused, graph "
+        f"step; {a.iters} timed runs after {a.warmup} warm-up (a later run, appended):")
+
+    def cost(t_base, t_new):
+        spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+        d = med(t_new) - med(t_base)
+        word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+        return f"off -> on: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+    # (a) the two stage launches alone, on the same columns: the first n sequences against n sequences drawn from the whole batch
+    groups = [(LR.COMMANDER_STAGE_COLS[:L.STAGE_MAX_COLS], 20), (LR.COMMANDER_STAGE_COLS[L.STAGE_MAX_COLS:], 1)]
+    cols = {k: b[k].contiguous() for k in LR.COMMANDER_STAGE_COLS}
+    cols["mask"], cols["seq_len"] = cols["mask"].to(torch.uint8), cols["seq_len"].to(torch.int32)
+    order = torch.from_numpy(LR.sequence_order(S, 6, 0, 0, 0).astype(np.int32)).to(dev)
+    cur, nv = torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+    for size in (256, 16384):
+        n = LR.minibatch_partition(seq_len, size)[0][1]
+        staged = {k: torch.zeros((n,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev) for k, c in cols.items()}
+        sched = torch.tensor([(0, n, 0, 0)], dtype=torch.int32, device=dev)
+        nbytes = 2 * sum(st.numel() * st.element_size() for st in staged.values())
+
+        def plain():
+            for ks, chunk_len in groups:
+                LR.minibatch_stage([cols[k] for k in ks], [staged[k] for k in ks], chunk_len, sched, cur, nv)
+
+        def gather():
+            for ks, chunk_len in groups:
+                LR.minibatch_stage_gather([cols[k] for k in ks], [staged[k] for k in ks], chunk_len, order, sched, cur, nv)
+        t_p, t_g = events(plain, a.iters, a.warmup), events(gather, a.iters, a.warmup)
+        say(f"    the two stage launches alone, ten columns, {n} sequences ({nbytes / 1e6:.2f} MB read + written): hh_minibatch_stage {q(t_p)} = "
+            f"{nbytes / med(t_p) / 1e6:.1f} GB/s; hh_minibatch_stage_gather {q(t_g)} = {nbytes / med(t_g) / 1e6:.1f} GB/s; {cost(t_p, t_g)}")
+    # (b) the graph step
+    K = 50
+    for size in (256, 16384):
+        sub, _, n_seq, n_rows = _one_minibatch(b, seq_len, size)
+        n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+        ts, bursts = {}, {}
+        for flag in (False, True):
+            lr, _ = _graph_learner(sub, n_total, shuffle_sequences=flag, **FUSED)
+            ts[flag] = events(lambda: lr.graph_replay(1), a.iters, a.warmup)
+            out = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                lr.graph_replay(K)
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / K)
+            bursts[flag] = out
+            del lr
+        say(f"graph step (2 stages + forward + loss + backward + Adam + commit), {n_rows} unpadded rows in {n_seq} sequences, every pass over this one "
+            f"minibatch: shuffle off {q(ts[False])}; on {q(ts[True])}; {cost(ts[False], ts[True])}")
+        say(f"    {K} replays back to back, ms per step, three runs: off {', '.join(f'{x:.4f}' for x in bursts[False])} | on "
+            f"{', '.join(f'{x:.4f}' for x in bursts[True])}")
+    # (c) one whole update, kl_coeff = 0 so that only a changed cap captures again
+    res = {}
+    for flag in (False, True):
+        lr = LR.CommanderLearner.trainable_init(dev, seed=6, num_sgd_iter=a.passes, sgd_minibatch_size=256, kl_coeff=0.0, shuffle_sequences=flag, **GRAPH,
+                                                **FUSED)
+        times = []
+        for _ in range(a.warmup + a.iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = lr.update(ro.episodes, net)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+        res[flag] = (times[a.warmup:], st, lr._book.captures)
+    (t_off, st_off, c_off), (t_on, st_on, c_on) = res[False], res[True]
+    say(f"one update ({a.passes} pass(es), minibatches of >= 256 rows: {st_off['steps']} steps over {st_off['rows']} rows; shuffled: {st_on['steps']} "
+        f"steps in the last one), graph, host clock to a synchronise, {a.iters} updates after {a.warmup}: shuffle off {q(t_off)} ({c_off} capture(s) in all); "
+        f"on {q(t_on)} ({c_on} capture(s) in all: a pass whose largest minibatch has another size captures again); {cost(t_off, t_on)}")
+    # (d) the host's part and the table
+    t_h = []
+    for i in range(a.warmup + a.iters):
+        t0 = time.perf_counter()
+        order_h, sched_h = LR.shuffled_schedule(seq_len, 256, 30, 6, i, 0)
+        t_h.append((time.perf_counter() - t0) * 1e3)
+    t_s = []
+    for i in range(a.warmup + a.iters):
+        t0 = time.perf_counter()
+        LR.sequence_schedule(seq_len, 256, 30, 6, i, 0)
+        t_s.append((time.perf_counter() - t0) * 1e3)
+    say(f"    host: shuffled_schedule of 30 passes over {S} sequences ({len(sched_h)} steps) {q(t_h[a.warmup:])}; sequence_schedule (shuffle off) "
+        f"{q(t_s[a.warmup:])}; {cost(t_s[a.warmup:], t_h[a.warmup:])}")
+    say(f"    order table: 4 x 30 x {S} = {order_h.nbytes} bytes ({order_h.nbytes / 1e6:.2f} MB) for {int(seq_len.sum())} rows")
+
+
 def tile_lengths(n_seq, L, seed, device):
     """n_seq ragged lengths drawn as `sequences` draws them (nine in ten full), the first one full"""
     import torch
@@ -520,11 +626,12 @@ def main():
     ap.add_argument("--trunk", action="store_true", help="only the trunk=\"fused\" against trunk=\"torch\" section; appended to --out")
     ap.add_argument("--graph", action="store_true", help="only the step=\"graph\" against the eager step section; appended to --out")
     ap.add_argument("--clip", action="store_true", help="only the grad_clip against grad_clip = None section; appended to --out")
+    ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences against shuffle_sequences = False section; appended to --out")
     ap.add_argument("--tile", action="store_true", help="only the GRU tile instances, each through HH_GRU_TILE in a child; appended to --out")
     ap.add_argument("--tile-seqs", default="13,26,52,104,208,416,854", help="the sequence counts of --tile's GRUs-alone timing")
     ap.add_argument("--launches", choices=["eager", "graph"], help="with --step graph: only --launch-count steps of this form (for a kernel trace)")
     ap.add_argument("--launch-count", type=int, default=20)
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip", "shuffle"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     a.tile_seqs = [int(x) for x in a.tile_seqs.split(",")]
     if a.step:
@@ -539,13 +646,15 @@ def main():
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
         {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk, "graph": step_graph,
-         "tile": step_tile, "clip": step_clip}[a.step](a, say)
+         "tile": step_tile, "clip": step_clip, "shuffle": step_shuffle}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
     if a.graph:
         sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step graph {' '.join(fwd)}", shell=True))
     if a.clip:
         sys.exit(subprocess.call(f"timeout -k 10 300 '{sys.executable}' '{os.path.abspath(__file__)}' --step clip {' '.join(fwd)}", shell=True))
+    if a.shuffle:
+        sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step shuffle {' '.join(fwd)}", shell=True))
     if a.tile:
         fwd.append("--tile-seqs " + ",".join(str(s) for s in a.tile_seqs))
         sys.exit(run_tiles(a, fwd))

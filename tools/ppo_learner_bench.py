@@ -45,6 +45,13 @@
           hh_adam_step at 64 Mi elements (the same 28 B per element); (b) the Fight1 graph step with attention="fused", inputs="fused"
           at 256 and 65536 rows with and without grad_clip (a threshold that binds), one replay per timing and 50 back to back.  A step
           with grad_clip has two launches more: the norm's partials and its final.  The same rule for gain / loss
+  shuffle --shuffle runs this section alone and appends its lines to --out: PPOLearner(shuffle_sequences=True) as a COST next to
+          shuffle_sequences=False in the same run: (a) the stage launch alone, hh_minibatch_stage on the first n chunks against
+          hh_minibatch_stage_gather on n chunks drawn from the whole batch, the 8 Fight1 columns at 14 and 3560 chunks of 20 and 8 Esc1
+          columns at 271 and 65544 rows; (b) the Fight1 graph step at 256 and 65536 rows, one replay per timing and 50 back to back;
+          (c) one whole graph update at --step-minibatch (medians of --iters updates, kl_coeff = 0); (d) the host time of
+          shuffled_schedule against sequence_schedule for 30 passes, and the order table's bytes.  The same spread rule, worded cost /
+          gain / no difference
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -53,6 +60,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -84,6 +92,7 @@ def main():
     ap.add_argument("--trunk", action="store_true", help="only the shared-layer section; its lines are appended to --out")
     ap.add_argument("--step", action="store_true", help="only the graph-step section; its lines are appended to --out")
     ap.add_argument("--clip", action="store_true", help="only the gradient-clipping section; its lines are appended to --out")
+    ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences section; its lines are appended to --out")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
     ap.add_argument("--step-count", type=int, default=16)
@@ -610,6 +619,126 @@ def main():
     if a.clip:
         lines.clear()
         clip_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def shuffle_section():
+        """shuffle_sequences=True against shuffle_sequences=False: the stage launch alone, the graph step, one update, the host's schedule"""
+        from hhmarl_2d_amd import policy_nets as PN
+        med = statistics.median
+
+        def cost(t_base, t_new):
+            spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+            d = med(t_new) - med(t_base)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+            return f"off -> on: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+        FUSED = dict(attention="fused", inputs="fused", trunk="torch")
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        base = make()
+        with torch.no_grad():
+            old = base.old_logits(rows["obs"], bank, ro.episodes.N)
+            b = base.policy_batch(rows, old, 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        S, R = len(seq_len), int(seq_len.sum())
+        say(f"# tools/ppo_learner_bench.py --shuffle on {torch.cuda.get_device_name(0)}: PPOLearner(shuffle_sequences=True) against shuffle_sequences=False "
+            f"(the step as it was), both in this run; {a.arenas} arenas, T = {a.T}: {S} chunks of 20, {R} rows per policy; attention = fused, inputs = "
+            f"fused, trunk = torch; {a.iters} timed runs after {a.warmup} warm-up (a later run, appended):")
+        # (a) the stage launch alone, on the same columns: the first n chunks against n chunks drawn from the whole batch
+        cur, nv = torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+
+        def stage_pair(label, cols, chunk_len, n):
+            total = cols[0].shape[0]
+            staged = [torch.zeros((n,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev) for c in cols]
+            sched = torch.tensor([(0, n, 0, 0)], dtype=torch.int32, device=dev)
+            order = torch.from_numpy(LR.sequence_order(total, 1, 0, 0, 0).astype(np.int32)).to(dev)
+            nbytes = 2 * sum(st.numel() * st.element_size() for st in staged)
+            t_p = events(lambda: LR.minibatch_stage(cols, staged, chunk_len, sched, cur, nv))
+            t_g = events(lambda: LR.minibatch_stage_gather(cols, staged, chunk_len, order, sched, cur, nv))
+            say(f"    the stage launch alone, {label}, {n} of {total} chunks of {chunk_len} ({nbytes / 1e6:.2f} MB read + written): hh_minibatch_stage {q(t_p)} = "
+                f"{nbytes / med(t_p) / 1e6:.1f} GB/s; hh_minibatch_stage_gather {q(t_g)} = {nbytes / med(t_g) / 1e6:.1f} GB/s; {cost(t_p, t_g)}")
+
+        names = [k for k in b if k != "seq_len"]
+        fight_cols = [b[k].contiguous() for k in names]
+        for n in (14, 3560):
+            stage_pair(f"the {len(names)} columns of a Fight1 batch", fight_cols, 20, min(n, S))
+        d1, a1, d2, a2 = PN.CRITIC_DIMS[PN.ESC1]
+        g = torch.Generator(device=dev).manual_seed(3)
+        esc_cols = [torch.rand((R, PN.OBS_DIM[PN.ESC1]), generator=g, device=dev), torch.rand((R, d1 + a1 + d2 + a2), generator=g, device=dev),
+                    torch.zeros((R, 4), dtype=torch.int8, device=dev), torch.rand((R,), generator=g, device=dev), torch.rand((R,), generator=g, device=dev),
+                    torch.rand((R,), generator=g, device=dev), torch.rand((R, 32), generator=g, device=dev), torch.ones((R,), dtype=torch.uint8, device=dev)]
+        for n in (271, 65544):
+            stage_pair("the 8 columns of an Esc1 batch of as many rows (synthetic content)", esc_cols, 1, min(n, R))
+        del esc_cols
+        # (b) the graph step: every pass over ONE minibatch, so the gather draws from that minibatch's chunks
+        K = 50
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+            n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+            ts, bursts = {}, {}
+            for flag in (False, True):
+                lr = make(optimizer="fused", step="graph", num_sgd_iter=n_total, sgd_minibatch_size=1 << 30, shuffle_sequences=flag)
+                lr.graph_prepare(0, sub)
+                ts[flag] = events(lambda: lr.graph_replay(0, 1))
+                out = []
+                for _ in range(3):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    lr.graph_replay(0, K)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    out.append(e0.elapsed_time(e1) / K)
+                bursts[flag] = out
+                del lr
+            say(f"graph step (Fight1, stage + forward + loss + backward + Adam + commit), {int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} chunks of 20: "
+                f"shuffle off {q(ts[False])}; on {q(ts[True])}; {cost(ts[False], ts[True])}")
+            say(f"    {K} replays back to back, ms per step, three runs: off {', '.join(f'{x:.4f}' for x in bursts[False])} | on "
+                f"{', '.join(f'{x:.4f}' for x in bursts[True])}")
+        # (c) one whole update of both policies, kl_coeff = 0 so that only a changed cap captures again
+        res = {}
+        for flag in (False, True):
+            lr = make(optimizer="fused", step="graph", num_sgd_iter=a.passes, sgd_minibatch_size=a.step_minibatch, kl_coeff=0.0, shuffle_sequences=flag)
+            times = []
+            for _ in range(a.warmup + a.iters):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                st = lr.update(ro.episodes, bank)
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3)
+            res[flag] = (times[a.warmup:], st, [bk.captures for bk in lr._books])
+            del lr
+        (t_off, st_off, c_off), (t_on, st_on, c_on) = res[False], res[True]
+        say(f"one update of both policies ({a.passes} pass(es), minibatches of >= {a.step_minibatch} rows: {st_off[0]['steps']} + {st_off[1]['steps']} steps "
+            f"over {st_off[0]['rows']} rows each; shuffled: {st_on[0]['steps']} + {st_on[1]['steps']} in the last one), graph, host clock to a synchronise, "
+            f"{a.iters} updates after {a.warmup}: shuffle off {q(t_off)} (captures in all {c_off}); on {q(t_on)} (captures in all {c_on}: an update whose "
+            f"largest minibatch has another size captures again); {cost(t_off, t_on)}")
+        # (d) the host's part and the table
+        for label, lens in ((f"{S} chunks of <= 20 rows", seq_len), (f"the same {R} rows as escape rows", np.ones(R, dtype=np.int64))):
+            t_h, t_s = [], []
+            for i in range(a.warmup + a.iters):
+                t0 = time.perf_counter()
+                order_h, sched_h = LR.shuffled_schedule(lens, 256, 30, 1, i, 0)
+                t_h.append((time.perf_counter() - t0) * 1e3)
+                t0 = time.perf_counter()
+                LR.sequence_schedule(lens, 256, 30, 1, i, 0)
+                t_s.append((time.perf_counter() - t0) * 1e3)
+            say(f"    host, {label}, 30 passes of minibatches of >= 256 rows ({len(sched_h)} steps): shuffled_schedule {q(t_h[a.warmup:])}; sequence_schedule "
+                f"(shuffle off) {q(t_s[a.warmup:])}; {cost(t_s[a.warmup:], t_h[a.warmup:])}")
+            say(f"    order table, {label}: 4 x 30 x {len(lens)} = {order_h.nbytes} bytes ({order_h.nbytes / 1e6:.2f} MB)")
+
+    if a.shuffle:
+        lines.clear()
+        shuffle_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
