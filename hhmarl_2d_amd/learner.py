@@ -692,6 +692,19 @@ def shuffled_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, p
     return order, np.asarray(rows, dtype=np.int32).reshape(-1, 4)
 
 
+def update_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, policy, shuffle):
+    """The minibatch steps of one policy's update as the ONE table that every step mode walks row by row, the eager loop on the host and
+    the graph's cursor on the device -> (order, sched int32 [n_steps, 4], need).  shuffle False: order is None and sched is
+    sequence_schedule's — rows (first chunk, last chunk + 1, unpadded rows, 0), per pass in minibatch_order's order.  True:
+    shuffled_schedule's (order, sched), the rows naming positions of order.  need: the chunks of the largest minibatch, the smallest
+    staging capacity (1 where there is no minibatch)."""
+    if shuffle:
+        order, sched = shuffled_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, policy)
+        return order, sched, int((sched[:, 1] - sched[:, 0]).max()) if len(sched) else 1
+    parts, sched = sequence_schedule(seq_len, sgd_minibatch_size, num_sgd_iter, seed, update, policy)
+    return None, sched, max((s1 - s0 for s0, s1 in parts), default=1)
+
+
 def _shuffle_flag(shuffle_sequences):
     """RLlib's shuffle_sequences: a bool and nothing else (1, "yes" and None are refused)"""
     if not isinstance(shuffle_sequences, bool):
@@ -1012,7 +1025,8 @@ class _StepBook:
         self.table = torch.zeros((0, len(L.PPO_STATS)), dtype=torch.float64, device=device)
         self.schedule = torch.zeros((0, 4), dtype=torch.int32, device=device)
         self.src, self.staged, self.graph, self.key, self.keep = {}, {}, None, None, None
-        self.order = None       # shuffle_sequences: the order table int32 [>= num_sgd_iter * S] (load_order); never allocated without it
+        self.order, self.order_len = None, 0    # shuffle_sequences: the order table int32 [>= num_sgd_iter * S] and its entries in use (load_order); never allocated without it
+        self.n_steps = self.cap = 0             # graph_prepare: the schedule's rows in use and the staging capacity
         self.captures = 0
 
     @staticmethod
@@ -1046,6 +1060,204 @@ class _StepBook:
         self.order = self._grown(self.order, order.shape[0], (), torch.int32, self.device)
         self.order[:order.shape[0]].copy_(order)
         self.order_len = order.shape[0]
+
+
+class _PolicySGD:
+    """One optimizer's minibatch steps, the same code for PPOLearner's two policies and for CommanderLearner's one: it owns the module's
+    optimizer (DeviceAdam | torch.optim.Adam), the _StepBook (None with torch.optim.Adam), clip_grad_norm_'s norms of the running update
+    and the policy's kl_coeff, and walks update_schedule's table — row by row from Python (step="eager") or by the cursor of ONE captured
+    HIP graph (step="graph").  What differs between the learners comes in as plain callables:
+      forward(mb) -> (logits, vf);  loss(logits, vf, mb, kl_coeff) -> (total, stats f64 [6]);
+      stage_groups(column names) -> [(names of up to _lib.STAGE_MAX_COLS columns, rows per chunk), ...]: one stage launch each;
+      policy: the index in minibatch_order's and sequence_order's keys;  noun: what a chunk is called in messages.
+    cfg is the learner itself, read at every call (never written) for device, step, grad_clip, shuffle_sequences, use_kl, kl_target, num_sgd_iter,
+    sgd_minibatch_size, seed and updates."""
+
+    def __init__(self, cfg, module, lr, kl_coeff, device_adam, forward, loss, stage_groups, policy, noun):
+        self.cfg, self.module, self.kl_coeff, self.gnorms = cfg, module, float(kl_coeff), []
+        self.forward, self.loss, self.stage_groups, self.policy, self.noun = forward, loss, stage_groups, int(policy), noun
+        if device_adam:
+            self.optimizer, self.book = DeviceAdam(module.parameters(), lr=lr, max_norm=cfg.grad_clip), _StepBook(cfg.device, gnorm=cfg.grad_clip is not None)
+        else:
+            self.optimizer, self.book = torch.optim.Adam(module.parameters(), lr=lr), None
+
+    def kl_term(self):
+        """the KL term's coefficient as the loss takes it: ray tests config["kl_coeff"], the initial value, for the term and for update_kl"""
+        return self.kl_coeff if self.cfg.use_kl else 0.0
+
+    def schedule(self, seq_len):
+        cfg = self.cfg
+        return update_schedule(seq_len, cfg.sgd_minibatch_size, cfg.num_sgd_iter, cfg.seed, cfg.updates, self.policy, cfg.shuffle_sequences)
+
+    def minibatch_step(self, mb):
+        """forward, loss, backward, Adam step on one minibatch (a dict of the policy batch's columns, with n_valid) -> stats f64 [6] (device)"""
+        opt, book, clip = self.optimizer, self.book, self.cfg.grad_clip
+        logits, vf = self.forward(mb)
+        total, stats = self.loss(logits, vf, mb, self.kl_term())
+        opt.zero_grad(set_to_none=True)
+        total.backward()
+        if clip is not None and book is None:       # DeviceAdam: inside opt.step()
+            self.gnorms.append(torch.nn.utils.clip_grad_norm_(self.module.parameters(), clip))
+        opt.step()
+        if book is not None:        # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
+            train_commit(stats, book.table, book.cursor, opt.t)
+        return stats
+
+    # ---- the step as one HIP graph (step="graph")
+    def graph_prepare(self, cols, seq_len, cap=None):
+        """Everything the update needs before its first replay: the schedule of the chunks' lengths `seq_len` (host integers [S]) and the
+        columns `cols` (dict of contiguous [S, ...] tensors, staged in this order) uploaded into persistent device buffers — with
+        shuffle_sequences the order table beside them — the cursor set to 0, and the graph of ONE minibatch step captured unless the graph of
+        an earlier call still fits: it is kept while the key is what it was — cap, kl_coeff (by value in hh_ppo_loss_params), the columns
+        and the buffers' addresses; then (grad_clip, which travels by value, the norm table's address and rows) when clipping; then (True,
+        the order buffer's address and rows) when shuffling.  cap: the staging capacity in chunks; default and minimum: the largest
+        minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)"""
+        cfg, book = self.cfg, self.book
+        order, sched, need = self.schedule(seq_len)
+        cap = need if cap is None else int(cap)
+        if cap < need:
+            raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} {self.noun})")
+        book.begin(len(sched), self.optimizer)
+        book.load(cols, sched)
+        if order is not None:
+            book.load_order(order)
+        book.n_steps, book.cap = len(sched), cap
+        src_chunks = min(t.shape[0] for t in book.src.values())
+        names = tuple(cols)
+        key = (cap, self.kl_term(), names, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(),
+               book.table.shape[0]) + tuple(book.src[k].data_ptr() for k in names)
+        if cfg.grad_clip is not None:
+            key += (cfg.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
+        if cfg.shuffle_sequences:
+            key += (True, book.order.data_ptr(), book.order.shape[0])
+        if book.graph is None or book.key != key:
+            self._capture(names, src_chunks)
+            book.key = key
+        return len(sched), int(np.sum(seq_len))
+
+    def _capture(self, names, src_chunks):
+        """stage(s) -> forward -> loss -> backward -> (norm ->) Adam -> commit on one stream as one graph, after a warm-up of the stages,
+        forward and backward only"""
+        book, opt, dev, shuffle = self.book, self.optimizer, self.cfg.device, self.cfg.shuffle_sequences
+        if book.staged.get("obs") is None or book.staged["obs"].shape[0] != book.cap or tuple(book.staged) != names:
+            book.staged = {k: torch.zeros((book.cap,) + tuple(book.src[k].shape[1:]), dtype=book.src[k].dtype, device=dev) for k in names}
+        mb = dict(book.staged, n_valid=book.n_valid)
+        # one launch per group; all of them only read the cursor, the schedule and the order and write the same n_valid
+        groups = [([book.src[k][:src_chunks] for k in ks], [book.staged[k] for k in ks], chunk_len) for ks, chunk_len in self.stage_groups(names)]
+
+        def stage():
+            for srcs, staged, chunk_len in groups:
+                if shuffle:
+                    minibatch_stage_gather(srcs, staged, chunk_len, book.order, book.schedule, book.cursor, book.n_valid)
+                else:
+                    minibatch_stage(srcs, staged, chunk_len, book.schedule, book.cursor, book.n_valid)
+
+        def forward_backward():
+            logits, vf = self.forward(mb)
+            total, stats = self.loss(logits, vf, mb, self.kl_term())
+            total.backward()
+            return stats
+        # the warm-up: forward and backward only (rocBLAS and autograd initialise), on a side stream as torch's capture recipe has it;
+        # it reads schedule[0] through the cursor and writes nothing but the staging buffers and gradients that are thrown away
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            stage()
+            for _ in range(2):
+                opt.zero_grad(set_to_none=True)
+                forward_backward()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        opt.zero_grad(set_to_none=True)     # backward inside the capture assigns the gradients from the graph's pool: their addresses are fixed
+        book.graph = None
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):       # what the forward allocates (the GRU's scratch and y among it) comes from the graph's pool as well
+            stage()
+            stats = forward_backward()
+            opt.step()
+            train_commit(stats, book.table, book.cursor, opt.t)
+        book.graph, book.keep = graph, stats
+        book.captures += 1
+
+    def graph_replay(self, n=1):
+        """n minibatch steps from the captured graph, no host work between them"""
+        graph = self.book.graph
+        for _ in range(int(n)):
+            graph.replay()
+
+    def graph_stats(self, n):
+        """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
+        return self.book.table[:int(n)]
+
+    def grad_gnorm(self, n):
+        """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
+        if n == 0:
+            return float("nan")
+        if self.book is not None:
+            return float(self.book.gnorm[:int(n)].mean())
+        return float(torch.stack(self.gnorms[:int(n)]).double().mean())
+
+    # ---- one update
+    def result(self, m, steps, rows):
+        """an update's dict from the means of the steps' statistics; with grad_clip also grad_gnorm"""
+        clipped = {} if self.cfg.grad_clip is None else dict(grad_gnorm=self.grad_gnorm(steps))
+        return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=steps, rows=rows, **clipped)
+
+    def empty(self):
+        """the dict of an update over no rows: no step, every statistic NaN"""
+        return self.result([float("nan")] * 5, 0, 0)
+
+    def run(self, cols, seq_len):
+        """One update of this policy over the columns `cols` (dict of [S, ...] tensors) whose chunks hold `seq_len` (host integers [S])
+        unpadded rows: every row of update_schedule's table once, in its order — replayed (step="graph": cols as graph_prepare takes them)
+        or stepped from here, an unshuffled row's chunks sliced, a shuffled row's gathered by its order entries — then KLCoeffMixin.update_kl
+        on the mean of the steps' mean_kl -> the update's dict."""
+        cfg = self.cfg
+        if cfg.step == "graph":
+            n, rows = self.graph_prepare(cols, seq_len)
+            self.graph_replay(n)
+            table = self.graph_stats(n)
+        else:
+            order, sched, _ = self.schedule(seq_len)
+            dev = cols["obs"].device
+            n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(dev)
+            if order is not None:
+                order = torch.from_numpy(order).to(dev).long()
+            self.gnorms = []
+            if self.book is not None:
+                self.book.begin(len(sched), self.optimizer)
+            all_stats = []
+            for i, (c0, c1) in enumerate(sched[:, :2].tolist()):
+                if order is None:
+                    mb = {k: v[c0:c1] for k, v in cols.items()}
+                else:
+                    idx = order[c0:c1]
+                    mb = {k: v.index_select(0, idx) for k, v in cols.items()}
+                mb["n_valid"] = n_valid[i:i + 1]
+                all_stats.append(self.minibatch_step(mb))
+            n, rows = len(all_stats), int(np.sum(seq_len))
+            table = torch.stack(all_stats) if all_stats else None
+        m = table.mean(dim=0).tolist() if n else [float("nan")] * 6
+        if cfg.use_kl and n:
+            self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], cfg.kl_target)
+        return self.result(m, n, rows)
+
+
+def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused, floats, ints):
+    """what both learners' constructors take the same way, set on `learner`: the modes, grad_clip and the flag validated in this order
+    before the device is looked at, then the device and the PPO hyper-parameters (floats and ints by name) -> the optimizer mode"""
+    mode = _optimizer_mode(optimizer)
+    learner.step = _step_mode(step, optimizer)
+    learner.grad_clip = _grad_clip(grad_clip)
+    learner.shuffle_sequences = _shuffle_flag(shuffle_sequences)
+    _need_gpu(who)
+    learner.device = torch.device(device) if not isinstance(device, torch.device) else device
+    for k, v in floats.items():
+        setattr(learner, k, float(v))
+    for k, v in ints.items():
+        setattr(learner, k, int(v))
+    learner.use_kl = kl_coeff > 0.0         # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
+    learner.fused, learner.updates = bool(fused), 0
+    return mode
 
 
 # ------------------------------------------------------------------------------------------------------------------ the learner
@@ -1109,37 +1321,40 @@ class PPOLearner:
         device buffer of 4 * num_sgd_iter * S bytes for S chunks, grown to twice the need so that its address outlives batches of varying
         size (30 passes: about 6.6 MB for 1.09 M fight rows in chunks of 20, about 131 MB for the same rows as escape rows).  RLlib's own
         permutation is unseeded, so equality with it is not claimed; what shuffling does to learning curves has not been measured here."""
-        self.optimizer = _optimizer_mode(optimizer)
-        self.step = _step_mode(step, optimizer)
-        self.grad_clip = _grad_clip(grad_clip)
-        self.shuffle_sequences = _shuffle_flag(shuffle_sequences)
-        if not torch.cuda.is_available():
-            raise RuntimeError("hhmarl_2d_amd.PPOLearner needs a ROCm GPU (no CPU fallback)")
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.optimizer = _learner_options(
+            self, "PPOLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
+            dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
+            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed))
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
         self.attention, self.inputs, self.trunk = attention, inputs, _trunk_mode(trunk)
+        # tied once, before the move: tie hands every module the first one's shared_layer MODULE, and nn.Module.to() moves a module's
+        # tensors in place without ever replacing a submodule object, so the one layer stays the one layer on the device
         self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs, trunk=trunk).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
                             for k, sd in zip(self.kinds, state_dicts)])
         for m in self.modules:
             m.to(self.device)
-        tie(self.modules)
-        if self.optimizer == "fused":
-            self.optimizers = [DeviceAdam(m.parameters(), lr=lr, max_norm=self.grad_clip) for m in self.modules]
-        else:
-            self.optimizers = [torch.optim.Adam(m.parameters(), lr=lr) for m in self.modules]
-        self._books = [_StepBook(self.device, gnorm=self.grad_clip is not None) for _ in self.modules] if self.optimizer == "fused" else None
-        self._gnorms = [[], []]                 # optimizer="torch" with grad_clip: clip_grad_norm_'s norms of the running update, per policy
-        self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
-        self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
-        self.use_kl = kl_coeff > 0.0            # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
-        self.kl_coeff = [float(kl_coeff), float(kl_coeff)]
-        self.num_sgd_iter, self.sgd_minibatch_size, self.max_seq_len = int(num_sgd_iter), int(sgd_minibatch_size), int(max_seq_len)
-        self.seed, self.fused, self.updates = int(seed), bool(fused), 0
         self.recurrent = PN.HAS_ATT[self.kinds[0]]
         esc = not self.recurrent
+        # per policy its own driver: the module's Adam, the step book, kl_coeff; one stage launch of every column
+        self._sgd = [_PolicySGD(self, m, lr, kl_coeff, self.optimizer == "fused", forward=lambda mb, m=m: m(mb["obs"], mb["critic"]),
+                                loss=lambda logits, vf, mb, kl, a=a: self.loss(a, logits, vf, mb, kl),
+                                stage_groups=lambda names: [(names, 1 if esc else self.max_seq_len)], policy=a, noun="chunks")
+                     for a, m in enumerate(self.modules)]
+        self.optimizers = [d.optimizer for d in self._sgd]
+        self._books = [d.book for d in self._sgd] if self.optimizer == "fused" else None
         self._sel = (pilots.SEL_ESC1 if esc else pilots.SEL_FIGHT1, pilots.SEL_ESC2 if esc else pilots.SEL_FIGHT2)
         self._tmp = None
+
+    @property
+    def kl_coeff(self):
+        """per policy the current coefficient of the KL term (the drivers hold them; update_kl moves each after its policy's passes)"""
+        return [d.kl_coeff for d in self._sgd]
+
+    @kl_coeff.setter
+    def kl_coeff(self, values):
+        for d, v in zip(self._sgd, values):
+            d.kl_coeff = float(v)
 
     @classmethod
     def trainable_init(cls, device, mode="fight", seed=0, **kw):
@@ -1200,136 +1415,49 @@ class PPOLearner:
         return b
 
     # ---- one minibatch step
-    def loss(self, agent, logits, vf, mb):
-        kw = dict(n_comp=n_comp_of(self.kinds[agent]), clip_param=self.clip_param, vf_clip_param=self.vf_clip_param,
-                  vf_loss_coeff=self.vf_loss_coeff, entropy_coeff=self.entropy_coeff, kl_coeff=self.kl_coeff[agent] if self.use_kl else 0.0)
+    def loss(self, agent, logits, vf, mb, kl_coeff=None):
+        """the policy's loss of one minibatch; kl_coeff: the KL term's coefficient, default the policy's current one"""
+        kw = dict(n_comp=n_comp_of(self.kinds[agent]), clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
+                  entropy_coeff=self.entropy_coeff, kl_coeff=self._sgd[agent].kl_term() if kl_coeff is None else kl_coeff)
         return (ppo_loss if self.fused else ppo_loss_torch)(logits, vf, mb, **kw)
 
+    def _columns(self, b, staged=False):
+        """policy_batch's dict as the driver takes it -> (columns [S, ...], host seq_len [S]: the chunks' lengths, ones for escape rows).
+        staged: as the graph's stage reads them — contiguous, the mask uint8, and for the escape kinds a mask of ones, which the padding
+        rows of the staging buffers need"""
+        cols = {k: (v.contiguous() if staged else v) for k, v in b.items() if k != "seq_len"}
+        S = cols["obs"].shape[0]
+        seq_len = b["seq_len"].cpu().numpy() if self.recurrent else np.ones(S, dtype=np.int64)
+        if staged:
+            if not self.recurrent:
+                cols["mask"] = torch.ones((S,), dtype=torch.uint8, device=self.device)
+            cols["mask"] = cols["mask"].to(torch.uint8)
+        return cols, seq_len
+
+    # the steps themselves are the driver's (_PolicySGD): one per policy
     def minibatch_step(self, agent, mb):
         """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with n_valid) -> stats f64 [6] (device)"""
-        opt = self.optimizers[agent]
-        logits, vf = self.modules[agent](mb["obs"], mb["critic"])
-        total, stats = self.loss(agent, logits, vf, mb)
-        opt.zero_grad(set_to_none=True)
-        total.backward()
-        if self.grad_clip is not None and self.optimizer == "torch":      # "fused": inside opt.step()
-            self._gnorms[agent].append(torch.nn.utils.clip_grad_norm_(self.modules[agent].parameters(), self.grad_clip))
-        opt.step()
-        if self.optimizer == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
-            book = self._books[agent]
-            train_commit(stats, book.table, book.cursor, opt.t)
-        return stats
+        return self._sgd[agent].minibatch_step(mb)
 
-    # ---- the step as one HIP graph (step="graph")
     def graph_prepare(self, agent, b, cap=None):
-        """Everything one policy's pass needs before its first replay: the schedule of policy_batch `b` (minibatch_partition, then
-        minibatch_order per pass) and the batch's columns uploaded into persistent device buffers, the cursor set to 0, and the graph of ONE
-        minibatch step captured — stage, forward, loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only —
-        unless the graph of an earlier call still fits: it is kept while cap, kl_coeff (which travels by value in hh_ppo_loss_params) and the
-        buffers' addresses are what they were (with grad_clip also its value, which travels by value, and the norm table's address).  cap: the staging capacity in chunks (escape: rows); default and minimum: the largest
-        minibatch.  Weights, m, v, t are left bit for bit as they were.  -> (n_steps, rows)
-        With shuffle_sequences the schedule is shuffled_schedule's, its order table is uploaded beside it (4 bytes per pass and chunk), the
-        stage is minibatch_stage_gather, cap defaults to the largest minibatch over all passes, and the key also holds the flag and the
-        order buffer's address and length."""
+        """Everything one policy's pass needs before its first replay (_PolicySGD.graph_prepare on policy_batch `b`): the schedule and the
+        batch's columns uploaded, the cursor set to 0, and the graph of ONE minibatch step — stage, forward, loss, backward, Adam, commit —
+        captured unless an earlier one still fits.  cap: the staging capacity in chunks (escape: rows).  -> (n_steps, rows)"""
         if self.step != "graph":
             raise ValueError('graph_prepare needs PPOLearner(step="graph")')
-        book = self._books[agent]
-        cols = {k: v.contiguous() for k, v in b.items() if k != "seq_len"}
-        S = cols["obs"].shape[0]
-        if self.recurrent:
-            seq_len = b["seq_len"].cpu().numpy()
-        else:
-            seq_len = np.ones(S, dtype=np.int64)
-            cols["mask"] = torch.ones((S,), dtype=torch.uint8, device=self.device)      # padding rows of the staging buffers need one
-        cols["mask"] = cols["mask"].to(torch.uint8)
-        order = None
-        if self.shuffle_sequences:      # per pass its own order of the chunks and that order's partition; the stage gathers through the table
-            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, agent)
-            need = int((sched[:, 1] - sched[:, 0]).max()) if len(sched) else 1
-        else:
-            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-            csum = np.concatenate([[0], np.cumsum(seq_len)])
-            sched = minibatch_schedule(parts, [csum[s1] - csum[s0] for s0, s1 in parts], self.num_sgd_iter, self.seed, self.updates, agent)
-            need = max(s1 - s0 for s0, s1 in parts)
-        cap = need if cap is None else int(cap)
-        if cap < need:
-            raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} chunks)")
-        book.begin(len(sched), self.optimizers[agent])
-        book.load(cols, sched)
-        if order is not None:
-            book.load_order(order)
-        book.n_steps, book.cap = len(sched), cap
-        src_chunks = min(t.shape[0] for t in book.src.values())
-        names = tuple(cols)
-        kl = self.kl_coeff[agent] if self.use_kl else 0.0
-        key = (cap, kl, names, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(), book.table.shape[0]) + tuple(
-            book.src[k].data_ptr() for k in names)
-        if self.grad_clip is not None:
-            key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
-        if self.shuffle_sequences:
-            key += (True, book.order.data_ptr(), book.order.shape[0])
-        if book.graph is None or book.key != key:
-            self._capture(agent, book, names, src_chunks)
-            book.key = key
-        return len(sched), int(seq_len.sum())
-
-    def _capture(self, agent, book, names, src_chunks):
-        opt, module, dev = self.optimizers[agent], self.modules[agent], self.device
-        if book.staged.get("obs") is None or book.staged["obs"].shape[0] != book.cap or tuple(book.staged) != names:
-            book.staged = {k: torch.zeros((book.cap,) + tuple(book.src[k].shape[1:]), dtype=book.src[k].dtype, device=dev) for k in names}
-        srcs, staged = [book.src[k][:src_chunks] for k in names], [book.staged[k] for k in names]
-        mb = dict(book.staged, n_valid=book.n_valid)
-        Lc = self.max_seq_len if self.recurrent else 1
-
-        def stage():
-            if self.shuffle_sequences:
-                minibatch_stage_gather(srcs, staged, Lc, book.order, book.schedule, book.cursor, book.n_valid)
-            else:
-                minibatch_stage(srcs, staged, Lc, book.schedule, book.cursor, book.n_valid)
-
-        def forward_backward():
-            logits, vf = module(mb["obs"], mb["critic"])
-            total, stats = self.loss(agent, logits, vf, mb)
-            total.backward()
-            return stats
-        # the warm-up: forward and backward only (rocBLAS and autograd initialise), on a side stream as torch's capture recipe has it;
-        # it reads schedule[0] through the cursor and writes nothing but the staging buffers and gradients that are thrown away
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            stage()
-            for _ in range(2):
-                opt.zero_grad(set_to_none=True)
-                forward_backward()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        opt.zero_grad(set_to_none=True)     # backward inside the capture assigns the gradients from the graph's pool: their addresses are fixed
-        book.graph = None
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            stage()
-            stats = forward_backward()
-            opt.step()
-            train_commit(stats, book.table, book.cursor, opt.t)
-        book.graph, book.keep = graph, stats
-        book.captures += 1
+        return self._sgd[agent].graph_prepare(*self._columns(b, staged=True), cap)
 
     def graph_replay(self, agent, n=1):
         """n minibatch steps of policy `agent` from its captured graph, no host work between them"""
-        graph = self._books[agent].graph
-        for _ in range(int(n)):
-            graph.replay()
+        self._sgd[agent].graph_replay(n)
 
     def graph_stats(self, agent, n):
         """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
-        return self._books[agent].table[:int(n)]
+        return self._sgd[agent].graph_stats(n)
 
     def grad_gnorm(self, agent, n):
         """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
-        if n == 0:
-            return float("nan")
-        if self.optimizer == "fused":
-            return float(self._books[agent].gnorm[:int(n)].mean())
-        return float(torch.stack(self._gnorms[agent][:int(n)]).double().mean())
+        return self._sgd[agent].grad_gnorm(n)
 
     # ---- one update
     def update(self, episodes, bank=None):
@@ -1339,63 +1467,12 @@ class PPOLearner:
         An EpisodeBatch built with train_batch_size hands over its accumulated batch (RLlib's train_batch_size: update once
         `episodes.ready()`, e.g. after `PPORollout.collect_batch()`); nothing else changes here."""
         rows = episodes.rows()
-        out = []
-        clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
         if rows["obs"].shape[0] == 0:
-            return [dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
-                         kl_coeff=self.kl_coeff[a], steps=0, rows=0, **clipped) for a in range(2)]
+            return [d.empty() for d in self._sgd]
         with torch.no_grad():
             old = self.batch_old_logits(rows, bank, episodes.N)
             batches = [self.policy_batch(rows, old, a) for a in range(2)]
-        for agent, b in enumerate(batches):
-            if self.step == "graph":
-                n_steps, n_rows = self.graph_prepare(agent, b)
-                self.graph_replay(agent, n_steps)
-                m = self.graph_stats(agent, n_steps).mean(dim=0).tolist()
-                if self.use_kl:
-                    self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
-                if self.grad_clip is not None:
-                    clipped = dict(grad_gnorm=self.grad_gnorm(agent, n_steps))
-                out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
-                                steps=n_steps, rows=n_rows, **clipped))
-                continue
-            if self.recurrent:
-                seq_len = b["seq_len"].cpu().numpy()
-            else:
-                seq_len = np.ones(b["obs"].shape[0], dtype=np.int64)
-            cols = [k for k in b if k != "seq_len"]
-            all_stats = []
-            self._gnorms[agent] = []
-            if self.shuffle_sequences:      # shuffled_schedule's steps in its order, each minibatch gathered by its order entries
-                order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, agent)
-                order = torch.from_numpy(order).to(b["obs"].device).long()
-                n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(b["obs"].device)
-                if self.optimizer == "fused":
-                    self._books[agent].begin(len(sched), self.optimizers[agent])
-                for i, (o0, o1) in enumerate(sched[:, :2].tolist()):
-                    idx = order[o0:o1]
-                    mb = {k: b[k].index_select(0, idx) for k in cols}
-                    mb["n_valid"] = n_valid[i:i + 1]
-                    all_stats.append(self.minibatch_step(agent, mb))
-            else:
-                parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-                csum = np.concatenate([[0], np.cumsum(seq_len)])
-                n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
-                if self.optimizer == "fused":
-                    self._books[agent].begin(self.num_sgd_iter * len(parts), self.optimizers[agent])
-                for sgd_pass in range(self.num_sgd_iter):
-                    for i in minibatch_order(len(parts), self.seed, self.updates, agent, sgd_pass):
-                        s0, s1 = parts[i]
-                        mb = {k: b[k][s0:s1] for k in cols}
-                        mb["n_valid"] = n_valid[i:i + 1]
-                        all_stats.append(self.minibatch_step(agent, mb))
-            m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
-            if self.use_kl and all_stats:
-                self.kl_coeff[agent] = kl_coeff_update(self.kl_coeff[agent], m[3], self.kl_target)
-            if self.grad_clip is not None:
-                clipped = dict(grad_gnorm=self.grad_gnorm(agent, len(all_stats)))
-            out.append(dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff[agent],
-                            steps=len(all_stats), rows=int(seq_len.sum()), **clipped))
+        out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
         self.updates += 1
         return out
 
@@ -1768,28 +1845,29 @@ class CommanderLearner:
         hh_minibatch_stage_gather through one order table of 4 * num_sgd_iter * 3 S bytes, uploaded once per update into a persistent
         buffer (grown to twice the need).  Slot 0 of a staged minibatch is a real sequence, so seq_len[0] >= 1 holds as before.  What
         shuffling does to learning curves has not been measured here."""
-        self.optimizer_mode = _optimizer_mode(optimizer)
-        self.step = _step_mode(step, optimizer)
-        self.grad_clip = _grad_clip(grad_clip)
-        self.shuffle_sequences = _shuffle_flag(shuffle_sequences)
-        if not torch.cuda.is_available():
-            raise RuntimeError("hhmarl_2d_amd.CommanderLearner needs a ROCm GPU (no CPU fallback)")
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.optimizer_mode = _learner_options(
+            self, "CommanderLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
+            dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
+            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed))
         self.inputs, self.trunk = inputs, _trunk_mode(trunk)
         self.module = CommanderTrainable(inputs=inputs, trunk=trunk).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
-        if self.optimizer_mode == "fused":
-            self.optimizer = DeviceAdam(self.module.parameters(), lr=lr, max_norm=self.grad_clip)
-        else:
-            self.optimizer = torch.optim.Adam(self.module.parameters(), lr=lr)
-        self._book = _StepBook(self.device, gnorm=self.grad_clip is not None) if self.optimizer_mode == "fused" else None
-        self._gnorms = []                       # optimizer="torch" with grad_clip: clip_grad_norm_'s norms of the running update
-        self.clip_param, self.kl_target, self.vf_clip_param = float(clip_param), float(kl_target), float(vf_clip_param)
-        self.vf_loss_coeff, self.entropy_coeff = float(vf_loss_coeff), float(entropy_coeff)
-        self.use_kl = kl_coeff > 0.0
-        self.kl_coeff = float(kl_coeff)
-        self.num_sgd_iter, self.sgd_minibatch_size, self.max_seq_len = int(num_sgd_iter), int(sgd_minibatch_size), int(max_seq_len)
-        self.seed, self.fused, self.updates = int(seed), bool(fused), 0
+        # the one policy's driver.  hh_minibatch_stage takes 8 columns: the per-step columns (chunks of max_seq_len rows) in one launch, the
+        # per-sequence ones (state_in, seq_len: chunks of one row) in a second
+        self._sgd = _PolicySGD(self, self.module, lr, kl_coeff, self.optimizer_mode == "fused",
+                               forward=lambda mb: self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused),
+                               loss=self.loss, stage_groups=lambda names: [(names[:L.STAGE_MAX_COLS], self.max_seq_len), (names[L.STAGE_MAX_COLS:], 1)],
+                               policy=0, noun="sequences")
+        self.optimizer, self._book = self._sgd.optimizer, self._sgd.book
+
+    @property
+    def kl_coeff(self):
+        """the current coefficient of the KL term (the driver holds it; update_kl moves it after the passes)"""
+        return self._sgd.kl_coeff
+
+    @kl_coeff.setter
+    def kl_coeff(self, value):
+        self._sgd.kl_coeff = float(value)
 
     @classmethod
     def trainable_init(cls, device, seed=0, **kw):
@@ -1838,135 +1916,52 @@ class CommanderLearner:
         return self.old_logits(self.policy_batch(seqs) if b is None else b)
 
     # ---- one minibatch step
-    def loss(self, logits, vf, mb):
+    def loss(self, logits, vf, mb, kl_coeff=None):
+        """the loss of one minibatch; kl_coeff: the KL term's coefficient, default the current one"""
         kw = dict(clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
-                  entropy_coeff=self.entropy_coeff, kl_coeff=self.kl_coeff if self.use_kl else 0.0)
+                  entropy_coeff=self.entropy_coeff, kl_coeff=self._sgd.kl_term() if kl_coeff is None else kl_coeff)
         return (ppo_loss_categorical if self.fused else ppo_loss_categorical_torch)(logits, vf, mb, **kw)
 
-    def minibatch_step(self, mb):
-        """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with old_logits and n_valid)
-        -> stats f64 [6] (device)"""
-        logits, vf = self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused)
-        total, stats = self.loss(logits, vf, mb)
-        self.optimizer.zero_grad(set_to_none=True)
-        total.backward()
-        if self.grad_clip is not None and self.optimizer_mode == "torch":      # "fused": inside optimizer.step()
-            self._gnorms.append(torch.nn.utils.clip_grad_norm_(self.module.parameters(), self.grad_clip))
-        self.optimizer.step()
-        if self.optimizer_mode == "fused":      # the statistics into the device table, cursor and Adam's t advanced: after the Adam launch
-            train_commit(stats, self._book.table, self._book.cursor, self.optimizer.t)
-        return stats
-
-    # ---- the step as one HIP graph (step="graph")
-    def graph_prepare(self, b, cap=None):
-        """Everything one update needs before its first replay: the schedule of policy_batch `b` (with old_logits) and the batch's ten
-        columns — COMMANDER_STAGE_COLS: eight per step, then state_in and seq_len per sequence — uploaded into persistent device buffers,
-        the cursor set to 0, and the graph of ONE minibatch step captured — stage (per-step columns), stage (per-sequence columns), forward,
-        loss, backward, Adam, commit on one stream, after a warm-up of forward and backward only — unless the graph of an earlier call still
-        fits: it is kept while cap, kl_coeff (by value in hh_ppo_loss_params), the columns and the buffers' addresses are what they were
-        (with grad_clip also its value, which travels by value, and the norm table's address).
-        cap: the staging capacity in sequences; default and minimum: the largest minibatch.  The sequences of the staging buffers beyond a
-        minibatch's are zero in every column: sequences of length 0 (hh_gru_seq_*'s contract) whose rows the mask drops.  Weights, m, v, t
-        are left bit for bit as they were.  -> (n_steps, rows)
-        With shuffle_sequences the schedule is shuffled_schedule's, its order table is uploaded beside it, both stages are
-        minibatch_stage_gather, and the key also holds the flag and the order buffer's address and length."""
-        if self.step != "graph":
-            raise ValueError('graph_prepare needs CommanderLearner(step="graph")')
+    def _columns(self, b, staged=False):
+        """policy_batch's dict (with old_logits) as the driver takes it -> (columns [3 S, ...], host seq_len [3 S]).  staged: as the graph's
+        two stages read them — the ten COMMANDER_STAGE_COLS in that order, eight per step and then state_in and seq_len per sequence,
+        contiguous, mask uint8 and seq_len int32.  The sequences of the staging buffers beyond a minibatch's are zero in every column:
+        sequences of length 0 (hh_gru_seq_*'s contract) whose rows the mask drops"""
+        if not staged:
+            return b, b["seq_len"].cpu().numpy()
         missing = [k for k in COMMANDER_STAGE_COLS if k not in b]
         if missing:
             raise ValueError(f"graph_prepare: the policy batch lacks {missing} (policy_batch, then old_logits from batch_old_logits)")
-        book = self._book
         cols = {k: b[k].contiguous() for k in COMMANDER_STAGE_COLS}
         cols["mask"], cols["seq_len"] = cols["mask"].to(torch.uint8), cols["seq_len"].to(torch.int32)
-        seq_len = cols["seq_len"].cpu().numpy()
-        order = None
-        if self.shuffle_sequences:      # per pass its own order of the sequences and that order's partition; both stages gather through the table
-            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
-            need = int((sched[:, 1] - sched[:, 0]).max()) if len(sched) else 1
-        else:
-            parts, sched = sequence_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
-            need = max(s1 - s0 for s0, s1 in parts)
-        cap = need if cap is None else int(cap)
-        if cap < need:
-            raise ValueError(f"cap = {cap} is smaller than the largest minibatch ({need} sequences)")
-        book.begin(len(sched), self.optimizer)
-        book.load(cols, sched)
-        if order is not None:
-            book.load_order(order)
-        book.n_steps, book.cap = len(sched), cap
-        src_chunks = min(t.shape[0] for t in book.src.values())
-        kl = self.kl_coeff if self.use_kl else 0.0
-        key = (cap, kl, COMMANDER_STAGE_COLS, src_chunks, book.schedule.data_ptr(), book.schedule.shape[0], book.table.data_ptr(),
-               book.table.shape[0]) + tuple(book.src[k].data_ptr() for k in COMMANDER_STAGE_COLS)
-        if self.grad_clip is not None:
-            key += (self.grad_clip, book.gnorm.data_ptr(), book.gnorm.shape[0])
-        if self.shuffle_sequences:
-            key += (True, book.order.data_ptr(), book.order.shape[0])
-        if book.graph is None or book.key != key:
-            self._capture(book, src_chunks)
-            book.key = key
-        return len(sched), int(seq_len.sum())
+        return cols, cols["seq_len"].cpu().numpy()
 
-    def _capture(self, book, src_chunks):
-        opt, dev, names = self.optimizer, self.device, COMMANDER_STAGE_COLS
-        if book.staged.get("obs") is None or book.staged["obs"].shape[0] != book.cap or tuple(book.staged) != names:
-            book.staged = {k: torch.zeros((book.cap,) + tuple(book.src[k].shape[1:]), dtype=book.src[k].dtype, device=dev) for k in names}
-        mb = dict(book.staged, n_valid=book.n_valid)
-        # hh_minibatch_stage takes 8 columns: the per-step columns (chunks of max_seq_len rows) in one call, the per-sequence ones (state_in,
-        # seq_len: chunks of one row) in a second.  Both only read the cursor and the schedule and write the same n_valid.
-        groups = [(names[:L.STAGE_MAX_COLS], self.max_seq_len), (names[L.STAGE_MAX_COLS:], 1)]
+    # the steps themselves are the driver's (_PolicySGD), as PPOLearner's are
+    def minibatch_step(self, mb):
+        """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with old_logits and n_valid)
+        -> stats f64 [6] (device)"""
+        return self._sgd.minibatch_step(mb)
 
-        def stage():
-            for ks, chunk_len in groups:
-                srcs, staged = [book.src[k][:src_chunks] for k in ks], [book.staged[k] for k in ks]
-                if self.shuffle_sequences:
-                    minibatch_stage_gather(srcs, staged, chunk_len, book.order, book.schedule, book.cursor, book.n_valid)
-                else:
-                    minibatch_stage(srcs, staged, chunk_len, book.schedule, book.cursor, book.n_valid)
-
-        def forward_backward():
-            logits, vf = self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused)
-            total, stats = self.loss(logits, vf, mb)
-            total.backward()
-            return stats
-        # the warm-up: forward and backward only (rocBLAS and autograd initialise), on a side stream as torch's capture recipe has it;
-        # it reads schedule[0] through the cursor and writes nothing but the staging buffers and gradients that are thrown away
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            stage()
-            for _ in range(2):
-                opt.zero_grad(set_to_none=True)
-                forward_backward()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        opt.zero_grad(set_to_none=True)     # backward inside the capture assigns the gradients from the graph's pool: their addresses are fixed
-        book.graph = None
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):       # the GRU's scratch and y (torch.empty in _GruSeq.forward) come from the graph's pool as well
-            stage()
-            stats = forward_backward()
-            opt.step()
-            train_commit(stats, book.table, book.cursor, opt.t)
-        book.graph, book.keep = graph, stats
-        book.captures += 1
+    def graph_prepare(self, b, cap=None):
+        """Everything one update needs before its first replay (_PolicySGD.graph_prepare on policy_batch `b` with old_logits): the schedule
+        and the batch's ten columns uploaded, the cursor set to 0, and the graph of ONE minibatch step — stage (per-step columns), stage
+        (per-sequence columns), forward, loss, backward, Adam, commit — captured unless an earlier one still fits.  cap: the staging
+        capacity in sequences.  -> (n_steps, rows)"""
+        if self.step != "graph":
+            raise ValueError('graph_prepare needs CommanderLearner(step="graph")')
+        return self._sgd.graph_prepare(*self._columns(b, staged=True), cap)
 
     def graph_replay(self, n=1):
         """n minibatch steps from the captured graph, no host work between them"""
-        graph = self._book.graph
-        for _ in range(int(n)):
-            graph.replay()
+        self._sgd.graph_replay(n)
 
     def graph_stats(self, n):
         """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
-        return self._book.table[:int(n)]
+        return self._sgd.graph_stats(n)
 
     def grad_gnorm(self, n):
         """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
-        if n == 0:
-            return float("nan")
-        if self.optimizer_mode == "fused":
-            return float(self._book.gnorm[:int(n)].mean())
-        return float(torch.stack(self._gnorms[:int(n)]).double().mean())
+        return self._sgd.grad_gnorm(n)
 
     # ---- one update
     def update(self, episodes, net=None):
@@ -1977,61 +1972,17 @@ class CommanderLearner:
         also grad_gnorm.  A CommanderEpisodeBatch built with train_batch_size hands over its accumulated batch (update once
         `episodes.ready()`, e.g. after `CommanderRollout.collect_batch()`); nothing else changes here."""
         seqs = episodes.sequences()
-        clipped = {} if self.grad_clip is None else dict(grad_gnorm=float("nan"))
         if seqs["obs"].shape[1] != self.max_seq_len:
             raise ValueError(f"CommanderLearner(max_seq_len={self.max_seq_len}) was given sequences of {seqs['obs'].shape[1]} steps: the rollout "
                              "cuts them, so both take the same max_seq_len")
         if seqs["obs"].shape[0] == 0:
-            return dict(total_loss=float("nan"), policy_loss=float("nan"), vf_loss=float("nan"), kl=float("nan"), entropy=float("nan"),
-                        kl_coeff=self.kl_coeff, steps=0, rows=0, **clipped)
+            return self._sgd.empty()
         with torch.no_grad():
             b = self.policy_batch(seqs)
             b["old_logits"] = self.batch_old_logits(seqs, b)
-        if self.step == "graph":
-            n_steps, n_rows = self.graph_prepare(b)
-            self.graph_replay(n_steps)
-            m = self.graph_stats(n_steps).mean(dim=0).tolist()
-            if self.use_kl:
-                self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
-            self.updates += 1
-            if self.grad_clip is not None:
-                clipped = dict(grad_gnorm=self.grad_gnorm(n_steps))
-            return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=n_steps, rows=n_rows,
-                        **clipped)
-        seq_len = b["seq_len"].cpu().numpy()
-        all_stats = []
-        self._gnorms = []
-        if self.shuffle_sequences:      # shuffled_schedule's steps in its order, every column (state_in and seq_len too) gathered by the order entries
-            order, sched = shuffled_schedule(seq_len, self.sgd_minibatch_size, self.num_sgd_iter, self.seed, self.updates, 0)
-            order = torch.from_numpy(order).to(b["obs"].device).long()
-            n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(b["obs"].device)
-            if self.optimizer_mode == "fused":
-                self._book.begin(len(sched), self.optimizer)
-            for i, (o0, o1) in enumerate(sched[:, :2].tolist()):
-                idx = order[o0:o1]
-                mb = {k: v.index_select(0, idx) for k, v in b.items()}
-                mb["n_valid"] = n_valid[i:i + 1]
-                all_stats.append(self.minibatch_step(mb))
-        else:
-            parts = minibatch_partition(seq_len, self.sgd_minibatch_size)
-            csum = np.concatenate([[0], np.cumsum(seq_len)])
-            n_valid = torch.tensor([csum[s1] - csum[s0] for s0, s1 in parts], dtype=torch.int32, device=b["obs"].device)
-            if self.optimizer_mode == "fused":
-                self._book.begin(self.num_sgd_iter * len(parts), self.optimizer)
-            for sgd_pass in range(self.num_sgd_iter):
-                for i in minibatch_order(len(parts), self.seed, self.updates, 0, sgd_pass):
-                    s0, s1 = parts[i]
-                    mb = {k: v[s0:s1] for k, v in b.items()}
-                    mb["n_valid"] = n_valid[i:i + 1]
-                    all_stats.append(self.minibatch_step(mb))
-        m = torch.stack(all_stats).mean(dim=0).tolist() if all_stats else [float("nan")] * 6
-        if self.use_kl and all_stats:
-            self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], self.kl_target)
+        out = self._sgd.run(*self._columns(b, staged=self.step == "graph"))
         self.updates += 1
-        if self.grad_clip is not None:
-            clipped = dict(grad_gnorm=self.grad_gnorm(len(all_stats)))
-        return dict(total_loss=m[0], policy_loss=m[1], vf_loss=m[2], kl=m[3], entropy=m[4], kl_coeff=self.kl_coeff, steps=len(all_stats),
-                    rows=int(seq_len.sum()), **clipped)
+        return out
 
     def publish(self, net):
         """the new weights into the sampler's CommanderNet on the current stream (refresh_weights): captured collects replay with them"""
