@@ -7,7 +7,7 @@ variances share their divisor, which cancels.  With no episode every mean / min 
 
 `bounds` gives the float64 reordering bounds the device results are held to: a sum of n terms added in another order differs by at most
 (n - 1) u sum|x| (1 + O(n u)) from this one's, u = 2^-53 — each of the two orders is within that of the exact sum, twice that apart:
-n 2^-52 sum|x| covers it for every n >= 1."""
+n 2^-52 sum|x| covers it for every n >= 1.  `explained_variance_bound` carries the same bound of the two M2 sums through their ratio."""
 import numpy as np
 
 EPS = 2.0 ** -52
@@ -34,6 +34,29 @@ def explained_variance(target, vf):
     with np.errstate(divide="ignore", invalid="ignore"):
         ev = 1.0 - np.float64(m2[0]) / np.float64(m2[1])
     return float(-1.0 if ev < -1.0 else ev)
+
+
+def explained_variance_bound(target, vf):
+    """the reordering bound for explained_variance(target, vf), derived as the bounds of the means are: each of the two M2 is a sum of n
+    non-negative terms x = (value - mean)^2, so the same terms added in another order give a sum within n 2^-52 sum|x| = rho M2 of this
+    one's, rho = n 2^-52 (module docstring).  Through the ratio: with both sums within a factor 1 +- rho of the restatement's, M2(d) /
+    M2(t) lies within a factor (1 + rho) / (1 - rho) of the restatement's r, i.e. within r 2 rho / (1 - rho); the division and the
+    subtraction from 1 round once each on either side: 2^-52 (r + |1 - r|) covers both.  The clamp at -1 moves two values no further
+    apart.  0.0 where the restatement's value is nan (nothing to compare) — the caller checks nan against nan.
+    The bound is NOT widened for the means the deviations are taken from, themselves sums in another order and off by at most eta =
+    2^-52 sum|value| each: that moves one two-pass M2 by at most n eta^2, and per-tile M2 combined around the global mean (sum M2_i +
+    n_i (mean_i - mean)^2, the device's way) by at most 4 eta sqrt(n M2) + n eta^2 with a tile's eta.  Both stay orders of magnitude
+    inside rho M2 unless |mean| dwarfs the standard deviation; leaving them out makes this bound tighter, never wider."""
+    t = np.asarray(target, dtype=np.float64)
+    d = t - np.asarray(vf, dtype=np.float64)
+    n = len(t)
+    if n == 0:
+        return 0.0
+    m2 = [_seq_sum((x - _seq_sum(x) / n) ** 2) for x in (d, t)]
+    if not m2[1] > 0.0:
+        return 0.0
+    rho, r = n * EPS, float(m2[0] / m2[1])
+    return r * 2.0 * rho / (1.0 - rho) + EPS * (r + abs(1.0 - r))
 
 
 def restate_metrics(reward, vf, target, ep_start, ep_len):
