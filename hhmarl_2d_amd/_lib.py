@@ -133,7 +133,8 @@ LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_cate
                    "hh_residual_normalize_backward", "hh_input_stage_scratch_bytes", "hh_input_stage_forward",
                    "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward",
                    "hh_adam_step", "hh_minibatch_stage", "hh_train_commit", "hh_gru_seq_tile",
-                   "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped", "hh_minibatch_stage_gather"]  # include/hh_learner.h
+                   "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped", "hh_minibatch_stage_gather",
+                   "hh_heads_loss_scratch_bytes", "hh_heads_loss_geometry", "hh_heads_loss"]  # include/hh_learner.h
 GRU_TILES = (16, 8, 4)  # the compiled instances of hh_k_gru_seq_fwd / _bwd (HH_GRU_TILE forces one; hh_gru_seq_tile tells which a call uses)
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
@@ -168,6 +169,7 @@ class HHDenseSrc(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("x", C.c_void_p), ("ld", C.c_int64), ("y", C.c_void_p), ("d_y", C.c_void_p), ("d_x", C.c_void_p)]
 
 
+HEADS_K, HEADS_N_OUT = 500, {4: 26, 3: 24, 1: 3}  # hh_heads_loss: shared_layer's width, the logits per n_comp (include/hh_learner.h)
 ADAM_MAX_TENSORS, STAGE_MAX_COLS = 64, 8  # HH_ADAM_MAX_TENSORS, HH_STAGE_MAX_COLS (include/hh_learner.h)
 CLIP_OUT = 2  # HH_CLIP_OUT: hh_grad_norm's clip f64 [2] = (the norm before clipping, the coefficient)
 
@@ -288,6 +290,9 @@ def lib():
         L.hh_grad_norm_scratch_bytes.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), C.POINTER(C.c_int64)]
         L.hh_grad_norm.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), C.c_double, vp, vp, vp, C.c_int32, vp, C.c_int64, vp]
         L.hh_adam_step_clipped.argtypes = [C.c_int32, C.POINTER(HHAdamTensor), vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+        L.hh_heads_loss_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_heads_loss_geometry.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.hh_heads_loss.argtypes = [C.c_int64] + [vp] * 13 + [C.POINTER(HHPpoLossParams)] + [vp] * 10 + [C.c_int64, vp]
         _lib = L
     return _lib
 

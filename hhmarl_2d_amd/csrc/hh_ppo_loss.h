@@ -89,6 +89,47 @@ __device__ __forceinline__ void hhl_component(float *__restrict__ rn, float *__r
     if (want_kl) kl += K;
 }
 
+/* one row that the mask keeps, on the lane's LDS rows rn (the learner's logits, NOUT of them; the columns up to ld are zeroed) and ro (the
+ * sampler's): rn becomes d total / d logits, the four row terms come back as float64, -> d total / d vf.  Shared by hh_k_ppo_loss and
+ * hh_k_heads_loss (hh_heads_loss.h), so the formulas and the kink conventions exist once. */
+template <int NCOMP>
+__device__ __forceinline__ float hhl_row(float *__restrict__ rn, float *__restrict__ ro, int ld, int64_t row, const int32_t *__restrict__ actions,
+                                         float old_logp, float A, float vf, float target, float inv_n, float clip, float vf_clip, float vf_coeff,
+                                         float ent_coeff, float kl_coeff, double &t_pol, double &t_vf, double &t_kl, double &t_ent) {
+    constexpr int NOUT = NCOMP == 4 ? 26 : (NCOMP == 3 ? 24 : HH_CMD_ACTIONS);
+    const bool want_kl = kl_coeff > 0.0f;
+    const float cE = ent_coeff * inv_n, cK = kl_coeff * inv_n;
+    float logp = 0.0f, ent = 0.0f, kl = 0.0f;
+    if constexpr (NCOMP == 1) {
+        hhl_component<HH_CMD_ACTIONS, 0>(rn, ro, (int)reinterpret_cast<const int8_t *>(actions)[row], cE, cK, want_kl, logp, ent, kl);
+    } else {
+        const int32_t aw = actions[row];
+        hhl_component<13, 0>(rn, ro, (int)(int8_t)(aw & 0xff), cE, cK, want_kl, logp, ent, kl);
+        hhl_component<9, 13>(rn, ro, (int)(int8_t)((aw >> 8) & 0xff), cE, cK, want_kl, logp, ent, kl);
+        hhl_component<2, 22>(rn, ro, (int)(int8_t)((aw >> 16) & 0xff), cE, cK, want_kl, logp, ent, kl);
+        if (NCOMP == 4) hhl_component<2, 24>(rn, ro, (int)(int8_t)((aw >> 24) & 0xff), cE, cK, want_kl, logp, ent, kl);
+    }
+    const float ratio = expf(logp - old_logp);
+    const float lo = 1.0f - clip, hi = 1.0f + clip;
+    const float s1 = A * ratio, s2 = A * fminf(fmaxf(ratio, lo), hi);
+    const float surr = fminf(s1, s2);
+    const bool inside = ratio >= lo && ratio <= hi;
+    const float wr = (inside || s1 < s2) ? s1 * inv_n : 0.0f;   /* d surrogate / d logp = adv * ratio where the gradient passes */
+    const float dv = vf - target;
+    const float sq = dv * dv;
+    const float vl = fminf(fmaxf(sq, 0.0f), vf_clip);
+    float gv = 0.0f;
+    if (sq <= vf_clip) gv = vf_coeff * inv_n * (2.0f * dv);
+#pragma unroll
+    for (int j = 0; j < NOUT; j++) rn[j] = rn[j] - wr * ro[j];
+    for (int j = NOUT; j < ld; j++) rn[j] = 0.0f;
+    t_pol = (double)(-surr);
+    t_vf = (double)vl;
+    t_kl = (double)kl;
+    t_ent = (double)ent;
+    return gv;
+}
+
 template <int NCOMP>
 __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, const float *__restrict__ logits, const float *__restrict__ old_logits,
                                                           const int32_t *__restrict__ actions /* i8 [R, 4] as one word per row; NCOMP = 1: i8 [R] */,
@@ -148,37 +189,8 @@ __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, con
         const bool on = mask == nullptr || mask[row] != 0;
         float gv = 0.0f;
         if (on) {
-            const float inv_n = 1.0f / (float)n_valid[0];
-            const bool want_kl = kl_coeff > 0.0f;
-            const float cE = ent_coeff * inv_n, cK = kl_coeff * inv_n;
-            float logp = 0.0f, ent = 0.0f, kl = 0.0f;
-            if constexpr (NCOMP == 1) {
-                hhl_component<HH_CMD_ACTIONS, 0>(rn, ro, (int)reinterpret_cast<const int8_t *>(actions)[row], cE, cK, want_kl, logp, ent, kl);
-            } else {
-                const int32_t aw = actions[row];
-                hhl_component<13, 0>(rn, ro, (int)(int8_t)(aw & 0xff), cE, cK, want_kl, logp, ent, kl);
-                hhl_component<9, 13>(rn, ro, (int)(int8_t)((aw >> 8) & 0xff), cE, cK, want_kl, logp, ent, kl);
-                hhl_component<2, 22>(rn, ro, (int)(int8_t)((aw >> 16) & 0xff), cE, cK, want_kl, logp, ent, kl);
-                if (NCOMP == 4) hhl_component<2, 24>(rn, ro, (int)(int8_t)((aw >> 24) & 0xff), cE, cK, want_kl, logp, ent, kl);
-            }
-            const float A = adv[row];
-            const float ratio = expf(logp - old_logp[row]);
-            const float lo = 1.0f - clip, hi = 1.0f + clip;
-            const float s1 = A * ratio, s2 = A * fminf(fmaxf(ratio, lo), hi);
-            const float surr = fminf(s1, s2);
-            const bool inside = ratio >= lo && ratio <= hi;
-            const float wr = (inside || s1 < s2) ? s1 * inv_n : 0.0f;   /* d surrogate / d logp = adv * ratio where the gradient passes */
-            const float dv = vf[row] - target[row];
-            const float sq = dv * dv;
-            const float vl = fminf(fmaxf(sq, 0.0f), vf_clip);
-            if (sq <= vf_clip) gv = vf_coeff * inv_n * (2.0f * dv);
-#pragma unroll
-            for (int j = 0; j < NOUT; j++) rn[j] = rn[j] - wr * ro[j];
-            for (int j = NOUT; j < ld; j++) rn[j] = 0.0f;
-            t_pol = (double)(-surr);
-            t_vf = (double)vl;
-            t_kl = (double)kl;
-            t_ent = (double)ent;
+            gv = hhl_row<NCOMP>(rn, ro, ld, row, actions, old_logp[row], adv[row], vf[row], target[row], 1.0f / (float)n_valid[0], clip, vf_clip,
+                                vf_coeff, ent_coeff, kl_coeff, t_pol, t_vf, t_kl, t_ent);
         } else {
             for (int j = 0; j < ld; j++) rn[j] = 0.0f;
         }
@@ -217,9 +229,10 @@ __global__ __launch_bounds__(HHL_ROWS) void hh_k_ppo_loss(int64_t R, int ld, con
     }
 }
 
-/* the partials of all workgroups in a fixed order: lane t adds workgroups t, t + 256, ...; then a fixed tree over the 256 lanes */
-__global__ __launch_bounds__(256) void hh_k_ppo_loss_final(int n_blocks, const double *__restrict__ partial, const int32_t *__restrict__ n_valid,
-                                                           float vf_coeff, float ent_coeff, float kl_coeff, double *__restrict__ stats) {
+/* the partials of all workgroups in a fixed order: lane t adds workgroups t, t + 256, ...; then a fixed tree over the 256 lanes.  One
+ * workgroup of 256 lanes, all of them in the call (hh_k_ppo_loss_final, and the last workgroup of hh_k_heads_final) */
+__device__ __forceinline__ void hhl_final_stats(int n_blocks, const double *__restrict__ partial, const int32_t *__restrict__ n_valid, float vf_coeff,
+                                                float ent_coeff, float kl_coeff, double *__restrict__ stats) {
     __shared__ double s[4][256];
     const int tid = threadIdx.x;
     double a[4] = {0.0, 0.0, 0.0, 0.0};
@@ -244,6 +257,11 @@ __global__ __launch_bounds__(256) void hh_k_ppo_loss_final(int n_blocks, const d
         stats[4] = ent;
         stats[5] = n;
     }
+}
+
+__global__ __launch_bounds__(256) void hh_k_ppo_loss_final(int n_blocks, const double *__restrict__ partial, const int32_t *__restrict__ n_valid,
+                                                           float vf_coeff, float ent_coeff, float kl_coeff, double *__restrict__ stats) {
+    hhl_final_stats(n_blocks, partial, n_valid, vf_coeff, ent_coeff, kl_coeff, stats);
 }
 
 static inline int64_t hhl_blocks(int64_t n_rows) { return (n_rows + HHL_ROWS - 1) / HHL_ROWS; }

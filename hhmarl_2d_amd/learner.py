@@ -9,6 +9,9 @@ Opt-in as well (`inputs="fused"`, all five networks): the layers in front of sha
 (`input_stage`: hh_input_stage_*); the default path slices, concatenates and runs them one by one.
 And (`trunk="fused"`, all five networks): shared_layer with its bias and tanh over the actor's and the critic's rows as ONE call
 on the matrix cores (`dense_tanh`: hh_dense_tanh_*, split-fp16 MFMA); the default path is two float32 GEMMs and two tanh.
+And (`heads="fused"`, all five networks, not with trunk="fused"): what follows shared_layer's GEMM — tanh, act_out and val_out, the PPO
+loss, and the backward of all of it down to shared_layer's pre-activations — as ONE row pass and a fixed-order final sum (`heads_loss`:
+hh_heads_loss); the default path is tanh, two GEMMs, hh_ppo_loss and autograd's backward of each.
 And (`PPOLearner(optimizer="fused", step="graph")`): Adam on the device (`adam_step`: hh_adam_step) and the whole minibatch step — the
 minibatch staged by a device schedule (`minibatch_stage`: hh_minibatch_stage), forward, loss, backward, Adam and the step's bookkeeping
 (`train_commit`: hh_train_commit) — replayed from ONE HIP graph per policy; the default is torch.optim.Adam and the eager step.
@@ -29,6 +32,7 @@ The commander half (train_hier.py with models/ac_models_hier.py:CommanderGru) is
 `ppo_loss_categorical` (hh_ppo_loss_categorical), `CommanderTrainable` and `CommanderLearner`, which does for
 `commander.CommanderRollout(batch_mode="complete_episodes")` what `PPOLearner` does for `PPORollout`."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -487,6 +491,130 @@ def _trunk_mode(trunk):
     return trunk
 
 
+# ------------------------------------------------------------------------------------------------------------------ the heads and the loss
+HEADS_MODES = ("torch", "fused")
+
+
+def _heads_mode(heads, trunk="torch"):
+    if heads not in HEADS_MODES:
+        raise ValueError(f"heads is one of {HEADS_MODES}, got {heads!r}")
+    if heads == "fused" and trunk == "fused":
+        raise ValueError('heads="fused" needs trunk="torch": dense_tanh has the tanh inside, so there are no pre-activations to hand over')
+    return heads
+
+
+def _heads_keyword(init):
+    """a learner's __init__ with one more argument, `heads`, that can only be given by keyword: it is taken off before `init` runs and
+    kept as `self._heads_arg`, which `init` hands to _learner_options for validation in its place.  The constructors' own signatures stay
+    as they are — grad_clip their last parameter, so no positional caller moves — and functools.wraps keeps them what introspection
+    and help() show; the docstrings describe `heads`."""
+    @functools.wraps(init)
+    def __init__(self, *args, heads="torch", **kw):
+        self._heads_arg = heads
+        init(self, *args, **kw)
+    return __init__
+
+
+class _HeadsLoss(torch.autograd.Function):
+    """forward: hh_heads_loss (tanh, both heads, the loss, and all six gradients in one pass); backward: the kept gradients, times the
+    incoming one where the call asked for that"""
+
+    @staticmethod
+    def forward(ctx, za, zc, w_act, b_act, w_val, b_val, old_logits, actions, old_logp, adv, target, mask, n_valid, prm, scale_grad):
+        dev = za.device
+        R = za.numel() // L.HEADS_K
+        e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
+        stats = torch.empty((len(L.PPO_STATS),), dtype=torch.float64, device=dev)
+        grads = (e(za), e(zc), e(w_act), e(b_act), e(w_val), e(b_val))
+        nbytes = C.c_int64()
+        lib = L.lib()
+        L.check(lib.hh_heads_loss_scratch_bytes(R, prm.n_comp, C.byref(nbytes)))
+        scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=dev)
+        L.check(lib.hh_heads_loss(R, _p(za), _p(zc), _p(w_act), _p(b_act), _p(w_val), _p(b_val), _p(old_logits), _p(actions), _p(old_logp), _p(adv),
+                                  _p(target), _p(mask), _p(n_valid), C.byref(prm), _p(stats), *[_p(g) for g in grads], None, None, _p(scratch),
+                                  nbytes.value, _stream(dev)))
+        ctx.save_for_backward(*grads)
+        ctx.scale_grad = scale_grad
+        ctx.mark_non_differentiable(stats)
+        return stats[0].float(), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, g_stats):
+        grads = list(ctx.saved_tensors)
+        if ctx.scale_grad:
+            torch._foreach_mul_(grads, g_total)
+        return tuple(grads) + (None,) * 9
+
+
+def _head_params(head):
+    """(weight, bias) of an output head given as that pair, as an nn.Linear or as a module that keeps one in `_model.0` (_FC)"""
+    if isinstance(head, (tuple, list)):
+        return head[0], head[1]
+    lin = head._model[0] if hasattr(head, "_model") else head
+    return lin.weight, lin.bias
+
+
+def _flat_heads_batch(R, batch, n_comp, device):
+    """_flat_batch / _flat_batch_cat without the learner's outputs: the batch columns as contiguous rows for R rows of pre-activations"""
+    old_ld, act_w = (CMD_LD, None) if n_comp == 1 else (OLD_LD, 4)
+    col = lambda k, dt, w=None: batch[k].reshape((R,) if w is None else (R, w)).to(dt).contiguous()
+    mask = batch.get("mask")
+    mask = None if mask is None else col("mask", torch.uint8)
+    n_valid = batch.get("n_valid")
+    if n_valid is None:
+        n_valid = (torch.full((1,), R, dtype=torch.int32, device=device) if mask is None else mask.ne(0).sum(dtype=torch.int32).reshape(1))
+    return (col("old_logits", torch.float32, old_ld), col("actions", torch.int8, act_w), col("old_logp", torch.float32), col("adv", torch.float32),
+            col("target", torch.float32), mask, n_valid.reshape(1))
+
+
+def heads_loss(za, zc, act_out, val_out, batch, *, n_comp, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2,
+               scale_grad=True):
+    """Everything behind shared_layer's GEMM in one fused pass (hh_heads_loss, include/hh_learner.h): h = tanh(za), y = tanh(zc),
+    logits = act_out(h), vf = val_out(y), then ppo_loss (n_comp 4 | 3) or ppo_loss_categorical (n_comp 1) — and, in the same pass, the
+    gradient of the total with respect to za, zc and the four head parameters.
+    za, zc f32 [..., 500]: shared_layer's outputs for the actor's and the critic's rows, bias added, before tanh (TrainableNet.pre_heads,
+    CommanderTrainable.pre_heads); contiguous CUDA tensors of one shape.  act_out, val_out: the heads as (weight, bias) pairs, nn.Linear
+    or _FC modules: [n_out, 500], [n_out] and [1, 500], [1], contiguous float32 on the same device.  batch: as ppo_loss /
+    ppo_loss_categorical take it, over za's leading shape.
+    -> (total loss: float32 0-d tensor, differentiable with respect to za, zc and the four head parameters (first order, ONE backward
+        per call); stats f64 [6] as ppo_loss).
+    The six gradients are computed by the forward call and kept.  scale_grad=True (the default) multiplies them by the gradient that
+    arrives at `total`, in place, with one multi-tensor launch, so the function is correct under any upstream gradient;
+    scale_grad=False hands them over as they are, which is right exactly when that gradient is 1 — `total.backward()`, what the learners
+    call — and saves the pass over two [R, 500] tensors.  No host synchronisation; a missing library or GPU is an error."""
+    _need_gpu("heads_loss")
+    (w_act, b_act), (w_val, b_val) = _head_params(act_out), _head_params(val_out)
+    n_out = L.HEADS_N_OUT.get(int(n_comp))
+    if n_out is None:
+        raise ValueError(f"heads_loss: n_comp is one of {sorted(L.HEADS_N_OUT)}, got {n_comp!r}")
+    for what, t in (("za", za), ("zc", zc), ("act_out's weight", w_act), ("act_out's bias", b_act), ("val_out's weight", w_val), ("val_out's bias", b_val)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == za.device):
+            raise ValueError(f"heads_loss: {what} is a contiguous float32 CUDA tensor on za's device (the torch-op form for other dtypes and devices is heads_loss_torch)")
+    if (za.dim() < 1 or za.shape[-1] != L.HEADS_K or za.shape != zc.shape or za.numel() == 0 or tuple(w_act.shape) != (n_out, L.HEADS_K)
+            or tuple(b_act.shape) != (n_out,) or w_val.numel() != L.HEADS_K or b_val.numel() != 1):
+        raise ValueError(f"heads_loss: za and zc [..., {L.HEADS_K}] of one shape with at least one row, act_out [{n_out}, {L.HEADS_K}] + [{n_out}], val_out "
+                         f"[1, {L.HEADS_K}] + [1]; got {tuple(za.shape)}, {tuple(zc.shape)}, {tuple(w_act.shape)}, {tuple(b_act.shape)}, "
+                         f"{tuple(w_val.shape)}, {tuple(b_val.shape)}")
+    flat = _flat_heads_batch(za.numel() // L.HEADS_K, batch, int(n_comp), za.device)
+    prm = L.HHPpoLossParams(n_comp=int(n_comp), reserved0=0, clip_param=clip_param, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff,
+                            entropy_coeff=entropy_coeff, kl_coeff=kl_coeff, reserved1=0.0)
+    return _HeadsLoss.apply(za, zc, w_act, b_act, w_val, b_val, *flat, prm, bool(scale_grad))
+
+
+def heads_loss_torch(za, zc, act_out, val_out, batch, *, n_comp, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0,
+                     kl_coeff=0.2, scale_grad=True):
+    """heads_loss with torch ops on any device, in za's dtype (the A/B partner): tanh, F.linear, then ppo_loss_torch (n_comp 4 | 3) or
+    ppo_loss_categorical_torch (n_comp 1); autograd does the backward, so scale_grad has nothing to switch"""
+    (w_act, b_act), (w_val, b_val) = _head_params(act_out), _head_params(val_out)
+    logits = F.linear(torch.tanh(za), w_act, b_act)
+    vf = F.linear(torch.tanh(zc), w_val.reshape(1, -1), b_val.reshape(1)).squeeze(-1)
+    kw = dict(clip_param=clip_param, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff, kl_coeff=kl_coeff)
+    if int(n_comp) == 1:
+        return ppo_loss_categorical_torch(logits, vf, batch, **kw)
+    return ppo_loss_torch(logits, vf, batch, n_comp=n_comp, **kw)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the networks
 class _FC(nn.Module):
     """a linear layer under the reference's parameter names (RLlib's SlimFC keeps its nn.Linear in `_model.0`)"""
@@ -523,12 +651,18 @@ class TrainableNet(nn.Module):
     trunk = "torch" (the default) applies shared_layer and tanh to the actor's and to the critic's rows one after the other.  "fused" (any
     kind, float32 on the GPU) runs both through ONE dense_tanh (split-fp16 MFMA, bias and tanh in its epilogue); the _FC module stays
     the parameter holder, so state_dict(), tie and publish are the same, and a tied layer receives gradients only from the module that
-    ran.  Independent of `attention` and `inputs`."""
+    ran.  Independent of `attention` and `inputs`.
 
-    def __init__(self, kind, attention="torch", inputs="torch", trunk="torch"):
+    heads = "torch" (the default) changes nothing.  "fused" (any kind, trunk="torch") marks the module for the learners' fused tail:
+    `pre_heads(obs_own, critic_row) -> (za, zc)` is everything up to shared_layer's pre-activations, and heads_loss takes it from there
+    with this module's act_out and val_out.  `forward` is the same code and returns the same bytes in both modes (the sampler-form
+    forward, old_logits and the golden-file tests use it); state_dict() is the same."""
+
+    def __init__(self, kind, attention="torch", inputs="torch", trunk="torch", heads="torch"):
         super().__init__()
         self.kind = int(kind)
         self.trunk = _trunk_mode(trunk)
+        self.heads = _heads_mode(heads, self.trunk)
         if inputs not in INPUT_MODES:
             raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
         self.inputs = inputs
@@ -563,7 +697,8 @@ class TrainableNet(nn.Module):
         a, _ = att(h, h, h, need_weights=False)
         return F.normalize(h + a, dim=-1)
 
-    def forward(self, obs_own, critic_row):
+    def _front(self, obs_own, critic_row):
+        """-> (h, y, flat): the actor's and the critic's rows as shared_layer sees them; flat: 2-D fight inputs, run as chunks of length 1"""
         kind = self.kind
         flat = PN.HAS_ATT[kind] and obs_own.dim() == 2
         if flat:
@@ -589,6 +724,19 @@ class TrainableNet(nn.Module):
             attend = self._attend_fused if self.attention == "fused" else self._attend_torch
             h[-1], y[-1] = attend(self.att_act, h[-1]), attend(self.att_val, y[-1])
         h, y = (t[0] if len(t) == 1 else torch.cat(t, dim=-1) for t in (h, y))
+        return h, y, flat
+
+    def pre_heads(self, obs_own, critic_row):
+        """forward up to shared_layer's pre-activations -> (za, zc) [..., 500] (fight kinds: [S, L, 500], or [R, 500] for 2-D inputs):
+        what heads_loss takes.  trunk="torch" only: dense_tanh keeps no pre-activation."""
+        if self.trunk == "fused":
+            raise ValueError('pre_heads needs trunk="torch": dense_tanh has the tanh inside')
+        h, y, flat = self._front(obs_own, critic_row)
+        za, zc = self.shared_layer(h), self.shared_layer(y)
+        return (za.squeeze(1), zc.squeeze(1)) if flat else (za, zc)
+
+    def forward(self, obs_own, critic_row):
+        h, y, flat = self._front(obs_own, critic_row)
         if self.trunk == "fused":
             lin = self.shared_layer._model[0]
             h, y = dense_tanh((h, y), lin.weight, lin.bias)
@@ -1242,13 +1390,16 @@ class _PolicySGD:
         return self.result(m, n, rows)
 
 
-def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused, floats, ints):
-    """what both learners' constructors take the same way, set on `learner`: the modes, grad_clip and the flag validated in this order
-    before the device is looked at, then the device and the PPO hyper-parameters (floats and ints by name) -> the optimizer mode"""
+def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused, floats, ints, heads="torch", trunk="torch"):
+    """what both learners' constructors take the same way, set on `learner`: the modes, grad_clip, the flag and `heads` validated in this
+    order before the device is looked at, then the device and the PPO hyper-parameters (floats and ints by name) -> the optimizer mode"""
     mode = _optimizer_mode(optimizer)
     learner.step = _step_mode(step, optimizer)
     learner.grad_clip = _grad_clip(grad_clip)
     learner.shuffle_sequences = _shuffle_flag(shuffle_sequences)
+    learner.heads = _heads_mode(heads, trunk)
+    if learner.heads == "fused" and not fused:
+        raise ValueError('heads="fused" needs fused=True: the fused tail has the loss kernel inside')
     _need_gpu(who)
     learner.device = torch.device(device) if not isinstance(device, torch.device) else device
     for k, v in floats.items():
@@ -1294,6 +1445,7 @@ class PPOLearner:
     Inside a minibatch step nothing synchronises with the host (beyond what torch.optim.Adam does by itself); `update` itself synchronises
     when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
 
+    @_heads_keyword
     def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
                  vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch",
                  optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
@@ -1320,25 +1472,32 @@ class PPOLearner:
         index_select; step="graph" stages through hh_minibatch_stage_gather from an order table uploaded once per update into a persistent
         device buffer of 4 * num_sgd_iter * S bytes for S chunks, grown to twice the need so that its address outlives batches of varying
         size (30 passes: about 6.6 MB for 1.09 M fight rows in chunks of 20, about 131 MB for the same rows as escape rows).  RLlib's own
-        permutation is unseeded, so equality with it is not claimed; what shuffling does to learning curves has not been measured here."""
+        permutation is unseeded, so equality with it is not claimed; what shuffling does to learning curves has not been measured here.
+        heads (keyword only, taken by _heads_keyword in front of this signature): "torch" (the default): nothing changes.  "fused" (needs fused=True and trunk="torch"): the modules are built
+        with heads="fused", every minibatch step's forward stops at shared_layer's pre-activations (TrainableNet.pre_heads) and tanh, the
+        two heads, the loss and their backward run as one hh_heads_loss (heads_loss, unscaled: the step calls total.backward()), in all
+        three step modes, with grad_clip and shuffle_sequences as before."""
         self.optimizer = _learner_options(
             self, "PPOLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
             dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
-            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed))
+            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed), self._heads_arg, trunk)
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
         self.attention, self.inputs, self.trunk = attention, inputs, _trunk_mode(trunk)
         # tied once, before the move: tie hands every module the first one's shared_layer MODULE, and nn.Module.to() moves a module's
         # tensors in place without ever replacing a submodule object, so the one layer stays the one layer on the device
-        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs, trunk=trunk).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs, trunk=trunk, heads=self.heads).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
                             for k, sd in zip(self.kinds, state_dicts)])
         for m in self.modules:
             m.to(self.device)
         self.recurrent = PN.HAS_ATT[self.kinds[0]]
         esc = not self.recurrent
         # per policy its own driver: the module's Adam, the step book, kl_coeff; one stage launch of every column
-        self._sgd = [_PolicySGD(self, m, lr, kl_coeff, self.optimizer == "fused", forward=lambda mb, m=m: m(mb["obs"], mb["critic"]),
-                                loss=lambda logits, vf, mb, kl, a=a: self.loss(a, logits, vf, mb, kl),
+        # (heads="fused": the forward callable stops at the pre-activations and the loss callable is the fused tail)
+        tail = self.heads == "fused"
+        self._sgd = [_PolicySGD(self, m, lr, kl_coeff, self.optimizer == "fused",
+                                forward=(lambda mb, m=m: m.pre_heads(mb["obs"], mb["critic"])) if tail else (lambda mb, m=m: m(mb["obs"], mb["critic"])),
+                                loss=(lambda za, zc, mb, kl, a=a: self.heads_loss(a, za, zc, mb, kl)) if tail else (lambda logits, vf, mb, kl, a=a: self.loss(a, logits, vf, mb, kl)),
                                 stage_groups=lambda names: [(names, 1 if esc else self.max_seq_len)], policy=a, noun="chunks")
                      for a, m in enumerate(self.modules)]
         self.optimizers = [d.optimizer for d in self._sgd]
@@ -1420,6 +1579,14 @@ class PPOLearner:
         kw = dict(n_comp=n_comp_of(self.kinds[agent]), clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
                   entropy_coeff=self.entropy_coeff, kl_coeff=self._sgd[agent].kl_term() if kl_coeff is None else kl_coeff)
         return (ppo_loss if self.fused else ppo_loss_torch)(logits, vf, mb, **kw)
+
+    def heads_loss(self, agent, za, zc, mb, kl_coeff=None):
+        """heads="fused": the policy's loss of one minibatch from pre_heads' (za, zc), through heads_loss with the module's act_out and
+        val_out; the gradients are handed to total.backward() unscaled"""
+        m = self.modules[agent]
+        return heads_loss(za, zc, m.act_out, m.val_out, mb, n_comp=n_comp_of(self.kinds[agent]), clip_param=self.clip_param, vf_clip_param=self.vf_clip_param,
+                          vf_loss_coeff=self.vf_loss_coeff, entropy_coeff=self.entropy_coeff,
+                          kl_coeff=self._sgd[agent].kl_term() if kl_coeff is None else kl_coeff, scale_grad=False)
 
     def _columns(self, b, staged=False):
         """policy_batch's dict as the driver takes it -> (columns [S, ...], host seq_len [S]: the chunks' lengths, ones for escape rows).
@@ -1729,11 +1896,14 @@ class CommanderTrainable(nn.Module):
     inputs = "fused" (float32 on the GPU) runs inp1..inp4 and v1..v4 as one input_stage each (commander_stage_tables()) that read obs_own and
     critic_row as they are; the default "torch" slices, concatenates and runs the eight layers one by one.  state_dict() is the same.
     trunk = "fused" (float32 on the GPU) runs shared_layer, its bias and tanh over the actor's and the critic's rows as ONE dense_tanh; the
-    default "torch" applies the layer twice.  state_dict() is the same; independent of `inputs`."""
+    default "torch" applies the layer twice.  state_dict() is the same; independent of `inputs`.
+    heads = "fused" (trunk="torch"): TrainableNet's argument — `pre_heads(obs_own, critic_row, state_in, seq_len, fused_gru=True) -> (za, zc)`
+    [S, L, 500] is the forward up to shared_layer's pre-activations, for heads_loss(n_comp=1); `forward` and state_dict() are unchanged."""
 
-    def __init__(self, inputs="torch", trunk="torch"):
+    def __init__(self, inputs="torch", trunk="torch", heads="torch"):
         super().__init__()
         self.trunk = _trunk_mode(trunk)
+        self.heads = _heads_mode(heads, self.trunk)
         if inputs not in INPUT_MODES:
             raise ValueError(f"inputs is one of {INPUT_MODES}, got {inputs!r}")
         self.inputs = inputs
@@ -1744,7 +1914,8 @@ class CommanderTrainable(nn.Module):
         self.v1, self.v2, self.v3, self.v4 = _FC(35, 100), _FC(35, 100), _FC(35, 100), _FC(105, 200)
         self.val_out = _FC(500, 1)
 
-    def forward(self, obs_own, critic_row, state_in, seq_len, fused_gru=True, return_states=False):
+    def _front(self, obs_own, critic_row, state_in, seq_len, fused_gru):
+        """-> (the actor's rows, the critic's rows as shared_layer sees them, y_a, y_v: the GRUs' outputs)"""
         if self.inputs == "fused":
             tables = commander_stage_tables()
             x, x_full = input_stage(obs_own.contiguous(), *stage_groups(self, COMMANDER_STAGE_LAYERS["actor"], tables["actor"]))
@@ -1769,13 +1940,24 @@ class CommanderTrainable(nn.Module):
             y_a, y_v = gru_sequence_torch(*act, seq_len), gru_sequence_torch(*val, seq_len)
         x_full = F.normalize(x_full + y_a, dim=-1)
         z_full = F.normalize(z_full + y_v, dim=-1)
+        return torch.cat((x, x_full), dim=-1), torch.cat((z, z_full), dim=-1), y_a, y_v
+
+    def pre_heads(self, obs_own, critic_row, state_in, seq_len, fused_gru=True):
+        """forward up to shared_layer's pre-activations -> (za, zc) [S, L, 500]: what heads_loss(n_comp=1) takes.  trunk="torch" only."""
+        if self.trunk == "fused":
+            raise ValueError('pre_heads needs trunk="torch": dense_tanh has the tanh inside')
+        xa, xc, _, _ = self._front(obs_own, critic_row, state_in, seq_len, fused_gru)
+        return self.shared_layer(xa), self.shared_layer(xc)
+
+    def forward(self, obs_own, critic_row, state_in, seq_len, fused_gru=True, return_states=False):
+        xa, xc, y_a, y_v = self._front(obs_own, critic_row, state_in, seq_len, fused_gru)
         if self.trunk == "fused":
             lin = self.shared_layer._model[0]
-            h, y = dense_tanh((torch.cat((x, x_full), dim=-1), torch.cat((z, z_full), dim=-1)), lin.weight, lin.bias)
+            h, y = dense_tanh((xa, xc), lin.weight, lin.bias)
             logits, value = self.act_out(h), self.val_out(y).squeeze(-1)
         else:
-            logits = self.act_out(torch.tanh(self.shared_layer(torch.cat((x, x_full), dim=-1))))
-            value = self.val_out(torch.tanh(self.shared_layer(torch.cat((z, z_full), dim=-1)))).squeeze(-1)
+            logits = self.act_out(torch.tanh(self.shared_layer(xa)))
+            value = self.val_out(torch.tanh(self.shared_layer(xc))).squeeze(-1)
         if not return_states:
             return logits, value
         last = (seq_len.long() - 1).clamp(min=0)[:, None, None].expand(-1, 1, GRU_H)
@@ -1828,6 +2010,7 @@ class CommanderLearner:
     optimizer="fused", step="graph" replays every minibatch step from one captured HIP graph, as PPOLearner's do (graph_prepare;
     DESIGN.md section 19): the same minibatches in the same order, no Python, autograd dispatch or torch.optim.Adam between launches."""
 
+    @_heads_keyword
     def __init__(self, state_dict, device, lr=1e-4, clip_param=0.25, kl_target=0.05, kl_coeff=0.2, vf_clip_param=10.0, vf_loss_coeff=1.0,
                  entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, inputs="torch", trunk="torch",
                  optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
@@ -1844,19 +2027,24 @@ class CommanderLearner:
         seq_len travel with their sequences.  The eager modes gather with index_select; the graph's two stage launches become
         hh_minibatch_stage_gather through one order table of 4 * num_sgd_iter * 3 S bytes, uploaded once per update into a persistent
         buffer (grown to twice the need).  Slot 0 of a staged minibatch is a real sequence, so seq_len[0] >= 1 holds as before.  What
-        shuffling does to learning curves has not been measured here."""
+        shuffling does to learning curves has not been measured here.
+        heads (keyword only, taken by _heads_keyword in front of this signature): PPOLearner's argument ("torch", the default: nothing changes; "fused", with fused=True and trunk="torch": the
+        step's forward stops at CommanderTrainable.pre_heads and the tail is one hh_heads_loss with n_comp = 1)."""
         self.optimizer_mode = _learner_options(
             self, "CommanderLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
             dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
-            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed))
+            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed), self._heads_arg, trunk)
         self.inputs, self.trunk = inputs, _trunk_mode(trunk)
-        self.module = CommanderTrainable(inputs=inputs, trunk=trunk).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        self.module = CommanderTrainable(inputs=inputs, trunk=trunk, heads=self.heads).load_numpy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
                                                        for k, v in state_dict.items()}).to(self.device)
         # the one policy's driver.  hh_minibatch_stage takes 8 columns: the per-step columns (chunks of max_seq_len rows) in one launch, the
         # per-sequence ones (state_in, seq_len: chunks of one row) in a second
+        # (heads="fused": the forward callable stops at the pre-activations and the loss callable is the fused tail)
+        args = lambda mb: (mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"])
+        tail = self.heads == "fused"
         self._sgd = _PolicySGD(self, self.module, lr, kl_coeff, self.optimizer_mode == "fused",
-                               forward=lambda mb: self.module(mb["obs"], mb["critic"], mb["state_in"], mb["seq_len"], fused_gru=self.fused),
-                               loss=self.loss, stage_groups=lambda names: [(names[:L.STAGE_MAX_COLS], self.max_seq_len), (names[L.STAGE_MAX_COLS:], 1)],
+                               forward=(lambda mb: self.module.pre_heads(*args(mb), fused_gru=self.fused)) if tail else (lambda mb: self.module(*args(mb), fused_gru=self.fused)),
+                               loss=self.heads_loss if tail else self.loss, stage_groups=lambda names: [(names[:L.STAGE_MAX_COLS], self.max_seq_len), (names[L.STAGE_MAX_COLS:], 1)],
                                policy=0, noun="sequences")
         self.optimizer, self._book = self._sgd.optimizer, self._sgd.book
 
@@ -1921,6 +2109,14 @@ class CommanderLearner:
         kw = dict(clip_param=self.clip_param, vf_clip_param=self.vf_clip_param, vf_loss_coeff=self.vf_loss_coeff,
                   entropy_coeff=self.entropy_coeff, kl_coeff=self._sgd.kl_term() if kl_coeff is None else kl_coeff)
         return (ppo_loss_categorical if self.fused else ppo_loss_categorical_torch)(logits, vf, mb, **kw)
+
+    def heads_loss(self, za, zc, mb, kl_coeff=None):
+        """heads="fused": the loss of one minibatch from pre_heads' (za, zc), through heads_loss(n_comp=1) with the module's act_out and
+        val_out; the gradients are handed to total.backward() unscaled"""
+        m = self.module
+        return heads_loss(za, zc, m.act_out, m.val_out, mb, n_comp=1, clip_param=self.clip_param, vf_clip_param=self.vf_clip_param,
+                          vf_loss_coeff=self.vf_loss_coeff, entropy_coeff=self.entropy_coeff,
+                          kl_coeff=self._sgd.kl_term() if kl_coeff is None else kl_coeff, scale_grad=False)
 
     def _columns(self, b, staged=False):
         """policy_batch's dict (with old_logits) as the driver takes it -> (columns [3 S, ...], host seq_len [3 S]).  staged: as the graph's

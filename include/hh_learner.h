@@ -321,6 +321,43 @@ int hh_minibatch_stage_gather(int32_t n_cols, const hh_stage_col *cols, int32_t 
  * [0, table_rows)), cursor[0] += 1, step[0] += 1.  All pointers [dev]. */
 int hh_train_commit(const double *stats, double *table, int32_t table_rows, int32_t *cursor, int32_t *step, void *stream);
 
+/* ---- the tail of the minibatch step as ONE row pass: tanh, both output heads, the PPO loss, and the backward of all three ----
+ *
+ * What lies between shared_layer's GEMM and the gradient that flows back into it (learner.heads_loss), for n_rows rows:
+ *     h = tanh(za);  y = tanh(zc);  logits = h w_act^T + b_act;  vf = y . w_val + b_val
+ *     stats, d_logits, d_vf: hh_ppo_loss's (prm->n_comp = 4 | 3) or hh_ppo_loss_categorical's (prm->n_comp = 1), by the same device code
+ *     d_za = (d_logits w_act) (1 - h^2);  d_zc = d_vf w_val (1 - y^2)
+ *     d_w_act = d_logits^T h;  d_b_act = column sums of d_logits;  d_w_val = d_vf^T y;  d_b_val = sum of d_vf
+ * with n_out = 26 | 24 | 3 logits for n_comp = 4 | 3 | 1.  All [dev], float32 unless said:
+ *   za, zc          [n_rows, 500]   shared_layer's output for the actor's and the critic's rows, bias added, BEFORE tanh
+ *   w_act, b_act    [n_out, 500], [n_out]   act_out;    w_val, b_val  [500], [1]   val_out
+ *   old_logits      [n_rows, 32] (n_comp 4 | 3) or [n_rows, 4] (n_comp 1);  actions i8 [n_rows, 4] or i8 [n_rows]
+ *   old_logp, adv, target [n_rows];  mask u8 [n_rows] or NULL;  n_valid i32 [1]: as hh_ppo_loss / hh_ppo_loss_categorical take them
+ *   stats           f64 [HH_PPO_STATS]: the same six slots (hh_train_commit takes it as it stands)
+ *   d_za, d_zc      [n_rows, 500]   d total / d pre-activation;  d_w_act [n_out, 500], d_b_act [n_out], d_w_val [500], d_b_val [1]
+ *   logits, vf      [n_rows, n_out], [n_rows]: optional (NULL = not written); 0.0f in masked rows
+ *   scratch         scratch_bytes >= hh_heads_loss_scratch_bytes(n_rows, n_comp): per workgroup 4 + n_out + 1 float64 sums and
+ *                   (n_out + 1) * 500 float32 partial sums; at most 256 workgroups (13.9 MB at n_out = 26)
+ * Two launches, ordered on `stream`; no host synchronisation, no allocation, no atomics, HIP-graph capturable.  The same inputs give the
+ * same bytes on every run: the mapping of the 16-row tiles to workgroups and the order of every addition depend on n_rows and n_comp
+ * only (hh_heads_loss_geometry reports both numbers).  Per-row arithmetic is float32 fmaf, accumulated in float32; d_w's partial sums are
+ * float32 inside a workgroup and added across workgroups in float64, rounded once; d_b and the five loss sums are float64 throughout.
+ * A row with mask == 0 may hold anything, NaN included, in every input, za and zc among them: nothing of it reaches an output, its d_za
+ * and d_zc rows are exactly 0.0f, and the weight sums step over it (selection, not a multiplication by 0).  With n_valid <= 0 every row
+ * counts as masked: every gradient is exactly 0.0f and stats is what hh_ppo_loss documents for n_valid = 0.
+ * HH_E_ARG, with nothing written: a NULL pointer other than mask, logits, vf; za, zc, d_za or d_zc not 16-byte aligned (scratch, stats:
+ * 8-byte; actions of n_comp 4 | 3: 4-byte); n_comp outside {1, 3, 4}; a non-zero reserved field; n_rows < 1 (or > 2^30); a scratch
+ * smaller than hh_heads_loss_scratch_bytes says.  An output may not overlap any other tensor of the call. */
+int hh_heads_loss_scratch_bytes(int64_t n_rows, int32_t n_comp, int64_t *bytes);
+/* the geometry a call of n_rows rows uses: rows per tile, and the workgroups that walk the tiles grid-stride (tile t goes to workgroup
+ * t mod n_workgroups).  Host only. */
+int hh_heads_loss_geometry(int64_t n_rows, int32_t n_comp, int32_t *tile_rows, int32_t *n_workgroups);
+int hh_heads_loss(int64_t n_rows, const float *za, const float *zc, const float *w_act, const float *b_act, const float *w_val,
+                  const float *b_val, const float *old_logits, const int8_t *actions, const float *old_logp, const float *adv,
+                  const float *target, const uint8_t *mask, const int32_t *n_valid, const hh_ppo_loss_params *prm, double *stats,
+                  float *d_za, float *d_zc, float *d_w_act, float *d_b_act, float *d_w_val, float *d_b_val, float *logits, float *vf,
+                  void *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,11 @@
           whole update at sgd_minibatch_size = 256 eager against graph (captures included) and the cost of one capture; its lines are
           appended to --out.  The same rule for gain / loss, with eager + torch Adam as the base.  `--step graph --launches eager|graph`
           runs nothing but --launch-count steps of that form after the set-up: the program of a kernel trace that counts launches
+          (--heads-mode fused: of a heads="fused" learner)
+  heads   --heads: CommanderLearner(heads="fused") (hh_heads_loss, n_comp = 1) against heads="torch", both in one process, inputs="fused":
+          the kernel alone at 280 and 71200 rows against its algorithmic bytes, the minibatch step at 256 and 16384 rows eager + torch
+          Adam and as graph replay, 50 replays back to back, and one whole graph update at sgd_minibatch_size = 256; appended to --out.
+          The same rule for gain / loss
   tile    --tile: the compiled tiles of hh_k_gru_seq_fwd / _bwd, each forced through HH_GRU_TILE in a child process of its own: both GRUs'
           forward + backward kernels alone at --tile-seqs sequence counts (13 ... 854) and the graph step at 256 rows; then every narrow
           tile against tile 16 by the same rule; appended to --out
@@ -301,7 +306,7 @@ def step_graph(a, say):
     import torch
     from hhmarl_2d_amd import learner as LR
     dev = torch.device("cuda", 0)
-    FUSED = dict(inputs="fused")
+    FUSED = dict(inputs="fused", heads=a.heads_mode if a.launches else "torch")
     make = lambda **kw: LR.CommanderLearner.trainable_init(dev, seed=6, **FUSED, **kw)
     ro, net, b, seq_len = _policy_batch(a, **FUSED)
     if a.launches:       # for a kernel trace: nothing but launch_count steps of one form after the set-up
@@ -364,6 +369,84 @@ def step_graph(a, say):
         f"{t_e:.1f} ms; graph {t_g:.1f} ms; eager / graph = {t_e / t_g:.2f}x")
     say(f"    mean statistics, eager: { {k: round(v, 6) for k, v in st_e.items()} }")
     say(f"    mean statistics, graph: { {k: round(v, 6) for k, v in st_g.items()} }")
+
+
+def step_heads(a, say):
+    """CommanderLearner(heads="fused") (hh_heads_loss with n_comp = 1: tanh, act_out, val_out, the Categorical's loss and their backward as one
+    row pass) against heads="torch", both in this run, inputs = fused: the kernel alone at 280 and 71200 rows, the minibatch step at 256 and
+    16384 rows (eager + torch Adam, and the graph step: one replay per timing and 50 back to back), one whole graph update."""
+    import ctypes as C
+    import torch
+    from hhmarl_2d_amd import _lib as L
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    med = statistics.median
+    K = 50
+    say(f"# tools/commander_learner_bench.py --heads on {torch.cuda.get_device_name(0)}: CommanderLearner(heads=\"fused\") against the default "
+        f"heads=\"torch\", both in this run; inputs = fused; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+    lib = L.lib()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    for R in (280, 71200):
+        g = torch.Generator().manual_seed(R)
+        r = lambda *shape: torch.randn(shape, generator=g).to(dev)
+        za, zc, w_act, b_act, w_val, b_val = r(R, 500), r(R, 500), 0.04 * r(3, 500), 0.04 * r(3), 0.04 * r(500), 0.04 * r(1)
+        old, act, old_logp, adv, target = r(R, 4), torch.zeros((R,), dtype=torch.int8, device=dev), -1.0 + 0.1 * r(R), r(R), r(R)
+        n_valid = torch.full((1,), R, dtype=torch.int32, device=dev)
+        outs = [torch.empty_like(t) for t in (za, zc, w_act, b_act, w_val, b_val)]
+        stats = torch.empty((6,), dtype=torch.float64, device=dev)
+        nb = C.c_int64()
+        L.check(lib.hh_heads_loss_scratch_bytes(R, 1, C.byref(nb)))
+        scratch = torch.empty((nb.value // 8,), dtype=torch.float64, device=dev)
+        prm = L.HHPpoLossParams(n_comp=1, reserved0=0, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2, reserved1=0.0)
+        fn = lambda: L.check(lib.hh_heads_loss(R, p(za), p(zc), p(w_act), p(b_act), p(w_val), p(b_val), p(old), p(act), p(old_logp), p(adv), p(target),
+                                               None, p(n_valid), C.byref(prm), p(stats), *[p(o) for o in outs], None, None, p(scratch), nb.value, st))
+        t = events(fn, a.iters, a.warmup)
+        nbytes = R * (4 * 500 * 4 + 4 * 4 + 1 + 12) + 2 * 4 * 501 * 4
+        say(f"    hh_heads_loss alone (two launches), n_comp = 1, {R} rows: {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB algorithmic "
+            f"bytes ({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+        del za, zc, outs, scratch
+
+    def burst(fn):
+        out = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) / K)
+        return " ".join(f"{d:.3f}" for d in out)
+
+    make = lambda **kw: LR.CommanderLearner.trainable_init(dev, seed=6, inputs="fused", **kw)
+    ro, net, b, seq_len = _policy_batch(a, inputs="fused")
+    eager = {h: make(heads=h) for h in ("torch", "fused")}
+    for size in (256, 16384):
+        sub, mb, n_seq, n_rows = _one_minibatch(b, seq_len, size)
+        n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+        graphs = {h: _graph_learner(sub, n_total, inputs="fused", heads=h)[0] for h in ("torch", "fused")}
+        t_e = {h: events(lambda lr=lr: lr.minibatch_step(mb), a.iters, a.warmup) for h, lr in eager.items()}
+        t_g = {h: events(lambda lr=lr: lr.graph_replay(1), a.iters, a.warmup) for h, lr in graphs.items()}
+        say(f"minibatch step (forward + loss + backward + Adam, fused GRU), {n_rows} unpadded rows in {n_seq} sequences: eager + torch Adam: heads = torch "
+            f"{q(t_e['torch'])}; heads = fused {q(t_e['fused'])} [{verdict(t_e['torch'], t_e['fused'], 'torch')}]")
+        say(f"    graph step: heads = torch {q(t_g['torch'])}; heads = fused {q(t_g['fused'])} [{verdict(t_g['torch'], t_g['fused'], 'torch')}]")
+        say(f"    {K} graph replays back to back, ms per step, three runs: heads = torch {burst(lambda: graphs['torch'].graph_replay(K))} | heads = fused "
+            f"{burst(lambda: graphs['fused'].graph_replay(K))}")
+        del graphs
+    res = {}
+    for h in ("torch", "fused", "torch", "fused"):
+        lr = make(heads=h, num_sgd_iter=a.passes, sgd_minibatch_size=256, kl_coeff=0.0, **GRAPH)
+        lr.update(ro.episodes, net)                # the first update captures
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stu = lr.update(ro.episodes, net)
+            torch.cuda.synchronize()
+            res.setdefault(h, []).append((time.perf_counter() - t0) * 1e3)
+    say(f"one whole graph update at {a.arenas} arenas, T = {a.T} ({a.passes} pass(es), minibatches of >= 256 rows: {stu['steps']} steps over {stu['rows']} "
+        f"rows, kl_coeff = 0 so that no graph is captured again), host clock to a synchronise, 2 x 3 updates after the capturing one, learners alternating: "
+        f"heads = torch {q(res['torch'])}; heads = fused {q(res['fused'])} [{verdict(res['torch'], res['fused'], 'torch')}]")
 
 
 def step_clip(a, say):
@@ -629,9 +712,11 @@ def main():
     ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences against shuffle_sequences = False section; appended to --out")
     ap.add_argument("--tile", action="store_true", help="only the GRU tile instances, each through HH_GRU_TILE in a child; appended to --out")
     ap.add_argument("--tile-seqs", default="13,26,52,104,208,416,854", help="the sequence counts of --tile's GRUs-alone timing")
+    ap.add_argument("--heads", action="store_true", help="only the heads=\"fused\" against heads=\"torch\" section; appended to --out")
+    ap.add_argument("--heads-mode", choices=["torch", "fused"], default="torch", help="with --launches: the learner's heads option")
     ap.add_argument("--launches", choices=["eager", "graph"], help="with --step graph: only --launch-count steps of this form (for a kernel trace)")
     ap.add_argument("--launch-count", type=int, default=20)
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip", "shuffle"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip", "shuffle", "heads"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     a.tile_seqs = [int(x) for x in a.tile_seqs.split(",")]
     if a.step:
@@ -646,9 +731,11 @@ def main():
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
         {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk, "graph": step_graph,
-         "tile": step_tile, "clip": step_clip, "shuffle": step_shuffle}[a.step](a, say)
+         "tile": step_tile, "clip": step_clip, "shuffle": step_shuffle, "heads": step_heads}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
+    if a.heads:
+        sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step heads {' '.join(fwd)}", shell=True))
     if a.graph:
         sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step graph {' '.join(fwd)}", shell=True))
     if a.clip:

@@ -52,6 +52,12 @@
           (c) one whole graph update at --step-minibatch (medians of --iters updates, kl_coeff = 0); (d) the host time of
           shuffled_schedule against sequence_schedule for 30 passes, and the order table's bytes.  The same spread rule, worded cost /
           gain / no difference
+  heads   --heads runs this section alone and appends its lines to --out: PPOLearner(heads="fused") (hh_heads_loss: tanh, act_out, val_out,
+          the loss and their backward as one row pass) against heads="torch" in the same run, attention="fused", inputs="fused" where they
+          apply: (a) hh_heads_loss alone at 280 and 71200 rows as bytes/s of its algorithmic bytes (8 KB per row: za, zc in, d_za, d_zc
+          out; plus the head weights in and their gradients out); (b) the Fight1 and the Esc1 minibatch step at 256 and 65536 rows, eager
+          + torch Adam and the graph step, one step per timing and 50 replays back to back; (c) one whole graph update at
+          --step-minibatch.  The same rule for gain / loss.  --step-launches with --heads-mode fused counts the launches of that path
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -93,6 +99,8 @@ def main():
     ap.add_argument("--step", action="store_true", help="only the graph-step section; its lines are appended to --out")
     ap.add_argument("--clip", action="store_true", help="only the gradient-clipping section; its lines are appended to --out")
     ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences section; its lines are appended to --out")
+    ap.add_argument("--heads", action="store_true", help="only the fused-tail section; its lines are appended to --out")
+    ap.add_argument("--heads-mode", choices=("torch", "fused"), default="torch", help="--step-launches: the learner's heads option")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
     ap.add_argument("--step-count", type=int, default=16)
@@ -415,7 +423,7 @@ def main():
             word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
             return f"eager+torch / this = {med(t_base) / med(t_new):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
 
-        FUSED = dict(attention="fused", inputs="fused", trunk="torch")
+        FUSED = dict(attention="fused", inputs="fused", trunk="torch", heads=a.heads_mode if a.step_launches else "torch")
         make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
         w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
         bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
@@ -635,7 +643,7 @@ def main():
             word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
             return f"off -> on: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
 
-        FUSED = dict(attention="fused", inputs="fused", trunk="torch")
+        FUSED = dict(attention="fused", inputs="fused", trunk="torch", heads=a.heads_mode if a.step_launches else "torch")
         make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
         w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
         bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
@@ -739,6 +747,124 @@ def main():
     if a.shuffle:
         lines.clear()
         shuffle_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def heads_section():
+        """heads="fused" against heads="torch": the kernel alone, the Fight1 and Esc1 minibatch step (eager and graph), one graph update"""
+        import ctypes as C
+        from hhmarl_2d_amd import _lib as L
+        med = statistics.median
+        K = 50
+
+        def verdict(t_torch, t_fused):
+            spread = max(max(t_torch) - min(t_torch), max(t_fused) - min(t_fused))
+            d = med(t_torch) - med(t_fused)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"torch / fused = {med(t_torch) / med(t_fused):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --heads on {torch.cuda.get_device_name(0)}: PPOLearner(heads=\"fused\") against the default heads=\"torch\", both in "
+            f"this run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended):")
+        # (a) the kernel alone
+        lib = L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        for n_comp, n_out in ((4, 26), (3, 24)):
+            for R in (280, 71200):
+                g = torch.Generator().manual_seed(R + n_comp)
+                r = lambda *shape: torch.randn(shape, generator=g).to(dev)
+                za, zc, w_act, b_act, w_val, b_val = r(R, 500), r(R, 500), 0.04 * r(n_out, 500), 0.04 * r(n_out), 0.04 * r(500), 0.04 * r(1)
+                old, act = r(R, 32), torch.zeros((R, 4), dtype=torch.int8, device=dev)
+                old_logp, adv, target = -6.0 + 0.1 * r(R), r(R), r(R)
+                n_valid = torch.full((1,), R, dtype=torch.int32, device=dev)
+                outs = [torch.empty_like(t) for t in (za, zc, w_act, b_act, w_val, b_val)]
+                stats = torch.empty((6,), dtype=torch.float64, device=dev)
+                nb, tile, wgs = C.c_int64(), C.c_int32(), C.c_int32()
+                L.check(lib.hh_heads_loss_scratch_bytes(R, n_comp, C.byref(nb)))
+                L.check(lib.hh_heads_loss_geometry(R, n_comp, C.byref(tile), C.byref(wgs)))
+                scratch = torch.empty((nb.value // 8,), dtype=torch.float64, device=dev)
+                prm = L.HHPpoLossParams(n_comp=n_comp, reserved0=0, clip_param=0.25, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2, reserved1=0.0)
+                fn = lambda: L.check(lib.hh_heads_loss(R, p(za), p(zc), p(w_act), p(b_act), p(w_val), p(b_val), p(old), p(act), p(old_logp), p(adv), p(target),
+                                                       None, p(n_valid), C.byref(prm), p(stats), *[p(o) for o in outs], None, None, p(scratch), nb.value, st))
+                t = events(fn)
+                nbytes = R * (4 * 500 * 4 + 32 * 4 + 4 + 12) + 2 * (n_out + 1) * 501 * 4
+                say(f"    hh_heads_loss alone (two launches), n_comp = {n_comp}, {R} rows ({wgs.value} workgroups, tiles of {tile.value} rows, {nb.value / 1e6:.2f} MB of "
+                    f"scratch): {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB algorithmic bytes "
+                    f"({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+                del za, zc, outs, scratch
+
+        def burst(fn):
+            out = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / K)
+            return " ".join(f"{d:.3f}" for d in out)
+
+        # (b) the minibatch step, (c) the whole update
+        for mode, name, opts in (("fight", "Fight1", dict(attention="fused", inputs="fused")), ("escape", "Esc1", dict(inputs="fused"))):
+            make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode=mode, seed=1, **opts, **kw)
+            w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon, agent_mode=1 if mode == "escape" else 0), device=0)
+            bank = PolicyBank.trainable_init(dev, mode=mode, seed=1, max_rows=2 * a.arenas)
+            ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+            for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+                ro.collect()
+            rows = ro.episodes.rows()
+            eager = {h: make(heads=h) for h in ("torch", "fused")}
+            with torch.no_grad():
+                old = eager["torch"].old_logits(rows["obs"], bank, ro.episodes.N)
+                b = eager["torch"].policy_batch(rows, old, 0)
+            cols, seq_len = eager["torch"]._columns(b)
+            for size in (256, 65536):
+                s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+                sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+                mb = {k: v for k, v in sub.items() if k != "seq_len"}
+                n_rows = int(seq_len[s0:s1].sum())
+                mb["n_valid"] = torch.tensor([n_rows], dtype=torch.int32, device=dev)
+                n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+                graphs = {h: make(heads=h, optimizer="fused", step="graph", num_sgd_iter=n_total, sgd_minibatch_size=1 << 30) for h in ("torch", "fused")}
+                for lr in graphs.values():
+                    lr.graph_prepare(0, sub)
+                t_e = {h: events(lambda lr=lr: lr.minibatch_step(0, mb)) for h, lr in eager.items()}
+                t_g = {h: events(lambda lr=lr: lr.graph_replay(0, 1)) for h, lr in graphs.items()}
+                say(f"minibatch step ({name}, forward + loss + backward + Adam), {n_rows} unpadded rows in {s1 - s0} {'chunks of 20' if mode == 'fight' else 'rows'}: "
+                    f"eager + torch Adam: heads = torch {q(t_e['torch'])}; heads = fused {q(t_e['fused'])} [{verdict(t_e['torch'], t_e['fused'])}]")
+                say(f"    graph step: heads = torch {q(t_g['torch'])}; heads = fused {q(t_g['fused'])} [{verdict(t_g['torch'], t_g['fused'])}]")
+                say(f"    {K} graph replays back to back, ms per step, three runs: heads = torch {burst(lambda: graphs['torch'].graph_replay(0, K))} | "
+                    f"heads = fused {burst(lambda: graphs['fused'].graph_replay(0, K))}")
+                del graphs
+        # (c) one whole graph update at 1024 arenas (a world of its own: the steps above need the large batch, this does not)
+        N_UPD = 1024
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, attention="fused", inputs="fused", **kw)
+        w = World(make_config(n_arenas=N_UPD, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * N_UPD)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        res = {}
+        for h in ("torch", "fused", "torch", "fused"):
+            lr = make(heads=h, optimizer="fused", step="graph", num_sgd_iter=a.passes, sgd_minibatch_size=a.step_minibatch, kl_coeff=0.0)
+            lr.update(ro.episodes, bank)           # the first update captures
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                stu = lr.update(ro.episodes, bank)
+                torch.cuda.synchronize()
+                res.setdefault(h, []).append((time.perf_counter() - t0) * 1e3)
+        say(f"one whole graph update of both Fight policies at {N_UPD} arenas ({a.passes} pass(es), minibatches of >= {a.step_minibatch} rows, "
+            f"{stu[0]['steps']} + {stu[1]['steps']} steps over {stu[0]['rows']} rows each, kl_coeff = 0 so that no graph is captured again), host clock to a "
+            f"synchronise, 2 x 3 updates after the capturing one, learners alternating: heads = torch {q(res['torch'])}; heads = fused {q(res['fused'])} "
+            f"[{verdict(res['torch'], res['fused'])}]")
+
+    if a.heads:
+        lines.clear()
+        heads_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
