@@ -330,7 +330,8 @@ class CommanderRollout:
     0.0 wherever it reports valid = 0, and in an auto-resetting world valid is 1 on every row — RLlib's rewards.get(agent_id, 0.0) is the
     world's reward as it stands, nothing is masked.
 
-    batch_mode = "truncate_episodes" (default): the buffers above are the result.  batch_mode = "complete_episodes" (train_hier.py:182):
+    batch_mode = "truncate_episodes" (default): the buffers above are the result, and `CommanderLearner.update_window(rollout)` trains on
+    them as they stand.  batch_mode = "complete_episodes" (train_hier.py:182):
     every collect still fills them exactly the same way, and then also `episodes`, a `CommanderEpisodeBatch` of every episode that ended
     in it, whole and cut into GRU sequences of at most `max_seq_len` steps; its launches join the collect's graph after the GAE.
 
@@ -402,6 +403,7 @@ class CommanderRollout:
         self.use_graph = use_graph
         self._graph = None
         self._started = False
+        self.collects = 0                   # collects so far: the window buffers hold a batch once it is non-zero
 
     def _own_pilot(self):
         from .pilots import NetPilot, VariantNetPilot
@@ -453,6 +455,7 @@ class CommanderRollout:
             self.start()
         if not (self.use_graph and self._own_pilot()):
             self._run()
+            self.collects += 1
             return self
         # the captured graph holds device pointers by value: the world's (trace ring, bound bank's row lists), the pilot bank's (weight blobs,
         # selector table, the kernel instance its tile width picks) and the commander's — re-capture whenever World.trace_enable / bind_policy or
@@ -474,6 +477,7 @@ class CommanderRollout:
             torch.cuda.current_stream(dev).wait_stream(side)
             self._graph, self._graph_gen = graph, gen
         self._graph.replay()
+        self.collects += 1
         return self
 
     def collect_batch(self, max_collects=None):

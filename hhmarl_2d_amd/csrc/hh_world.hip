@@ -914,3 +914,6 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 
 /* ---- tanh, the output heads, the PPO loss and their backward as one row pass behind shared_layer (C ABI in include/hh_learner.h) ---- */
 #include "hh_heads_loss.h"
+
+/* ---- a rollout's fixed [T, N] window as the learners' padded sequences: the cut and the gather (C ABI in include/hh_learner.h) ---- */
+#include "hh_window_batch.h"

@@ -15,6 +15,9 @@ hh_heads_loss); the default path is tanh, two GEMMs, hh_ppo_loss and autograd's 
 And (`PPOLearner(optimizer="fused", step="graph")`): Adam on the device (`adam_step`: hh_adam_step) and the whole minibatch step — the
 minibatch staged by a device schedule (`minibatch_stage`: hh_minibatch_stage), forward, loss, backward, Adam and the step's bookkeeping
 (`train_commit`: hh_train_commit) — replayed from ONE HIP graph per policy; the default is torch.optim.Adam and the eager step.
+Both learners also train from the rollouts' default batch_mode="truncate_episodes" (`update_window`): the fixed [T, N] window is cut into
+sequences (`window_cut`: hh_window_cut) and its columns gathered into the padded form (`window_gather`: hh_window_gather); from there on
+it is `update`.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -1122,6 +1125,131 @@ def train_commit(stats, table, cursor, t):
     L.check(L.lib().hh_train_commit(_p(stats), _p(table), table.shape[0], _p(cursor), _p(t), _stream(table.device)))
 
 
+# ------------------------------------------------------------------------------------------------------------------ the window batch
+def _cut_args(who, done, max_seq_len):
+    """the checks that window_cut and window_cut_torch share -> (T, N, max_seq_len)"""
+    if isinstance(max_seq_len, bool) or int(max_seq_len) != max_seq_len or not 1 <= int(max_seq_len) <= L.WINDOW_MAX_LEN:
+        raise ValueError(f"{who}: max_seq_len is an integer in 1 .. {L.WINDOW_MAX_LEN}, got {max_seq_len!r}")
+    if not isinstance(done, torch.Tensor) or done.dtype != torch.uint8 or done.dim() != 2 or done.shape[0] < 1 or done.shape[1] < 1:
+        raise ValueError(f"{who}: done is a uint8 tensor [T, N] with T, N >= 1 (the rollouts' done buffer)")
+    if done.shape[0] * done.shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: T N = {done.shape[0] * done.shape[1]} rows do not fit int32 sequence tables")
+    return done.shape[0], done.shape[1], int(max_seq_len)
+
+
+def window_cut(done, max_seq_len, out=None):
+    """The sequences of a rollout's [T, N] window (hh_window_cut, include/hh_learner.h): per arena, walking t, a sequence ends at a done
+    row (any non-zero byte of done u8 [T, N]), at its max_seq_len-th row, or at t = T-1 — chop_into_sequences on the window's
+    fragments.  -> (seq_t0, seq_arena, seq_len): int32 [S] device views, arena-major, then time; S <= T N.  Three launches, then ONE
+    synchronising read of the count, as EpisodeBatch.rows() makes one.  out: the three tables to write into (contiguous int32 CUDA
+    tensors of at least T N elements each; entries at and beyond S are left as they were); default: new ones."""
+    T, N, Lm = _cut_args("window_cut", done, max_seq_len)
+    _need_gpu("window_cut")
+    if not (done.is_cuda and done.is_contiguous()):
+        raise ValueError("window_cut: done is a contiguous CUDA tensor (the torch-op form is window_cut_torch)")
+    dev = done.device
+    if out is None:
+        out = tuple(torch.empty((T * N,), dtype=torch.int32, device=dev) for _ in range(3))
+    if len(out) != 3 or any(not (o.is_cuda and o.device == dev and o.dtype == torch.int32 and o.is_contiguous() and o.dim() == 1 and o.numel() >= T * N) for o in out):
+        raise ValueError(f"window_cut: out is three contiguous int32 CUDA tensors of at least T N = {T * N} elements on done's device")
+    small = torch.empty((N + 1,), dtype=torch.int32, device=dev)        # the scratch [N], then n_seq
+    L.check(L.lib().hh_window_cut(T, N, _p(done), Lm, _p(out[0]), _p(out[1]), _p(out[2]), _p(small[N:]), _p(small), _stream(dev)))
+    S = int(small[N])
+    return out[0][:S], out[1][:S], out[2][:S]
+
+
+def window_cut_torch(done, max_seq_len):
+    """window_cut with torch ops, any device -> (seq_t0, seq_arena, seq_len) int32 [S], the same entries in the same order"""
+    T, N, Lm = _cut_args("window_cut_torch", done, max_seq_len)
+    dev = done.device
+    end = (done != 0).t().contiguous()                                    # [N, T]: arena-major
+    end[:, T - 1] = True
+    t = torch.arange(T, device=dev)[None, :].expand(N, T)
+    first = torch.ones((N, T), dtype=torch.bool, device=dev)
+    first[:, 1:] = end[:, :-1]                                            # a fragment starts at t = 0 and behind every done row
+    frag_t0 = torch.cummax(torch.where(first, t, torch.zeros_like(t)), dim=1).values
+    r0 = torch.nonzero((first | ((t - frag_t0) % Lm == 0)).reshape(-1)).reshape(-1)   # every sequence's first row, r = n T + t
+    nxt = torch.cat([r0[1:], torch.full((1,), N * T, dtype=r0.dtype, device=dev)])    # t = 0 starts one in every arena: none crosses arenas
+    return (r0 % T).to(torch.int32), (r0 // T).to(torch.int32), (nxt - r0).to(torch.int32)
+
+
+def _gather_args(who, cols, tables, max_seq_len):
+    """the checks that window_gather and window_gather_torch share.  cols: per column (src, tail, offset, per_seq) — src a contiguous
+    tensor [T_src, N, ...] (a step-row is src[t, n]), tail the trailing shape of one gathered row in src's dtype, offset the BYTES from the
+    step-row's start to it, per_seq False | True -> (S, max_seq_len, T_src, N, [(src, tail, offset, width, step_bytes, per_seq)])"""
+    if isinstance(max_seq_len, bool) or int(max_seq_len) != max_seq_len or not 1 <= int(max_seq_len) <= L.WINDOW_MAX_LEN:
+        raise ValueError(f"{who}: max_seq_len is an integer in 1 .. {L.WINDOW_MAX_LEN}, got {max_seq_len!r}")
+    if not 1 <= len(cols) <= L.STAGE_MAX_COLS:
+        raise ValueError(f"{who}: 1 .. {L.STAGE_MAX_COLS} columns per call, got {len(cols)}")
+    if len(tables) != 3 or any(not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.dim() != 1 or x.numel() != tables[0].numel() for x in tables):
+        raise ValueError(f"{who}: tables is (seq_t0, seq_arena, seq_len), int32 [S] each (window_cut's)")
+    out, T_src, N = [], None, None
+    for col in cols:
+        src, tail, offset, per_seq = col
+        tail = tuple(int(x) for x in tail)
+        if not isinstance(src, torch.Tensor) or src.dim() < 2 or not src.is_contiguous() or src.shape[0] < 1 or src.shape[1] < 1:
+            raise ValueError(f"{who}: a column's source is a contiguous tensor [T_src, N, ...]")
+        if N is not None and src.shape[1] != N:
+            raise ValueError(f"{who}: the columns of one call hold the same N arenas")
+        N = src.shape[1]
+        T_src = src.shape[0] if T_src is None else min(T_src, src.shape[0])     # the rows EVERY column of the call holds
+        step_bytes = (src.numel() // (src.shape[0] * N)) * src.element_size()
+        width = int(np.prod(tail, dtype=np.int64)) * src.element_size()
+        if width < 1 or int(offset) < 0 or int(offset) % src.element_size() or int(offset) + width > step_bytes:
+            raise ValueError(f"{who}: a slice of {width} bytes at offset {offset} does not lie, element-aligned, inside its {step_bytes}-byte step-row")
+        out.append((src, tail, int(offset), width, step_bytes, bool(per_seq)))
+    return tables[0].numel(), int(max_seq_len), T_src, N, out
+
+
+def window_gather(cols, tables, max_seq_len, out=None):
+    """The window's columns as padded sequences in ONE launch (hh_window_gather, include/hh_learner.h).  cols: up to 8 tuples
+    (src, tail, offset, per_seq) — src a contiguous CUDA tensor [T_src, N, ...] (the rollout's buffer as it lies), tail the trailing shape
+    of one gathered row in src's dtype, offset the bytes from the step-row src[t, n] to that slice (one agent's part), per_seq True for
+    the first row of every sequence only; tables: window_cut's (seq_t0, seq_arena, seq_len).  -> per column a new tensor
+    [S, max_seq_len, *tail], zero beyond every sequence's length, or [S, *tail] with per_seq.  The kernel may read the rows that every
+    column of the call holds (T_src = the smallest of the sources' first dimensions).  A table entry that names no rows of the window
+    stages zeros.  out: the destinations to write into instead (contiguous, the same shapes and dtypes; every byte of them is written).
+    No host synchronisation, HIP-graph capturable."""
+    S, Lm, T_src, N, cs = _gather_args("window_gather", cols, tables, max_seq_len)
+    _need_gpu("window_gather")
+    dev = tables[0].device
+    if any(not (x.is_cuda and x.is_contiguous() and x.device == dev) for x in tables) or any(not (c[0].is_cuda and c[0].device == dev) for c in cs):
+        raise ValueError("window_gather: the tables and the sources are contiguous CUDA tensors on one device (the torch-op form is window_gather_torch)")
+    shapes = [((S,) if per_seq else (S, Lm)) + tail for _, tail, _, _, _, per_seq in cs]
+    if out is None:
+        out = [torch.empty(sh, dtype=c[0].dtype, device=dev) for sh, c in zip(shapes, cs)]
+    if len(out) != len(cs) or any(not (o.is_cuda and o.device == dev and o.is_contiguous() and o.dtype == c[0].dtype and tuple(o.shape) == sh)
+                                  for o, sh, c in zip(out, shapes, cs)):
+        raise ValueError("window_gather: out holds per column a contiguous CUDA tensor [S, max_seq_len, *tail] ([S, *tail] with per_seq) of the source's dtype")
+    if S == 0:
+        return list(out)
+    desc = (L.HHWindowCol * len(cs))()
+    for d, o, (src, _, offset, width, step_bytes, per_seq) in zip(desc, out, cs):
+        d.src, d.dst, d.step_bytes, d.offset, d.width, d.per_seq = src.data_ptr(), o.data_ptr(), step_bytes, offset, width, int(per_seq)
+    L.check(L.lib().hh_window_gather(len(cs), desc, S, Lm, T_src, N, _p(tables[0]), _p(tables[1]), _p(tables[2]), _stream(dev)))
+    return list(out)
+
+
+def window_gather_torch(cols, tables, max_seq_len):
+    """window_gather with torch ops, any device: the same arguments -> per column a new tensor with the same bytes (index_select through the
+    tables; an entry that names no rows of the window gives zeros)"""
+    S, Lm, T_src, N, cs = _gather_args("window_gather_torch", cols, tables, max_seq_len)
+    t0, n, ln = (x.long() for x in tables)
+    ok = (t0 >= 0) & (ln >= 0) & (ln <= Lm) & (n >= 0) & (n < N) & (t0 + ln <= T_src)
+    t0, n, ln = (torch.where(ok, x, torch.zeros_like(x)) for x in (t0, n, ln))
+    out = []
+    for src, tail, offset, width, step_bytes, per_seq in cs:
+        rows = 1 if per_seq else Lm
+        j = torch.arange(rows, device=src.device)[None, :]
+        keep = j < ln[:, None]                                                     # [S, rows]
+        r = torch.where(keep, (t0[:, None] + j) * N + n[:, None], torch.zeros_like(keep, dtype=torch.int64))
+        flat = src.reshape(src.shape[0] * N, -1).view(torch.uint8)[:, offset:offset + width]
+        got = flat.index_select(0, r.reshape(-1)).reshape(S, rows, width) * keep[:, :, None].to(torch.uint8)
+        got = got.contiguous().view(src.dtype).reshape((S, rows) + tail)
+        out.append(got[:, 0] if per_seq else got)
+    return out
+
+
 class DeviceAdam:
     """torch.optim.Adam(params, lr) with its state on the device: m and v per parameter and the step count t (int32 [1]), stepped by
     adam_step (hh_adam_step).  t is advanced by train_commit, not by step().
@@ -1639,6 +1767,78 @@ class PPOLearner:
         with torch.no_grad():
             old = self.batch_old_logits(rows, bank, episodes.N)
             batches = [self.policy_batch(rows, old, a) for a in range(2)]
+        out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
+        self.updates += 1
+        return out
+
+    # ---- one update from a fixed window (batch_mode = "truncate_episodes")
+    def _check_window(self, rollout):
+        """the refusals of window_batch / update_window -> (T, N)"""
+        if getattr(rollout, "semantics", "rllib") != "rllib":
+            raise ValueError("PPOLearner trains RLlib's unmasked view: a PPORollout(semantics='masked') window has its dead agents' rows cut out of adv and target")
+        for k in ("obs", "actions", "logp", "adv", "target", "done", "T", "w"):
+            if not hasattr(rollout, k):
+                raise ValueError(f"window_batch takes a PPORollout (its [T, N] buffers); this object has no `{k}`")
+        esc = rollout.w.cfg.agent_mode == L.MODE_ESCAPE
+        if rollout.obs.dim() != 4 or rollout.obs.shape[2] != 2 or esc == self.recurrent or rollout.obs.shape[3] < max(PN.OBS_DIM[k] for k in self.kinds):
+            raise ValueError(f"the rollout's world flies {'escape' if esc else 'fight'} mode with observations {tuple(rollout.obs.shape[2:])}; "
+                             f"this learner trains kinds {self.kinds} ({'fight' if self.recurrent else 'escape'})")
+        if not getattr(rollout, "collects", 0):
+            raise RuntimeError("the rollout has not collected yet: its window buffers hold nothing (rollout.collect() first)")
+        return rollout.T, rollout.w.N
+
+    def _window_shared(self, rollout, bank):
+        """what both policies' window batches share: the cut, the sampler's logits [T, N, 2, 32] and the advantages in arena-major rows"""
+        T, N = self._check_window(rollout)
+        tables = window_cut(rollout.done, self.max_seq_len if self.recurrent else 1)
+        if getattr(rollout, "record_logits", False):
+            logits = rollout.logits
+        else:
+            if bank is None:
+                raise ValueError("the rollout recorded no logits (PPORollout(record_logits=True)): a bank is needed to recompute them")
+            logits = self.old_logits(rollout.obs[:T].reshape(T * N, 2, rollout.obs.shape[3]), bank, N).reshape(T, N, 2, OLD_LD)
+        adv_rows = rollout.adv.transpose(0, 1).reshape(N * T, 2)      # [R, 2], r = n T + t: what the episode path's rows["adv"] would hold
+        return T, N, tables, logits.contiguous(), adv_rows
+
+    def window_batch(self, rollout, bank, agent, shared=None):
+        """the training batch of policy `agent` (0 | 1) from a PPORollout's [T, N] window, in policy_batch's format and — fed the same
+        rows as episodes (the window's fragments, arena-major) — with policy_batch's values: fight kinds [S, L, ...] chunks with seq_len
+        and mask (a chunk ends at a done row, at max_seq_len rows or at the window's end: window_cut), escape kinds [R, ...] with R = T N
+        rows, arena-major (r = n T + t: the cut with max_seq_len = 1, the length-1 axis dropped).  One hh_window_gather launch of seven
+        columns reads the rollout's buffers as they lie.  The trailing fragment of an arena carries RLlib's truncation bootstrap from
+        vf[T] in adv and target (hh_gae_rllib).  `bank` is read only when the rollout recorded no logits.  The advantages are standardised
+        over the agent's T N values (standardize).  shared: _window_shared's tuple (update_window builds it once for both policies)."""
+        T, N, tables, logits, adv_rows = self._window_shared(rollout, bank) if shared is None else shared
+        kind = self.kinds[agent]
+        Lm = self.max_seq_len if self.recurrent else 1
+        D, Dk = rollout.obs.shape[3], PN.OBS_DIM[kind]
+        critic = central_critic_rows(rollout.obs[:T], rollout.actions, agent + 1).contiguous()
+        adv = standardize(adv_rows[:, agent]).reshape(N, T).t().contiguous()          # back to [T, N]: where the gather reads a row (t, n)
+        names = ("obs", "critic", "actions", "old_logp", "adv", "target", "old_logits")
+        got = window_gather([(rollout.obs, (Dk,), agent * D * 4, False), (critic, (critic.shape[2],), 0, False),
+                             (rollout.actions, (4,), agent * 4, False), (rollout.logp, (), agent * 4, False), (adv, (), 0, False),
+                             (rollout.target, (), agent * 4, False), (logits, (OLD_LD,), agent * OLD_LD * 4, False)], tables, Lm)
+        if not self.recurrent:
+            return {k: v[:, 0] for k, v in zip(names, got)}
+        b = dict(zip(names, got))
+        b["seq_len"] = tables[2].long()
+        b["mask"] = chunk_mask(b["seq_len"], Lm).to(torch.uint8)
+        return b
+
+    def update_window(self, rollout, bank=None):
+        """one PPO update of both policies from a PPORollout's [T, N] window as the last collect left it (batch_mode =
+        "truncate_episodes", the rollouts' default; the buffers are the same in both modes) -> what `update` returns, with rows = T N.
+        Every row of the window was sampled by the weights the sampler holds, so nothing is carried, nothing overflows and no start()
+        is needed after publish:
+
+            ro.collect();  stats = learner.update_window(ro, bank);  learner.publish(bank)
+
+        The batches are window_batch's; from there on it is `update`: the same _columns and driver, so fused, attention, inputs, trunk,
+        heads, optimizer, step="graph", grad_clip and shuffle_sequences act as they do there, and the row count T N is the same in every
+        update.  The rollout's buffers are only read."""
+        with torch.no_grad():
+            shared = self._window_shared(rollout, bank)
+            batches = [self.window_batch(rollout, bank, a, shared) for a in range(2)]
         out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
         self.updates += 1
         return out
@@ -2174,6 +2374,47 @@ class CommanderLearner:
         if seqs["obs"].shape[0] == 0:
             return self._sgd.empty()
         with torch.no_grad():
+            b = self.policy_batch(seqs)
+            b["old_logits"] = self.batch_old_logits(seqs, b)
+        out = self._sgd.run(*self._columns(b, staged=self.step == "graph"))
+        self.updates += 1
+        return out
+
+    # ---- one update from a fixed window (batch_mode = "truncate_episodes")
+    def window_sequences(self, rollout):
+        """a CommanderRollout's [T, N] window in CommanderEpisodeBatch.sequences()' format: the window cut by THIS learner's max_seq_len
+        (window_cut; the rollout's own max_seq_len is not read) and whole step-rows gathered by hh_window_gather — obs f32 [S, L, 3, 34],
+        actions i8 / logp / vf / adv / target [S, L, 3] (zero past seq_len), seq_lens i32 [S], mask bool [S, L], state_in f32
+        [S, 3, 2, 200] = rollout.state_in[seq_t0, seq_arena] (the state the sequence's first step used: zero at an episode start, the
+        carried one where the window or a length cut opens mid-episode), and logits f32 [S, L, 3, 4] where the rollout recorded them.
+        Sequences arena-major, then time."""
+        for k in ("obs", "actions", "logp", "vf", "adv", "target", "done", "state_in", "T"):
+            if not hasattr(rollout, k):
+                raise ValueError(f"window_sequences takes a CommanderRollout (its [T, N] buffers and state_in); this object has no `{k}`")
+        if rollout.obs.dim() != 4 or tuple(rollout.obs.shape[2:]) != (3, 34) or tuple(rollout.state_in.shape[2:]) != (3, 2, GRU_H):
+            raise ValueError(f"the rollout's observations {tuple(rollout.obs.shape[2:])} / states {tuple(rollout.state_in.shape[2:])} are not the "
+                             "3-agent commander's ((3, 34) / (3, 2, 200))")
+        if not getattr(rollout, "collects", 0):
+            raise RuntimeError("the rollout has not collected yet: its window buffers hold nothing (rollout.collect() first)")
+        Lm = self.max_seq_len
+        tables = window_cut(rollout.done, Lm)
+        names = ["obs", "actions", "logp", "vf", "adv", "target"] + (["logits"] if getattr(rollout, "record_logits", False) else [])
+        cols = [(getattr(rollout, k), tuple(getattr(rollout, k).shape[2:]), 0, k == "state_in") for k in names + ["state_in"]]   # eight at most: one launch
+        out = dict(zip(names + ["state_in"], window_gather(cols, tables, Lm)))
+        out["seq_lens"] = tables[2]
+        out["mask"] = chunk_mask(tables[2].long(), Lm)
+        return out
+
+    def update_window(self, rollout):
+        """one PPO update of commander_policy from a CommanderRollout's [T, N] window as the last collect left it (batch_mode =
+        "truncate_episodes", the rollouts' default; the buffers are the same in both modes) -> what `update` returns, rows = 3 T N:
+
+            ro.collect();  stats = learner.update_window(ro);  learner.publish(net)
+
+        window_sequences, then `update`'s own policy_batch, batch_old_logits and driver.  The trailing fragment of an arena carries
+        RLlib's truncation bootstrap from vf[T] in adv and target.  The rollout's buffers are only read."""
+        with torch.no_grad():
+            seqs = self.window_sequences(rollout)
             b = self.policy_batch(seqs)
             b["old_logits"] = self.batch_old_logits(seqs, b)
         out = self._sgd.run(*self._columns(b, staged=self.step == "graph"))

@@ -440,7 +440,8 @@ class PPORollout:
     [T, N], adv / target f32 [T, N, 2]; `complete` / `segments` are derived from `done` on demand.  `critic_rows(agent)` gives the
     flattened CUR_OBS rows the reference's critic is trained on (actions filled in the way on_postprocess_trajectory does).
 
-    batch_mode = "truncate_episodes" (default): the buffers above are the result.  batch_mode = "complete_episodes" (train_hetero.py:212;
+    batch_mode = "truncate_episodes" (default): the buffers above are the result, and `PPOLearner.update_window(rollout, bank)` trains on
+    them as they stand (semantics = "rllib").  batch_mode = "complete_episodes" (train_hetero.py:212;
     semantics = "rllib" only): every collect still fills the buffers above exactly the same way, and then also `episodes`, an
     `EpisodeBatch` of every episode that ended in it — whole, its earlier rows carried on the device from the collects before — with
     advantages / value targets over the whole episode (last_r = 0): the batch RLlib hands its learner.  Its 4 launches are part of the
@@ -525,6 +526,7 @@ class PPORollout:
         self.use_graph = use_graph
         self._graph = None
         self._started = False
+        self.collects = 0                   # collects so far: the window buffers hold a batch once it is non-zero
 
     def start(self):
         """reset every arena; the first observation becomes row 0 of the next collect.  Also builds the row lists of the fixed agent ->
@@ -574,6 +576,7 @@ class PPORollout:
                 with torch.cuda.graph(self._graph):
                     self._run()
             self._graph.replay()
+        self.collects += 1
         return self
 
     def collect_batch(self, max_collects=None):

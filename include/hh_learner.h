@@ -358,6 +358,54 @@ int hh_heads_loss(int64_t n_rows, const float *za, const float *zc, const float 
                   float *d_za, float *d_zc, float *d_w_act, float *d_b_act, float *d_w_val, float *d_b_val, float *logits, float *vf,
                   void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the window batch: a rollout's fixed [T, N] window (batch_mode = "truncate_episodes") as the learners' padded sequences ----
+ *
+ * The rollouts' collect buffers are step-rows [T, N, ...]: row (t, n) of a column starts (t N + n) * step_bytes bytes into it, so the rows
+ * of one arena lie N step-rows apart.  hh_window_cut names the sequences of the window, hh_window_gather copies any columns of it into
+ * the [S, L, ...] form that the learners' drivers take.  Both are ordered on `stream`: no atomics, no allocation, no host
+ * synchronisation, HIP-graph capturable; the same inputs give the same bytes on every run.  All pointers are [dev]. */
+#define HH_WINDOW_MAX_LEN 32   /* the longest sequence (max_seq_len) */
+
+/* The cut, per arena n, walking t = 0 .. T-1: a sequence ends at row t when done[t, n] != 0 (done u8 [T, N]: any non-zero byte), or it
+ * holds max_seq_len rows, or t == T-1; the next one starts at t + 1.  Every row belongs to exactly one sequence, no sequence holds a done
+ * row except as its last, and a sequence never leaves its arena — RLlib's chop_into_sequences on the window's fragments (an arena's rows
+ * up to and including each done row, the last fragment ending at T-1).
+ *   seq_t0, seq_arena, seq_len  i32, capacity T N each: sequence s is rows seq_t0[s] .. seq_t0[s] + seq_len[s] - 1 of arena seq_arena[s],
+ *                               1 <= seq_len[s] <= max_seq_len; ARENA-MAJOR, then time.  Entries at and beyond n_seq are not written
+ *   n_seq                       i32 [1]: S <= T N, so there is no overflow case
+ *   scratch                     i32 [N]
+ * Three launches: one lane per arena counts its sequences (the lanes of a wave read neighbouring bytes of done at every t), one
+ * workgroup turns the counts into exclusive offsets and writes n_seq, the walk again writes every arena's entries from its offset.
+ * HH_E_ARG, with nothing enqueued: a null pointer, T < 1, N < 1, T N >= 2^31, max_seq_len outside 1 .. HH_WINDOW_MAX_LEN. */
+int hh_window_cut(int32_t T, int32_t N, const uint8_t *done, int32_t max_seq_len, int32_t *seq_t0, int32_t *seq_arena, int32_t *seq_len,
+                  int32_t *n_seq, int32_t *scratch, void *stream);
+
+typedef struct hh_window_col {   /* field order is ABI; host struct of device pointers, passed by value like hh_stage_col */
+    const void *src;             /* the window's column: [T_src, N] step-rows */
+    void *dst;                   /* [S, max_seq_len, width] bytes, or [S, width] with per_seq */
+    int64_t step_bytes;          /* bytes from step-row (t, n) to (t, n + 1) */
+    int64_t offset;              /* bytes from the step-row's start to the slice wanted (one agent's part); offset + width <= step_bytes */
+    int64_t width;               /* bytes copied per row, 1 .. 2^20 */
+    int32_t per_seq;             /* 0: every row of the sequence; 1: its first row only (the state a sequence starts from) */
+    int32_t reserved0;           /* must be 0 */
+} hh_window_col;
+
+/* ONE launch for n_cols <= HH_STAGE_MAX_COLS columns and S sequences (a host argument: hh_window_cut's n_seq, read back once).  With
+ * (t0, n, len) = (seq_t0[s], seq_arena[s], seq_len[s]):
+ *   per_seq = 0:  dst[s, j] = the `width` bytes at src + ((t0 + j) N + n) * step_bytes + offset  for j < len, and zero for len <= j < max_seq_len,
+ *                 written on every call (a destination need not be cleared)
+ *   per_seq = 1:  dst[s] = those bytes of row j = 0 (zero where len == 0)
+ * T_src is the step-rows per arena that every column of the call holds (the window's T, or T + 1 where all of them carry the row after
+ * the window) and N the arenas.  The kernel clamps what it reads from the tables: an entry with t0 < 0, len < 0, len > max_seq_len,
+ * t0 + len > T_src or an arena outside [0, N) stages zeros, so no table content makes it touch memory outside the columns and the
+ * destinations (hh_minibatch_stage's contract).  The copy unit of a column is the widest of 16, 8, 4, 2, 1 bytes that src, dst, step_bytes,
+ * offset and width are all multiples of.  A group of 1 .. 64 lanes copies one sequence of one column (about four copy units per lane) and
+ * reads its table entry once.  S == 0 succeeds without a launch.  HH_E_ARG, with nothing enqueued: a null pointer, n_cols outside
+ * 1 .. HH_STAGE_MAX_COLS, max_seq_len outside 1 .. HH_WINDOW_MAX_LEN, S < 0 (or >= 2^31), T_src < 1, N < 1, a width outside 1 .. 2^20, a negative
+ * offset, offset + width > step_bytes, per_seq other than 0 | 1, a non-zero reserved field. */
+int hh_window_gather(int32_t n_cols, const hh_window_col *cols, int64_t S, int32_t max_seq_len, int32_t T_src, int32_t N,
+                     const int32_t *seq_t0, const int32_t *seq_arena, const int32_t *seq_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

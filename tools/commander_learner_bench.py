@@ -28,6 +28,10 @@
           launches alone (hh_minibatch_stage against hh_minibatch_stage_gather drawing from the whole batch), the graph step at 256 and
           16384 rows, one whole update at sgd_minibatch_size = 256 (medians of --iters updates), the host time of shuffled_schedule and
           the order table's bytes; appended to --out.  The same spread rule, worded cost / gain / no difference
+  window  --window: CommanderLearner.update_window on a CommanderRollout's fixed [T, N] window (batch_mode = "truncate_episodes") next to
+          update on whole episodes, both in one process: window_cut and hh_window_gather against their torch twins (the gather as bytes/s of
+          what it reads and writes), window_sequences against CommanderEpisodeBatch.sequences(), policy_batch on both, one whole update each,
+          and the graph captures over three windows with kl_coeff = 0; appended to --out.  The same spread rule
 Every GPU step runs as a child process of its own under `timeout -k 10`, the steps chained with && in one shell command: the first one
 that fails or runs out of time ends the run, nothing is retried.
     python tools/commander_learner_bench.py [--arenas 8192] [--T 16] [--iters 20] [--out profiles/commander_learner.log]"""
@@ -695,6 +699,94 @@ def step_update(a, say):
         say(f"    statistics of the second update: {st}")
 
 
+def step_window(a, say):
+    """CommanderLearner.update_window on a CommanderRollout's [T, N] window (batch_mode = "truncate_episodes") next to update on whole
+    episodes, both in this process: the batch build (kernels against torch twins), one whole update each, the graph captures over three windows"""
+    import torch
+    from hhmarl_2d_amd import _lib as L
+    from hhmarl_2d_amd import learner as LR
+    from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weights
+    from hhmarl_2d_amd.pilots import VariantNetPilot
+    from hhmarl_2d_amd.world import World, make_config
+    med = statistics.median
+    dev = torch.device("cuda", 0)
+
+    def cost(t_base, t_new, words=("twin -> kernel", "loss", "gain")):
+        spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+        d = med(t_new) - med(t_base)
+        word = "no difference beyond the spread" if abs(d) <= spread else (words[1] if d > 0 else words[2])
+        return f"{words[0]}: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+    def host(fn):
+        out = []
+        for _ in range(a.warmup + a.iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return out[a.warmup:]
+
+    N, T, Lm = a.arenas, a.T, 20
+    ro_e, net = _rollout(a)                                    # whole episodes, as every other section of this file
+    w = World(make_config(n_arenas=N, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=21, auto_reset=True, horizon=a.horizon), device=0)
+    ro = CommanderRollout(w, net, VariantNetPilot(w, seed=8), T)
+    for _ in range(max(3, a.horizon // (12 * T) + 2)):
+        ro.collect()
+    torch.cuda.synchronize()
+    say(f"# tools/commander_learner_bench.py --window on {torch.cuda.get_device_name(0)}: CommanderLearner.update_window on a CommanderRollout's [T, N] "
+        f"window (batch_mode = truncate_episodes) next to update on whole episodes, both in this run; {N} arenas, T = {T}, horizon {a.horizon}; {a.iters} "
+        f"timed runs after {a.warmup} warm-up, medians, (max - min) spread rule (a later run, appended):")
+    ln = LR.CommanderLearner.trainable_init(dev, seed=6, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+    with torch.no_grad():
+        t_cut, t_cut_t = host(lambda: LR.window_cut(ro.done, Lm)), host(lambda: LR.window_cut_torch(ro.done, Lm))
+        tables = LR.window_cut(ro.done, Lm)
+        S = tables[0].numel()
+        names = ["obs", "actions", "logp", "vf", "adv", "target", "state_in"]
+        cols = [(getattr(ro, k), tuple(getattr(ro, k).shape[2:]), 0, k == "state_in") for k in names]
+        outs = LR.window_gather(cols, tables, Lm)
+        t_g = events(lambda: LR.window_gather(cols, tables, Lm, out=outs), a.iters, a.warmup)
+        t_g_t = events(lambda: LR.window_gather_torch(cols, tables, Lm), a.iters, a.warmup)
+        wrote = sum(o.numel() * o.element_size() for o in outs)
+        read = sum((S if per_seq else T * N) * (src[0, 0].numel() * src.element_size()) for src, _, _, per_seq in cols) + 12 * S
+        t_ws = host(lambda: ln.window_sequences(ro))
+        t_es = host(lambda: ro_e.episodes.sequences())
+        seqs_w, seqs_e = ln.window_sequences(ro), ro_e.episodes.sequences()
+        t_pb_w, t_pb_e = host(lambda: ln.policy_batch(seqs_w)), host(lambda: ln.policy_batch(seqs_e))
+    say(f"the window has {T * N} arena rows in {S} sequences of <= {Lm}; the episode batch of the last collect {int(seqs_e['seq_lens'].sum())} arena rows in "
+        f"{seqs_e['obs'].shape[0]} sequences")
+    say(f"    the cut (three launches + the read of n_seq, host clock): window_cut {q(t_cut)}; window_cut_torch {q(t_cut_t)}; {cost(t_cut_t, t_cut)}")
+    say(f"    the gather of seven columns, state_in per sequence (ONE launch, device events): hh_window_gather {q(t_g)} = {(read + wrote) / med(t_g) / 1e6:.1f} GB/s of "
+        f"{read / 1e6:.1f} MB read + {wrote / 1e6:.1f} MB written = {100 * (read + wrote) / med(t_g) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches; "
+        f"window_gather_torch {q(t_g_t)}; {cost(t_g_t, t_g)}")
+    say(f"    the padded sequences (host clock to a synchronise): window_sequences {q(t_ws)}; CommanderEpisodeBatch.sequences() on the episode batch {q(t_es)}")
+    say(f"    policy_batch (critic rows, agent-major concatenation, masked standardisation; torch ops in both paths): on the window's sequences {q(t_pb_w)}; on the "
+        f"episode batch's {q(t_pb_e)}")
+    del outs, seqs_w, seqs_e
+    ln_e = LR.CommanderLearner.trainable_init(dev, seed=6, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+    t_w, t_u = host(lambda: ln.update_window(ro)), host(lambda: ln_e.update(ro_e.episodes, net))
+    st_w, st_u = ln.update_window(ro), ln_e.update(ro_e.episodes, net)
+    say(f"    one update ({a.passes} pass(es), minibatches of >= {a.minibatch} rows, eager, old logits from the module, host clock to a synchronise): update_window "
+        f"{q(t_w)} ({st_w['steps']} steps over {st_w['rows']} rows); update {q(t_u)} ({st_u['steps']} steps over {st_u['rows']} rows); "
+        f"{cost(t_u, t_w, ('update -> update_window', 'slower', 'faster'))} (the row counts differ: per row {1e3 * med(t_w) / st_w['rows']:.3f} us against "
+        f"{1e3 * med(t_u) / max(st_u['rows'], 1):.3f} us)")
+    del ln, ln_e, ro_e
+    lg = LR.CommanderLearner.trainable_init(dev, seed=6, num_sgd_iter=a.passes, sgd_minibatch_size=1024, kl_coeff=0.0, inputs="fused", optimizer="fused", step="graph")
+    caps, steps, t3 = [], [], []
+    for _ in range(3):
+        ro.collect()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = lg.update_window(ro)
+        lg.publish(net)
+        torch.cuda.synchronize()
+        t3.append((time.perf_counter() - t0) * 1e3)
+        caps.append(lg._book.captures)
+        steps.append(st["steps"])
+    say(f"    step=\"graph\", kl_coeff = 0, inputs = fused, minibatches of >= 1024 rows, three windows (collect, update_window, publish; no start()): captures after each "
+        f"window {caps}, steps {steps}, update_window + publish {', '.join(f'{x:.1f}' for x in t3)} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arenas", type=int, default=8192)
@@ -713,10 +805,11 @@ def main():
     ap.add_argument("--tile", action="store_true", help="only the GRU tile instances, each through HH_GRU_TILE in a child; appended to --out")
     ap.add_argument("--tile-seqs", default="13,26,52,104,208,416,854", help="the sequence counts of --tile's GRUs-alone timing")
     ap.add_argument("--heads", action="store_true", help="only the heads=\"fused\" against heads=\"torch\" section; appended to --out")
+    ap.add_argument("--window", action="store_true", help="only the update_window against update section; appended to --out")
     ap.add_argument("--heads-mode", choices=["torch", "fused"], default="torch", help="with --launches: the learner's heads option")
     ap.add_argument("--launches", choices=["eager", "graph"], help="with --step graph: only --launch-count steps of this form (for a kernel trace)")
     ap.add_argument("--launch-count", type=int, default=20)
-    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip", "shuffle", "heads"], help="run one step in this process (what the parent starts)")
+    ap.add_argument("--step", choices=[s for s, _ in STEPS] + ["inputs", "trunk", "graph", "tile", "clip", "shuffle", "heads", "window"], help="run one step in this process (what the parent starts)")
     a = ap.parse_args()
     a.tile_seqs = [int(x) for x in a.tile_seqs.split(",")]
     if a.step:
@@ -731,9 +824,11 @@ def main():
         if a.step == "gru":
             say(f"# tools/commander_learner_bench.py on {torch.cuda.get_device_name(0)}: {a.iters} timed iterations after {a.warmup} warm-up, device events")
         {"gru": step_gru, "step": step_step, "update": step_update, "inputs": step_inputs, "trunk": step_trunk, "graph": step_graph,
-         "tile": step_tile, "clip": step_clip, "shuffle": step_shuffle, "heads": step_heads}[a.step](a, say)
+         "tile": step_tile, "clip": step_clip, "shuffle": step_shuffle, "heads": step_heads, "window": step_window}[a.step](a, say)
         return
     fwd = [f"--{k} {getattr(a, k)}" for k in ("arenas", "T", "horizon", "iters", "warmup", "passes", "minibatch")] + [f"--out '{a.out}'"]
+    if a.window:
+        sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step window {' '.join(fwd)}", shell=True))
     if a.heads:
         sys.exit(subprocess.call(f"timeout -k 10 480 '{sys.executable}' '{os.path.abspath(__file__)}' --step heads {' '.join(fwd)}", shell=True))
     if a.graph:

@@ -58,6 +58,10 @@
           out; plus the head weights in and their gradients out); (b) the Fight1 and the Esc1 minibatch step at 256 and 65536 rows, eager
           + torch Adam and the graph step, one step per timing and 50 replays back to back; (c) one whole graph update at
           --step-minibatch.  The same rule for gain / loss.  --step-launches with --heads-mode fused counts the launches of that path
+--window: PPOLearner.update_window on a PPORollout's fixed [T, N] window (batch_mode = "truncate_episodes") next to update on whole
+          episodes, fight and escape, in the same run: (a) the batch build — window_cut and hh_window_gather against their torch twins (the
+          gather as bytes/s of what it reads and writes), the torch parts (critic rows, standardisation), window_batch against policy_batch
+          on the episode batch of the last collect; (b) one whole update each; (c) the graph captures over three windows with kl_coeff = 0
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -100,6 +104,7 @@ def main():
     ap.add_argument("--clip", action="store_true", help="only the gradient-clipping section; its lines are appended to --out")
     ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences section; its lines are appended to --out")
     ap.add_argument("--heads", action="store_true", help="only the fused-tail section; its lines are appended to --out")
+    ap.add_argument("--window", action="store_true", help="only the window-batch section (update_window); its lines are appended to --out")
     ap.add_argument("--heads-mode", choices=("torch", "fused"), default="torch", help="--step-launches: the learner's heads option")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
@@ -865,6 +870,110 @@ def main():
     if a.heads:
         lines.clear()
         heads_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def window_section():
+        """update_window (batch_mode = "truncate_episodes") next to update (complete_episodes): the batch build, kernels against torch twins,
+        one whole update each, and the graph captures over three windows"""
+        from hhmarl_2d_amd import policy_nets as PN
+        from hhmarl_2d_amd.rollout import central_critic_rows
+        med = statistics.median
+
+        def cost(t_base, t_new, words=("twin -> kernel", "loss", "gain")):
+            spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+            d = med(t_new) - med(t_base)
+            word = "no difference beyond the spread" if abs(d) <= spread else (words[1] if d > 0 else words[2])
+            return f"{words[0]}: medians {d * 1e3:+.1f} us apart, larger spread {spread * 1e3:.1f} us: {word}"
+
+        def host(fn):
+            out = []
+            for _ in range(a.warmup + a.iters):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return out[a.warmup:]
+
+        say(f"# tools/ppo_learner_bench.py --window on {torch.cuda.get_device_name(0)}: PPOLearner.update_window on a PPORollout's [T, N] window "
+            f"(batch_mode = truncate_episodes) next to update on whole episodes, both in this run; {a.arenas} arenas, T = {a.T}, horizon {a.horizon}, "
+            f"level 3; {a.iters} timed runs after {a.warmup} warm-up, medians, (max - min) spread rule (a later run, appended):")
+        N, T = a.arenas, a.T
+        for mode in ("fight", "escape"):
+            cfg = dict(n_arenas=N, level=3, seed=7, auto_reset=True, horizon=a.horizon, agent_mode=1 if mode == "escape" else 0)
+            bank = PolicyBank.trainable_init(dev, mode=mode, seed=1, max_rows=2 * N)
+            ro = PPORollout(World(make_config(**cfg), device=0), bank, T, record_logits=True)
+            ro_e = PPORollout(World(make_config(**cfg), device=0), bank, T, batch_mode="complete_episodes", record_logits=True)
+            for _ in range(max(2, (a.horizon + T - 1) // T)):
+                ro.collect()
+                ro_e.collect()
+            ln = LR.PPOLearner.trainable_init(dev, mode=mode, seed=1, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+            Lm = ln.max_seq_len if ln.recurrent else 1
+            with torch.no_grad():
+                # (a) the pieces of the batch build
+                t_cut, t_cut_t = host(lambda: LR.window_cut(ro.done, Lm)), host(lambda: LR.window_cut_torch(ro.done, Lm))
+                shared = ln._window_shared(ro, bank)
+                _, _, tables, logits, adv_rows = shared
+                S = tables[0].numel()
+                t_crit = events(lambda: central_critic_rows(ro.obs[:T], ro.actions, 1).contiguous())
+                t_std = events(lambda: LR.standardize(ro.adv.transpose(0, 1).reshape(N * T, 2)[:, 0]).reshape(N, T).t().contiguous())
+                critic = central_critic_rows(ro.obs[:T], ro.actions, 1).contiguous()
+                adv = LR.standardize(adv_rows[:, 0]).reshape(N, T).t().contiguous()
+                Dk = PN.OBS_DIM[ln.kinds[0]]
+                cols = [(ro.obs, (Dk,), 0, False), (critic, (critic.shape[2],), 0, False), (ro.actions, (4,), 0, False), (ro.logp, (), 0, False),
+                        (adv, (), 0, False), (ro.target, (), 0, False), (logits, (LR.OLD_LD,), 0, False)]
+                outs = LR.window_gather(cols, tables, Lm)
+                t_g, t_g_t = events(lambda: LR.window_gather(cols, tables, Lm, out=outs)), events(lambda: LR.window_gather_torch(cols, tables, Lm))
+                wrote = sum(o.numel() * o.element_size() for o in outs)
+                read = T * N * sum(int(np.prod(c[1], dtype=np.int64)) * c[0].element_size() for c in cols) + 12 * S
+                t_b = host(lambda: ln.window_batch(ro, bank, 0, shared))
+                t_b_all = host(lambda: ln.window_batch(ro, bank, 0))
+                rows_e = ro_e.episodes.rows()
+                old_e = ln.batch_old_logits(rows_e, bank, N)
+                t_pb = host(lambda: ln.policy_batch(rows_e, old_e, 0))
+            say(f"{mode}: the window has {T * N} rows in {S} sequences of <= {Lm}; the episode batch of the last collect {rows_e['obs'].shape[0]} rows in "
+                f"{rows_e['ep_len'].shape[0]} episodes")
+            say(f"    the cut (three launches + the read of n_seq, host clock): window_cut {q(t_cut)}; window_cut_torch {q(t_cut_t)}; {cost(t_cut_t, t_cut)}")
+            say(f"    the gather of policy 0's seven columns (ONE launch, device events): hh_window_gather {q(t_g)} = {(read + wrote) / med(t_g) / 1e6:.1f} GB/s of "
+                f"{read / 1e6:.1f} MB read + {wrote / 1e6:.1f} MB written = {100 * (read + wrote) / med(t_g) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy "
+                f"reaches; window_gather_torch {q(t_g_t)}; {cost(t_g_t, t_g)}")
+            say(f"    torch parts of the build (device events): central_critic_rows on [T, N] {q(t_crit)}; the advantages to arena-major rows, standardize, and back {q(t_std)}")
+            say(f"    window_batch of policy 0 (host clock to a synchronise): from the shared cut and logits {q(t_b)}; with the cut and the shared parts {q(t_b_all)}; "
+                f"policy_batch of policy 0 on the episode batch ({rows_e['obs'].shape[0]} rows) {q(t_pb)}")
+            # (b) one whole update each
+            t_w = host(lambda: ln.update_window(ro, bank))
+            ln_e = LR.PPOLearner.trainable_init(dev, mode=mode, seed=1, num_sgd_iter=a.passes, sgd_minibatch_size=a.minibatch)
+            t_u = host(lambda: ln_e.update(ro_e.episodes, bank))
+            st_w, st_u = ln.update_window(ro, bank), ln_e.update(ro_e.episodes, bank)
+            say(f"    one update of both policies ({a.passes} pass(es), minibatches of >= {a.minibatch} rows, eager, recorded logits, host clock to a synchronise): "
+                f"update_window {q(t_w)} ({st_w[0]['steps']} + {st_w[1]['steps']} steps over {st_w[0]['rows']} rows each); update {q(t_u)} "
+                f"({st_u[0]['steps']} + {st_u[1]['steps']} steps over {st_u[0]['rows']} rows each); {cost(t_u, t_w, ('update -> update_window', 'slower', 'faster'))} "
+                f"(the row counts differ: per row {1e3 * med(t_w) / st_w[0]['rows']:.3f} us against {1e3 * med(t_u) / max(st_u[0]['rows'], 1):.3f} us)")
+            del ln_e, ro_e, rows_e, old_e, outs, critic, adv, shared, logits, adv_rows
+            # (c) the graph step over three windows: the row count is constant, so is the schedule's shape
+            lg = LR.PPOLearner.trainable_init(dev, mode=mode, seed=1, num_sgd_iter=a.passes, sgd_minibatch_size=a.step_minibatch, kl_coeff=0.0,
+                                              optimizer="fused", step="graph")
+            caps, steps, t3 = [], [], []
+            for _ in range(3):
+                ro.collect()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                st = lg.update_window(ro, bank)
+                lg.publish(bank)
+                torch.cuda.synchronize()
+                t3.append((time.perf_counter() - t0) * 1e3)
+                caps.append([bk.captures for bk in lg._books])
+                steps.append((st[0]["steps"], st[1]["steps"]))
+            say(f"    step=\"graph\", kl_coeff = 0, minibatches of >= {a.step_minibatch} rows, three windows (collect, update_window, publish; no start()): captures "
+                f"after each window {caps}, steps {steps}, update_window + publish {', '.join(f'{x:.1f}' for x in t3)} ms")
+            del lg, ln, ro, bank
+
+    if a.window:
+        lines.clear()
+        window_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
