@@ -1,0 +1,322 @@
+"""PPOLearner: the PPO update of train_hetero.py's two policies"""
+import weakref
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .. import pilots
+from .. import policy_nets as PN
+from ..rollout import central_critic_rows
+from .batch import chunk_mask, cut_chunks, pad_chunks, standardize, window_cut, window_gather
+from .loss import OLD_LD, _loss_kw, heads_loss, n_comp_of, ppo_loss, ppo_loss_torch
+from .nets import TrainableNet, tie
+from .ops import _trunk_mode
+from .step import _heads_keyword, _learner_options, _PolicySGD
+
+# ------------------------------------------------------------------------------------------------------------------ the learner
+class PPOLearner:
+    """One PPO update of train_hetero.py's two policies from the `EpisodeBatch` of a `PPORollout(batch_mode="complete_episodes")`:
+
+        learner = PPOLearner.trainable_init(device, mode="fight", seed=0)     # the weights of PolicyBank.trainable_init(seed)
+        stats = learner.update(ro.episodes, bank)
+        learner.publish(bank)
+
+    Defaults: train_hetero.py:216 (lr, clip_param, kl_target), config.py:36-37 (sgd_minibatch_size) and RLlib 2.4's PPO defaults for the
+    rest.  Per policy (agent 1, then agent 2; each with its own Adam over its module's parameters, the tied shared layer in both):
+      * rows: the agent's column of every emitted row — nothing is masked by `valid` (semantics = "rllib"); own observation cut to the
+        kind's width, critic rows from central_critic_rows (actions filled in);
+      * old_logits (RLlib's ACTION_DIST_INPUTS, which the KL term and so kl_coeff are computed from): `batch_old_logits`.  With
+        PPORollout(record_logits=True) the batch carries a `logits` column — for every row the logits of the sampler call that drew its
+        action and wrote its logp, whatever weights the bank held at that tick — and that column is used as it stands: no bank call,
+        and rows sampled before the last publish (the head of an episode that was still running then) keep the logits of the weights
+        that sampled them, so old_logp and old_logits of a row always come from one forward.
+        Without the column they are recomputed once per update from `bank`, which still holds the pre-update weights, in
+        ceil(R / N) greedy calls of the rollout's own shape ([N, 2] rows, the same selectors, so the row lists a captured collect
+        re-uses stay what they were).  Only then does this approximation apply: rows carried over from before the last publish were
+        sampled by older weights — their stored logp, and so the ratio, is exact, but their recomputed old_logits are the newer
+        weights', so the KL term sees them as on-policy (`rollout.start()` after `publish` avoids it by throwing the running episodes
+        away; record_logits = True makes that unnecessary);
+      * advantages standardised over the policy's whole batch;
+      * fight kinds: each episode cut into chunks of max_seq_len, zero-padded, mask = the unpadded rows;
+      * num_sgd_iter passes; in each the chunks (escape: rows), in batch order, are split into consecutive minibatches of at least
+        sgd_minibatch_size unpadded rows, visited in the order of minibatch_order(seed, update count, policy, pass).  RLlib's own
+        order is drawn from an unseeded generator and shuffles the chunks themselves; this one is reproducible by construction, and
+        shuffle_sequences=True shuffles the chunks themselves as well, per pass, from a seeded stream of its own (shuffled_schedule);
+      * after the passes KLCoeffMixin.update_kl on the mean of the minibatches' mean_kl.
+    fused = False computes the loss with torch ops (ppo_loss_torch) instead of hh_ppo_loss; nothing else differs.
+    Inside a minibatch step nothing synchronises with the host (beyond what torch.optim.Adam does by itself); `update` itself synchronises
+    when it reads the batch's row count, cuts the minibatches and reads the statistics.  (CommanderRollout's batches: CommanderLearner.)"""
+
+    @_heads_keyword
+    def __init__(self, kinds, state_dicts, device, lr=1e-4, clip_param=0.25, kl_target=0.025, kl_coeff=0.2, vf_clip_param=10.0,
+                 vf_loss_coeff=1.0, entropy_coeff=0.0, num_sgd_iter=30, sgd_minibatch_size=256, max_seq_len=20, seed=0, fused=True, attention="torch", inputs="torch", trunk="torch",
+                 optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
+        """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
+        torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
+        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
+        inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*).
+        trunk: TrainableNet's argument too ("fused": shared_layer, bias and tanh of both sides through hh_dense_tanh_*).
+        optimizer: "torch" (the default) steps with torch.optim.Adam; "fused" keeps each policy's m, v and step count on the device
+        (DeviceAdam: hh_adam_step) and gathers the steps' statistics in a device table (hh_train_commit).
+        step: "eager" (the default) issues every minibatch step's launches from Python; "graph" (needs optimizer="fused") captures
+        stage -> forward -> loss -> backward -> Adam -> commit once per policy as ONE HIP graph and replays it per step (graph_prepare).
+        grad_clip: RLlib's grad_clip.  None (the default, and the reference's value): nothing is clipped and nothing changes.  A finite float
+        > 0: in every minibatch step the gradients of ONE optimizer — one policy's parameter list, the tied shared layer in it, as RLlib's
+        apply_grad_clipping takes one optimizer's param groups — are scaled so that their global L2 norm does not exceed it, and every dict
+        of update() also has grad_gnorm, the mean over the update's steps of the norm BEFORE clipping (RLlib reports it under the same
+        condition).  optimizer="torch" calls torch.nn.utils.clip_grad_norm_ (float32 norm, scales .grad in place); "fused" computes the
+        norm in float64 on the device and scales inside the Adam step (DeviceAdam(max_norm=...): .grad keeps the unscaled gradient), and
+        the graph's chain becomes stage -> forward -> loss -> backward -> norm -> clipped Adam -> commit.
+        shuffle_sequences: RLlib's shuffle_sequences (its default is True; here False, and then nothing changes).  True: every pass draws
+        its own order of the chunks (escape: rows), sequence_order(seed, update count, policy, pass), and cuts THAT order into consecutive
+        minibatches of at least sgd_minibatch_size unpadded rows (shuffled_schedule), visited in position order: the minibatches hold
+        different chunks in every pass, and a pass may take one step more or fewer than another.  The eager modes gather each minibatch with
+        index_select; step="graph" stages through hh_minibatch_stage_gather from an order table uploaded once per update into a persistent
+        device buffer of 4 * num_sgd_iter * S bytes for S chunks, grown to twice the need so that its address outlives batches of varying
+        size (30 passes: about 6.6 MB for 1.09 M fight rows in chunks of 20, about 131 MB for the same rows as escape rows).  RLlib's own
+        permutation is unseeded, so equality with it is not claimed; what shuffling does to learning curves has not been measured here.
+        heads (keyword only, taken by _heads_keyword in front of this signature): "torch" (the default): nothing changes.  "fused" (needs fused=True and trunk="torch"): the modules are built
+        with heads="fused", every minibatch step's forward stops at shared_layer's pre-activations (TrainableNet.pre_heads) and tanh, the
+        two heads, the loss and their backward run as one hh_heads_loss (heads_loss, unscaled: the step calls total.backward()), in all
+        three step modes, with grad_clip and shuffle_sequences as before."""
+        self.optimizer = _learner_options(
+            self, "PPOLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
+            dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
+            dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed), self._heads_arg, trunk)
+        self.kinds = tuple(int(k) for k in kinds)
+        assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
+        self.attention, self.inputs, self.trunk = attention, inputs, _trunk_mode(trunk)
+        # tied once, before the move: tie hands every module the first one's shared_layer MODULE, and nn.Module.to() moves a module's
+        # tensors in place without ever replacing a submodule object, so the one layer stays the one layer on the device
+        self.modules = tie([TrainableNet(k, attention=attention, inputs=inputs, trunk=trunk, heads=self.heads).load_numpy({k2: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k2, v in sd.items()})
+                            for k, sd in zip(self.kinds, state_dicts)])
+        for m in self.modules:
+            m.to(self.device)
+        self.recurrent = PN.HAS_ATT[self.kinds[0]]
+        esc = not self.recurrent
+        # per policy its own driver: the module's Adam, the step book, kl_coeff; one stage launch of every column
+        # (heads="fused": the forward callable stops at the pre-activations and the loss callable is the fused tail)
+        tail = self.heads == "fused"
+        # the drivers and their callables reach the learner through a weak proxy: no reference cycle, so a dropped learner and its captured
+        # graphs are freed at once by reference counting, never later by the cyclic collector in the middle of some other capture
+        me = weakref.proxy(self)
+        self._sgd = [_PolicySGD(me, m, lr, kl_coeff, self.optimizer == "fused",
+                                forward=(lambda mb, m=m: m.pre_heads(mb["obs"], mb["critic"])) if tail else (lambda mb, m=m: m(mb["obs"], mb["critic"])),
+                                loss=(lambda za, zc, mb, kl, a=a: me.heads_loss(a, za, zc, mb, kl)) if tail else (lambda logits, vf, mb, kl, a=a: me.loss(a, logits, vf, mb, kl)),
+                                stage_groups=lambda names: [(names, 1 if esc else me.max_seq_len)], policy=a, noun="chunks")
+                     for a, m in enumerate(self.modules)]
+        self.optimizers = [d.optimizer for d in self._sgd]
+        self._books = [d.book for d in self._sgd] if self.optimizer == "fused" else None
+        self._sel = (pilots.SEL_ESC1 if esc else pilots.SEL_FIGHT1, pilots.SEL_ESC2 if esc else pilots.SEL_FIGHT2)
+        self._tmp = None
+
+    @property
+    def kl_coeff(self):
+        """per policy the current coefficient of the KL term (the drivers hold them; update_kl moves each after its policy's passes)"""
+        return [d.kl_coeff for d in self._sgd]
+
+    @kl_coeff.setter
+    def kl_coeff(self, values):
+        for d, v in zip(self._sgd, values):
+            d.kl_coeff = float(v)
+
+    @classmethod
+    def trainable_init(cls, device, mode="fight", seed=0, **kw):
+        """the learner whose weights equal PolicyBank.trainable_init(device, mode, seed)'s (tied shared layer)"""
+        kinds = (PN.FIGHT1, PN.FIGHT2) if mode == "fight" else (PN.ESC1, PN.ESC2)
+        sds = [dict(PN.random_weights(k, seed), **PN.random_critic_weights(k, seed)) for k in kinds]
+        return cls(kinds, sds, device, seed=seed, **kw)
+
+    # ---- the batch
+    def old_logits(self, obs, bank, n_arenas):
+        """the sampler's logits of every row of obs f32 [R, 2, D] from `bank` -> f32 [R, 2, 32]; calls of [n_arenas, 2] rows each"""
+        R, _, D = obs.shape
+        N = int(n_arenas)
+        assert 2 * N <= bank.max_rows, "the bank serves the rollout's [N, 2] rows"
+        n_calls = (R + N - 1) // N
+        out = torch.zeros((max(n_calls, 1) * N, 2, OLD_LD), dtype=torch.float32, device=obs.device)
+        if self._tmp is None or self._tmp[0].shape[0] != N or self._tmp[0].shape[2] != D:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=obs.device)
+            self._tmp = (z((N, 2, D), torch.float32), z((N, 2, 4), torch.int8), z((N, 2), torch.float32),
+                         torch.tensor(self._sel, dtype=torch.uint8, device=obs.device).repeat(N, 1).contiguous())
+        stage, act, logp, sel = self._tmp
+        for i in range(n_calls):
+            src = obs[i * N:(i + 1) * N]
+            if src.shape[0] < N:
+                stage.zero_()
+                stage[:src.shape[0]].copy_(src)
+                src = stage
+            bank.sample(src, sel, greedy=True, actions=act, logp=logp, logits=out[i * N:(i + 1) * N], want_vf=False)
+        return out[:R]
+
+    def batch_old_logits(self, rows, bank, n_arenas=None):
+        """old_logits f32 [R, 2, 32] of an emitted batch (`rows`: EpisodeBatch.rows()): the batch's own `logits` column where the
+        rollout recorded one (the very tensor, no bank call); otherwise recomputed from `bank` (old_logits; n_arenas: the rollout's N)"""
+        if "logits" in rows:
+            lg = rows["logits"]
+            if lg.dtype != torch.float32 or tuple(lg.shape) != (rows["obs"].shape[0], 2, OLD_LD):
+                raise ValueError(f"the batch's logits column must be f32 [R, 2, {OLD_LD}], got {lg.dtype} {tuple(lg.shape)}")
+            return lg
+        if bank is None or n_arenas is None:
+            raise ValueError("the batch has no logits column (PPORollout(record_logits=True)): a bank and n_arenas are needed to recompute them")
+        return self.old_logits(rows["obs"], bank, n_arenas)
+
+    def policy_batch(self, rows, old_logits, agent):
+        """the training batch of policy `agent` (0 | 1) from the emitted rows: dict of [S, L, ...] chunks (fight) or [R, ...] rows (escape)
+        and, for chunks, seq_len [S] and mask [S, L]"""
+        kind = self.kinds[agent]
+        b = {"obs": rows["obs"][:, agent, :PN.OBS_DIM[kind]].contiguous(),
+             "critic": central_critic_rows(rows["obs"], rows["actions"], agent + 1),
+             "actions": rows["actions"][:, agent].contiguous(), "old_logp": rows["logp"][:, agent].contiguous(),
+             "adv": standardize(rows["adv"][:, agent]), "target": rows["target"][:, agent].contiguous(),
+             "old_logits": old_logits[:, agent].contiguous()}
+        if not self.recurrent:
+            return b
+        seq_start, seq_len = cut_chunks(rows["ep_start"], rows["ep_len"], self.max_seq_len)
+        b = {k: pad_chunks(v, seq_start, seq_len, self.max_seq_len) for k, v in b.items()}
+        b["seq_len"] = seq_len
+        b["mask"] = chunk_mask(seq_len, self.max_seq_len).to(torch.uint8)
+        return b
+
+    # ---- one minibatch step
+    def loss(self, agent, logits, vf, mb, kl_coeff=None):
+        """the policy's loss of one minibatch; kl_coeff: the KL term's coefficient, default the policy's current one"""
+        return (ppo_loss if self.fused else ppo_loss_torch)(logits, vf, mb, n_comp=n_comp_of(self.kinds[agent]), **_loss_kw(self, self._sgd[agent], kl_coeff))
+
+    def heads_loss(self, agent, za, zc, mb, kl_coeff=None):
+        """heads="fused": the policy's loss of one minibatch from pre_heads' (za, zc), through heads_loss with the module's act_out and
+        val_out; the gradients are handed to total.backward() unscaled"""
+        m = self.modules[agent]
+        return heads_loss(za, zc, m.act_out, m.val_out, mb, n_comp=n_comp_of(self.kinds[agent]), scale_grad=False, **_loss_kw(self, self._sgd[agent], kl_coeff))
+
+    def _columns(self, b, staged=False):
+        """policy_batch's dict as the driver takes it -> (columns [S, ...], host seq_len [S]: the chunks' lengths, ones for escape rows).
+        staged: as the graph's stage reads them — contiguous, the mask uint8, and for the escape kinds a mask of ones, which the padding
+        rows of the staging buffers need"""
+        cols = {k: (v.contiguous() if staged else v) for k, v in b.items() if k != "seq_len"}
+        S = cols["obs"].shape[0]
+        seq_len = b["seq_len"].cpu().numpy() if self.recurrent else np.ones(S, dtype=np.int64)
+        if staged:
+            if not self.recurrent:
+                cols["mask"] = torch.ones((S,), dtype=torch.uint8, device=self.device)
+            cols["mask"] = cols["mask"].to(torch.uint8)
+        return cols, seq_len
+
+    # the steps themselves are the driver's (_PolicySGD): one per policy
+    def minibatch_step(self, agent, mb):
+        """forward, loss, backward, Adam step on one minibatch (a dict sliced from policy_batch's, with n_valid) -> stats f64 [6] (device)"""
+        return self._sgd[agent].minibatch_step(mb)
+
+    def graph_prepare(self, agent, b, cap=None):
+        """Everything one policy's pass needs before its first replay (_PolicySGD.graph_prepare on policy_batch `b`): the schedule and the
+        batch's columns uploaded, the cursor set to 0, and the graph of ONE minibatch step — stage, forward, loss, backward, Adam, commit —
+        captured unless an earlier one still fits.  cap: the staging capacity in chunks (escape: rows).  -> (n_steps, rows)"""
+        if self.step != "graph":
+            raise ValueError('graph_prepare needs PPOLearner(step="graph")')
+        return self._sgd[agent].graph_prepare(*self._columns(b, staged=True), cap)
+
+    def graph_replay(self, agent, n=1):
+        """n minibatch steps of policy `agent` from its captured graph, no host work between them"""
+        self._sgd[agent].graph_replay(n)
+
+    def graph_stats(self, agent, n):
+        """the statistics rows f64 [n, 6] of the first n steps since graph_prepare (one device tensor; reading it synchronises)"""
+        return self._sgd[agent].graph_stats(n)
+
+    def grad_gnorm(self, agent, n):
+        """grad_clip: the mean of the first n steps' norms before clipping since the update began (a float; reading it synchronises)"""
+        return self._sgd[agent].grad_gnorm(n)
+
+    # ---- one update
+    def update(self, episodes, bank=None):
+        """one PPO update of both policies from episodes (an EpisodeBatch after a collect) -> per policy a dict: total_loss, policy_loss,
+        vf_loss, kl, entropy (means over the minibatch steps), kl_coeff (after the update), steps (minibatch steps taken), rows.
+        `bank` is read only when the batch has no `logits` column (batch_old_logits).  With grad_clip also grad_gnorm.
+        An EpisodeBatch built with train_batch_size hands over its accumulated batch (RLlib's train_batch_size: update once
+        `episodes.ready()`, e.g. after `PPORollout.collect_batch()`); nothing else changes here."""
+        rows = episodes.rows()
+        if rows["obs"].shape[0] == 0:
+            return [d.empty() for d in self._sgd]
+        with torch.no_grad():
+            old = self.batch_old_logits(rows, bank, episodes.N)
+            batches = [self.policy_batch(rows, old, a) for a in range(2)]
+        out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
+        self.updates += 1
+        return out
+
+    # ---- one update from a fixed window (batch_mode = "truncate_episodes")
+    def _check_window(self, rollout):
+        """the refusals of window_batch / update_window -> (T, N)"""
+        if getattr(rollout, "semantics", "rllib") != "rllib":
+            raise ValueError("PPOLearner trains RLlib's unmasked view: a PPORollout(semantics='masked') window has its dead agents' rows cut out of adv and target")
+        for k in ("obs", "actions", "logp", "adv", "target", "done", "T", "w"):
+            if not hasattr(rollout, k):
+                raise ValueError(f"window_batch takes a PPORollout (its [T, N] buffers); this object has no `{k}`")
+        esc = rollout.w.cfg.agent_mode == L.MODE_ESCAPE
+        if rollout.obs.dim() != 4 or rollout.obs.shape[2] != 2 or esc == self.recurrent or rollout.obs.shape[3] < max(PN.OBS_DIM[k] for k in self.kinds):
+            raise ValueError(f"the rollout's world flies {'escape' if esc else 'fight'} mode with observations {tuple(rollout.obs.shape[2:])}; "
+                             f"this learner trains kinds {self.kinds} ({'fight' if self.recurrent else 'escape'})")
+        if not getattr(rollout, "collects", 0):
+            raise RuntimeError("the rollout has not collected yet: its window buffers hold nothing (rollout.collect() first)")
+        return rollout.T, rollout.w.N
+
+    def _window_shared(self, rollout, bank):
+        """what both policies' window batches share: the cut, the sampler's logits [T, N, 2, 32] and the advantages in arena-major rows"""
+        T, N = self._check_window(rollout)
+        tables = window_cut(rollout.done, self.max_seq_len if self.recurrent else 1)
+        if getattr(rollout, "record_logits", False):
+            logits = rollout.logits
+        else:
+            if bank is None:
+                raise ValueError("the rollout recorded no logits (PPORollout(record_logits=True)): a bank is needed to recompute them")
+            logits = self.old_logits(rollout.obs[:T].reshape(T * N, 2, rollout.obs.shape[3]), bank, N).reshape(T, N, 2, OLD_LD)
+        adv_rows = rollout.adv.transpose(0, 1).reshape(N * T, 2)      # [R, 2], r = n T + t: what the episode path's rows["adv"] would hold
+        return T, N, tables, logits.contiguous(), adv_rows
+
+    def window_batch(self, rollout, bank, agent, shared=None):
+        """the training batch of policy `agent` (0 | 1) from a PPORollout's [T, N] window, in policy_batch's format and — fed the same
+        rows as episodes (the window's fragments, arena-major) — with policy_batch's values: fight kinds [S, L, ...] chunks with seq_len
+        and mask (a chunk ends at a done row, at max_seq_len rows or at the window's end: window_cut), escape kinds [R, ...] with R = T N
+        rows, arena-major (r = n T + t: the cut with max_seq_len = 1, the length-1 axis dropped).  One hh_window_gather launch of seven
+        columns reads the rollout's buffers as they lie.  The trailing fragment of an arena carries RLlib's truncation bootstrap from
+        vf[T] in adv and target (hh_gae_rllib).  `bank` is read only when the rollout recorded no logits.  The advantages are standardised
+        over the agent's T N values (standardize).  shared: _window_shared's tuple (update_window builds it once for both policies)."""
+        T, N, tables, logits, adv_rows = self._window_shared(rollout, bank) if shared is None else shared
+        kind = self.kinds[agent]
+        Lm = self.max_seq_len if self.recurrent else 1
+        D, Dk = rollout.obs.shape[3], PN.OBS_DIM[kind]
+        critic = central_critic_rows(rollout.obs[:T], rollout.actions, agent + 1).contiguous()
+        adv = standardize(adv_rows[:, agent]).reshape(N, T).t().contiguous()          # back to [T, N]: where the gather reads a row (t, n)
+        names = ("obs", "critic", "actions", "old_logp", "adv", "target", "old_logits")
+        got = window_gather([(rollout.obs, (Dk,), agent * D * 4, False), (critic, (critic.shape[2],), 0, False),
+                             (rollout.actions, (4,), agent * 4, False), (rollout.logp, (), agent * 4, False), (adv, (), 0, False),
+                             (rollout.target, (), agent * 4, False), (logits, (OLD_LD,), agent * OLD_LD * 4, False)], tables, Lm)
+        if not self.recurrent:
+            return {k: v[:, 0] for k, v in zip(names, got)}
+        b = dict(zip(names, got))
+        b["seq_len"] = tables[2].long()
+        b["mask"] = chunk_mask(b["seq_len"], Lm).to(torch.uint8)
+        return b
+
+    def update_window(self, rollout, bank=None):
+        """one PPO update of both policies from a PPORollout's [T, N] window as the last collect left it (batch_mode =
+        "truncate_episodes", the rollouts' default; the buffers are the same in both modes) -> what `update` returns, with rows = T N.
+        Every row of the window was sampled by the weights the sampler holds, so nothing is carried, nothing overflows and no start()
+        is needed after publish:
+
+            ro.collect();  stats = learner.update_window(ro, bank);  learner.publish(bank)
+
+        The batches are window_batch's; from there on it is `update`: the same _columns and driver, so fused, attention, inputs, trunk,
+        heads, optimizer, step="graph", grad_clip and shuffle_sequences act as they do there, and the row count T N is the same in every
+        update.  The rollout's buffers are only read."""
+        with torch.no_grad():
+            shared = self._window_shared(rollout, bank)
+            batches = [self.window_batch(rollout, bank, a, shared) for a in range(2)]
+        out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
+        self.updates += 1
+        return out
+
+    def publish(self, bank):
+        """the new weights into the sampler's bank on the current stream (PolicyBank.refresh_trainable): captured collects replay with them"""
+        bank.refresh_trainable(self.modules)

@@ -1,5 +1,5 @@
 """Sequential float64 restatement of gradient clipping by global norm (learner.grad_norm: hh_grad_norm; learner.adam_step(clip=...):
-hh_adam_step_clipped), written from the formulas of include/hh_learner.h and from nothing in learner.py, and the tests' gradient lists.
+hh_adam_step_clipped), written from the formulas of include/hh_learner.h and from nothing in the learner package, and the tests' gradient lists.
 No test in here."""
 import numpy as np
 

@@ -1,6 +1,6 @@
 """Plain-numpy restatements that the shuffle_sequences tests hold the code against (learner.sequence_order, learner.shuffled_schedule,
 learner.minibatch_stage_gather: hh_minibatch_stage_gather), written from the contract in include/hh_learner.h and DESIGN.md section 22
-and from nothing in learner.py."""
+and from nothing in the learner package."""
 import numpy as np
 
 

@@ -30,6 +30,29 @@ def _commander(shuffle, step):
     return ln, [(ln._sgd, TC._policy_batch(ln.module, 41), 0)]
 
 
+@pytest.mark.parametrize("make", (_fight, _commander), ids=("fight", "commander"))
+def test_a_dropped_graph_learner_is_freed_by_reference_counting(make):
+    """A learner that has captured its step holds a HIP graph with a memory pool of its own.  Were the learner part of a reference cycle
+    (its driver holding it back), the graph would live until the cyclic collector runs — which may be in the middle of another capture,
+    where freeing a pool aborts the process.  With the collector switched off, dropping the last reference frees learner and step book."""
+    import gc
+    import weakref
+    ln, todo = make(False, "graph")
+    driver, b, _ = todo[0]
+    driver.run(*ln._columns(b, staged=True))
+    torch.cuda.synchronize()
+    assert driver.book.captures == 1 and driver.book.graph is not None
+    refs = [weakref.ref(ln), weakref.ref(driver), weakref.ref(driver.book)]
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        del ln, todo, driver, b
+        assert [r() for r in refs] == [None, None, None]
+    finally:
+        if was_on:
+            gc.enable()
+
+
 @pytest.mark.parametrize("shuffle", (False, True), ids=("in order", "shuffled"))
 @pytest.mark.parametrize("make", (_fight, _commander), ids=("fight", "commander"))
 def test_eager_and_graph_walk_the_same_table(make, shuffle):

@@ -153,6 +153,43 @@ def test_bad_arguments_are_refused():
     assert L.lib().hh_last_error()
 
 
+@pytest.mark.parametrize("lead,n_comp,ld,masked", [((3, 4), 4, 26, True), ((5,), 3, 24, False)])
+def test_gradients_under_an_upstream_gradient_of_one_half(lead, n_comp, ld, masked):
+    """learner.ppo_loss under (0.5 * total).backward() — the tests above and below only ever send an upstream gradient of exactly 1 — on
+    the smallest shapes that reach the padded-mask path ([3, 4, 26] logits, 32-wide old_logits, a mask) and the flat path ([5, 24], no
+    mask): the gradients of logits and vf are exactly half those of total.backward(), and against a float64 run of learner.ppo_loss_torch
+    under the same upstream gradient the fused path's largest error is at most 4 x the float32 torch path's (the bound of
+    test_autograd_into_the_network_fused_against_unfused)."""
+    from hhmarl_2d_amd import learner as LR
+    dev = torch.device("cuda", 0)
+    R = 1
+    for n in lead:
+        R *= n
+    inp = REF.make_inputs(R, n_comp, ld, masked, 2)
+    shaped = lambda t: t.reshape(lead + tuple(t.shape[1:])).to(dev)
+    batch = {k: shaped(inp[k]) for k in ("old_logits", "actions", "old_logp", "adv", "target")}
+    assert batch["old_logits"].shape[-1] == 32
+    if masked:
+        batch["mask"] = shaped(inp["mask"])
+    kw = _kw(n_comp, 0.2, 0.01)
+
+    def grads(loss_fn, dt, upstream):
+        logits, vf = shaped(inp["logits"]).to(dt).requires_grad_(True), shaped(inp["vf"]).to(dt).requires_grad_(True)
+        total, _ = loss_fn(logits, vf, batch, **kw)
+        (upstream * total).backward()
+        assert logits.grad.shape == logits.shape and vf.grad.shape == vf.shape
+        return logits.grad.double(), vf.grad.double()
+
+    g64, gun, gfu = grads(LR.ppo_loss_torch, torch.float64, 0.5), grads(LR.ppo_loss_torch, torch.float32, 0.5), grads(LR.ppo_loss, torch.float32, 0.5)
+    one = grads(LR.ppo_loss, torch.float32, 1.0)
+    assert all(torch.isfinite(g).all() for g in gfu) and gfu[0].abs().max().item() > 0 and gfu[1].abs().max().item() > 0
+    assert torch.equal(2.0 * gfu[0], one[0]) and torch.equal(2.0 * gfu[1], one[1])
+    e_un = max((a - b).abs().max().item() for a, b in zip(gun, g64))
+    e_fu = max((a - b).abs().max().item() for a, b in zip(gfu, g64))
+    print(f"lead={lead} n_comp={n_comp}: error against float64 under upstream 0.5: unfused {e_un:.3e}, fused {e_fu:.3e}")
+    assert e_fu <= 4.0 * e_un
+
+
 @pytest.mark.parametrize("kind,masked", [(0, True), (1, True), (2, False), (3, False)])
 def test_autograd_into_the_network_fused_against_unfused(kind, masked):
     """gradients of a TrainableNet's parameters through learner.ppo_loss (hh_ppo_loss) and through learner.ppo_loss_torch, both against a

@@ -111,6 +111,32 @@ def test_same_bytes_every_run_and_the_torch_form_agrees():
     assert (st.cpu() - a[0]).abs()[:5].max().item() <= 1e-4
 
 
+def test_gradients_under_an_upstream_gradient_of_one_half():
+    """learner.ppo_loss_categorical under (0.5 * total).backward() — _kernel only ever sends an upstream gradient of exactly 1 — on the
+    smallest shape that reaches the pad-to-4 path ([3, 4, 3] logits, a mask): the gradients of logits and vf are exactly half those of
+    total.backward() and agree with learner.ppo_loss_categorical_torch's under the same upstream gradient within the 1e-4 that
+    test_same_bytes_every_run_and_the_torch_form_agrees holds the two forms to."""
+    from hhmarl_2d_amd import learner as LR
+    kw = dict(clip_param=CLIP, vf_clip_param=VCLIP, vf_loss_coeff=1.0, entropy_coeff=0.01, kl_coeff=0.2)
+    inp = make_inputs(12, True, 7)
+    shaped = lambda t: t.reshape((3, 4) + tuple(t.shape[1:])).cuda()
+    batch = {k: shaped(inp[k]) for k in ("old_logits", "actions", "old_logp", "adv", "target", "mask")}
+
+    def grads(loss_fn, upstream):
+        logits, vf = shaped(inp["logits"][:, :3]).requires_grad_(True), shaped(inp["vf"]).requires_grad_(True)
+        total, _ = loss_fn(logits, vf, batch, **kw)
+        (upstream * total).backward()
+        assert logits.grad.shape == (3, 4, 3) and vf.grad.shape == (3, 4)
+        return logits.grad, vf.grad
+
+    fused, torch_form, one = grads(LR.ppo_loss_categorical, 0.5), grads(LR.ppo_loss_categorical_torch, 0.5), grads(LR.ppo_loss_categorical, 1.0)
+    assert all(torch.isfinite(g).all() for g in fused) and fused[0].abs().max().item() > 0 and fused[1].abs().max().item() > 0
+    assert torch.equal(2.0 * fused[0], one[0]) and torch.equal(2.0 * fused[1], one[1])
+    err = [(a - b).abs().max().item() for a, b in zip(fused, torch_form)]
+    print(f"upstream 0.5: fused against the torch form, d_logits {err[0]:.3e}, d_vf {err[1]:.3e}")
+    assert max(err) <= 1e-4
+
+
 def test_bad_arguments_are_refused():
     import ctypes as C
     from hhmarl_2d_amd import _lib as L

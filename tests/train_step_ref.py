@@ -1,5 +1,5 @@
 """Float64 / plain-numpy restatements that the train-step tests hold the device code against (learner.adam_step: hh_adam_step,
-learner.minibatch_stage: hh_minibatch_stage), written from the formulas of include/hh_learner.h and from nothing in learner.py."""
+learner.minibatch_stage: hh_minibatch_stage), written from the formulas of include/hh_learner.h and from nothing in the learner package."""
 import math
 
 import numpy as np
