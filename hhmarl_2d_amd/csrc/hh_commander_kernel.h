@@ -337,105 +337,11 @@ extern "C" int hh_commander_destroy(hh_commander *c) {
     return HH_OK;
 }
 
-/* the first layer's blocks (hhc_set_weights and the device refresh, hh_weight_refresh.h): first input column, last + 1 | width, output
+/* the first layer's blocks (the packer and hh_commander_set_weights, hh_weight_refresh.h): first input column, last + 1 | width, output
  * width and first output column in S order [e (300) | 0 | f (200) | 0] — actor inp1..inp4 on the observation, critic v1..v4 on
  * [obs_own|act_own|obs_o1|act_o1|obs_o2|act_o2] */
 static const int HHC_L1A_C0[4] = {0, 4, 24, 0}, HHC_L1A_C1[4] = {4, 24, 34, 34}, HHC_L1A_WD[4] = {50, 200, 50, 200}, HHC_L1A_OUT0[4] = {0, 50, 250, HHC_FOFF};
 static const int HHC_L1V_C0[4] = {0, 35, 70, 0}, HHC_L1V_IN[4] = {35, 35, 35, 105}, HHC_L1V_WD[4] = {100, 100, 100, 200}, HHC_L1V_OUT0[4] = {0, 100, 200, HHC_FOFF};
-
-/* host repack: every matrix as (hi, lo) fp16 fragment planes in hhp_hidx order, biases and the output layers in fp32 */
-static int hhc_set_weights(hh_commander *c, const hh_commander_weights *w) {
-    const float *need[] = {w->act_w_ih, w->act_w_hh, w->act_b_ih, w->act_b_hh, w->shared_w, w->shared_b, w->act_out_w, w->act_out_b,
-                           w->val_w_ih, w->val_w_hh, w->val_b_ih, w->val_b_hh, w->val_out_w, w->val_out_b};
-    for (const float *p : need) if (!p) { g_err = "hh_commander_set_weights: missing weight pointer"; return HH_E_ARG; }
-    for (int k = 0; k < 4; k++) if (!w->inp_w[k] || !w->inp_b[k] || !w->v_w[k] || !w->v_b[k]) { g_err = "hh_commander_set_weights: missing input layer"; return HH_E_ARG; }
-    const int K1[2] = {48, 112};
-    /* halves: w1 actor | w1 critic | wg actor | wg critic | ws */
-    const size_t h_w1a = 0, h_w1c = h_w1a + (size_t)48 * 512, h_wga = h_w1c + (size_t)112 * 512, h_wgc = h_wga + (size_t)HHC_KG * HHC_JG,
-                 h_ws = h_wgc + (size_t)HHC_KG * HHC_JG, h_total = h_ws + (size_t)HHC_KS * HHC_KS;
-    /* floats: b1 a | b1 c | bg a | bg c | bs | wo a [3][512] | wo c [512] | bo a [4] | bo c [4] */
-    const size_t f_b1a = 0, f_b1c = 512, f_bga = 1024, f_bgc = f_bga + 896, f_bs = f_bgc + 896, f_woa = f_bs + 512, f_woc = f_woa + 1536,
-                 f_boa = f_woc + 512, f_boc = f_boa + 4, f_total = f_boc + 4;
-    std::vector<uint16_t> Hh(h_total, 0), Hl(h_total, 0);
-    std::vector<float> F(f_total, 0.0f);
-    /* L1: output column of hidden unit o of input block k; S order [e (300) | 0 | f (200) | 0] */
-    const int *a_c0 = HHC_L1A_C0, *a_c1 = HHC_L1A_C1, *a_wd = HHC_L1A_WD, *out0 = HHC_L1A_OUT0;
-    for (int k = 0; k < 4; k++)
-        for (int o = 0; o < a_wd[k]; o++) {
-            for (int ci = a_c0[k]; ci < a_c1[k]; ci++) hhp_split_put(Hh, Hl, h_w1a, ci, out0[k] + o, 512, w->inp_w[k][(size_t)o * (a_c1[k] - a_c0[k]) + ci - a_c0[k]]);
-            F[f_b1a + out0[k] + o] = w->inp_b[k][o];
-        }
-    const int *v_c0 = HHC_L1V_C0, *v_in = HHC_L1V_IN, *v_wd = HHC_L1V_WD, *vout0 = HHC_L1V_OUT0;
-    for (int k = 0; k < 4; k++)
-        for (int o = 0; o < v_wd[k]; o++) {
-            for (int ci = 0; ci < v_in[k]; ci++) hhp_split_put(Hh, Hl, h_w1c, v_c0[k] + ci, vout0[k] + o, 512, w->v_w[k][(size_t)o * v_in[k] + ci]);
-            F[f_b1c + vout0[k] + o] = w->v_b[k][o];
-        }
-    /* GRU: hidden tile t, unit u = 32 t + j: columns 128 t + j (r), + 32 (z), + 64 (W_in f), + 96 (W_hn h); rows 0..199 = f, 208..407 = h */
-    const float *wih[2] = {w->act_w_ih, w->val_w_ih}, *whh[2] = {w->act_w_hh, w->val_w_hh}, *bih[2] = {w->act_b_ih, w->val_b_ih}, *bhh[2] = {w->act_b_hh, w->val_b_hh};
-    const size_t h_wg[2] = {h_wga, h_wgc}, f_bg[2] = {f_bga, f_bgc};
-    for (int b = 0; b < 2; b++)
-        for (int u = 0; u < HH_CMD_HIDDEN; u++) {
-            const int col = 128 * (u >> 5) + (u & 31);
-            for (int k = 0; k < HH_CMD_HIDDEN; k++) {
-                hhp_split_put(Hh, Hl, h_wg[b], k, col, HHC_JG, wih[b][(size_t)u * 200 + k]);                           /* r */
-                hhp_split_put(Hh, Hl, h_wg[b], 208 + k, col, HHC_JG, whh[b][(size_t)u * 200 + k]);
-                hhp_split_put(Hh, Hl, h_wg[b], k, col + 32, HHC_JG, wih[b][(size_t)(200 + u) * 200 + k]);              /* z */
-                hhp_split_put(Hh, Hl, h_wg[b], 208 + k, col + 32, HHC_JG, whh[b][(size_t)(200 + u) * 200 + k]);
-                hhp_split_put(Hh, Hl, h_wg[b], k, col + 64, HHC_JG, wih[b][(size_t)(400 + u) * 200 + k]);              /* W_in */
-                hhp_split_put(Hh, Hl, h_wg[b], 208 + k, col + 96, HHC_JG, whh[b][(size_t)(400 + u) * 200 + k]);        /* W_hn */
-            }
-            F[f_bg[b] + u] = bih[b][u] + bhh[b][u];
-            F[f_bg[b] + 224 + u] = bih[b][200 + u] + bhh[b][200 + u];
-            F[f_bg[b] + 448 + u] = bih[b][400 + u];
-            F[f_bg[b] + 672 + u] = bhh[b][400 + u];
-        }
-    /* shared layer: input row k of S order <- reference input column (k < 300: k; 304 <= k < 504: k - 4) */
-    for (int o = 0; o < 500; o++) {
-        for (int k = 0; k < HHC_KS; k++) {
-            const int src = k < 300 ? k : ((k >= HHC_FOFF && k < HHC_FOFF + 200) ? k - 4 : -1);
-            if (src >= 0) hhp_split_put(Hh, Hl, h_ws, k, o, HHC_KS, w->shared_w[(size_t)o * 500 + src]);
-        }
-        F[f_bs + o] = w->shared_b[o];
-        for (int j = 0; j < 3; j++) F[f_woa + (size_t)j * 512 + o] = w->act_out_w[(size_t)j * 500 + o];
-        F[f_woc + o] = w->val_out_w[o];
-    }
-    for (int j = 0; j < 3; j++) F[f_boa + j] = w->act_out_b[j];
-    F[f_boc] = w->val_out_b[0];
-
-    HH_GUARD(c);
-    const size_t plane_bytes = h_total * sizeof(uint16_t), bytes = 2 * plane_bytes + f_total * sizeof(float);
-    if (!c->blob) HIPCHK(hipMalloc(&c->blob, bytes));
-    char *d = c->blob;
-    HIPCHK(hipMemcpy(d, Hh.data(), plane_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + plane_bytes, Hl.data(), plane_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 2 * plane_bytes, F.data(), f_total * sizeof(float), hipMemcpyHostToDevice));
-    const uint16_t *bh = reinterpret_cast<const uint16_t *>(d), *bl = reinterpret_cast<const uint16_t *>(d + plane_bytes);
-    const float *bf = reinterpret_cast<const float *>(d + 2 * plane_bytes);
-    HhcNet &N = c->net;
-    const size_t h_w1[2] = {h_w1a, h_w1c}, f_b1[2] = {f_b1a, f_b1c}, f_wo[2] = {f_woa, f_woc}, f_bo[2] = {f_boa, f_boc};
-    for (int b = 0; b < 2; b++) {
-        HhcBranch &Br = N.br[b];
-        Br.w1h = reinterpret_cast<const float4 *>(bh + h_w1[b]); Br.w1l = reinterpret_cast<const float4 *>(bl + h_w1[b]);
-        Br.wgh = reinterpret_cast<const float4 *>(bh + h_wg[b]); Br.wgl = reinterpret_cast<const float4 *>(bl + h_wg[b]);
-        Br.b1 = bf + f_b1[b]; Br.bg = bf + f_bg[b]; Br.wo = bf + f_wo[b]; Br.bo = bf + f_bo[b];
-        Br.k1 = K1[b];
-    }
-    N.wsh = reinterpret_cast<const float4 *>(bh + h_ws); N.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
-    N.bs = bf + f_bs;
-    c->loaded = 1;
-    return HH_OK;
-}
-
-extern "C" int hh_commander_set_weights(hh_commander *c, const hh_commander_weights *w) {
-    if (!c || !w) { g_err = "hh_commander_set_weights: bad argument"; return HH_E_ARG; }
-    try { /* the repacking buffers are std::vectors: an allocation failure must not unwind through the C ABI */
-        return hhc_set_weights(c, w);
-    } catch (const std::exception &e) {
-        g_err = std::string("hh_commander_set_weights: ") + e.what();
-        return HH_E_HIP;
-    }
-}
 
 extern "C" int hh_commander_sample(hh_commander *c, const float *obs, int32_t n_arenas, float *h_in, float *h_out, const uint8_t *fresh,
                                    hh_world *w, const double *uniforms, const float *crit_act, int32_t greedy, int8_t *actions, float *logp,

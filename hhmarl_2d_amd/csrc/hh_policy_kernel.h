@@ -12,7 +12,7 @@
  * This is the one dense contraction on the whole path, so it runs on the matrix cores.  gfx950 has no tf32-like mode and its fp32-in MFMA runs
  * at the vector rate, so every operand is split into two fp16 halves and a product is accumulated in fp32 as hi hi + lo hi + hi lo
  * (hh_policy_kernel_h16.h: logits within 1e-6 of a float64 forward, like PyTorch's own fp32 forward).  This header holds what the forms share
- * — the bank of loaded networks (weights packed on the host), the row binning by network (hh_k_policy_bin), the choice of a form per call —
+ * — the bank of loaded networks (weights packed by hh_weight_refresh.h), the row binning by network (hh_k_policy_bin), the choice of a form per call —
  * and the C ABI; the kernels:
  *     hh_k_policy_h<1|2>     hh_policy_kernel_h16.h   activations in an LDS tile of 32 | 64 rows, weights out of L2              small calls
  *     hh_k_policy_w16<4|8>   hh_policy_kernel_w16.h   weights streamed through LDS, activations in registers, 64 | 128-row tiles  >= 40 rows x n_CU
@@ -248,131 +248,6 @@ extern "C" int hh_policy_destroy(hh_policy *p) {
     return HH_OK;
 }
 
-static int hhp_set_net(hh_policy *p, int32_t slot, const hh_net_weights *w);
-extern "C" int hh_policy_set_net(hh_policy *p, int32_t slot, const hh_net_weights *w) {
-    try { /* the repacking buffers are std::vectors: an allocation failure must not unwind through the C ABI */
-        return hhp_set_net(p, slot, w);
-    } catch (const std::exception &e) {
-        g_err = std::string("hh_policy_set_net: ") + e.what();
-        return HH_E_HIP;
-    }
-}
-static int hhp_set_net(hh_policy *p, int32_t slot, const hh_net_weights *w) {
-    if (!p || !w || slot < 0 || slot >= HH_POLICY_MAX_NETS || w->kind < 0 || w->kind > 3) { g_err = "bad argument"; return HH_E_ARG; }
-    const bool att = w->kind <= HH_NET_FIGHT2;
-    if (!w->shared_w || !w->shared_b || !w->out_w || !w->out_b || (att && (!w->att_in_proj_w || !w->att_in_proj_b || !w->att_out_w || !w->att_out_b))) {
-        g_err = "hh_policy_set_net: missing weight pointer"; return HH_E_ARG;
-    }
-    for (int k = 0; k < 3; k++) if (!w->inp_w[k] || !w->inp_b[k]) { g_err = "hh_policy_set_net: missing input layer"; return HH_E_ARG; }
-    HH_GUARD(p);
-    /* the slot's value branch holds its own permuted copy of the shared layer and the input widths of the kind it was loaded for: a new
-     * actor makes both stale.  hh_policy_sample refuses vf for the slot until hh_policy_set_critic is called again (set_net + set_critic
-     * are a pair; the old copy stays allocated and is simply never read) */
-    p->cbank.c[slot].loaded = 0;
-    p->cbankx.c[slot].loaded = 0;
-    const int n_out = (w->kind == HH_NET_FIGHT1 || w->kind == HH_NET_ESC1) ? 26 : 24;
-    /* blob: w1p | b1 | wovp | bov | wsp | bs | wap | ba   (float counts; every section 16-byte aligned) */
-    const size_t n_w1 = 4 * 2 * HHP_H * 4, n_wov = 13 * 2 * HHP_ATT_J * 4, n_ws = 64 * 2 * HHP_H * 4, n_wa = 64 * 2 * HHP_OUT * 4;
-    const size_t o_w1 = 0, o_b1 = o_w1 + n_w1, o_wov = o_b1 + HHP_H, o_bov = o_wov + n_wov, o_ws = o_bov + HHP_ATT_J, o_bs = o_ws + n_ws,
-                 o_wa = o_bs + HHP_H, o_ba = o_wa + n_wa, total = o_ba + HHP_OUT;
-    std::vector<float> B(total, 0.0f);
-    /* the same four matrices as (hi, lo) fp16 fragment planes for hh_k_policy_h: w1 | wov | ws | wa, each [K/16][2][J][8] */
-    const size_t h_w1 = 0, h_wov = h_w1 + (size_t)2 * 2 * HHP_H * 8, h_ws = h_wov + (size_t)7 * 2 * HHP_ATT_J * 8, h_wa = h_ws + (size_t)32 * 2 * HHP_H * 8,
-                 h_total = h_wa + (size_t)32 * 2 * HHP_OUT * 8;
-    std::vector<uint16_t> Hh(h_total, 0), Hl(h_total, 0);
-    int off = 0, obs_dim = 0;
-    for (int k = 0; k < 3; k++) {
-        const int c0 = HHP_INPUTS[w->kind][k][0], c1 = HHP_INPUTS[w->kind][k][1], wd = HHP_INPUTS[w->kind][k][2];
-        for (int o = 0; o < wd; o++) {
-            for (int c = c0; c < c1; c++) {
-                const float v = w->inp_w[k][(size_t)o * (c1 - c0) + (c - c0)];
-                B[o_w1 + hhp_pidx(c, off + o, HHP_H)] = v;
-                hhp_split_put(Hh, Hl, h_w1, c, off + o, HHP_H, v);
-            }
-            B[o_b1 + off + o] = w->inp_b[k][o];
-        }
-        off += wd;
-        if (c1 > obs_dim) obs_dim = c1;
-    }
-    if (att) { /* out_proj(v_proj(x)): Wov = Wo Wv, bov = Wo bv + bo, folded in double */
-        const float *wv = w->att_in_proj_w + (size_t)200 * 100, *bv = w->att_in_proj_b + 200;
-        for (int j = 0; j < 100; j++) {
-            for (int k = 0; k < 100; k++) {
-                double s = 0.0;
-                for (int m = 0; m < 100; m++) s += (double)w->att_out_w[(size_t)j * 100 + m] * (double)wv[(size_t)m * 100 + k];
-                B[o_wov + hhp_pidx(k, j, HHP_ATT_J)] = (float)s;
-                hhp_split_put(Hh, Hl, h_wov, k, j, HHP_ATT_J, (float)s);
-            }
-            double s = (double)w->att_out_b[j];
-            for (int m = 0; m < 100; m++) s += (double)w->att_out_w[(size_t)j * 100 + m] * (double)bv[m];
-            B[o_bov + j] = (float)s;
-        }
-    }
-    for (int j = 0; j < 500; j++) {
-        for (int k = 0; k < 500; k++) { B[o_ws + hhp_pidx(k, j, HHP_H)] = w->shared_w[(size_t)j * 500 + k]; hhp_split_put(Hh, Hl, h_ws, k, j, HHP_H, w->shared_w[(size_t)j * 500 + k]); }
-        B[o_bs + j] = w->shared_b[j];
-    }
-    for (int j = 0; j < n_out; j++) {
-        for (int k = 0; k < 500; k++) { B[o_wa + hhp_pidx(k, j, HHP_OUT)] = w->out_w[(size_t)j * 500 + k]; hhp_split_put_t(Hh, Hl, h_wa, k, j, HHP_OUT, w->out_w[(size_t)j * 500 + k]); }
-        B[o_ba + j] = w->out_b[j];
-    }
-    { /* the same four matrices as ONE linear stream of 1 KB fragments in consumption order (hh_policy_kernel_w16.h) */
-        auto w1 = [&](int k, int col) { return k < HHP_XK ? B[o_w1 + hhp_pidx(k, col, HHP_H)] : 0.0f; };
-        auto wov = [&](int k, int col) { return (att && k < 100 && col < 100) ? B[o_wov + hhp_pidx(k, col, HHP_ATT_J)] : 0.0f; };
-        auto wsf = [&](int k, int col) { return (k < 500 && col < 500) ? w->shared_w[(size_t)col * 500 + k] : 0.0f; };
-        auto waf = [&](int k, int col) { return (k < 500 && col < n_out) ? w->out_w[(size_t)col * 500 + k] : 0.0f; };
-        /* the fragment shape of hh_k_policy_w16 (16 columns x 32 k per piece; chunk order of hh_policy_kernel_w16.h) */
-        std::vector<uint16_t> X((size_t)HHX_STREAM_PIECES * (HHW_PIECE / 2), 0);
-        for (int T = 0; T < 32; T++)
-            for (int k = 0; k < 32; k++)
-                for (int c = 0; c < 16; c++) hhx_put(X, (size_t)T * 2, k, 16 * T + c, true, w1(k, 16 * T + c));
-        for (int j = 0; j < 7; j++)
-            for (int kb = 0; kb < 4; kb++)
-                for (int wq = 0; wq < 32; wq++)
-                    for (int c = 0; c < 16; c++) { /* K = hidden columns 384 + 32 kb + wq; the block's own index is that - 400 */
-                        const int kh = 384 + 32 * kb + wq - 400;
-                        hhx_put(X, (size_t)HHX_L1_PIECES + (size_t)(j * 4 + kb) * 2, wq, 16 * j + c, false, kh >= 0 ? wov(kh, 16 * j + c) : 0.0f);
-                    }
-        for (int pp = 0; pp < 8; pp++)
-            for (int q = 0; q < 4; q++)
-                for (int kk = 0; kk < 4; kk++)
-                    for (int t = 0; t < 4; t++)
-                        for (int wq = 0; wq < 32; wq++)
-                            for (int c = 0; c < 16; c++)
-                                hhx_put(X, (size_t)HHX_L1_PIECES + HHX_ATT_PIECES + (size_t)((pp * 4 + q) * 16 + kk * 4 + t) * 2, wq, c, false,
-                                        wsf(32 * (4 * q + kk) + wq, 16 * (4 * pp + t) + c));
-        for (int kb = 0; kb < 16; kb++)
-            for (int t = 0; t < 2; t++)
-                for (int wq = 0; wq < 32; wq++)
-                    for (int c = 0; c < 16; c++)
-                        hhx_put(X, (size_t)HHX_L1_PIECES + HHX_ATT_PIECES + HHX_L2_PIECES + (size_t)(kb * 2 + t) * 2, wq, c, false, waf(32 * kb + wq, 16 * t + c));
-        if (!p->xblob[slot]) HIPCHK(hipMalloc(&p->xblob[slot], (size_t)HHX_STREAM_PIECES * HHW_PIECE));
-        HIPCHK(hipMemcpy(p->xblob[slot], X.data(), (size_t)HHX_STREAM_PIECES * HHW_PIECE, hipMemcpyHostToDevice));
-        p->bankx.stream[slot] = p->xblob[slot];
-    }
-    static_assert(HHP_SLOT_BYTES >= (size_t)2 * 1024 * 1024 + 2 * 309248 * 2, "slot too small");
-    if (total * sizeof(float) > (size_t)2 * 1024 * 1024 || 2 * h_total * sizeof(uint16_t) > HHP_SLOT_BYTES - (size_t)2 * 1024 * 1024) { g_err = "internal: blob exceeds its slot"; return HH_E_ARG; }
-    p->blob[slot] = reinterpret_cast<float *>(p->slab + (size_t)slot * HHP_SLOT_BYTES);                                   /* first 2 MB of the slot */
-    p->blobh[slot] = reinterpret_cast<uint16_t *>(p->slab + (size_t)slot * HHP_SLOT_BYTES + (size_t)2 * 1024 * 1024);      /* second 2 MB */
-    HIPCHK(hipMemcpy(p->blob[slot], B.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->blobh[slot], Hh.data(), h_total * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->blobh[slot] + h_total, Hl.data(), h_total * sizeof(uint16_t), hipMemcpyHostToDevice));
-    {
-        HhpNetH &Hn = p->bankh.net[slot];
-        const uint16_t *bh = p->blobh[slot], *bl = p->blobh[slot] + h_total;
-        Hn.w1h = reinterpret_cast<const float4 *>(bh + h_w1); Hn.w1l = reinterpret_cast<const float4 *>(bl + h_w1);
-        Hn.wovh = reinterpret_cast<const float4 *>(bh + h_wov); Hn.wovl = reinterpret_cast<const float4 *>(bl + h_wov);
-        Hn.wsh = reinterpret_cast<const float4 *>(bh + h_ws); Hn.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
-        Hn.wah = reinterpret_cast<const float4 *>(bh + h_wa); Hn.wal = reinterpret_cast<const float4 *>(bl + h_wa);
-    }
-    HhpNet &N = p->bank.net[slot];
-    float *b = p->blob[slot];
-    N.w1p = b + o_w1; N.b1 = b + o_b1; N.wovp = b + o_wov; N.bov = b + o_bov; N.wsp = b + o_ws; N.bs = b + o_bs; N.wap = b + o_wa; N.ba = b + o_ba;
-    N.kind = w->kind; N.n_out = n_out; N.obs_dim = obs_dim; N.has_att = att ? 1 : 0;
-    if (slot + 1 > p->n_nets) p->n_nets = slot + 1;
-    return HH_OK;
-}
-
 extern "C" int hh_policy_set_lut(hh_policy *p, const uint8_t *lut) {
     if (!p || !lut) { g_err = "null argument"; return HH_E_ARG; }
     for (int i = 0; i < 256; i++) if (lut[i] > HH_POLICY_MAX_NETS || (lut[i] && !p->blob[lut[i] - 1])) { g_err = "hh_policy_set_lut: selector maps to an empty slot"; return HH_E_ARG; }
@@ -530,135 +405,6 @@ static const int HHC_DIMS[4][4] = {
 /* hidden column of the reference's concatenation cat(v1, v2, y3) (ac_models_hetero.py:274-281) in the kernel's order y3 | pad | v1 | v2
  * (escape nets: the identity) */
 __host__ __device__ inline int hhc_hcol(bool att, int c) { return att ? (c < 350 ? HHC_V12_OFF + c : HHC_V3_OFF + (c - 350)) : c; }
-static int hhp_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w);
-extern "C" int hh_policy_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w) {
-    try {
-        return hhp_set_critic(p, slot, w);
-    } catch (const std::exception &e) {
-        g_err = std::string("hh_policy_set_critic: ") + e.what();
-        return HH_E_HIP;
-    }
-}
-static int hhp_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w) {
-    if (!p || !w || slot < 0 || slot >= HH_POLICY_MAX_NETS || w->kind < 0 || w->kind > 3) { g_err = "bad argument"; return HH_E_ARG; }
-    if (!p->blob[slot] || p->bank.net[slot].kind != w->kind) { g_err = "hh_policy_set_critic: load the actor of the same kind into this slot first (hh_policy_set_net)"; return HH_E_ARG; }
-    const bool att = w->kind <= HH_NET_FIGHT2;
-    if (!w->v_w[0] || !w->v_b[0] || !w->shared_w || !w->shared_b || !w->val_w || !w->val_b ||
-        (att && (!w->v_w[1] || !w->v_b[1] || !w->v_w[2] || !w->v_b[2] || !w->att_in_proj_w || !w->att_in_proj_b || !w->att_out_w || !w->att_out_b))) {
-        g_err = "hh_policy_set_critic: missing weight pointer"; return HH_E_ARG;
-    }
-    HH_GUARD(p);
-    const int d1 = HHC_DIMS[w->kind][0], a1 = HHC_DIMS[w->kind][1], d2 = HHC_DIMS[w->kind][2], a2 = HHC_DIMS[w->kind][3];
-    const int n_in = d1 + a1 + d2 + a2; /* 57 | 66 */
-    /* fragment planes (halves): w1 [80 x 512] | wov [160 x 256] | ws [512 x 512] | wa [512 x 32]; then the float biases b1 | bs | bov | ba */
-    const size_t h_w1 = 0, h_wov = h_w1 + (size_t)(HHC_XK / 16) * 2 * HHP_H * 8, h_ws = h_wov + (size_t)(HHC_ATT_W / 16) * 2 * HHC_ATT_J * 8,
-                 h_wa = h_ws + (size_t)32 * 2 * HHP_H * 8, h_total = h_wa + (size_t)32 * 2 * HHP_OUT * 8;
-    std::vector<uint16_t> Hh(h_total, 0), Hl(h_total, 0);
-    const size_t o_b1 = 0, o_bs = 512, o_bov = 1024, o_ba = 1024 + HHC_ATT_W, n_bias = o_ba + HHP_OUT;
-    std::vector<float> Bf(n_bias, 0.0f);
-    auto hcol = [att](int c) { return hhc_hcol(att, c); };
-    if (att) {
-        const int in0[3] = {0, d1 + a1, 0}, in1[3] = {d1 + a1, n_in, n_in}, wd[3] = {175, 175, 150}, out0[3] = {0, 175, 350};
-        for (int b = 0; b < 3; b++)
-            for (int o = 0; o < wd[b]; o++) {
-                for (int c = in0[b]; c < in1[b]; c++) hhp_split_put(Hh, Hl, h_w1, c, hcol(out0[b] + o), HHP_H, w->v_w[b][(size_t)o * (in1[b] - in0[b]) + (c - in0[b])]);
-                Bf[o_b1 + hcol(out0[b] + o)] = w->v_b[b][o];
-            }
-        /* att_val over one key: out_proj(v_proj(t)), folded in double like the actor's */
-        const float *wv = w->att_in_proj_w + (size_t)300 * 150, *bv = w->att_in_proj_b + 300;
-        for (int j = 0; j < 150; j++) {
-            for (int k = 0; k < 150; k++) {
-                double s = 0.0;
-                for (int m = 0; m < 150; m++) s += (double)w->att_out_w[(size_t)j * 150 + m] * (double)wv[(size_t)m * 150 + k];
-                hhp_split_put(Hh, Hl, h_wov, k, j, HHC_ATT_J, (float)s);
-            }
-            double s = (double)w->att_out_b[j];
-            for (int m = 0; m < 150; m++) s += (double)w->att_out_w[(size_t)j * 150 + m] * (double)bv[m];
-            Bf[o_bov + j] = (float)s;
-        }
-    } else {
-        for (int o = 0; o < 500; o++) {
-            for (int c = 0; c < n_in; c++) hhp_split_put(Hh, Hl, h_w1, c, o, HHP_H, w->v_w[0][(size_t)o * n_in + c]);
-            Bf[o_b1 + o] = w->v_b[0][o];
-        }
-    }
-    for (int j = 0; j < 500; j++) {
-        for (int k = 0; k < 500; k++) hhp_split_put(Hh, Hl, h_ws, hcol(k), j, HHP_H, w->shared_w[(size_t)j * 500 + k]);
-        Bf[o_bs + j] = w->shared_b[j];
-    }
-    for (int k = 0; k < 500; k++) hhp_split_put_t(Hh, Hl, h_wa, k, 0, HHP_OUT, w->val_w[k]);
-    Bf[o_ba] = w->val_b[0];
-    { /* the same value branch as ONE linear stream of 1 KB fragments for hh_k_policy_w16_ppo (chunk order of hhx_critic_tile) + its biases */
-        std::vector<float> W1d((size_t)96 * 512, 0.0f), Wovd((size_t)160 * 160, 0.0f), Wsd((size_t)512 * 512, 0.0f);
-        if (att) {
-            const int in0[3] = {0, d1 + a1, 0}, in1[3] = {d1 + a1, n_in, n_in}, wd[3] = {175, 175, 150}, out0[3] = {0, 175, 350};
-            for (int b = 0; b < 3; b++)
-                for (int o = 0; o < wd[b]; o++)
-                    for (int c = in0[b]; c < in1[b]; c++) W1d[(size_t)c * 512 + hcol(out0[b] + o)] = w->v_w[b][(size_t)o * (in1[b] - in0[b]) + (c - in0[b])];
-            const float *wv = w->att_in_proj_w + (size_t)300 * 150;
-            for (int j = 0; j < 150; j++)
-                for (int k = 0; k < 150; k++) {
-                    double sacc = 0.0;
-                    for (int m = 0; m < 150; m++) sacc += (double)w->att_out_w[(size_t)j * 150 + m] * (double)wv[(size_t)m * 150 + k];
-                    Wovd[(size_t)k * 160 + j] = (float)sacc;
-                }
-        } else {
-            for (int o = 0; o < 500; o++)
-                for (int c = 0; c < n_in; c++) W1d[(size_t)c * 512 + o] = w->v_w[0][(size_t)o * n_in + c];
-        }
-        for (int j = 0; j < 500; j++)
-            for (int k = 0; k < 500; k++) Wsd[(size_t)hcol(k) * 512 + j] = w->shared_w[(size_t)j * 500 + k];
-        std::vector<uint16_t> X((size_t)HHXC_STREAM_PIECES * (HHW_PIECE / 2), 0);
-        for (int T = 0; T < 32; T++) /* chunk c = T / 4: tile (T & 3), k-block kb: hi, lo */
-            for (int kb = 0; kb < 3; kb++)
-                for (int wq = 0; wq < 32; wq++)
-                    for (int c = 0; c < 16; c++) hhx_put(X, (size_t)(T * 3 + kb) * 2, wq, c, true, W1d[(size_t)(32 * kb + wq) * 512 + 16 * T + c]);
-        for (int j = 0; j < 10; j++)
-            for (int kb = 0; kb < 5; kb++)
-                for (int wq = 0; wq < 32; wq++)
-                    for (int c = 0; c < 16; c++) hhx_put(X, (size_t)HHXC_L1_PIECES + (size_t)(j * 5 + kb) * 2, wq, c, false, Wovd[(size_t)(32 * kb + wq) * 160 + 16 * j + c]);
-        for (int pp = 0; pp < 8; pp++)
-            for (int q = 0; q < 4; q++)
-                for (int kk = 0; kk < 4; kk++)
-                    for (int t = 0; t < 4; t++)
-                        for (int wq = 0; wq < 32; wq++)
-                            for (int c = 0; c < 16; c++)
-                                hhx_put(X, (size_t)HHXC_L1_PIECES + HHXC_ATT_PIECES + (size_t)((pp * 4 + q) * 16 + kk * 4 + t) * 2, wq, c, false,
-                                        Wsd[(size_t)(32 * (4 * q + kk) + wq) * 512 + 16 * (4 * pp + t) + c]);
-        for (int kb = 0; kb < 16; kb++)
-            for (int wq = 0; wq < 32; wq++) { const int k = 32 * kb + wq; hhx_put(X, (size_t)HHXC_L1_PIECES + HHXC_ATT_PIECES + HHX_L2_PIECES + (size_t)kb * 2, wq, 0, false, k < 500 ? w->val_w[k] : 0.0f); }
-        const size_t xbytes = (size_t)HHXC_STREAM_PIECES * HHW_PIECE, xbias = (size_t)(512 + 512 + 160 + 32) * sizeof(float);
-        if (!p->cxblob[slot]) HIPCHK(hipMalloc(&p->cxblob[slot], xbytes + xbias));
-        HIPCHK(hipMemcpy(p->cxblob[slot], X.data(), xbytes, hipMemcpyHostToDevice));
-        std::vector<float> Xb(512 + 512 + 160 + 32, 0.0f);
-        for (int i = 0; i < 512; i++) { Xb[i] = Bf[o_b1 + i]; Xb[512 + i] = Bf[o_bs + i]; }
-        for (int i = 0; i < 160; i++) Xb[1024 + i] = Bf[o_bov + i];
-        Xb[1184] = Bf[o_ba];
-        HIPCHK(hipMemcpy(p->cxblob[slot] + xbytes, Xb.data(), xbias, hipMemcpyHostToDevice));
-        HhpCritX &Cx = p->cbankx.c[slot];
-        const float *xb = reinterpret_cast<const float *>(p->cxblob[slot] + xbytes);
-        Cx.stream = reinterpret_cast<const unsigned char *>(p->cxblob[slot]);
-        Cx.b1 = xb; Cx.bs = xb + 512; Cx.bov = xb + 1024; Cx.ba = xb + 1184;
-        Cx.d1 = d1; Cx.a1 = a1; Cx.d2 = d2; Cx.a2 = a2; Cx.has_att = att ? 1 : 0; Cx.loaded = 1;
-    }
-    const size_t plane_bytes = h_total * sizeof(uint16_t), bytes = 2 * plane_bytes + n_bias * sizeof(float);
-    if (!p->cblob[slot]) HIPCHK(hipMalloc(&p->cblob[slot], bytes));
-    char *d = p->cblob[slot];
-    HIPCHK(hipMemcpy(d, Hh.data(), plane_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + plane_bytes, Hl.data(), plane_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 2 * plane_bytes, Bf.data(), n_bias * sizeof(float), hipMemcpyHostToDevice));
-    HhpCrit &Cn = p->cbank.c[slot];
-    const uint16_t *bh = reinterpret_cast<const uint16_t *>(d), *bl = reinterpret_cast<const uint16_t *>(d + plane_bytes);
-    const float *bf = reinterpret_cast<const float *>(d + 2 * plane_bytes);
-    Cn.w1h = reinterpret_cast<const float4 *>(bh + h_w1); Cn.w1l = reinterpret_cast<const float4 *>(bl + h_w1);
-    Cn.wovh = reinterpret_cast<const float4 *>(bh + h_wov); Cn.wovl = reinterpret_cast<const float4 *>(bl + h_wov);
-    Cn.wsh = reinterpret_cast<const float4 *>(bh + h_ws); Cn.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
-    Cn.wah = reinterpret_cast<const float4 *>(bh + h_wa); Cn.wal = reinterpret_cast<const float4 *>(bl + h_wa);
-    Cn.b1 = bf + o_b1; Cn.bs = bf + o_bs; Cn.bov = bf + o_bov; Cn.ba = bf + o_ba;
-    Cn.d1 = d1; Cn.a1 = a1; Cn.d2 = d2; Cn.a2 = a2; Cn.has_att = att ? 1 : 0; Cn.loaded = 1;
-    return HH_OK;
-}
-
 extern "C" int hh_policy_sample(hh_policy *p, const float *obs, int32_t n_rows, int32_t obs_stride, const uint8_t *sel, hh_world *w,
                                 const double *uniforms, const float *crit_act, int32_t greedy, int8_t *actions, float *logp, float *vf, float *logits,
                                 void *stream) {

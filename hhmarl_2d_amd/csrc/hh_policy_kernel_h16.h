@@ -520,8 +520,8 @@ __global__ __launch_bounds__(256 * RH, RH == 1 ? 2 : 1) void hh_k_policy_h(HhpBa
     hhp_consume_counts(counts, consume);
 }
 
-/* ---- fp32 -> (hi, lo) fp16, round to nearest even, subnormals kept.  Software rounding on both sides: the host repack (hhp_set_net ...)
- * and the device refresh (hh_weight_refresh.h) produce the same halves by construction ---- */
+/* ---- fp32 -> (hi, lo) fp16, round to nearest even, subnormals kept.  Software rounding: the halves the packer (hh_weight_refresh.h)
+ * writes do not depend on the hardware's conversion modes ---- */
 __host__ __device__ static inline uint16_t hhp_f2h(float f) {
     uint32_t x;
     memcpy(&x, &f, 4);
@@ -553,17 +553,4 @@ __host__ __device__ static inline float hhp_h2f(uint16_t h) {
     memcpy(&v, &b, 4);
     return v;
 }
-/* element (k, col) of the fp32 operand M[k][col] (K x J, zero padded) -> the two fragment planes */
-static inline void hhp_split_put(std::vector<uint16_t> &hi, std::vector<uint16_t> &lo, size_t off, int k, int col, int J, float v) {
-    const uint16_t h = hhp_f2h(v);
-    hi[off + hhp_hidx(k, col, J)] = h;
-    lo[off + hhp_hidx(k, col, J)] = hhp_f2h(v - hhp_h2f(h));
-}
-/* the same in the k order of hhp_hidx_t (the output layer, contracted with the shared layer's C tile in registers) */
-static inline void hhp_split_put_t(std::vector<uint16_t> &hi, std::vector<uint16_t> &lo, size_t off, int k, int col, int J, float v) {
-    const uint16_t h = hhp_f2h(v);
-    hi[off + hhp_hidx_t(k, col, J)] = h;
-    lo[off + hhp_hidx_t(k, col, J)] = hhp_f2h(v - hhp_h2f(h));
-}
-
 #endif /* HH_POLICY_KERNEL_H16_H */

@@ -732,20 +732,13 @@ __global__ __launch_bounds__(256, 2) void hh_k_policy_w16_ppo(HhpBank bank, HhpB
     hhp_consume_counts(counts, consume);
 }
 
-/* host: element (k, col) of a [K x J] operand into piece `piece_hi` (16 columns x 32 k; the lo plane is the next piece): natural k order
- * (nat: k group = (k & 31) >> 3, e = k & 7) or hhw16_korder */
-__host__ __device__ inline size_t hhx_at(int k, int col, bool nat) { /* halves into the piece */
+/* where element (k, col) of a [K x J] operand sits in its fragment piece (16 columns x 32 k), in halves: natural k order (nat: k group =
+ * (k & 31) >> 3, e = k & 7) or hhw16_korder.  The packer (hh_weight_refresh.h) writes the hi half there and the lo half in the next piece */
+__host__ __device__ inline size_t hhx_at(int k, int col, bool nat) {
     int kg, e;
     if (nat) { kg = (k & 31) >> 3; e = k & 7; }
     else hhw16_korder(k & 31, kg, e);
     return (size_t)((kg * 16 + (col & 15)) * 8 + e);
 }
-static inline void hhx_put(std::vector<uint16_t> &S, size_t piece_hi, int k, int col, bool nat, float v) {
-    const size_t at = hhx_at(k, col, nat);
-    const uint16_t h = hhp_f2h(v);
-    S[piece_hi * (HHW_PIECE / 2) + at] = h;
-    S[(piece_hi + 1) * (HHW_PIECE / 2) + at] = hhp_f2h(v - hhp_h2f(h));
-}
-
 
 #endif /* HH_POLICY_KERNEL_W16_H */

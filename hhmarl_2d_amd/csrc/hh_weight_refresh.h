@@ -1,16 +1,21 @@
 /*
- * hh_weight_refresh.h — the learner's new weights into the samplers on the device (C ABI: hh_policy_refresh / hh_policy_copy_packed in
- * include/hh_policy.h, hh_commander_refresh_weights / hh_commander_copy_packed in include/hh_commander.h).
+ * hh_weight_refresh.h — THE packer of the samplers' weights: the only place where a weight element's packed destinations are computed
+ * (C ABI: hh_policy_set_net / hh_policy_set_critic / hh_policy_refresh / hh_policy_copy_packed in include/hh_policy.h,
+ * hh_commander_set_weights / hh_commander_refresh_weights / hh_commander_copy_packed in include/hh_commander.h).
  *
- * hh_policy_set_net / hh_policy_set_critic / hh_commander_set_weights repack fp32 HOST arrays on the CPU and upload them with synchronous
- * copies.  The kernels here read the learner's fp32 DEVICE tensors (the reference's state_dict layout) and write, in place and ordered on
- * the caller's stream, the same bytes into the same buffers: the fp32 blob, the (hi, lo) fp16 fragment planes, the 1 KB fragment streams
- * and, for Fight1 / Fight2, the folded attention (Wov = Wo Wv, bov = Wo bv + bo in fp64, m = 0, 1, ... in order, multiply and add
- * rounded separately like the host's loop).  One thread per SOURCE element (and one per bias row): it computes the destination of every
- * packed form the element feeds through the index maps the host loops use (hhp_pidx, hhp_hidx, hhp_hidx_t, hhx_at / hhw16_korder) and
- * splits with the host's own hhp_f2h / hhp_h2f.  The sections' addresses are the bank's own (HhpNet, HhpNetH, HhpBankX, HhpCrit,
- * HhpCritX, HhcNet), i.e. exactly where the forward kernels read.  Padding is never written: the host load zeroed it and a refresh keeps
- * the kind, hence the layout.  No allocation, no host synchronisation, no scratch: a refresh can be captured into a HIP graph.
+ * The kernels here read fp32 DEVICE tensors (the reference's state_dict layout) and write, in place and ordered on the caller's stream,
+ * every packed form the forward kernels read: the fp32 blob, the (hi, lo) fp16 fragment planes, the 1 KB fragment streams and, for
+ * Fight1 / Fight2, the folded attention (Wov = Wo Wv, bov = Wo bv + bo in fp64, m = 0, 1, ... in order, multiply and add rounded
+ * separately).  One thread per SOURCE element (and one per bias row): it computes the destination of every packed form the element
+ * feeds through the index maps the forward kernels read by (hhp_pidx, hhp_hidx, hhp_hidx_t, hhx_at / hhw16_korder) and splits with
+ * hhp_f2h / hhp_h2f.  The sections' addresses are the bank's own (HhpNet, HhpNetH, HhpBankX, HhpCrit, HhpCritX, HhcNet), i.e. exactly
+ * where the forward kernels read.  Padding is never written.
+ *
+ * Both ways in run these kernels.  A REFRESH (hh_policy_refresh, hh_commander_refresh_weights: the learner's device tensors into a
+ * loaded slot) is the launch alone — no allocation, no memset, no host synchronisation, no scratch: capturable into a HIP graph; the
+ * kind, hence the layout and the zero padding, stays.  A LOAD (the set_* calls: host arrays, possibly another kind than the slot held)
+ * lays the sections out and allocates what is missing, stages the host arrays in one temporary device buffer (HhrStage), zeroes the
+ * whole destination, launches the same kernel on the default stream and waits for it.
  */
 #ifndef HH_WEIGHT_REFRESH_H
 #define HH_WEIGHT_REFRESH_H
@@ -22,11 +27,11 @@ __device__ __forceinline__ void hhr_split(uint16_t *hi, uint16_t *lo, size_t at,
     hi[at] = h;
     lo[at] = hhp_f2h(v - hhp_h2f(h));
 }
-/* hhx_put on the device: element (k, col) into fragment piece `piece_hi` of a stream (its lo half is the next piece) */
+/* element (k, col) into fragment piece `piece_hi` of a stream (its lo half is the next piece) */
 __device__ __forceinline__ void hhr_xput(uint16_t *S, size_t piece_hi, int k, int col, bool nat, float v) {
     hhr_split(S + piece_hi * (HHW_PIECE / 2), S + (piece_hi + 1) * (HHW_PIECE / 2), hhx_at(k, col, nat), v);
 }
-/* the host's attention fold: s = 0; s += Wo[j][m] Wv[m][k] for m = 0 .. n - 1 in fp64 (the bias: s = bo[j]; s += Wo[j][m] bv[m]) */
+/* the attention fold: s = 0; s += Wo[j][m] Wv[m][k] for m = 0 .. n - 1 in fp64 (the bias: s = bo[j]; s += Wo[j][m] bv[m]) */
 __device__ __forceinline__ float hhr_fold(const float *wo, const float *wv, int j, int k, int n) {
     double s = 0.0;
     for (int m = 0; m < n; m++) s = __dadd_rn(s, __dmul_rn((double)wo[(size_t)j * n + m], (double)wv[(size_t)m * n + k]));
@@ -38,7 +43,7 @@ __device__ __forceinline__ float hhr_fold_bias(const float *wo, const float *bo,
     return (float)s;
 }
 
-/* ---- actor: hhp_set_net's four forms.  Sections (flat thread index, cumulative ends): inp1..inp3 as [wd][nc + 1] (column nc = the
+/* ---- actor: the four forms (blob, planes, stream, folded attention).  Sections (flat thread index, cumulative ends): inp1..inp3 as [wd][nc + 1] (column nc = the
  * bias), shared_layer [500][501], act_out [n_out][501], the attention fold [100][101] (fight nets; column 100 = bov) */
 struct HhrActorArgs {
     hh_net_weights w;                                                   /* [dev] sources */
@@ -88,7 +93,7 @@ __global__ __launch_bounds__(HHR_THREADS) void hh_k_refresh_actor(HhrActorArgs a
     }
 }
 
-/* ---- value branch: hhp_set_critic's planes + biases and its hh_k_policy_w16_ppo stream (with the branch's own copy of the shared layer).
+/* ---- value branch: the planes + biases of hh_k_policy_ppo and the hh_k_policy_w16_ppo stream (with the branch's own copy of the shared layer).
  * Sections: the input FCs as [wd][nin + 1] (three for fight nets, one for escape nets; column nin = the bias), shared_layer [500][501],
  * val_out [501], the att_val fold [150][151] (fight nets) */
 struct HhrCriticArgs {
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(HHR_THREADS) void hh_k_refresh_critic(HhrCriticArgs
     }
 }
 
-/* ---- commander: hhc_set_weights' planes and fp32 section.  Sections: the eight first-layer blocks (actor inp1..inp4, critic v1..v4) as
+/* ---- commander: the planes and the fp32 section.  Sections: the eight first-layer blocks (actor inp1..inp4, critic v1..v4) as
  * [wd][nc + 1], the two GRUs as [200][201] (column 200: the gate biases), shared_layer [500][501] (column 500: its bias and the output
  * layers' column o) */
 struct HhrCommanderArgs {
@@ -210,6 +215,198 @@ static bool hhr_critic_complete(const hh_critic_weights *w, bool att) {
 }
 static uint16_t *hhr_h16(const float4 *q) { return reinterpret_cast<uint16_t *>(const_cast<float4 *>(q)); }
 
+/* A load's sources: `at` = a pointer member of the load's own copy of the weights struct, holding the caller's HOST array of n floats.
+ * upload() copies them back to back into ONE temporary device buffer and rewrites every member to its device copy, which turns the
+ * struct into what the kernels take.  The buffer goes with the HhrStage, i.e. after the load has waited for its kernel. */
+struct HhrSrc { const float **at; size_t n; };
+struct HhrStage {
+    float *buf = nullptr;
+    ~HhrStage() { if (buf) (void)hipFree(buf); }
+    hipError_t upload(const HhrSrc *src, int n_src) {
+        size_t total = 0;
+        for (int i = 0; i < n_src; i++) total += (src[i].n + 3) & ~(size_t)3; /* every array 16-byte aligned */
+        hipError_t e = hipMalloc(&buf, total * sizeof(float));
+        float *d = buf;
+        for (int i = 0; i < n_src && e == hipSuccess; i++) {
+            e = hipMemcpy(d, *src[i].at, src[i].n * sizeof(float), hipMemcpyHostToDevice);
+            *src[i].at = d;
+            d += (src[i].n + 3) & ~(size_t)3;
+        }
+        return e;
+    }
+};
+/* the end of a load: its kernel has run when the call returns, so the caller's arrays are free and a launch on any stream sees the weights */
+static int hhr_finish_load() {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return HH_OK;
+}
+
+/* the actor of a laid-out slot from [dev] sources: one launch on st */
+static void hhr_launch_actor(hh_policy *p, int slot, const hh_net_weights &w, hipStream_t st) {
+    const HhpNet &N = p->bank.net[slot];
+    HhrActorArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w = w;
+    a.B_w1 = const_cast<float *>(N.w1p); a.B_b1 = const_cast<float *>(N.b1); a.B_wov = const_cast<float *>(N.wovp); a.B_bov = const_cast<float *>(N.bov);
+    a.B_ws = const_cast<float *>(N.wsp); a.B_bs = const_cast<float *>(N.bs); a.B_wa = const_cast<float *>(N.wap); a.B_ba = const_cast<float *>(N.ba);
+    const HhpNetH &H = p->bankh.net[slot];
+    a.h_w1 = hhr_h16(H.w1h); a.l_w1 = hhr_h16(H.w1l); a.h_wov = hhr_h16(H.wovh); a.l_wov = hhr_h16(H.wovl);
+    a.h_ws = hhr_h16(H.wsh); a.l_ws = hhr_h16(H.wsl); a.h_wa = hhr_h16(H.wah); a.l_wa = hhr_h16(H.wal);
+    a.X = reinterpret_cast<uint16_t *>(p->xblob[slot]);
+    int e = 0;
+    for (int k = 0; k < 3; k++) {
+        a.c0[k] = HHP_INPUTS[N.kind][k][0]; a.nc[k] = HHP_INPUTS[N.kind][k][1] - a.c0[k]; a.wd[k] = HHP_INPUTS[N.kind][k][2];
+        a.end[k] = e += a.wd[k] * (a.nc[k] + 1);
+    }
+    a.end[3] = e += 500 * 501;
+    a.end[4] = e += N.n_out * 501;
+    a.end[5] = e += N.has_att ? 100 * 101 : 0;
+    hipLaunchKernelGGL(hh_k_refresh_actor, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, st, a);
+}
+
+/* the value branch's input FCs -> their number.  Fight nets: v1 [own obs | own act], v2 [other obs | other act], v3 [all] at columns 0,
+ * 175, 350 of cat(v1, v2, y3); escape nets: inp1_val [all] -> 500 */
+static int hhr_critic_blocks(int kind, int in0[3], int nin[3], int wd[3], int out0[3]) {
+    const int own = HHC_DIMS[kind][0] + HHC_DIMS[kind][1], n_in = own + HHC_DIMS[kind][2] + HHC_DIMS[kind][3];
+    if (kind > HH_NET_FIGHT2) { in0[0] = 0; nin[0] = n_in; wd[0] = 500; out0[0] = 0; return 1; }
+    in0[0] = 0; nin[0] = own; wd[0] = 175; out0[0] = 0;
+    in0[1] = own; nin[1] = n_in - own; wd[1] = 175; out0[1] = 175;
+    in0[2] = 0; nin[2] = n_in; wd[2] = 150; out0[2] = 350;
+    return 3;
+}
+/* the value branch of a laid-out slot from [dev] sources: one launch on st */
+static void hhr_launch_critic(hh_policy *p, int slot, const hh_critic_weights &w, hipStream_t st) {
+    const HhpCrit &Cn = p->cbank.c[slot];
+    const HhpCritX &Cx = p->cbankx.c[slot];
+    HhrCriticArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w = w;
+    a.h_w1 = hhr_h16(Cn.w1h); a.l_w1 = hhr_h16(Cn.w1l); a.h_wov = hhr_h16(Cn.wovh); a.l_wov = hhr_h16(Cn.wovl);
+    a.h_ws = hhr_h16(Cn.wsh); a.l_ws = hhr_h16(Cn.wsl); a.h_wa = hhr_h16(Cn.wah); a.l_wa = hhr_h16(Cn.wal);
+    a.b1 = const_cast<float *>(Cn.b1); a.bs = const_cast<float *>(Cn.bs); a.bov = const_cast<float *>(Cn.bov); a.ba = const_cast<float *>(Cn.ba);
+    a.xb1 = const_cast<float *>(Cx.b1); a.xbs = const_cast<float *>(Cx.bs); a.xbov = const_cast<float *>(Cx.bov); a.xba = const_cast<float *>(Cx.ba);
+    a.X = reinterpret_cast<uint16_t *>(p->cxblob[slot]);
+    a.att = Cn.has_att;
+    int wd[3], e = 0;
+    const int nb = hhr_critic_blocks(p->bank.net[slot].kind, a.in0, a.nin, wd, a.out0);
+    for (int b = 0; b < 3; b++) a.end[b] = e += b < nb ? wd[b] * (a.nin[b] + 1) : 0;
+    a.end[3] = e += 500 * 501;
+    a.end[4] = e += 501;
+    a.end[5] = e += a.att ? 150 * 151 : 0;
+    hipLaunchKernelGGL(hh_k_refresh_critic, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, st, a);
+}
+
+extern "C" int hh_policy_set_net(hh_policy *p, int32_t slot, const hh_net_weights *w) {
+    if (!p || !w || slot < 0 || slot >= HH_POLICY_MAX_NETS || w->kind < 0 || w->kind > 3) { g_err = "bad argument"; return HH_E_ARG; }
+    const bool att = w->kind <= HH_NET_FIGHT2;
+    if (!w->shared_w || !w->shared_b || !w->out_w || !w->out_b || (att && (!w->att_in_proj_w || !w->att_in_proj_b || !w->att_out_w || !w->att_out_b))) {
+        g_err = "hh_policy_set_net: missing weight pointer"; return HH_E_ARG;
+    }
+    for (int k = 0; k < 3; k++) if (!w->inp_w[k] || !w->inp_b[k]) { g_err = "hh_policy_set_net: missing input layer"; return HH_E_ARG; }
+    HH_GUARD(p);
+    const int n_out = (w->kind == HH_NET_FIGHT1 || w->kind == HH_NET_ESC1) ? 26 : 24;
+    hh_net_weights d = *w;
+    if (!att) d.att_in_proj_w = d.att_in_proj_b = d.att_out_w = d.att_out_b = nullptr;
+    HhrSrc src[14];
+    int n = 0, obs_dim = 0;
+    for (int k = 0; k < 3; k++) {
+        const int c0 = HHP_INPUTS[w->kind][k][0], c1 = HHP_INPUTS[w->kind][k][1], wd = HHP_INPUTS[w->kind][k][2];
+        src[n++] = {&d.inp_w[k], (size_t)wd * (c1 - c0)}; src[n++] = {&d.inp_b[k], (size_t)wd};
+        if (c1 > obs_dim) obs_dim = c1;
+    }
+    if (att) { src[n++] = {&d.att_in_proj_w, 300 * 100}; src[n++] = {&d.att_in_proj_b, 300}; src[n++] = {&d.att_out_w, 100 * 100}; src[n++] = {&d.att_out_b, 100}; }
+    src[n++] = {&d.shared_w, 500 * 500}; src[n++] = {&d.shared_b, 500}; src[n++] = {&d.out_w, (size_t)n_out * 500}; src[n++] = {&d.out_b, (size_t)n_out};
+    HhrStage stage;
+    HIPCHK(stage.upload(src, n));
+    /* the slot's value branch holds its own permuted copy of the shared layer and the input widths of the kind it was loaded for: a new
+     * actor makes both stale.  hh_policy_sample refuses vf for the slot until hh_policy_set_critic is called again (set_net + set_critic
+     * are a pair; the old copy stays allocated and is simply never read) */
+    p->cbank.c[slot].loaded = 0;
+    p->cbankx.c[slot].loaded = 0;
+    /* blob: w1p | b1 | wovp | bov | wsp | bs | wap | ba   (float counts; every section 16-byte aligned) */
+    const size_t n_w1 = 4 * 2 * HHP_H * 4, n_wov = 13 * 2 * HHP_ATT_J * 4, n_ws = 64 * 2 * HHP_H * 4, n_wa = 64 * 2 * HHP_OUT * 4;
+    const size_t o_w1 = 0, o_b1 = o_w1 + n_w1, o_wov = o_b1 + HHP_H, o_bov = o_wov + n_wov, o_ws = o_bov + HHP_ATT_J, o_bs = o_ws + n_ws,
+                 o_wa = o_bs + HHP_H, o_ba = o_wa + n_wa, total = o_ba + HHP_OUT;
+    /* the same four matrices as (hi, lo) fp16 fragment planes for hh_k_policy_h: w1 | wov | ws | wa, each [K/16][2][J][8] */
+    const size_t h_w1 = 0, h_wov = h_w1 + (size_t)2 * 2 * HHP_H * 8, h_ws = h_wov + (size_t)7 * 2 * HHP_ATT_J * 8, h_wa = h_ws + (size_t)32 * 2 * HHP_H * 8,
+                 h_total = h_wa + (size_t)32 * 2 * HHP_OUT * 8;
+    static_assert(HHP_SLOT_BYTES >= (size_t)2 * 1024 * 1024 + 2 * 309248 * 2, "slot too small");
+    if (total * sizeof(float) > (size_t)2 * 1024 * 1024 || 2 * h_total * sizeof(uint16_t) > HHP_SLOT_BYTES - (size_t)2 * 1024 * 1024) { g_err = "internal: blob exceeds its slot"; return HH_E_ARG; }
+    /* ... and as ONE linear stream of 1 KB fragments in consumption order (hh_policy_kernel_w16.h) */
+    const size_t xbytes = (size_t)HHX_STREAM_PIECES * HHW_PIECE;
+    if (!p->xblob[slot]) HIPCHK(hipMalloc(&p->xblob[slot], xbytes));
+    p->bankx.stream[slot] = p->xblob[slot];
+    p->blob[slot] = reinterpret_cast<float *>(p->slab + (size_t)slot * HHP_SLOT_BYTES);                                   /* first 2 MB of the slot */
+    p->blobh[slot] = reinterpret_cast<uint16_t *>(p->slab + (size_t)slot * HHP_SLOT_BYTES + (size_t)2 * 1024 * 1024);      /* second 2 MB */
+    {
+        HhpNetH &Hn = p->bankh.net[slot];
+        const uint16_t *bh = p->blobh[slot], *bl = p->blobh[slot] + h_total;
+        Hn.w1h = reinterpret_cast<const float4 *>(bh + h_w1); Hn.w1l = reinterpret_cast<const float4 *>(bl + h_w1);
+        Hn.wovh = reinterpret_cast<const float4 *>(bh + h_wov); Hn.wovl = reinterpret_cast<const float4 *>(bl + h_wov);
+        Hn.wsh = reinterpret_cast<const float4 *>(bh + h_ws); Hn.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
+        Hn.wah = reinterpret_cast<const float4 *>(bh + h_wa); Hn.wal = reinterpret_cast<const float4 *>(bl + h_wa);
+    }
+    HhpNet &N = p->bank.net[slot];
+    float *b = p->blob[slot];
+    N.w1p = b + o_w1; N.b1 = b + o_b1; N.wovp = b + o_wov; N.bov = b + o_bov; N.wsp = b + o_ws; N.bs = b + o_bs; N.wap = b + o_wa; N.ba = b + o_ba;
+    N.kind = w->kind; N.n_out = n_out; N.obs_dim = obs_dim; N.has_att = att ? 1 : 0;
+    if (slot + 1 > p->n_nets) p->n_nets = slot + 1;
+    /* the kernel writes no padding, and the slot may have held another kind: all of it to zero first */
+    HIPCHK(hipMemsetAsync(p->blob[slot], 0, total * sizeof(float), nullptr));
+    HIPCHK(hipMemsetAsync(p->blobh[slot], 0, 2 * h_total * sizeof(uint16_t), nullptr));
+    HIPCHK(hipMemsetAsync(p->xblob[slot], 0, xbytes, nullptr));
+    hhr_launch_actor(p, slot, d, nullptr);
+    return hhr_finish_load();
+}
+
+extern "C" int hh_policy_set_critic(hh_policy *p, int32_t slot, const hh_critic_weights *w) {
+    if (!p || !w || slot < 0 || slot >= HH_POLICY_MAX_NETS || w->kind < 0 || w->kind > 3) { g_err = "bad argument"; return HH_E_ARG; }
+    if (!p->blob[slot] || p->bank.net[slot].kind != w->kind) { g_err = "hh_policy_set_critic: load the actor of the same kind into this slot first (hh_policy_set_net)"; return HH_E_ARG; }
+    const bool att = w->kind <= HH_NET_FIGHT2;
+    if (!hhr_critic_complete(w, att)) { g_err = "hh_policy_set_critic: missing weight pointer"; return HH_E_ARG; }
+    HH_GUARD(p);
+    hh_critic_weights d = *w;
+    if (!att) d.v_w[1] = d.v_w[2] = d.v_b[1] = d.v_b[2] = d.att_in_proj_w = d.att_in_proj_b = d.att_out_w = d.att_out_b = nullptr;
+    HhrSrc src[14];
+    int n = 0, in0[3], nin[3], wd[3], out0[3];
+    const int nb = hhr_critic_blocks(w->kind, in0, nin, wd, out0);
+    for (int b = 0; b < nb; b++) { src[n++] = {&d.v_w[b], (size_t)wd[b] * nin[b]}; src[n++] = {&d.v_b[b], (size_t)wd[b]}; }
+    if (att) { src[n++] = {&d.att_in_proj_w, 450 * 150}; src[n++] = {&d.att_in_proj_b, 450}; src[n++] = {&d.att_out_w, 150 * 150}; src[n++] = {&d.att_out_b, 150}; }
+    src[n++] = {&d.shared_w, 500 * 500}; src[n++] = {&d.shared_b, 500}; src[n++] = {&d.val_w, 500}; src[n++] = {&d.val_b, 1};
+    HhrStage stage;
+    HIPCHK(stage.upload(src, n));
+    const int d1 = HHC_DIMS[w->kind][0], a1 = HHC_DIMS[w->kind][1], d2 = HHC_DIMS[w->kind][2], a2 = HHC_DIMS[w->kind][3];
+    /* fragment planes (halves): w1 [80 x 512] | wov [160 x 256] | ws [512 x 512] | wa [512 x 32]; then the float biases b1 | bs | bov | ba */
+    const size_t h_w1 = 0, h_wov = h_w1 + (size_t)(HHC_XK / 16) * 2 * HHP_H * 8, h_ws = h_wov + (size_t)(HHC_ATT_W / 16) * 2 * HHC_ATT_J * 8,
+                 h_wa = h_ws + (size_t)32 * 2 * HHP_H * 8, h_total = h_wa + (size_t)32 * 2 * HHP_OUT * 8;
+    const size_t o_b1 = 0, o_bs = 512, o_bov = 1024, o_ba = 1024 + HHC_ATT_W, n_bias = o_ba + HHP_OUT;
+    const size_t plane_bytes = h_total * sizeof(uint16_t), bytes = 2 * plane_bytes + n_bias * sizeof(float);
+    /* the same value branch as ONE linear stream of 1 KB fragments for hh_k_policy_w16_ppo (chunk order of hhx_critic_tile) + its biases */
+    const size_t xbytes = (size_t)HHXC_STREAM_PIECES * HHW_PIECE, xbias = (size_t)(512 + 512 + 160 + 32) * sizeof(float);
+    if (!p->cxblob[slot]) HIPCHK(hipMalloc(&p->cxblob[slot], xbytes + xbias));
+    if (!p->cblob[slot]) HIPCHK(hipMalloc(&p->cblob[slot], bytes));
+    HhpCritX &Cx = p->cbankx.c[slot];
+    const float *xb = reinterpret_cast<const float *>(p->cxblob[slot] + xbytes);
+    Cx.stream = reinterpret_cast<const unsigned char *>(p->cxblob[slot]);
+    Cx.b1 = xb; Cx.bs = xb + 512; Cx.bov = xb + 1024; Cx.ba = xb + 1184;
+    Cx.d1 = d1; Cx.a1 = a1; Cx.d2 = d2; Cx.a2 = a2; Cx.has_att = att ? 1 : 0; Cx.loaded = 1;
+    char *c = p->cblob[slot];
+    HhpCrit &Cn = p->cbank.c[slot];
+    const uint16_t *bh = reinterpret_cast<const uint16_t *>(c), *bl = reinterpret_cast<const uint16_t *>(c + plane_bytes);
+    const float *bf = reinterpret_cast<const float *>(c + 2 * plane_bytes);
+    Cn.w1h = reinterpret_cast<const float4 *>(bh + h_w1); Cn.w1l = reinterpret_cast<const float4 *>(bl + h_w1);
+    Cn.wovh = reinterpret_cast<const float4 *>(bh + h_wov); Cn.wovl = reinterpret_cast<const float4 *>(bl + h_wov);
+    Cn.wsh = reinterpret_cast<const float4 *>(bh + h_ws); Cn.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
+    Cn.wah = reinterpret_cast<const float4 *>(bh + h_wa); Cn.wal = reinterpret_cast<const float4 *>(bl + h_wa);
+    Cn.b1 = bf + o_b1; Cn.bs = bf + o_bs; Cn.bov = bf + o_bov; Cn.ba = bf + o_ba;
+    Cn.d1 = d1; Cn.a1 = a1; Cn.d2 = d2; Cn.a2 = a2; Cn.has_att = att ? 1 : 0; Cn.loaded = 1;
+    HIPCHK(hipMemsetAsync(p->cblob[slot], 0, bytes, nullptr));
+    HIPCHK(hipMemsetAsync(p->cxblob[slot], 0, xbytes + xbias, nullptr));
+    hhr_launch_critic(p, slot, d, nullptr);
+    return hhr_finish_load();
+}
+
 extern "C" int hh_policy_refresh(hh_policy *p, int32_t slot, const hh_net_weights *w, const hh_critic_weights *cw, void *stream) {
     if (!p || !w || slot < 0 || slot >= HH_POLICY_MAX_NETS) { g_err = "hh_policy_refresh: bad argument"; return HH_E_ARG; }
     if (!p->blob[slot] || !p->xblob[slot]) { g_err = "hh_policy_refresh: the slot is empty (load it once with hh_policy_set_net)"; return HH_E_ARG; }
@@ -223,57 +420,8 @@ extern "C" int hh_policy_refresh(hh_policy *p, int32_t slot, const hh_net_weight
     if (cw && cw->kind != N.kind) { g_err = "hh_policy_refresh: critic->kind differs from the network loaded in the slot"; return HH_E_ARG; }
     if (cw && !hhr_critic_complete(cw, att)) { g_err = "hh_policy_refresh: missing critic weight pointer"; return HH_E_ARG; }
     HH_GUARD(p);
-    hipStream_t st = (hipStream_t)stream;
-    {
-        HhrActorArgs a;
-        memset(&a, 0, sizeof(a));
-        a.w = *w;
-        a.B_w1 = const_cast<float *>(N.w1p); a.B_b1 = const_cast<float *>(N.b1); a.B_wov = const_cast<float *>(N.wovp); a.B_bov = const_cast<float *>(N.bov);
-        a.B_ws = const_cast<float *>(N.wsp); a.B_bs = const_cast<float *>(N.bs); a.B_wa = const_cast<float *>(N.wap); a.B_ba = const_cast<float *>(N.ba);
-        const HhpNetH &H = p->bankh.net[slot];
-        a.h_w1 = hhr_h16(H.w1h); a.l_w1 = hhr_h16(H.w1l); a.h_wov = hhr_h16(H.wovh); a.l_wov = hhr_h16(H.wovl);
-        a.h_ws = hhr_h16(H.wsh); a.l_ws = hhr_h16(H.wsl); a.h_wa = hhr_h16(H.wah); a.l_wa = hhr_h16(H.wal);
-        a.X = reinterpret_cast<uint16_t *>(p->xblob[slot]);
-        int e = 0;
-        for (int k = 0; k < 3; k++) {
-            a.c0[k] = HHP_INPUTS[N.kind][k][0]; a.nc[k] = HHP_INPUTS[N.kind][k][1] - a.c0[k]; a.wd[k] = HHP_INPUTS[N.kind][k][2];
-            a.end[k] = e += a.wd[k] * (a.nc[k] + 1);
-        }
-        a.end[3] = e += 500 * 501;
-        a.end[4] = e += N.n_out * 501;
-        a.end[5] = e += att ? 100 * 101 : 0;
-        hipLaunchKernelGGL(hh_k_refresh_actor, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, st, a);
-    }
-    if (cw) {
-        const HhpCrit &Cn = p->cbank.c[slot];
-        const HhpCritX &Cx = p->cbankx.c[slot];
-        HhrCriticArgs a;
-        memset(&a, 0, sizeof(a));
-        a.w = *cw;
-        a.h_w1 = hhr_h16(Cn.w1h); a.l_w1 = hhr_h16(Cn.w1l); a.h_wov = hhr_h16(Cn.wovh); a.l_wov = hhr_h16(Cn.wovl);
-        a.h_ws = hhr_h16(Cn.wsh); a.l_ws = hhr_h16(Cn.wsl); a.h_wa = hhr_h16(Cn.wah); a.l_wa = hhr_h16(Cn.wal);
-        a.b1 = const_cast<float *>(Cn.b1); a.bs = const_cast<float *>(Cn.bs); a.bov = const_cast<float *>(Cn.bov); a.ba = const_cast<float *>(Cn.ba);
-        a.xb1 = const_cast<float *>(Cx.b1); a.xbs = const_cast<float *>(Cx.bs); a.xbov = const_cast<float *>(Cx.bov); a.xba = const_cast<float *>(Cx.ba);
-        a.X = reinterpret_cast<uint16_t *>(p->cxblob[slot]);
-        a.att = att ? 1 : 0;
-        const int d1 = HHC_DIMS[N.kind][0], a1 = HHC_DIMS[N.kind][1], n_in = d1 + a1 + HHC_DIMS[N.kind][2] + HHC_DIMS[N.kind][3];
-        int e = 0;
-        if (att) { /* v1 [own obs | own act], v2 [other obs | other act], v3 [all]: columns 0, 175, 350 of cat(v1, v2, y3) */
-            const int in0[3] = {0, d1 + a1, 0}, in1[3] = {d1 + a1, n_in, n_in}, wd[3] = {175, 175, 150}, out0[3] = {0, 175, 350};
-            for (int b = 0; b < 3; b++) {
-                a.in0[b] = in0[b]; a.nin[b] = in1[b] - in0[b]; a.out0[b] = out0[b];
-                a.end[b] = e += wd[b] * (a.nin[b] + 1);
-            }
-        } else { /* inp1_val [all] -> 500 */
-            a.nin[0] = n_in;
-            a.end[0] = e += 500 * (n_in + 1);
-            a.end[1] = a.end[2] = e;
-        }
-        a.end[3] = e += 500 * 501;
-        a.end[4] = e += 501;
-        a.end[5] = e += att ? 150 * 151 : 0;
-        hipLaunchKernelGGL(hh_k_refresh_critic, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, st, a);
-    }
+    hhr_launch_actor(p, slot, *w, (hipStream_t)stream);
+    if (cw) hhr_launch_critic(p, slot, *cw, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }
@@ -319,16 +467,18 @@ extern "C" int hh_policy_copy_packed(hh_policy *p, int32_t slot, int32_t part, v
     return HH_OK;
 }
 
-extern "C" int hh_commander_refresh_weights(hh_commander *c, const hh_commander_weights *w, void *stream) {
-    if (!c || !w) { g_err = "hh_commander_refresh_weights: bad argument"; return HH_E_ARG; }
-    if (!c->loaded || !c->blob) { g_err = "hh_commander_refresh_weights: no weights loaded (hh_commander_set_weights allocates the buffers once)"; return HH_E_ARG; }
+static bool hhr_commander_complete(const hh_commander_weights *w, const char *who) {
     const float *need[] = {w->act_w_ih, w->act_w_hh, w->act_b_ih, w->act_b_hh, w->shared_w, w->shared_b, w->act_out_w, w->act_out_b,
                            w->val_w_ih, w->val_w_hh, w->val_b_ih, w->val_b_hh, w->val_out_w, w->val_out_b};
-    for (const float *q : need) if (!q) { g_err = "hh_commander_refresh_weights: missing weight pointer"; return HH_E_ARG; }
-    for (int k = 0; k < 4; k++) if (!w->inp_w[k] || !w->inp_b[k] || !w->v_w[k] || !w->v_b[k]) { g_err = "hh_commander_refresh_weights: missing input layer"; return HH_E_ARG; }
+    for (const float *q : need) if (!q) { g_err = std::string(who) + ": missing weight pointer"; return false; }
+    for (int k = 0; k < 4; k++) if (!w->inp_w[k] || !w->inp_b[k] || !w->v_w[k] || !w->v_b[k]) { g_err = std::string(who) + ": missing input layer"; return false; }
+    return true;
+}
+/* a laid-out commander from [dev] sources: one launch on st */
+static void hhr_launch_commander(hh_commander *c, const hh_commander_weights &w, hipStream_t st) {
     HhrCommanderArgs a;
     memset(&a, 0, sizeof(a));
-    a.w = *w;
+    a.w = w;
     const HhcNet &N = c->net;
     for (int b = 0; b < 2; b++) {
         const HhcBranch &Br = N.br[b];
@@ -347,8 +497,59 @@ extern "C" int hh_commander_refresh_weights(hh_commander *c, const hh_commander_
     a.end[8] = e += HH_CMD_HIDDEN * (HH_CMD_HIDDEN + 1);
     a.end[9] = e += HH_CMD_HIDDEN * (HH_CMD_HIDDEN + 1);
     a.end[10] = e += 500 * 501;
+    hipLaunchKernelGGL(hh_k_refresh_commander, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, st, a);
+}
+
+extern "C" int hh_commander_set_weights(hh_commander *c, const hh_commander_weights *w) {
+    if (!c || !w) { g_err = "hh_commander_set_weights: bad argument"; return HH_E_ARG; }
+    if (!hhr_commander_complete(w, "hh_commander_set_weights")) return HH_E_ARG;
     HH_GUARD(c);
-    hipLaunchKernelGGL(hh_k_refresh_commander, dim3((e + HHR_THREADS - 1) / HHR_THREADS), dim3(HHR_THREADS), 0, (hipStream_t)stream, a);
+    hh_commander_weights d = *w;
+    HhrSrc src[30];
+    int n = 0;
+    for (int k = 0; k < 4; k++) {
+        src[n++] = {&d.inp_w[k], (size_t)HHC_L1A_WD[k] * (HHC_L1A_C1[k] - HHC_L1A_C0[k])}; src[n++] = {&d.inp_b[k], (size_t)HHC_L1A_WD[k]};
+        src[n++] = {&d.v_w[k], (size_t)HHC_L1V_WD[k] * HHC_L1V_IN[k]}; src[n++] = {&d.v_b[k], (size_t)HHC_L1V_WD[k]};
+    }
+    const size_t gw = (size_t)3 * HH_CMD_HIDDEN * HH_CMD_HIDDEN, gb = 3 * HH_CMD_HIDDEN; /* gate rows r | z | n */
+    src[n++] = {&d.act_w_ih, gw}; src[n++] = {&d.act_w_hh, gw}; src[n++] = {&d.act_b_ih, gb}; src[n++] = {&d.act_b_hh, gb};
+    src[n++] = {&d.val_w_ih, gw}; src[n++] = {&d.val_w_hh, gw}; src[n++] = {&d.val_b_ih, gb}; src[n++] = {&d.val_b_hh, gb};
+    src[n++] = {&d.shared_w, 500 * 500}; src[n++] = {&d.shared_b, 500};
+    src[n++] = {&d.act_out_w, HH_CMD_ACTIONS * 500}; src[n++] = {&d.act_out_b, HH_CMD_ACTIONS}; src[n++] = {&d.val_out_w, 500}; src[n++] = {&d.val_out_b, 1};
+    HhrStage stage;
+    HIPCHK(stage.upload(src, n));
+    const int K1[2] = {48, 112};
+    /* halves: w1 actor | w1 critic | wg actor | wg critic | ws */
+    const size_t n_w1a = (size_t)48 * 512, n_w1c = (size_t)112 * 512, n_wg = (size_t)HHC_KG * HHC_JG;
+    const size_t h_w1[2] = {0, n_w1a}, h_wg[2] = {n_w1a + n_w1c, n_w1a + n_w1c + n_wg}, h_ws = n_w1a + n_w1c + 2 * n_wg, h_total = h_ws + (size_t)HHC_KS * HHC_KS;
+    /* floats: b1 a | b1 c | bg a | bg c | bs | wo a [3][512] | wo c [512] | bo a [4] | bo c [4] */
+    const size_t f_b1[2] = {0, 512}, f_bg[2] = {1024, 1920}, f_bs = 2816, f_wo[2] = {3328, 4864}, f_bo[2] = {5376, 5380}, f_total = 5384;
+    const size_t plane_bytes = h_total * sizeof(uint16_t), bytes = 2 * plane_bytes + f_total * sizeof(float);
+    if (!c->blob) HIPCHK(hipMalloc(&c->blob, bytes));
+    const uint16_t *bh = reinterpret_cast<const uint16_t *>(c->blob), *bl = reinterpret_cast<const uint16_t *>(c->blob + plane_bytes);
+    const float *bf = reinterpret_cast<const float *>(c->blob + 2 * plane_bytes);
+    HhcNet &N = c->net;
+    for (int b = 0; b < 2; b++) {
+        HhcBranch &Br = N.br[b];
+        Br.w1h = reinterpret_cast<const float4 *>(bh + h_w1[b]); Br.w1l = reinterpret_cast<const float4 *>(bl + h_w1[b]);
+        Br.wgh = reinterpret_cast<const float4 *>(bh + h_wg[b]); Br.wgl = reinterpret_cast<const float4 *>(bl + h_wg[b]);
+        Br.b1 = bf + f_b1[b]; Br.bg = bf + f_bg[b]; Br.wo = bf + f_wo[b]; Br.bo = bf + f_bo[b];
+        Br.k1 = K1[b];
+    }
+    N.wsh = reinterpret_cast<const float4 *>(bh + h_ws); N.wsl = reinterpret_cast<const float4 *>(bl + h_ws);
+    N.bs = bf + f_bs;
+    c->loaded = 1;
+    HIPCHK(hipMemsetAsync(c->blob, 0, bytes, nullptr)); /* the kernel writes no padding */
+    hhr_launch_commander(c, d, nullptr);
+    return hhr_finish_load();
+}
+
+extern "C" int hh_commander_refresh_weights(hh_commander *c, const hh_commander_weights *w, void *stream) {
+    if (!c || !w) { g_err = "hh_commander_refresh_weights: bad argument"; return HH_E_ARG; }
+    if (!c->loaded || !c->blob) { g_err = "hh_commander_refresh_weights: no weights loaded (hh_commander_set_weights allocates the buffers once)"; return HH_E_ARG; }
+    if (!hhr_commander_complete(w, "hh_commander_refresh_weights")) return HH_E_ARG;
+    HH_GUARD(c);
+    hhr_launch_commander(c, *w, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return HH_OK;
 }

@@ -44,12 +44,15 @@ typedef struct hh_commander_weights {
 int hh_commander_create(int device, int32_t max_rows, hh_commander **out);
 int hh_commander_destroy(hh_commander *c);
 
-/* load (or replace) the weights: repacked on the host into the kernel's split-fp16 fragment layout and copied.  Synchronous. */
+/* load (or replace) the weights from [host] arrays: staged in a temporary device buffer and packed there into the kernel's split-fp16
+ * fragment layout by the kernel hh_commander_refresh_weights launches (csrc/hh_weight_refresh.h), after the destination is cleared.
+ * Synchronous: the packed bytes are in place when the call returns, the arrays may be freed or overwritten, and a launch issued
+ * afterwards on any stream sees the new weights.  An invalid argument (HH_E_ARG) or a failed staging (HH_E_HIP) changes nothing. */
 int hh_commander_set_weights(hh_commander *c, const hh_commander_weights *w);
 
 /* The learner's new weights without a host round trip (csrc/hh_weight_refresh.h): the same struct with [dev] fp32 pointers in the same
  * layout; what hh_commander_set_weights writes is rewritten in place with the same bytes (fp16 planes, fp32 section; the GRU bias sums
- * b_ih + b_hh are fp32 adds as on the host) by one kernel ordered on `stream`: no host synchronisation, no allocation, graph-capturable,
+ * b_ih + b_hh are fp32 adds) by the same kernel, one launch ordered on `stream`: no host synchronisation, no allocation, graph-capturable,
  * device addresses unchanged.  HH_E_ARG, nothing enqueued: no weights loaded yet, or a missing pointer. */
 int hh_commander_refresh_weights(hh_commander *c, const hh_commander_weights *w, void *stream);
 /* Test hook: one packed part (HH_COMMANDER_PART_*) to dst [dev] (cap bytes) on `stream`; *bytes = its size (dst == NULL: the size only) */

@@ -46,9 +46,12 @@ typedef struct hh_policy hh_policy;
 int hh_policy_create(int device, int32_t max_rows, hh_policy **out);
 int hh_policy_destroy(hh_policy *p);
 
-/* load (or replace) network `slot`: weights are repacked on the host into the kernel's k-interleaved layout (the two
- * attention projections folded into one 100x100 matrix in double precision: with a sequence of length 1 the softmax is 1
- * and the attention output is out_proj(v_proj(x))) and copied to the device.  Synchronous. */
+/* load (or replace) network `slot`, of any kind, from [host] arrays: they are staged in a temporary device buffer and packed there, by
+ * the one packer (csrc/hh_weight_refresh.h, the kernel hh_policy_refresh launches), into the forward kernels' layouts (the two attention
+ * projections folded into one 100x100 matrix in double precision: with a sequence of length 1 the softmax is 1 and the attention
+ * output is out_proj(v_proj(x))); what the slot held before is cleared first.  Synchronous: the packed bytes are in place when the call
+ * returns, the arrays may be freed or overwritten, and a launch issued afterwards on any stream sees the new weights.  An invalid
+ * argument (HH_E_ARG) or a failed staging (HH_E_HIP) leaves the slot as it was. */
 int hh_policy_set_net(hh_policy *p, int32_t slot, const hh_net_weights *w);
 
 /* selector byte -> network: lut[256] [host], value 0 = "no action for this row" (its action is written as zeros), s + 1 =
@@ -122,7 +125,8 @@ typedef struct hh_critic_weights {
     const float *val_w, *val_b;                                        /* val_out._model.0 [1,500], [1] */
 } hh_critic_weights;
 
-/* load (or replace) the value branch of network `slot` (its actor must be loaded: hh_policy_set_net).  Synchronous.
+/* load (or replace) the value branch of network `slot` (its actor must be loaded: hh_policy_set_net) from [host] arrays: staged and
+ * packed on the device like hh_policy_set_net, and synchronous in the same sense.
  * hh_policy_set_net and hh_policy_set_critic are a PAIR: the value branch keeps its own permuted copy of the shared layer (the reference
  * has ONE module-level SHARED_LAYER, models/ac_models_hetero.py:21) and the input widths of its kind, so loading a new actor into the slot
  * invalidates it — hh_policy_sample then refuses a value output (HH_E_ARG) until the value branch is loaded again. */
@@ -153,9 +157,10 @@ int hh_policy_sample(hh_policy *p, const float *obs, int32_t n_rows, int32_t obs
 
 /* ---- The learner's new weights into a loaded slot without a host round trip (csrc/hh_weight_refresh.h).  What hh_policy_set_net followed
  * by hh_policy_set_critic write, but from DEVICE pointers: `actor` / `critic` hold [dev] fp32 tensors in the reference layout described
- * above (row-major, contiguous).  Every packed form is rewritten in place with the same bytes the host path writes (fp32 blob, fp16
- * fragment planes, fragment streams of the actor and of the value branch, the attention folded in fp64 in the host's summation order),
- * by kernels ordered on `stream`: no host synchronisation, no allocation, graph-capturable.  Nothing the host keeps changes (kinds, loaded
+ * above (row-major, contiguous).  Every packed form is rewritten in place (fp32 blob, fp16 fragment planes, fragment streams of the
+ * actor and of the value branch, the attention folded in fp64) by the kernels a load runs, hence with the same bytes, here ordered on
+ * `stream` and with nothing around them: one launch for the actor, one for the value branch, no host synchronisation, no allocation, no
+ * memset, graph-capturable.  Nothing the host keeps changes (kinds, loaded
  * flags, device addresses), so a HIP graph captured before a refresh replays with the new weights.
  *   critic  non-NULL exactly when the slot's value branch is loaded: the branch's private copy of the shared layer is refreshed together
  *           with the actor (the set_net + set_critic pair rule); critic->shared_w / shared_b are the actor's tensors.

@@ -1,12 +1,15 @@
-"""The device weight refresh on the MI355X (hh_policy_refresh / hh_commander_refresh_weights): every packed form byte-equal to what the
-host path (set_net + set_critic, set_weights) writes for the same weights; captured rollout graphs that keep working across a refresh; a
-refresh captured into one graph with a collect; and the error paths, which leave the packed bytes as they were."""
+"""The samplers' weight packer on the MI355X, by both ways in — a load (set_net + set_critic, set_weights) and a device refresh
+(hh_policy_refresh / hh_commander_refresh_weights): every packed form byte-equal to the recorded digests of packed_weight_digests.py;
+a reload with another kind, the caller's arrays free on return, set_net's invalidation of the value branch; captured rollout graphs
+that keep working across a refresh; a refresh captured into one graph with a collect; and the error paths, which leave the packed bytes
+as they were."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import packed_weight_digests as PWD
 from hhmarl_2d_amd import _lib as L
 from hhmarl_2d_amd import commander as CM
 from hhmarl_2d_amd import pilots
@@ -61,6 +64,9 @@ def _policy_parts(bank, slots=(0, 1)):
 def test_policy_refresh_is_byte_identical_to_the_host_path(mode, seeds, tie):
     s1, s2 = seeds
     kinds, sds, csds = _dicts(mode, s2, tie, edges=seeds == (17, 5))
+    fix = PWD.load()["policy"][PWD.policy_case(mode, seeds, tie)]
+    assert PWD.weights_digest(sds + csds) == fix["weights_sha256"]           # else: the weight generator drifted, not the packer
+    want = fix["parts"]
     host = PolicyBank(DEV, 64)
     for slot in (0, 1):
         host.load_trainable(slot, kinds[slot], sds[slot], csds[slot])
@@ -68,15 +74,15 @@ def test_policy_refresh_is_byte_identical_to_the_host_path(mode, seeds, tie):
     d_sd, d_csd = _cuda(sds), _cuda(csds)
     if tie:
         assert d_sd[0]["shared_layer._model.0.weight"] is d_sd[1]["shared_layer._model.0.weight"]
-    before = _policy_parts(dev)
+    before = PWD.policy_digests(dev)
     gen, kinds_before = dev.generation, dict(dev.kinds)
     for slot in (0, 1):
         dev.refresh(slot, d_sd[slot], d_csd[slot])
-    want, got = _policy_parts(host), _policy_parts(dev)
-    torch.cuda.synchronize()
+    loaded, got = PWD.policy_digests(host), PWD.policy_digests(dev)
     for key in want:
-        assert not torch.equal(before[key], want[key]), key                  # the refresh had something to change
-        assert torch.equal(got[key], want[key]), key
+        assert before[key] != want[key], key                                 # the refresh had something to change
+        assert loaded[key] == want[key], key
+        assert got[key] == want[key], key
     assert dev.generation == gen and dev.kinds == kinds_before               # nothing a captured graph holds by value changed
 
 
@@ -88,14 +94,118 @@ def test_commander_refresh_is_byte_identical_to_the_host_path(seeds):
         sd["rnn_act.bias_ih_l0"][:4] = np.array([1e-39, 3.0, -0.0, 2.0 ** -25], np.float32)
         sd["rnn_act.bias_hh_l0"][:4] = np.array([-1e-39, 2.0 ** -24, 0.0, 1e-7], np.float32)
         sd["shared_layer._model.0.weight"][7, 295:305] = 6.1e-5
+    fix = PWD.load()["commander"][PWD.commander_case(seeds)]
+    assert PWD.weights_digest([sd]) == fix["weights_sha256"]
+    want = fix["parts"]
     host = CM.CommanderNet(0, 96).set_weights(sd)
     dev = CM.CommanderNet(0, 96).set_weights(CM.random_weights(s1))
-    before = [dev.packed(p) for p in (0, 1)]
+    before = PWD.commander_digests(dev)
     dev.refresh_weights(_cuda([sd])[0])
-    for p in (0, 1):
-        want, got = host.packed(p), dev.packed(p)
-        torch.cuda.synchronize()
-        assert not torch.equal(before[p], want) and torch.equal(got, want), p
+    loaded, got = PWD.commander_digests(host), PWD.commander_digests(dev)
+    for p in want:
+        assert before[p] != want[p] and loaded[p] == want[p] and got[p] == want[p], p
+
+
+def _recorded(mode, seeds=(3, 11), tie=True):
+    """a recorded policy case: its weights (kinds, actor dicts, critic dicts) and the digests of its packed parts"""
+    return _dicts(mode, seeds[1], tie), PWD.load()["policy"][PWD.policy_case(mode, seeds, tie)]["parts"]
+
+
+@pytest.mark.parametrize("first, then", [("fight", "escape"), ("escape", "fight")])
+def test_reload_with_another_kind_leaves_nothing_of_the_old_one(first, then):
+    """the packer writes no padding and only fight nets have attention sections: a load has to clear what the slot held (a fresh
+    allocation is usually zero and would hide a missing clear; a slot that held the other kind does not)"""
+    bank = PolicyBank(DEV, 64)
+    for mode in (first, then):
+        (kinds, sds, csds), want = _recorded(mode)
+        for slot in (0, 1):
+            bank.load_trainable(slot, kinds[slot], sds[slot], csds[slot])
+    assert PWD.policy_digests(bank) == want
+
+
+def _own_and_poison(d):
+    """after a load returned: the arrays were the caller's own (no copy stood in between) and may be overwritten at once"""
+    for v in d.values():
+        assert v.dtype == np.float32 and v.flags["C_CONTIGUOUS"]          # set_net / set_critic / set_weights pass such an array through
+        v.fill(np.nan)
+
+
+def test_the_callers_arrays_are_free_when_a_load_returns():
+    """every source array is overwritten with NaN right after the call that read it returns, with no synchronisation; the packed parts,
+    read on another stream than the default one, are the recorded ones"""
+    (kinds, sds, csds), want = _recorded("fight", tie=False)
+    bank = PolicyBank(DEV, 64)
+    for slot in (0, 1):
+        shared = {k: sds[slot][k].copy() for k in ("shared_layer._model.0.weight", "shared_layer._model.0.bias")}   # set_critic's
+        bank.set_net(slot, kinds[slot], sds[slot])
+        _own_and_poison(sds[slot])
+        bank.set_critic(slot, kinds[slot], shared, csds[slot])
+        _own_and_poison(csds[slot])
+        _own_and_poison(shared)
+    sd = PWD.commander_weights((2, 9))
+    net = CM.CommanderNet(0, 96).set_weights(sd)
+    _own_and_poison(sd)
+    with torch.cuda.stream(torch.cuda.Stream(DEV)):
+        assert PWD.policy_digests(bank) == want
+        assert PWD.commander_digests(net) == PWD.load()["commander"]["2-9"]["parts"]
+
+
+def _fight_rows(n_arenas=16):
+    obs = torch.zeros((n_arenas, 2, 30), dtype=torch.float32, device=DEV)
+    sel = torch.tensor([pilots.SEL_FIGHT1, pilots.SEL_FIGHT2], dtype=torch.uint8, device=DEV).repeat(n_arenas, 1).contiguous()
+    return obs, sel
+
+
+def test_set_net_alone_invalidates_the_value_branch():
+    (kinds, sds, csds), want = _recorded("fight")
+    bank = PolicyBank.trainable_init(DEV, mode="fight", seed=3, max_rows=64)
+    obs, sel = _fight_rows()
+    bank.sample(obs, sel, greedy=True)                                          # both value branches loaded: vf is given
+    bank.set_net(0, kinds[0], sds[0])
+    with pytest.raises(RuntimeError, match=r"vf asked for, but a loaded network has no value branch \(hh_policy_set_critic\)"):
+        bank.sample(obs, sel, greedy=True)
+    bank.sample(obs, sel, greedy=True, want_vf=False)
+    bank.set_critic(0, kinds[0], sds[0], csds[0])
+    _, _, vf = bank.sample(obs, sel, greedy=True)
+    assert torch.isfinite(vf).all()
+    got = PWD.policy_digests(bank, slots=(0,))
+    assert got["0/3"] == want["0/3"] and got["0/4"] == want["0/4"]
+
+
+def test_load_error_paths_leave_the_packed_bytes_unchanged():
+    """a missing pointer on a LOADED slot / commander: HH_E_ARG with the message of the check, every packed part as it was, and the value
+    branch still loaded (validation comes before anything is touched)"""
+    bank = PolicyBank.trainable_init(DEV, mode="fight", seed=5, max_rows=64)
+    before = PWD.policy_digests(bank)
+    kinds, sds, csds = _dicts("fight", 9, True)
+    lib = L.lib()
+    hp = lambda d: (lambda k: d[k].ctypes.data_as(C.c_void_p) if k in d else None)
+    crit = {**csds[0], **{k: sds[0][k] for k in ("shared_layer._model.0.weight", "shared_layer._model.0.bias")}}
+
+    def refused(call, struct, field, index, msg):
+        w = struct()
+        if index is None:
+            setattr(w, field, None)
+        else:
+            getattr(w, field)[index] = None
+        assert call(w) == -1 and lib.hh_last_error().decode() == msg, (field, lib.hh_last_error().decode())
+
+    set_net = lambda w: lib.hh_policy_set_net(bank.h, 0, C.byref(w))
+    set_critic = lambda w: lib.hh_policy_set_critic(bank.h, 0, C.byref(w))
+    refused(set_net, lambda: pilots._net_struct(PN.FIGHT1, hp(sds[0])), "att_out_w", None, "hh_policy_set_net: missing weight pointer")
+    refused(set_net, lambda: pilots._net_struct(PN.FIGHT1, hp(sds[0])), "inp_b", 2, "hh_policy_set_net: missing input layer")
+    refused(set_critic, lambda: pilots._critic_struct(PN.FIGHT1, hp(crit)), "v_w", 2, "hh_policy_set_critic: missing weight pointer")
+    refused(set_critic, lambda: pilots._critic_struct(PN.FIGHT1, hp(crit)), "val_b", None, "hh_policy_set_critic: missing weight pointer")
+    assert PWD.policy_digests(bank) == before
+    _, _, vf = bank.sample(*_fight_rows(), greedy=True)
+    assert torch.isfinite(vf).all()
+    sd = CM.random_weights(2)
+    net = CM.CommanderNet(0, 96).set_weights(CM.random_weights(1))
+    cb = PWD.commander_digests(net)
+    set_weights = lambda w: lib.hh_commander_set_weights(net.h, C.byref(w))
+    refused(set_weights, lambda: CM._weights_struct(lambda k: sd[k].ctypes.data), "val_w_hh", None, "hh_commander_set_weights: missing weight pointer")
+    refused(set_weights, lambda: CM._weights_struct(lambda k: sd[k].ctypes.data), "v_b", 3, "hh_commander_set_weights: missing input layer")
+    assert PWD.commander_digests(net) == cb
 
 
 def _ppo(N, T, seed_w, graph):
