@@ -122,11 +122,13 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_bind_policy", "hh_policy_act_binned", "hh_kernel_instance", "hh_gae_rllib", "hh_math_eval",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux",
-           "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics", "hh_episodes_emit_append"]
+           "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics", "hh_episodes_emit_append",
+           "hh_world_snapshot_bytes", "hh_world_snapshot", "hh_world_restore", "hh_policy_snapshot_bytes", "hh_policy_snapshot", "hh_policy_restore"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
                      "hh_commander_copy_packed", "hh_commander_act_chain", "hh_commander_chain_kernel_name", "hh_commander_episodes_emit_aux",
-                     "hh_commander_episodes_emit_append"]  # include/hh_commander.h
+                     "hh_commander_episodes_emit_append", "hh_commander_snapshot_bytes", "hh_commander_snapshot",
+                     "hh_commander_restore"]  # include/hh_commander.h
 
 LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_categorical", "hh_gru_seq_scratch_bytes", "hh_gru_seq_forward",
                    "hh_gru_seq_backward", "hh_chunk_attn_forward", "hh_chunk_attn_backward", "hh_residual_normalize_forward",
@@ -304,8 +306,40 @@ def lib():
         L.hh_heads_loss.argtypes = [C.c_int64] + [vp] * 13 + [C.POINTER(HHPpoLossParams)] + [vp] * 10 + [C.c_int64, vp]
         L.hh_window_cut.argtypes = [C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.hh_window_gather.argtypes = [C.c_int32, C.POINTER(HHWindowCol), C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        for obj in ("world", "policy", "commander"):   # the snapshot triplets (hh_abi.h, hh_policy.h, hh_commander.h): handle, [host] buffer, bytes, stream
+            getattr(L, f"hh_{obj}_snapshot_bytes").argtypes = [vp, C.POINTER(C.c_int64)]
+            getattr(L, f"hh_{obj}_snapshot").argtypes = [vp, vp, C.c_int64, vp]
+            getattr(L, f"hh_{obj}_restore").argtypes = [vp, vp, C.c_int64, vp]
         _lib = L
     return _lib
+
+
+SNAPSHOT_MAGIC = {"world": b"HHSW", "policy": b"HHSP", "commander": b"HHSC"}   # HH_SNAP_MAGIC_* (csrc/hh_snapshot.h)
+
+
+def snapshot(obj, handle, stream):
+    """hh_<obj>_snapshot of `handle` (obj: "world" | "policy" | "commander") -> the blob, a uint8 CPU tensor; synchronises `stream`"""
+    import torch
+    n = C.c_int64(0)
+    check(getattr(lib(), f"hh_{obj}_snapshot_bytes")(handle, C.byref(n)))
+    blob = torch.empty((n.value,), dtype=torch.uint8)
+    check(getattr(lib(), f"hh_{obj}_snapshot")(handle, C.c_void_p(blob.data_ptr()), n.value, stream))
+    return blob
+
+
+def snapshot_bytes(obj, handle):
+    n = C.c_int64(0)
+    check(getattr(lib(), f"hh_{obj}_snapshot_bytes")(handle, C.byref(n)))
+    return n.value
+
+
+def restore(obj, handle, blob, stream):
+    """hh_<obj>_restore of a blob (uint8 CPU tensor, contiguous) into `handle`; a refusal (HH_E_ARG: the object is untouched) raises
+    ValueError with the library's message, any other failure RuntimeError"""
+    rc = getattr(lib(), f"hh_{obj}_restore")(handle, C.c_void_p(blob.data_ptr()), blob.numel(), stream)
+    if rc == -1:
+        raise ValueError(f"blob: {lib().hh_last_error().decode()}")
+    check(rc)
 
 
 def check(rc):

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from . import policy_nets as PN
-from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready
+from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready, rollout_load_plan, rollout_state_dict
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
 
@@ -120,6 +120,31 @@ class CommanderNet:
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         L.check(L.lib().hh_commander_copy_packed(self.h, int(part), C.c_void_p(out.data_ptr()), n.value, C.byref(n), st))
         return out
+
+    # ---- complete snapshots (checkpointing: hh_commander_snapshot / hh_commander_restore, include/hh_commander.h) ----
+    def snapshot(self):
+        """the packed weights exactly as the kernels read them, as an opaque blob (uint8 CPU tensor); synchronises the current stream"""
+        return L.snapshot("commander", self.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def restore(self, blob):
+        """a snapshot() blob back in place (same addresses: a captured CommanderRollout keeps replaying).  ValueError, the net untouched:
+        another geometry or format version, a net without weights on one side only, a truncated blob."""
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.device.type != "cpu":
+            raise ValueError("blob: a 1-D uint8 CPU tensor (CommanderNet.snapshot())")
+        L.restore("commander", self.h, blob.contiguous(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        self._w = None   # the host copy of set_weights is stale now
+
+    def state_dict(self):
+        return {"blob": self.snapshot()}
+
+    def _load_plan(self, sd):
+        from . import checkpoint as ck
+        ck.need_keys("CommanderNet", sd, ("blob",))
+        ck.check_blob("CommanderNet", sd["blob"], L.snapshot_bytes("commander", self.h), L.SNAPSHOT_MAGIC["commander"])
+        return lambda: self.restore(sd["blob"])
+
+    def load_state_dict(self, sd):
+        self._load_plan(sd)()
 
     def sample(self, obs, h_in, h_out, fresh=None, world=None, uniforms=None, crit_act=None, greedy=False, actions=None, logp=None,
                vf=None, logits=None, want_vf=True):
@@ -294,6 +319,13 @@ class CommanderEpisodeBatch(EpisodeBatch):
 
     def _parts(self):
         return super()._parts() + ((self.SEQ_TABLE + ("state_in",), 3),)   # rows() also holds the sequence table and state_in [S, 3, 2, 200]
+
+    def _options(self):
+        return dict(super()._options(), max_seq_len=self.L, seq_cap=int(self._bufs.seq_cap))
+
+    def _carry_lead(self, k, m):
+        """the state carry holds one entry per sequence start (within-episode steps 0, L, 2 L, ...) of the running episode"""
+        return m if k != "state" else min(-(-m // self.L) + 1, self._carry["state"].shape[1])
 
     def sequences(self):
         """the learner's padded form (RLlib's chop_into_sequences, all three agents of an arena row side by side; per agent it is the slice
@@ -485,6 +517,27 @@ class CommanderRollout:
         times (None: no limit; `episodes.ready()` tells afterwards whether the batch is complete) -> self"""
         collect_until_ready(self, max_collects)
         return self
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _window_names(self):
+        return ("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target", "state_in", "_fresh") + (("logits",) if self.record_logits else ())
+
+    def _options(self):
+        return {"T": self.T, "N": self.w.N, "gamma": self.gamma, "lam": self.lam, "batch_mode": self.batch_mode, "max_seq_len": self.max_seq_len,
+                "record_logits": self.record_logits}
+
+    def state_dict(self):
+        """the window buffers of the last collect with the GRU states (state_in[T] and obs[T] / vf[T] are the hand-over of the next one),
+        the episode-start flags, `collects`, `_started` and the CommanderEpisodeBatch; the world, the commander and the pilots' bank are
+        saved by themselves.  The captured graph is not saved.  Synchronises the device."""
+        return rollout_state_dict(self, self._window_names(), self._options())
+
+    def _load_plan(self, sd):
+        return rollout_load_plan(self, sd, self._window_names(), self._options())
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back in place; validated first (ValueError names the field, nothing changed)"""
+        self._load_plan(sd)()
 
     def critic_rows(self, agent):
         """the flattened CUR_OBS rows of `agent` (1..3) for the T collected steps with the actions filled in (central_critic_rows_hl)"""

@@ -1,6 +1,8 @@
 """The env-facing part of the reference's config.py (Config.args, config.py:17-54 and the derived
 fields of set_metrics, config.py:94-107).  Only the fields the environments read are kept; the
-trainer/checkpoint plumbing of the reference is out of scope."""
+reference's RLlib trainers and RLlib's own checkpoint format are out of scope.
+Saving and resuming a run of this project's own loop (worlds, samplers, rollouts, learners) is
+hhmarl_2d_amd/checkpoint.py."""
 from types import SimpleNamespace
 
 HORIZON_BY_LEVEL = {1: 150, 2: 200, 3: 300, 4: 350, 5: 400}  # config.py:94-95

@@ -10,7 +10,8 @@ from .batch import chunk_mask, standardize_masked, window_cut, window_gather
 from .loss import CMD_LD, _loss_kw, heads_loss, ppo_loss_categorical, ppo_loss_categorical_torch
 from .nets import CommanderTrainable
 from .ops import GRU_H, _trunk_mode
-from .step import _heads_keyword, _learner_options, _PolicySGD
+from .. import checkpoint as ck
+from .step import _heads_keyword, _learner_options, _learner_saved_options, _module_plan, _PolicySGD
 
 # what CommanderLearner(step="graph") stages per minibatch: eight columns [S, L, ...] per step, then two per sequence
 COMMANDER_STAGE_COLS = ("obs", "critic", "actions", "old_logp", "adv", "target", "mask", "old_logits", "state_in", "seq_len")
@@ -262,6 +263,36 @@ class CommanderLearner:
         out = self._sgd.run(*self._columns(b, staged=self.step == "graph"))
         self.updates += 1
         return out
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _options(self):
+        return _learner_saved_options(self, self.optimizer_mode, inputs=self.inputs, trunk=self.trunk)
+
+    def state_dict(self):
+        """the module (its one shared layer once), `updates` — it seeds minibatch_order and sequence_order —, kl_coeff and the Adam state
+        (DeviceAdam's m, v, t or torch.optim.Adam's own), and the constructor options that decide the arithmetic or the schedule.  The
+        captured step graph is not saved."""
+        return {"options": self._options(), "updates": int(self.updates), "module": {k: ck.cpu(v) for k, v in self.module.state_dict().items()},
+                "policy": self._sgd.state_dict()}
+
+    def _load_plan(self, sd):
+        ck.need_keys("CommanderLearner", sd, ("options", "updates", "module", "policy"))
+        ck.check_options("CommanderLearner", sd["options"], self._options())
+        if isinstance(sd["updates"], bool) or not isinstance(sd["updates"], int) or sd["updates"] < 0:
+            raise ValueError("CommanderLearner: `updates` is a count")
+        pairs = _module_plan("CommanderLearner module", self.module, sd["module"])
+        driver = self._sgd._load_plan(sd["policy"])
+
+        def commit():
+            ck.copy_pairs(pairs)
+            driver()
+            self.updates = sd["updates"]
+        return commit
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back in place (parameters, m, v, t by copy_: a captured step graph replays); everything is validated first —
+        ValueError names the field and nothing was changed"""
+        self._load_plan(sd)()
 
     def publish(self, net):
         """the new weights into the sampler's CommanderNet on the current stream (refresh_weights): captured collects replay with them"""

@@ -12,7 +12,8 @@ from .batch import chunk_mask, cut_chunks, pad_chunks, standardize, window_cut, 
 from .loss import OLD_LD, _loss_kw, heads_loss, n_comp_of, ppo_loss, ppo_loss_torch
 from .nets import TrainableNet, tie
 from .ops import _trunk_mode
-from .step import _heads_keyword, _learner_options, _PolicySGD
+from .. import checkpoint as ck
+from .step import _heads_keyword, _learner_options, _learner_saved_options, _module_plan, _PolicySGD
 
 # ------------------------------------------------------------------------------------------------------------------ the learner
 class PPOLearner:
@@ -316,6 +317,44 @@ class PPOLearner:
         out = [d.run(*self._columns(b, staged=self.step == "graph")) for d, b in zip(self._sgd, batches)]
         self.updates += 1
         return out
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    _SHARED = ("shared_layer._model.0.weight", "shared_layer._model.0.bias")
+
+    def _options(self):
+        return _learner_saved_options(self, self.optimizer, kinds=self.kinds, attention=self.attention, inputs=self.inputs, trunk=self.trunk)
+
+    def state_dict(self):
+        """the two modules (the tied shared layer once, with the first), `updates` — it seeds minibatch_order and sequence_order —, per
+        policy kl_coeff and the Adam state (DeviceAdam's m, v, t or torch.optim.Adam's own), and the constructor options that decide the
+        arithmetic or the schedule.  Captured step graphs are not saved."""
+        mods = [{k: ck.cpu(v) for k, v in m.state_dict().items() if not (a and k in self._SHARED)} for a, m in enumerate(self.modules)]
+        return {"options": self._options(), "updates": int(self.updates), "modules": mods, "policies": [d.state_dict() for d in self._sgd]}
+
+    def _load_plan(self, sd):
+        ck.need_keys("PPOLearner", sd, ("options", "updates", "modules", "policies"))
+        ck.check_options("PPOLearner", sd["options"], self._options())
+        if isinstance(sd["updates"], bool) or not isinstance(sd["updates"], int) or sd["updates"] < 0:
+            raise ValueError("PPOLearner: `updates` is a count")
+        for k in ("modules", "policies"):
+            if not isinstance(sd[k], (list, tuple)) or len(sd[k]) != 2:
+                raise ValueError(f"PPOLearner: `{k}` holds one entry per policy (2)")
+        pairs = []
+        for a, m in enumerate(self.modules):
+            pairs += _module_plan(f"PPOLearner modules[{a}]", m, sd["modules"][a], self._SHARED if a else ())
+        drivers = [d._load_plan(p) for d, p in zip(self._sgd, sd["policies"])]
+
+        def commit():
+            ck.copy_pairs(pairs)
+            for d in drivers:
+                d()
+            self.updates = sd["updates"]
+        return commit
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back in place (parameters, m, v, t by copy_: captured step graphs replay, the shared layer stays tied);
+        everything is validated first — ValueError names the field and nothing was changed"""
+        self._load_plan(sd)()
 
     def publish(self, bank):
         """the new weights into the sampler's bank on the current stream (PolicyBank.refresh_trainable): captured collects replay with them"""

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import checkpoint as ck
 from ._ffi import _need_gpu, _p, _stream
 from .batch import kl_coeff_update, update_schedule
 from .loss import _heads_mode
@@ -290,6 +291,72 @@ class DeviceAdam:
                   self.t, lr=self.lr, betas=self.betas, eps=self.eps, clip=self.clip)
 
 
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _options(self):
+        return {"lr": self.lr, "betas": self.betas, "eps": self.eps, "max_norm": self.max_norm, "n": len(self.params)}
+
+    def state_dict(self):
+        """m and v per parameter (in parameter order) and the step count t, with the hyper-parameters they were taken under; the clip
+        pair and the norm's scratch are rewritten by every step and not saved"""
+        return {"options": self._options(), "m": [ck.cpu(x) for x in self.m], "v": [ck.cpu(x) for x in self.v], "t": ck.cpu(self.t)}
+
+    def _load_plan(self, sd):
+        ck.need_keys("DeviceAdam", sd, ("options", "m", "v", "t"))
+        ck.check_options("DeviceAdam", sd["options"], self._options())
+        pairs = []
+        for name, live in (("m", self.m), ("v", self.v)):
+            if not isinstance(sd[name], (list, tuple)) or len(sd[name]) != len(live):
+                raise ValueError(f"DeviceAdam: `{name}` holds one tensor per parameter ({len(live)})")
+            for i, (dst, src) in enumerate(zip(live, sd[name])):
+                ck.check_tensor("DeviceAdam", f"{name}[{i}]", src, dst)
+                pairs.append((dst, src))
+        ck.check_tensor("DeviceAdam", "t", sd["t"], self.t)
+        pairs.append((self.t, sd["t"]))
+        return lambda: ck.copy_pairs(pairs)
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict into the existing m, v and t (copy_: a captured step graph holds their addresses); validated first"""
+        self._load_plan(sd)()
+
+
+def _torch_adam_state(opt):
+    """torch.optim.Adam's own state_dict with CPU tensors: a plain dict (state by parameter index, param_groups of scalars)"""
+    sd = opt.state_dict()
+    return {"state": {int(i): {k: (ck.cpu(v) if isinstance(v, torch.Tensor) else v) for k, v in st.items()} for i, st in sd["state"].items()},
+            "param_groups": [dict(g, params=list(g["params"])) for g in sd["param_groups"]]}
+
+
+def _torch_adam_plan(opt, sd):
+    """the validated load of _torch_adam_state's dict into a torch.optim.Adam over the same parameters"""
+    ck.need_keys("torch.optim.Adam state", sd, ("state", "param_groups"))
+    params = [p for g in opt.param_groups for p in g["params"]]
+    live = opt.state_dict()["param_groups"]
+    if not isinstance(sd["param_groups"], list) or len(sd["param_groups"]) != len(live):
+        raise ValueError("optimizer: `param_groups` differs in length from the live optimizer's")
+    for i, (a, b) in enumerate(zip(sd["param_groups"], live)):
+        if not isinstance(a, dict) or set(a) != set(b):
+            raise ValueError(f"optimizer: `param_groups[{i}]` has other keys than the live optimizer's")
+        for k in b:
+            va, vb = (tuple(x) if isinstance(x, (list, tuple)) else x for x in (a[k], b[k]))
+            if va != vb:
+                raise ValueError(f"optimizer: `param_groups[{i}].{k}` was {a[k]!r} when saved, the live optimizer has {b[k]!r}")
+    if not isinstance(sd["state"], dict):
+        raise ValueError("optimizer: `state` is a dict by parameter index")
+    for i, st in sd["state"].items():
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(params) or not isinstance(st, dict):
+            raise ValueError(f"optimizer: `state[{i!r}]` names no parameter of the live optimizer")
+        for k in ("exp_avg", "exp_avg_sq"):
+            if k not in st:
+                raise ValueError(f"optimizer: `state[{i}]` has no `{k}`")
+            ck.check_tensor("optimizer", f"state[{i}].{k}", st[k], params[i])
+        if "step" not in st:
+            raise ValueError(f"optimizer: `state[{i}]` has no `step`")
+
+    def commit():
+        opt.load_state_dict({"state": {i: dict(st) for i, st in sd["state"].items()}, "param_groups": [dict(g) for g in sd["param_groups"]]})
+    return commit
+
+
 class _StepBook:
     """what one policy's replayable step keeps on the device: the cursor, the statistics table, and for step="graph" the persistent copy
     of the policy batch, the schedule, the staging buffers and the captured graph"""
@@ -357,6 +424,23 @@ class _PolicySGD:
             self.optimizer, self.book = DeviceAdam(module.parameters(), lr=lr, max_norm=cfg.grad_clip), _StepBook(cfg.device, gnorm=cfg.grad_clip is not None)
         else:
             self.optimizer, self.book = torch.optim.Adam(module.parameters(), lr=lr), None
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def state_dict(self):
+        """kl_coeff and the optimizer's state (DeviceAdam's own, or torch.optim.Adam's); the step book holds nothing that outlives an update"""
+        opt = self.optimizer
+        return {"kl_coeff": float(self.kl_coeff), "adam": opt.state_dict() if self.book is not None else _torch_adam_state(opt)}
+
+    def _load_plan(self, sd):
+        ck.need_keys("the policy's driver", sd, ("kl_coeff", "adam"))
+        if isinstance(sd["kl_coeff"], bool) or not isinstance(sd["kl_coeff"], float):
+            raise ValueError("`kl_coeff` is a float")
+        adam = self.optimizer._load_plan(sd["adam"]) if self.book is not None else _torch_adam_plan(self.optimizer, sd["adam"])
+
+        def commit():
+            adam()
+            self.kl_coeff = sd["kl_coeff"]
+        return commit
 
     def kl_term(self):
         """the KL term's coefficient as the loss takes it: ray tests config["kl_coeff"], the initial value, for the term and for update_kl"""
@@ -547,6 +631,21 @@ def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_s
     learner.use_kl = kl_coeff > 0.0         # ray tests config["kl_coeff"], the initial value, for the KL term and for update_kl
     learner.fused, learner.updates = bool(fused), 0
     return mode
+
+
+LEARNER_OPTIONS = ("seed", "num_sgd_iter", "sgd_minibatch_size", "max_seq_len", "shuffle_sequences", "grad_clip", "step", "fused", "heads", "use_kl",
+                   "clip_param", "kl_target", "vf_clip_param", "vf_loss_coeff", "entropy_coeff")
+
+
+def _learner_saved_options(learner, mode, **more):
+    """the constructor options that decide a learner's arithmetic or its schedule, as its state dict records them"""
+    return dict({k: getattr(learner, k) for k in LEARNER_OPTIONS}, optimizer=mode, **more)
+
+
+def _module_plan(who, module, saved, skip=()):
+    """a module's parameters and buffers from `saved` (its state_dict() without the keys `skip`), copied in place: tied layers stay tied"""
+    live = {k: v for k, v in module.state_dict().items() if k not in skip}
+    return ck.plan_tensors(who, saved, live)
 
 
 def _heads_keyword(init):

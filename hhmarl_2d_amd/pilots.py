@@ -206,6 +206,43 @@ class PolicyBank:
         L.check(L.lib().hh_policy_copy_packed(self.h, int(slot), int(part), C.c_void_p(out.data_ptr()), n.value, C.byref(n), st))
         return out
 
+    # ---- complete snapshots (checkpointing: hh_policy_snapshot / hh_policy_restore, include/hh_policy.h) ----
+    def snapshot(self):
+        """the packed weights of every loaded slot exactly as the kernels read them, the selector table and the row lists, as an opaque
+        blob (uint8 CPU tensor); synchronises the current stream"""
+        return L.snapshot("policy", self.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def restore(self, blob):
+        """a snapshot() blob back into the device arrays in place (addresses, kinds and loaded flags stay: `generation` is not bumped and
+        captured graphs replay with the restored weights).  ValueError, the bank untouched: another max_rows or slot layout, another
+        format version, a truncated blob."""
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.device.type != "cpu":
+            raise ValueError("blob: a 1-D uint8 CPU tensor (PolicyBank.snapshot())")
+        L.restore("policy", self.h, blob.contiguous(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def _layout(self):
+        return {"max_rows": self.max_rows, "slots": tuple(sorted(self.kinds)), "kinds": tuple(self.kinds[k] for k in sorted(self.kinds)),
+                "critics": tuple(sorted(self._critics))}
+
+    def state_dict(self):
+        """the blob, the slot layout it was taken with and the host copy of the selector table"""
+        return {"blob": self.snapshot(), "options": self._layout(), "lut": torch.from_numpy(self._lut.copy())}
+
+    def _load_plan(self, sd):
+        from . import checkpoint as ck
+        ck.need_keys("PolicyBank", sd, ("blob", "options", "lut"))
+        ck.check_options("PolicyBank", sd["options"], self._layout())
+        ck.check_tensor("PolicyBank", "lut", sd["lut"], torch.from_numpy(self._lut))
+        ck.check_blob("PolicyBank", sd["blob"], L.snapshot_bytes("policy", self.h), L.SNAPSHOT_MAGIC["policy"])
+
+        def commit():
+            self.restore(sd["blob"])
+            self._lut = sd["lut"].numpy().copy()
+        return commit
+
+    def load_state_dict(self, sd):
+        self._load_plan(sd)()
+
     def kernel_name(self, n_rows, sampler=False):
         """the forward kernel instance a call of n_rows rows launches (hh_policy_kernel_name)"""
         buf = C.create_string_buffer(64)

@@ -6,6 +6,7 @@ import numbers
 import torch
 
 from . import _lib as L
+from . import checkpoint as ck
 
 ACTION_DIM_AC1, ACTION_DIM_AC2 = 4, 3
 
@@ -410,6 +411,97 @@ class EpisodeBatch:
         r = self.rows()
         return self._critic_rows(r["obs"], r["actions"], agent)
 
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _options(self):
+        """what a saved batch must share with the one it is loaded into"""
+        return {"N": self.N, "T": self.T, "carry_cap": self.carry_cap, "n_agents": self.n_agents, "D": self.D, "aux_name": self.aux_name,
+                "train_batch_size": self.train_batch_size, "metrics": self._metrics is not None, "row_cap": int(self._bufs.row_cap),
+                "ep_cap": int(self._bufs.ep_cap), "gamma": float(self._bufs.gamma), "lam": float(self._bufs.lam)}
+
+    def _whole(self):
+        """the small tensors saved whole: per-arena counts, the emitter's counts, the accumulator, the metrics' summary and totals"""
+        t = {"carried": self.carried, "finished": self._finished, "counts": self._counts}
+        if self._acc is not None:
+            t["acc"] = self._acc
+        if self._metrics is not None:
+            t.update(summary=self._summary, totals=self._totals)
+            if self._m_totals is not self._totals:
+                t["m_totals"] = self._m_totals
+        return t
+
+    def _carry_lead(self, k, m):
+        """entries per arena of carry column k that a carry of at most m rows uses"""
+        return m
+
+    def state_dict(self):
+        """The carry (cut to the longest running episode: rows beyond an arena's `carried` are never read), the per-arena counts, the
+        emitter's counts and the accumulator, the batch's columns and tables cut to what they hold (`rows()`'s cut: with
+        train_batch_size the batch accumulated so far), the metrics' summary and running totals, the aux column with the rest.  Scratch
+        is not saved.  Synchronises the device."""
+        torch.cuda.synchronize(self._device)
+        size = self._size.tolist()
+        m = int(self.carried.max().item()) if self.N else 0
+        return {"options": self._options(), "state": {k: ck.cpu(v) for k, v in self._whole().items()}, "carry_rows": m,
+                "carry": {k: ck.cpu(v[:, :self._carry_lead(k, m)]) for k, v in self._carry.items()},
+                "batch": {k: ck.cpu(getattr(self, k)[:size[i]]) for names, i in self._parts() for k in names}}
+
+    def _load_plan(self, sd):
+        who = type(self).__name__
+        ck.need_keys(who, sd, ("options", "state", "carry_rows", "carry", "batch"))
+        ck.check_options(who, sd["options"], self._options())
+        pairs = ck.plan_tensors(who, sd["state"], self._whole())
+        m = sd["carry_rows"]
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= max(self.carry_cap, 1):
+            raise ValueError(f"{who}: `carry_rows` is {m!r}, the carry holds 0 .. {max(self.carry_cap, 1)} rows per arena")
+        ck.need_keys(who + " carry", sd["carry"], tuple(self._carry))
+        for k, dst in self._carry.items():
+            view = dst[:, :self._carry_lead(k, m)]      # [N, the entries in use, ...]
+            ck.check_tensor(who, "carry." + k, sd["carry"][k], view)
+            pairs.append((view, sd["carry"][k]))
+        size = sd["state"]["acc" if self._acc is not None else "counts"].tolist()
+        parts = self._parts()
+        ck.need_keys(who + " batch", sd["batch"], tuple(k for names, _ in parts for k in names))
+        for names, i in parts:
+            for k in names:
+                ck.check_tensor(who, "batch." + k, sd["batch"][k], getattr(self, k), lead=size[i])
+                pairs.append((getattr(self, k)[:size[i]], sd["batch"][k]))
+        return lambda: ck.copy_pairs(pairs)
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back, in place (every device address stays): everything is validated first — the recorded capacities and
+        options against this batch's, every tensor's dtype and shape — ValueError names the field and nothing was changed"""
+        self._load_plan(sd)()
+
+
+def rollout_state_dict(ro, names, options):
+    """what both rollouts save: their options, the [T(+1), N, ...] window buffers `names` as the last collect left them (the hand-over
+    rows obs[T] / vf[T] among them; update_window directly after a load trains on them), `collects`, `_started` and their episode batch"""
+    torch.cuda.synchronize(ro.w.device)
+    return {"options": options, "window": {k: ck.cpu(getattr(ro, k)) for k in names}, "collects": int(ro.collects), "started": bool(ro._started),
+            "episodes": None if ro.episodes is None else ro.episodes.state_dict()}
+
+
+def rollout_load_plan(ro, sd, names, options):
+    who = type(ro).__name__
+    ck.need_keys(who, sd, ("options", "window", "collects", "started", "episodes"))
+    ck.check_options(who, sd["options"], options)
+    pairs = ck.plan_tensors(who + " window", sd["window"], {k: getattr(ro, k) for k in names})
+    if isinstance(sd["collects"], bool) or not isinstance(sd["collects"], int) or sd["collects"] < 0 or not isinstance(sd["started"], bool):
+        raise ValueError(f"{who}: `collects` is a count and `started` a bool")
+    if (sd["episodes"] is None) != (ro.episodes is None):
+        raise ValueError(f"{who}: `episodes` was {'not ' if sd['episodes'] is None else ''}saved, the live rollout has {'none' if ro.episodes is None else 'one'}")
+    sub = (lambda: None) if ro.episodes is None else ro.episodes._load_plan(sd["episodes"])
+
+    def commit():
+        ck.copy_pairs(pairs)
+        sub()
+        ro.collects, ro._started = sd["collects"], sd["started"]
+        if sd["started"] and getattr(ro, "_graph", None) is None:
+            # a started rollout never calls start(), whose launches are the first of this library in a fresh process: give the next
+            # collect's capture a process that has already launched from the library (a read-only kernel; nothing of the state changes)
+            ro.w.arena_status()
+    return commit
+
 
 class PPORollout:
     """What RLlib's rollout workers produce for train_hetero.py's PPO (train_hetero.py:206-243), for every arena of a `World` at once and
@@ -584,6 +676,27 @@ class PPORollout:
         times (None: no limit; `episodes.ready()` tells afterwards whether the batch is complete) -> self"""
         collect_until_ready(self, max_collects)
         return self
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _window_names(self):
+        return ("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target") + (("logits",) if self.record_logits else ())
+
+    def _options(self):
+        return {"T": self.T, "N": self.w.N, "D": self.w.D, "gamma": self.gamma, "lam": self.lam, "semantics": self.semantics,
+                "batch_mode": self.batch_mode, "record_logits": self.record_logits, "split": self.split}
+
+    def state_dict(self):
+        """the window buffers of the last collect (obs[T] / vf[T] are the hand-over rows of the next one), `collects`, `_started` and the
+        EpisodeBatch; the world and the banks are saved by themselves.  The captured graph is not saved: a fresh rollout captures at its
+        first collect as always, a rollout that has captured keeps replaying (the load writes in place).  Synchronises the device."""
+        return rollout_state_dict(self, self._window_names(), self._options())
+
+    def _load_plan(self, sd):
+        return rollout_load_plan(self, sd, self._window_names(), self._options())
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back in place; validated first (ValueError names the field, nothing changed)"""
+        self._load_plan(sd)()
 
     @property
     def segments(self):

@@ -294,7 +294,33 @@ class World:
         L.check(L.lib().hh_kernel_instance(self.h, int(which), buf, 128))
         return buf.value.decode()
 
-    # ---- host snapshots (parity tests, checkpointing) ----
+    # ---- complete snapshots (checkpointing a running world: hh_world_snapshot / hh_world_restore, include/hh_abi.h) ----
+    def snapshot(self):
+        """everything of this world that outlives a launch (get_state carries the simulation state only) as an opaque blob, a uint8
+        CPU tensor; the trace ring is not in it.  Synchronises the current stream."""
+        return L.snapshot("world", self.h, self._stream())
+
+    def restore(self, blob):
+        """a snapshot() blob back, in place (device addresses stay: captured graphs replay).  ValueError, the world untouched: a blob of a
+        world of another configuration (n_arenas, level, mode, seed, arena_offset, ...), of another bound-bank size, of another format
+        version, or a truncated one."""
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.device.type != "cpu":
+            raise ValueError("blob: a 1-D uint8 CPU tensor (World.snapshot())")
+        L.restore("world", self.h, blob.contiguous(), self._stream())
+
+    def state_dict(self):
+        return {"blob": self.snapshot()}
+
+    def _load_plan(self, sd):
+        from . import checkpoint as ck
+        ck.need_keys("World", sd, ("blob",))
+        ck.check_blob("World", sd["blob"], L.snapshot_bytes("world", self.h), L.SNAPSHOT_MAGIC["world"])
+        return lambda: self.restore(sd["blob"])
+
+    def load_state_dict(self, sd):
+        self._load_plan(sd)()
+
+    # ---- host snapshots of the simulation state (parity tests, golden injection) ----
     def _alloc_state(self):
         n, a = self.N, self.A
         return dict(

@@ -441,6 +441,31 @@ int hh_set_state(hh_world *w, const hh_state_view *view);
  * 24..31 missile launched this step (by unit slot); ten-slot arenas (more than 3 aircraft on a side): hh_spec.h HH_EV_BIT */
 int hh_get_event_masks(hh_world *w, uint32_t *masks, void *stream);
 
+/* Complete snapshots (checkpointing a RUNNING world; csrc/hh_snapshot.h).  hh_get_state / hh_set_state carry the simulation state only:
+ * a world also keeps, across launches, the running episode return and the statistics of the last finished episode (hh_episode_stats), the
+ * rewards accumulated inside a HighLevelEnv macro step and its eval_info counters (hh_eval_info), the sticky action-fault flags
+ * (hh_action_faults), the commands and pilot modes of the macro step in flight, the level-5 per-episode policy draw's counters
+ * (hh_opp_policy), the event masks, the macro-step counter words (hh_hl_tick_count) and, with a bound policy bank (hh_bind_policy), the
+ * bank's row counters and row lists.  A snapshot holds all of it, as opaque bytes [host]:
+ *     header (208 bytes): magic u32 "HHSW", format version u32 (1), digest u64 (FNV-1a of the creating hh_config), N i32, A i32,
+ *                         slot count i32 (0), sections i32 (4), layout words i32 [12] ([0] = max_rows of the bound bank, 0 without
+ *                         one), section sizes u64 [16]
+ *     sections, each on a 16-byte boundary: 0 the creating hh_config | 1 the world's device arrays (one slab) | 2 the bound bank's
+ *                         row counters | 3 its row lists (2, 3: empty without a bound bank)
+ * The trajectory ring of hh_trace_enable is NOT saved: a restore leaves tracing (on or off, the ring's rows and cursors) as the
+ * receiving world has it.  Kernel-instance choices (HH_FORCE_W and its like) belong to the receiving process too.
+ *   hh_world_snapshot_bytes  *bytes = size of this world's snapshot
+ *   hh_world_snapshot        host_buf [host] of at least that size <- the snapshot; ordered behind the work queued on `stream`
+ *   hh_world_restore         the snapshot -> the world.  The WHOLE header is checked before anything is written: a blob of another
+ *                            n_arenas, env kind, level, mode, seed, arena_offset (any other field of hh_config), another bound-bank
+ *                            size, another format version, or a buffer shorter than the snapshot returns HH_E_ARG with the reason in
+ *                            hh_last_error() and leaves the world untouched.
+ * Copies only (no kernel is launched); snapshot and restore synchronise `stream`, like hh_get_state.  A restore into a freshly created
+ * world of the same hh_config needs no hh_reset first. */
+int hh_world_snapshot_bytes(hh_world *w, int64_t *bytes);
+int hh_world_snapshot(hh_world *w, void *host_buf, int64_t bytes, void *stream);
+int hh_world_restore(hh_world *w, const void *host_buf, int64_t bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,16 @@ int hh_commander_episodes_emit_aux(const hh_commander_episode_bufs *b, const str
 int hh_commander_episodes_emit_append(const hh_commander_episode_bufs *b, const struct hh_episode_aux *x, int64_t train_rows,
                                       int32_t *acc, int64_t *totals, void *stream);
 
+/* Complete snapshot of a commander net (checkpointing; csrc/hh_snapshot.h, conventions of hh_world_snapshot in hh_abi.h): the packed
+ * weights exactly as the kernels read them (HH_COMMANDER_PART_PLANES, then HH_COMMANDER_PART_F32) in one section behind the 208-byte
+ * header (magic "HHSC", format version 1, digest of the geometry constants and the section size, N = 0, A = HH_CMD_AGENTS, slot count 1,
+ * layout word [0] = weights loaded).  hh_commander_restore checks the whole header first (HH_E_ARG, nothing written: another version or
+ * geometry, a net without weights on one side only, a short buffer) and writes in place: load the receiving net once with
+ * hh_commander_set_weights.  Copies only; both calls synchronise `stream`. */
+int hh_commander_snapshot_bytes(hh_commander *c, int64_t *bytes);
+int hh_commander_snapshot(hh_commander *c, void *host_buf, int64_t bytes, void *stream);
+int hh_commander_restore(hh_commander *c, const void *host_buf, int64_t bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

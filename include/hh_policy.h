@@ -178,6 +178,22 @@ int hh_policy_refresh(hh_policy *p, int32_t slot, const hh_net_weights *actor, c
 #define HH_POLICY_PART_CRITIC_STREAM 4 /* the value branch's fragment stream + its biases */
 int hh_policy_copy_packed(hh_policy *p, int32_t slot, int32_t part, void *dst, int64_t cap, int64_t *bytes, void *stream);
 
+/* Complete snapshot of a bank (checkpointing; csrc/hh_snapshot.h, conventions of hh_world_snapshot in hh_abi.h): the packed weights of
+ * every loaded slot EXACTLY as the kernels read them (the five HH_POLICY_PART_* parts, the value branch's two only where it is loaded),
+ * so that a restored bank samples the same bytes even when the save fell between a learner's update and its publish; the selector LUT;
+ * the row counters and row lists with the n_rows they were built for (a sel == NULL call after a restore re-uses them).
+ *     header (208 bytes): magic "HHSP", format version (1), digest (FNV-1a of the slot layout words and every part's size), N = max_rows,
+ *                         A = 0, slot count = HH_POLICY_MAX_NETS, sections (11), layout words ([0] n_rows of the current row lists — state,
+ *                         not checked; [1 + s] slot s: -1 empty, else kind | 16 with a loaded value branch), section sizes
+ *     sections: 0 LUT | 1 row counters | 2 row lists | 3 + s slot s (its parts in part order, each on a 16-byte boundary)
+ * hh_policy_restore checks the whole header first: another max_rows, another slot layout (a slot empty here and loaded there, another kind,
+ * a value branch on one side only), another version or a short buffer give HH_E_ARG and leave the bank untouched.  It writes device memory
+ * in place: addresses, kinds and loaded flags do not change, so a HIP graph captured before replays with the restored weights.  Load the
+ * receiving bank's slots once (hh_policy_set_net / hh_policy_set_critic, any weights) before restoring.  Copies only; both calls synchronise `stream`. */
+int hh_policy_snapshot_bytes(hh_policy *p, int64_t *bytes);
+int hh_policy_snapshot(hh_policy *p, void *host_buf, int64_t bytes, void *stream);
+int hh_policy_restore(hh_policy *p, const void *host_buf, int64_t bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
