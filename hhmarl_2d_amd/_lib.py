@@ -104,6 +104,13 @@ class HHEpisodeMetricsBufs(C.Structure):
         ("scratch_bytes", C.c_int64)]
 
 
+class HHWindowMetricsBufs(C.Structure):
+    """hh_window_metrics_bufs (include/hh_abi.h): sizes, then device pointers; field order is ABI"""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("n_agents", C.c_int32), ("reserved0", C.c_int32)] + [
+        (name, C.c_void_p) for name in ("reward", "vf", "target", "done", "run_return", "run_len", "ep_return", "ep_len", "ep_arena", "ep_end",
+                                        "counts", "summary", "totals", "scratch")] + [("scratch_bytes", C.c_int64)]
+
+
 EP_METRICS_MAX_AGENTS = 5  # HH_EP_METRICS_MAX_AGENTS
 # hh_episodes_emit_append's accumulator i32 [HH_EP_ACC], in slot order (slot 7 is reserved and stays 0)
 EP_ACC = ("rows", "episodes", "overflow", "sequences", "complete", "collects", "batches", "reserved")
@@ -123,6 +130,7 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_policy_set_critic", "hh_policy_sample", "hh_policy_kernel_name", "hh_action_faults", "hh_action_tape_uniform",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux",
            "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics", "hh_episodes_emit_append",
+           "hh_window_metrics_scratch_bytes", "hh_window_metrics",
            "hh_world_snapshot_bytes", "hh_world_snapshot", "hh_world_restore", "hh_policy_snapshot_bytes", "hh_policy_snapshot", "hh_policy_restore"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
@@ -246,7 +254,9 @@ def lib():
         L.hh_episodes_emit_append.argtypes = [C.POINTER(HHEpisodeBufs), C.POINTER(HHEpisodeAux), C.c_int64, vp, vp, vp]
         L.hh_episodes_metrics_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.hh_episodes_metrics.argtypes = [C.POINTER(HHEpisodeMetricsBufs), vp]
-        L.hh_math_eval.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.hh_window_metrics_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_window_metrics.argtypes = [C.POINTER(HHWindowMetricsBufs), vp]
+        L.hh_math_eval.argtypes =[C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
         L.hh_policy_destroy.argtypes = [vp]
         L.hh_policy_set_net.argtypes = [vp, C.c_int32, C.POINTER(HHNetWeights)]

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from . import policy_nets as PN
-from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready, rollout_load_plan, rollout_state_dict
+from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready, rollout_load_plan, rollout_state_dict, window_metrics_keyword
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
 
@@ -383,12 +383,19 @@ class CommanderRollout:
     accumulates the collects on the device until it holds at least B rows (commander steps of an arena) — whole collects, nothing
     trimmed — with the same launches per collect.  `collect_batch()` collects until `episodes.ready()`; the collect after a complete
     batch starts the next one.  See CommanderEpisodeBatch for the capacities (its seq_cap is a keyword of the batch, not of the
-    rollout: the rollout takes the safe default)."""
+    rollout: the rollout takes the safe default).
 
+    window_metrics = True (keyword-only; batch_mode = "truncate_episodes" only): the same result line for a run that trains from the
+    windows — `window_metrics`, a `rollout.WindowMetrics` with the per-agent entries keyed 1..3, carries every arena's running return and
+    length across collects and reports the episodes that finish inside each window: five more launches in the collect's graph right
+    behind the GAE.  With the default False it is None and nothing changes."""
+
+    @window_metrics_keyword(CommanderEpisodeBatch.AGENT_KEYS)
     def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
                  carry_cap=None, metrics=False, train_batch_size=None, record_logits=False):
         """batch_mode / max_seq_len / carry_cap: see CommanderEpisodeBatch (carry_cap None = default_carry_cap of the world); metrics /
-        train_batch_size / record_logits: pass them by keyword (record_logits stays the last parameter)"""
+        train_batch_size / record_logits: pass them by keyword (record_logits stays the last parameter); window_metrics is keyword-only
+        (rollout.window_metrics_keyword)"""
         if batch_mode not in ("truncate_episodes", "complete_episodes"):
             raise ValueError("batch_mode: 'truncate_episodes' (fixed [T, N] windows) or 'complete_episodes' (whole episodes cut into GRU "
                              "sequences: CommanderEpisodeBatch)")
@@ -432,6 +439,7 @@ class CommanderRollout:
                                                   self.max_seq_len, cap, self.gamma, self.lam,
                                                   aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
                                                   train_batch_size=train_batch_size)
+        self.window_metrics = None          # window_metrics_keyword puts a rollout.WindowMetrics here
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -448,6 +456,8 @@ class CommanderRollout:
         self.state_in[self.T].zero_()
         if self.episodes is not None:
             self.episodes.reset()
+        if self.window_metrics is not None:
+            self.window_metrics.reset()
         self._started = True
 
     def _run(self):
@@ -470,6 +480,8 @@ class CommanderRollout:
         L.check(L.lib().hh_gae_rllib(T, w.N, N_AGENTS, C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.vf.data_ptr()),
                                      C.c_void_p(self.done.data_ptr()), self.gamma, self.lam, C.c_void_p(self.adv.data_ptr()),
                                      C.c_void_p(self.target.data_ptr()), st))
+        if self.window_metrics is not None:
+            self.window_metrics.enqueue(st)
         if self.episodes is not None:
             self.episodes.emit(st)
 

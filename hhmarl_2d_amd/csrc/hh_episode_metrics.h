@@ -18,6 +18,8 @@
  *                         (sum M2_i + n_i (mean_i - mean)^2): two passes everywhere, never E[x^2] - E[x]^2.  Writes the summary and
  *                         accumulates the totals.  It reads 8 n_agents + 4 bytes per episode on one compute unit: a batch has a few
  *                         thousand episodes (N T / mean length), the table's capacity N T is reached only if every episode had one row.
+ * The bodies of 2. and 3. are the device functions hh_epm_rows_pass / hh_epm_final_fold: hh_window_metrics.h runs the same code over a
+ * rollout window's T N step-rows (its own kernels hh_k_wm_rows / hh_k_wm_final), with its own rule for a call without an episode.
  * Table entries that do not lie inside the emitted rows (possible only after an emitter overflow, which the sticky flag reports) are
  * not followed: their ep_return is NaN.
  *
@@ -93,13 +95,14 @@ __global__ __launch_bounds__(256) void hh_k_epm_episodes(hh_episode_metrics_bufs
     }
 }
 
+/* the row pass over n_rows rows of target / vf [n_rows, NA] -> partial [tiles, 4 NA]; shared by hh_k_epm_rows and the window metrics'
+   hh_k_wm_rows (hh_window_metrics.h), whose rows are a rollout window's T N step-rows */
 template <int NA>
-__global__ __launch_bounds__(256) void hh_k_epm_rows(hh_episode_metrics_bufs m) {
+__device__ __forceinline__ void hh_epm_rows_pass(const int n_rows, const float *__restrict__ target, const float *__restrict__ vf,
+                                                 double *__restrict__ partial) {
     __shared__ double s_w[4];
     const int tid = threadIdx.x;
-    const int n_rows = hh_epm_count(m.counts, 0, m.row_cap);
     const int tiles = (n_rows + HH_EPM_TILE - 1) / HH_EPM_TILE;
-    double *__restrict__ partial = static_cast<double *>(m.scratch);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // workgroup-uniform
         const int r0 = tile * HH_EPM_TILE, n = n_rows - r0 < HH_EPM_TILE ? n_rows - r0 : HH_EPM_TILE;
         double x[4][2 * NA];   // per row of this lane: target [NA], target - vf [NA]
@@ -110,8 +113,8 @@ __global__ __launch_bounds__(256) void hh_k_epm_rows(hh_episode_metrics_bufs m) 
             for (int a = 0; a < NA; a++) {
                 double t = 0.0, v = 0.0;
                 if (i < n) {
-                    t = (double)m.target[(size_t)(r0 + i) * NA + a];
-                    v = (double)m.vf[(size_t)(r0 + i) * NA + a];
+                    t = (double)target[(size_t)(r0 + i) * NA + a];
+                    v = (double)vf[(size_t)(r0 + i) * NA + a];
                 }
                 x[j][a] = t;
                 x[j][NA + a] = t - v;
@@ -139,12 +142,20 @@ __global__ __launch_bounds__(256) void hh_k_epm_rows(hh_episode_metrics_bufs m) 
 }
 
 template <int NA>
-__global__ __launch_bounds__(HH_EPM_FINAL) void hh_k_epm_final(hh_episode_metrics_bufs m) {
+__global__ __launch_bounds__(256) void hh_k_epm_rows(hh_episode_metrics_bufs m) {
+    hh_epm_rows_pass<NA>(hh_epm_count(m.counts, 0, m.row_cap), m.target, m.vf, static_cast<double *>(m.scratch));
+}
+
+/* the last launch's fold of n_eps table entries and the row pass's partials of n_rows rows into the summary and the totals; shared by
+   hh_k_epm_final and the window metrics' hh_k_wm_final.  WINDOW: a call without an episode still has its rows — episodes = 0, rows and
+   the explained variances as always, only the episode slots NaN, totals[1] += n_rows (hh_window_metrics in include/hh_abi.h) */
+template <int NA, bool WINDOW>
+__device__ __forceinline__ void hh_epm_final_fold(const int n_rows, const int n_eps, const double *__restrict__ ep_return,
+                                                  const int32_t *__restrict__ ep_len, const double *__restrict__ partial,
+                                                  double *__restrict__ out, int64_t *__restrict__ totals) {
     __shared__ double s_w[HH_EPM_FINAL / 64];
     const int tid = threadIdx.x;
-    const int n_rows = hh_epm_count(m.counts, 0, m.row_cap), n_eps = hh_epm_count(m.counts, 1, m.ep_cap);
-    double *__restrict__ out = m.summary;
-    if (n_eps == 0) {
+    if (!WINDOW && n_eps == 0) {
         if (tid < HH_EP_METRICS) out[tid] = tid == HH_EPM_EPISODES || tid == HH_EPM_ROWS ? 0.0 : (double)NAN;
         return;
     }
@@ -158,11 +169,11 @@ __global__ __launch_bounds__(HH_EPM_FINAL) void hh_k_epm_final(hh_episode_metric
         double tot = 0.0;
 #pragma unroll
         for (int a = 0; a < NA; a++) {
-            v[a] = m.ep_return[(size_t)e * NA + a];
+            v[a] = ep_return[(size_t)e * NA + a];
             tot += v[a];
         }
         v[NA] = tot;
-        v[NA + 1] = (double)m.ep_len[e];
+        v[NA + 1] = (double)ep_len[e];
 #pragma unroll
         for (int q = 0; q < Q; q++) { sum[q] += v[q]; lo[q] = fmin(lo[q], v[q]); hi[q] = fmax(hi[q], v[q]); }
     }
@@ -174,7 +185,6 @@ __global__ __launch_bounds__(HH_EPM_FINAL) void hh_k_epm_final(hh_episode_metric
     }
     // ---- rows: the tiles' partials [sum t | M2 t | sum d | M2 d] (NA each) -> global means, then M2 around them
     const int tiles = (n_rows + HH_EPM_TILE - 1) / HH_EPM_TILE;
-    const double *__restrict__ partial = static_cast<const double *>(m.scratch);
     double ev[NA];
 #pragma unroll
     for (int a = 0; a < NA; a++) {
@@ -196,22 +206,29 @@ __global__ __launch_bounds__(HH_EPM_FINAL) void hh_k_epm_final(hh_episode_metric
         ev[a] = e < -1.0 ? -1.0 : e;   // NaN (no variance in either) stays NaN
     }
     if (tid == 0) {
-        const double ne = (double)n_eps;
+        const bool none = WINDOW && n_eps == 0;   // the episode slots of a window without a finished episode: NaN (0 / 0, +-inf otherwise)
+        const double ne = (double)n_eps, nan = (double)NAN;
         out[HH_EPM_EPISODES] = ne;
         out[HH_EPM_ROWS] = (double)n_rows;
-        out[HH_EPM_REWARD_MEAN] = sum[NA] / ne; out[HH_EPM_REWARD_MIN] = lo[NA]; out[HH_EPM_REWARD_MAX] = hi[NA];
-        out[HH_EPM_LEN_MEAN] = sum[NA + 1] / ne; out[HH_EPM_LEN_MIN] = lo[NA + 1]; out[HH_EPM_LEN_MAX] = hi[NA + 1];
+        out[HH_EPM_REWARD_MEAN] = none ? nan : sum[NA] / ne; out[HH_EPM_REWARD_MIN] = none ? nan : lo[NA]; out[HH_EPM_REWARD_MAX] = none ? nan : hi[NA];
+        out[HH_EPM_LEN_MEAN] = none ? nan : sum[NA + 1] / ne; out[HH_EPM_LEN_MIN] = none ? nan : lo[NA + 1]; out[HH_EPM_LEN_MAX] = none ? nan : hi[NA + 1];
 #pragma unroll
         for (int a = 0; a < HH_EP_METRICS_MAX_AGENTS; a++) {
-            const bool on = a < NA;
-            out[HH_EPM_AGENT_MEAN + a] = on ? sum[a < NA ? a : 0] / ne : (double)NAN;
-            out[HH_EPM_AGENT_MIN + a] = on ? lo[a < NA ? a : 0] : (double)NAN;
-            out[HH_EPM_AGENT_MAX + a] = on ? hi[a < NA ? a : 0] : (double)NAN;
-            out[HH_EPM_AGENT_EXPLAINED_VAR + a] = on ? ev[a < NA ? a : 0] : (double)NAN;
+            const bool on = a < NA, ep = on && !none;
+            out[HH_EPM_AGENT_MEAN + a] = ep ? sum[a < NA ? a : 0] / ne : nan;
+            out[HH_EPM_AGENT_MIN + a] = ep ? lo[a < NA ? a : 0] : nan;
+            out[HH_EPM_AGENT_MAX + a] = ep ? hi[a < NA ? a : 0] : nan;
+            out[HH_EPM_AGENT_EXPLAINED_VAR + a] = on ? ev[a < NA ? a : 0] : nan;
         }
-        m.totals[0] += (int64_t)n_eps;
-        m.totals[1] += (int64_t)n_rows;
+        totals[0] += (int64_t)n_eps;
+        totals[1] += (int64_t)n_rows;
     }
+}
+
+template <int NA>
+__global__ __launch_bounds__(HH_EPM_FINAL) void hh_k_epm_final(hh_episode_metrics_bufs m) {
+    hh_epm_final_fold<NA, false>(hh_epm_count(m.counts, 0, m.row_cap), hh_epm_count(m.counts, 1, m.ep_cap), m.ep_return, m.ep_len,
+                                 static_cast<const double *>(m.scratch), m.summary, m.totals);
 }
 
 /* ---- host side ---- */

@@ -918,5 +918,8 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 /* ---- a rollout's fixed [T, N] window as the learners' padded sequences: the cut and the gather (C ABI in include/hh_learner.h) ---- */
 #include "hh_window_batch.h"
 
+/* ---- RLlib's episode metrics for fixed-window rollouts: a per-arena carry across windows (C ABI in include/hh_abi.h: hh_window_metrics) ---- */
+#include "hh_window_metrics.h"
+
 /* ---- opaque, complete snapshots of a world, a policy bank and a commander net: copies only (C ABI in include/hh_abi.h, hh_policy.h, hh_commander.h) ---- */
 #include "hh_snapshot.h"

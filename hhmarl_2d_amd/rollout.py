@@ -1,6 +1,8 @@
 """Rollout post-processing next to the environment: the centralised-critic input
 packing of train_hetero.py:113-181 and GAE (train_hetero.py:216) on device tensors."""
 import ctypes as C
+import functools
+import inspect
 import numbers
 
 import torch
@@ -107,6 +109,20 @@ def collect_until_ready(rollout, max_collects=None):
         n += 1
         if rollout.episodes.ready() or (max_collects is not None and n >= int(max_collects)):
             return n
+
+
+def metrics_dict(s, totals, agent_keys):
+    """a summary block (list of len(_lib.EP_METRICS) floats: hh_episodes_metrics' / hh_window_metrics' slots) and the totals [2] under
+    RLlib's result names: what EpisodeBatch.metrics() and WindowMetrics.metrics() return"""
+    slot = L.EP_METRICS_SLOT
+    per_agent = lambda name: {k: s[slot[name + "_0"] + a] for a, k in enumerate(agent_keys)}
+    out = {k: s[slot[k]] for k in ("episode_reward_mean", "episode_reward_min", "episode_reward_max", "episode_len_mean", "episode_len_min",
+                                   "episode_len_max")}
+    out.update(episodes_this_iter=int(s[slot["episodes"]]), timesteps_this_iter=int(s[slot["rows"]]),
+               policy_reward_mean=per_agent("agent_return_mean"), policy_reward_min=per_agent("agent_return_min"),
+               policy_reward_max=per_agent("agent_return_max"), vf_explained_var=per_agent("vf_explained_var"),
+               episodes_total=int(totals[0]), timesteps_total=int(totals[1]))
+    return out
 
 
 class EpisodeBatch:
@@ -387,15 +403,7 @@ class EpisodeBatch:
         s, totals, *flags = (h.tolist() for h in self._m_host)
         if any(f[2] for f in flags):
             raise self._overflow()
-        slot = L.EP_METRICS_SLOT
-        per_agent = lambda name: {k: s[slot[name + "_0"] + a] for a, k in enumerate(self.AGENT_KEYS)}
-        out = {k: s[slot[k]] for k in ("episode_reward_mean", "episode_reward_min", "episode_reward_max", "episode_len_mean", "episode_len_min",
-                                       "episode_len_max")}
-        out.update(episodes_this_iter=int(s[slot["episodes"]]), timesteps_this_iter=int(s[slot["rows"]]),
-                   policy_reward_mean=per_agent("agent_return_mean"), policy_reward_min=per_agent("agent_return_min"),
-                   policy_reward_max=per_agent("agent_return_max"), vf_explained_var=per_agent("vf_explained_var"),
-                   episodes_total=int(totals[0]), timesteps_total=int(totals[1]))
-        return out
+        return metrics_dict(s, totals, self.AGENT_KEYS)
 
     def rows(self):
         """synchronises; -> dict of views cut to the last collect (with train_batch_size: to the accumulated batch so far): the columns
@@ -473,18 +481,187 @@ class EpisodeBatch:
         self._load_plan(sd)()
 
 
+class WindowMetrics:
+    """RLlib's per-iteration episode metrics of a rollout in batch_mode = "truncate_episodes" (`PPORollout(..., window_metrics=True)`,
+    `CommanderRollout(..., window_metrics=True)`): the training curve of a run that trains from fixed [T, N] windows
+    (`update_window`), without the carry and the second batch of "complete_episodes".  A window cuts episodes, so a small per-arena
+    state lives on the device across collects — `run_return` f64 [N, n_agents] and `run_len` i32 [N], the return and the rows so far of
+    every arena's running episode — and hh_window_metrics (include/hh_abi.h: five launches in the collect's graph right behind the GAE,
+    float64, one sequential addition per row, no atomics, no host synchronisation) tabulates the episodes that finish inside each
+    window, their rows of earlier windows included, and summarises them under the names of `EpisodeBatch.metrics()`.
+
+    Device buffers, overwritten by every collect (the first n_episodes entries are valid; arena-major, then t): `ep_return` f64 [T N,
+    n_agents], `ep_len` / `ep_arena` / `ep_end` i32 [T N] (the whole episode's rows, its arena, the t of its done row in this window),
+    `counts` i32 [2] (episodes, rows = T N), `summary` f64 [len(_lib.EP_METRICS)], `totals` i64 [2] (episodes_total, timesteps_total
+    since start() / reset()).  12 + 8 n_agents bytes per window row and 8 + 8 n_agents per arena: 29.8 MB for N = 16384, T = 64 and two
+    agents (the table has room for an episode at every row, so it cannot overflow).
+
+    The two differences from RLlib of EpisodeBatch's metrics hold here too (the means are over the episodes finished in THIS window, no
+    smoothing over the last 100; `vf_explained_var` is the sampler's VF_PREDS against the value targets), and `vf_explained_var` is
+    taken over the window's T N rows, whose targets bootstrap at the window's end.  A window without a finished episode reports
+    episodes_this_iter = 0 and nan for the episode entries, but its timesteps and vf_explained_var as always."""
+
+    TABLES = ("ep_return", "ep_len", "ep_arena", "ep_end")
+
+    def __init__(self, collect, agent_keys):
+        """collect: the rollout's window buffers every call reads — reward f32 [T, N, n_agents], vf f32 [T+1, N, n_agents], target f32
+        [T, N, n_agents], done u8 [T, N]; agent_keys: the keys of metrics()' per-agent entries (the matching episode batch's AGENT_KEYS)"""
+        T, N = collect["done"].shape
+        self.T, self.N, self.n_agents = int(T), int(N), int(collect["reward"].shape[2])
+        self.AGENT_KEYS = tuple(agent_keys)
+        if not 1 <= self.n_agents <= L.EP_METRICS_MAX_AGENTS or len(self.AGENT_KEYS) != self.n_agents:
+            raise ValueError(f"window_metrics: {len(self.AGENT_KEYS)} agent keys, the collect has {self.n_agents} agents")
+        T, N, nA = self.T, self.N, self.n_agents
+        for k, shape, dt in (("reward", (T, N, nA), torch.float32), ("vf", (T + 1, N, nA), torch.float32), ("target", (T, N, nA), torch.float32),
+                             ("done", (T, N), torch.uint8)):
+            t = collect[k]
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"window_metrics: {k} must be a contiguous {dt} tensor of shape {shape}")
+        self._device = dev = collect["done"].device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        nbytes = C.c_int64(0)
+        L.check(L.lib().hh_window_metrics_scratch_bytes(T, N, nA, C.byref(nbytes)))
+        self.run_return, self.run_len = z((N, nA), torch.float64), z((N,), torch.int32)
+        self.ep_return = z((T * N, nA), torch.float64)
+        self.ep_len, self.ep_arena, self.ep_end = (z((T * N,), torch.int32) for _ in range(3))
+        self.counts = z((2,), torch.int32)
+        self.n_episodes = self.counts[0]
+        self._summary = z((len(L.EP_METRICS),), torch.float64)
+        self._totals = z((2,), torch.int64)
+        self._scratch = z((nbytes.value // 8,), torch.float64)
+        self._host = None                        # pinned host copies (summary, totals), made by the first metrics()
+        self._collect = collect                  # the struct holds raw pointers: keep the tensors alive
+        self._bufs = L.HHWindowMetricsBufs(
+            T=T, N=N, n_agents=nA, reserved0=0, reward=collect["reward"].data_ptr(), vf=collect["vf"].data_ptr(),
+            target=collect["target"].data_ptr(), done=collect["done"].data_ptr(), run_return=self.run_return.data_ptr(),
+            run_len=self.run_len.data_ptr(), ep_return=self.ep_return.data_ptr(), ep_len=self.ep_len.data_ptr(),
+            ep_arena=self.ep_arena.data_ptr(), ep_end=self.ep_end.data_ptr(), counts=self.counts.data_ptr(),
+            summary=self._summary.data_ptr(), totals=self._totals.data_ptr(), scratch=self._scratch.data_ptr(), scratch_bytes=nbytes.value)
+        self.reset()
+
+    def reset(self):
+        """no episode spans a reset: the carry and the running totals start again, and the summary is that of a window without a
+        finished episode, with 0 rows, until the next collect"""
+        self.run_return.zero_()
+        self.run_len.zero_()
+        self._totals.zero_()
+        self.counts.zero_()
+        self._summary.fill_(float("nan"))
+        self._summary[:2] = 0.0
+
+    def enqueue(self, stream):
+        """hh_window_metrics over the window as it stands, on `stream` (what the rollout's collect does right behind the GAE).  Every
+        call advances the carry and the totals by one window."""
+        L.check(L.lib().hh_window_metrics(C.byref(self._bufs), stream))
+
+    def metrics_device(self):
+        """the device tensors of the last collect's metrics, without synchronising: `summary` (slots: _lib.EP_METRICS_SLOT), `totals`,
+        the table `ep_return` / `ep_len` / `ep_arena` / `ep_end` (the first counts[0] entries are valid) and `counts`.  Overwritten by
+        the next collect."""
+        return {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return, "ep_len": self.ep_len,
+                "ep_arena": self.ep_arena, "ep_end": self.ep_end, "counts": self.counts}
+
+    def metrics(self):
+        """-> the last window's metrics under RLlib's result names, the keys and types of `EpisodeBatch.metrics()` (per-agent entries are
+        dicts keyed by AGENT_KEYS); copies the summary and the totals to the host: one synchronisation of the current stream.  After
+        reset() / start() and before the next collect: 0 episodes, 0 timesteps, nan, totals 0."""
+        src = (self._summary, self._totals)
+        if self._host is None:
+            self._host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in src)
+        for h, d in zip(self._host, src):
+            h.copy_(d, non_blocking=True)
+        torch.cuda.current_stream(self._device).synchronize()
+        s, totals = (h.tolist() for h in self._host)
+        return metrics_dict(s, totals, self.AGENT_KEYS)
+
+    def episodes(self):
+        """synchronises; -> dict of views cut to the episodes that finished in the last window: ep_return, ep_len, ep_arena, ep_end"""
+        torch.cuda.synchronize(self._device)
+        n = int(self.counts[0])
+        return {k: getattr(self, k)[:n] for k in self.TABLES}
+
+    # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
+    def _options(self):
+        return {"T": self.T, "N": self.N, "n_agents": self.n_agents}
+
+    def _whole(self):
+        return {"run_return": self.run_return, "run_len": self.run_len, "counts": self.counts, "summary": self._summary, "totals": self._totals}
+
+    def state_dict(self):
+        """the carry, the counts, the summary and the totals whole, the table cut to the count.  Scratch is not saved.  Synchronises the
+        device."""
+        torch.cuda.synchronize(self._device)
+        n = int(self.counts[0])
+        return {"options": self._options(), "state": {k: ck.cpu(v) for k, v in self._whole().items()},
+                "table": {k: ck.cpu(getattr(self, k)[:n]) for k in self.TABLES}}
+
+    def _load_plan(self, sd):
+        who = type(self).__name__
+        ck.need_keys(who, sd, ("options", "state", "table"))
+        ck.check_options(who, sd["options"], self._options())
+        pairs = ck.plan_tensors(who, sd["state"], self._whole())
+        n = int(sd["state"]["counts"][0])
+        if not 0 <= n <= self.T * self.N:
+            raise ValueError(f"{who}: `counts` names {n} episodes, a window of {self.T * self.N} rows ends at most that many")
+        ck.need_keys(who + " table", sd["table"], self.TABLES)
+        for k in self.TABLES:
+            ck.check_tensor(who, "table." + k, sd["table"][k], getattr(self, k), lead=n)
+            pairs.append((getattr(self, k)[:n], sd["table"][k]))
+        return lambda: ck.copy_pairs(pairs)
+
+    def load_state_dict(self, sd):
+        """state_dict()'s dict back, in place; validated first (ValueError names the field, nothing changed)"""
+        self._load_plan(sd)()
+
+
+def check_window_metrics(window_metrics, batch_mode, semantics="rllib"):
+    """window_metrics as both rollouts' constructors take it -> bool, or ValueError"""
+    if not window_metrics:
+        return False
+    if batch_mode != "truncate_episodes":
+        raise ValueError("window_metrics=True needs batch_mode='truncate_episodes': batch_mode='complete_episodes' already has metrics=True")
+    if semantics != "rllib":
+        raise ValueError("window_metrics=True is defined for RLlib's trajectory view only (semantics='rllib'): its targets are hh_gae_rllib's")
+    return True
+
+
+def window_metrics_keyword(agent_keys):
+    """Decorator of both rollouts' `__init__`: adds the keyword-only `window_metrics=False` behind the positional parameters.  It is
+    validated (check_window_metrics) before the constructor runs, so before the world is touched, and afterwards `self.window_metrics`
+    is a WindowMetrics over the new rollout's window buffers, or None.  A wrapper instead of one more parameter in the `def`: the
+    constructors' positional signature — what `inspect.signature` reports through `__wrapped__` — ends with `record_logits`, where its
+    callers and the signature tests expect it, and stays as it was."""
+    def wrap(init):
+        sig = inspect.signature(init)
+
+        @functools.wraps(init)
+        def __init__(self, *args, window_metrics=False, **kw):
+            a = sig.bind(self, *args, **kw)          # TypeError for arguments the constructor does not take, as from the constructor
+            a.apply_defaults()
+            on = check_window_metrics(window_metrics, a.arguments["batch_mode"], a.arguments.get("semantics", "rllib"))
+            init(self, *args, **kw)
+            self.window_metrics = WindowMetrics({k: getattr(self, k) for k in ("reward", "vf", "target", "done")}, agent_keys) if on else None
+        return __init__
+    return wrap
+
+
 def rollout_state_dict(ro, names, options):
     """what both rollouts save: their options, the [T(+1), N, ...] window buffers `names` as the last collect left them (the hand-over
-    rows obs[T] / vf[T] among them; update_window directly after a load trains on them), `collects`, `_started` and their episode batch"""
+    rows obs[T] / vf[T] among them; update_window directly after a load trains on them), `collects`, `_started` and their episode batch;
+    with window_metrics=True one more entry, `window_metrics`"""
     torch.cuda.synchronize(ro.w.device)
-    return {"options": options, "window": {k: ck.cpu(getattr(ro, k)) for k in names}, "collects": int(ro.collects), "started": bool(ro._started),
-            "episodes": None if ro.episodes is None else ro.episodes.state_dict()}
+    sd = {"options": options, "window": {k: ck.cpu(getattr(ro, k)) for k in names}, "collects": int(ro.collects), "started": bool(ro._started),
+          "episodes": None if ro.episodes is None else ro.episodes.state_dict()}
+    if ro.window_metrics is not None:
+        sd["window_metrics"] = ro.window_metrics.state_dict()
+    return sd
 
 
 def rollout_load_plan(ro, sd, names, options):
     who = type(ro).__name__
-    ck.need_keys(who, sd, ("options", "window", "collects", "started", "episodes"))
+    ck.need_keys(who, sd, ("options", "window", "collects", "started", "episodes") + (("window_metrics",) if ro.window_metrics is not None else ()))
     ck.check_options(who, sd["options"], options)
+    wm = (lambda: None) if ro.window_metrics is None else ro.window_metrics._load_plan(sd["window_metrics"])
     pairs = ck.plan_tensors(who + " window", sd["window"], {k: getattr(ro, k) for k in names})
     if isinstance(sd["collects"], bool) or not isinstance(sd["collects"], int) or sd["collects"] < 0 or not isinstance(sd["started"], bool):
         raise ValueError(f"{who}: `collects` is a count and `started` a bool")
@@ -495,6 +672,7 @@ def rollout_load_plan(ro, sd, names, options):
     def commit():
         ck.copy_pairs(pairs)
         sub()
+        wm()
         ro.collects, ro._started = sd["collects"], sd["started"]
         if sd["started"] and getattr(ro, "_graph", None) is None:
             # a started rollout never calls start(), whose launches are the first of this library in a fresh process: give the next
@@ -554,12 +732,19 @@ class PPORollout:
     train_batch_size = B (batch_mode = "complete_episodes" only; train_hetero.py:216 `train_batch_size=args.batch_size`): `episodes`
     accumulates the collects on the device until it holds at least B rows — whole collects, nothing trimmed — instead of being
     overwritten by each; the launches of a collect and its graph stay the same.  `collect_batch()` collects until `episodes.ready()`;
-    the collect after a complete batch starts the next one.  See EpisodeBatch for the capacities."""
+    the collect after a complete batch starts the next one.  See EpisodeBatch for the capacities.
 
+    window_metrics = True (keyword-only; batch_mode = "truncate_episodes" and semantics = "rllib" only): the same result line for a run
+    that trains from the windows — `window_metrics`, a `WindowMetrics`, carries every arena's running return and length on the device
+    across collects and reports the episodes that finish inside each window (`window_metrics.metrics()`: the keys of
+    `episodes.metrics()`): five more launches in the collect's graph right behind the GAE.  With the default False it is None, nothing
+    is allocated and the launches, the graph, the buffers and `state_dict()` are what they were."""
+
+    @window_metrics_keyword(EpisodeBatch.AGENT_KEYS)
     def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes",
                  metrics=False, train_batch_size=None, record_logits=False):
         """metrics / train_batch_size / record_logits: pass them by keyword (record_logits stays the last parameter, where its callers and
-        its test expect it).
+        its test expect it); window_metrics is keyword-only (window_metrics_keyword).
         opponents: levels 4-5 only (env_hetero.py:160-172: frozen-policy opponents observe and act between the agents' actions and the tick) —
         a `pilots.OpponentNets(world, skip_first=False)` (its bank bound, so that hh_step_begin lists the opponents' rows itself) or any
         callable(opp_obs f32 [N, 2, 30] on the device, None) -> int8 [N, 2, 4] that only enqueues work on the current stream"""
@@ -615,6 +800,7 @@ class PPORollout:
             self.episodes = EpisodeBatch({k: getattr(self, k) for k in EpisodeBatch.ROW_INPUTS + ("done",)}, max(world.cfg.horizon - 1, 0),
                                          self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
                                          train_batch_size=train_batch_size)
+        self.window_metrics = None          # window_metrics_keyword puts a WindowMetrics here
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -626,6 +812,8 @@ class PPORollout:
         self.w.reset(obs=self.obs[self.T])
         if self.episodes is not None:
             self.episodes.reset()
+        if self.window_metrics is not None:
+            self.window_metrics.reset()
         self.bank.sample(self.obs[self.T], self.sel, greedy=True, actions=self._tmp_act, logp=self._tmp_logp, vf=self.vf[self.T])
         self._started = True
 
@@ -652,6 +840,8 @@ class PPORollout:
         else:
             L.check(L.lib().hh_gae(T, self.w.N, 2, _p(self.reward), _p(self.vf), _p(self.valid), _p(self.done), self.gamma, self.lam,
                                    _p(self.adv), _p(self.target), st))
+        if self.window_metrics is not None:
+            self.window_metrics.enqueue(st)
         if self.episodes is not None:
             self.episodes.emit(st)
 

@@ -423,6 +423,51 @@ typedef struct hh_episode_metrics_bufs {
 int hh_episodes_metrics_scratch_bytes(int64_t ep_cap, int64_t row_cap, int32_t n_agents, int64_t *bytes);
 int hh_episodes_metrics(const hh_episode_metrics_bufs *m, void *stream);
 
+/* The same metrics for FIXED-WINDOW rollouts (batch_mode = "truncate_episodes"), computed on the device right behind the window's
+ * hh_gae_rllib.  A window of T steps cuts episodes, so every arena carries its running episode's return and length across calls, and
+ * the episodes that finish inside a window are tabulated and summarised.  Five launches on `stream`, no host synchronisation, no
+ * allocation (graph-capturable), no atomics of any kind.  For arena n, t = 0 .. T-1 in order:
+ *   run_return[n, a] += (double)reward[t, n, a]   ONE float64 addition per row, in time order, across windows: a host restatement with
+ *                                                 sequential sums gives the same bits, wherever the windows cut the episode
+ *   run_len[n] += 1
+ *   where done[t, n] != 0: the next table entry gets ep_arena = n, ep_end = t, ep_len = run_len[n], ep_return = run_return[n, :] — the
+ *                          rows of earlier windows included — and both running values go back to 0.
+ * The table is arena-major, then t; it has at most T N entries, so nothing can overflow; entries beyond counts[0] are never written.
+ *   counts           i32 [2] out: [0] episodes that ended in this window, [1] rows = T N
+ *   summary          f64 [HH_EP_METRICS]: the HH_EPM_* slots with exactly hh_episodes_metrics' meaning — an episode's reward is the sum
+ *                    of its agents' returns in agent order, the per-agent mean / min / max are over the window's finished episodes,
+ *                    the explained variance of agent a is over ALL T N rows of the window (target against rows 0 .. T-1 of vf), by the
+ *                    same two-pass tile scheme; rows = T N in every call.
+ *   totals           i64 [2], accumulated: [0] episodes_total += episodes, [1] timesteps_total += T N (environment steps).  The caller
+ *                    zeroes it, and run_return / run_len, before the first window.
+ * ONE DIFFERENCE from hh_episodes_metrics, on purpose: with 0 episodes, episodes = 0, rows = T N and the explained variances are still
+ * computed; only the episode slots (reward, length, per-agent mean / min / max) are NaN, and totals[1] += T N all the same — a window's
+ * steps count whether or not an episode ended in it.
+ * Determinism: float64; the carry is one sequential chain per arena and agent; the table's order comes from an exclusive scan of the
+ * arenas' counts; the summary's sums are hh_episodes_metrics' (fixed order, independent of the grid size) — the same inputs give the
+ * same bytes on every run.
+ * HH_E_ARG, nothing enqueued (hh_last_error() starts with "hh_window_metrics: "): m = NULL, a NULL pointer, T < 1, N < 1, T N above
+ * 2^31 - 1024, n_agents outside 1 .. HH_EP_METRICS_MAX_AGENTS, reserved0 != 0, reward / vf / target / run_len / ep_len / ep_arena /
+ * ep_end / counts not 4-byte aligned, run_return / ep_return / summary / totals / scratch not 8-byte aligned, scratch_bytes below
+ * hh_window_metrics_scratch_bytes(T, N, n_agents). */
+typedef struct hh_window_metrics_bufs {   /* field order is ABI; host struct of device pointers */
+    int32_t T, N, n_agents, reserved0;    /* n_agents 1 .. HH_EP_METRICS_MAX_AGENTS; reserved0 must be 0 */
+    const float *reward;                  /* [dev] f32 [T, N, n_agents]  the window as the rollouts hold it */
+    const float *vf;                      /* [dev] f32 [T+1, N, n_agents]; rows 0 .. T-1 are read */
+    const float *target;                  /* [dev] f32 [T, N, n_agents] */
+    const uint8_t *done;                  /* [dev] u8  [T, N] */
+    double *run_return;                   /* [dev] f64 [N, n_agents] in/out: return so far of every arena's running episode */
+    int32_t *run_len;                     /* [dev] i32 [N] in/out: its rows so far */
+    double *ep_return;                    /* [dev] f64 [T N, n_agents] out: episodes that ended in this window */
+    int32_t *ep_len, *ep_arena, *ep_end;  /* [dev] i32 [T N] out: rows of the whole episode, its arena, the t of its done row */
+    int32_t *counts;                      /* [dev] i32 [2] out: episodes, rows (= T N) */
+    double *summary;                      /* [dev] f64 [HH_EP_METRICS] out: the HH_EPM_* slots, unchanged */
+    int64_t *totals;                      /* [dev] i64 [2] in/out: episodes_total, timesteps_total */
+    void *scratch; int64_t scratch_bytes;
+} hh_window_metrics_bufs;
+int hh_window_metrics_scratch_bytes(int32_t T, int32_t N, int32_t n_agents, int64_t *bytes);
+int hh_window_metrics(const hh_window_metrics_bufs *m, void *stream);
+
 /* Test probe: the shared math of include/hh_math.h / hh_geodesic.h evaluated ON THE DEVICE over arrays of operands, so that a
  * -m gpu test can compare the kernels' arithmetic with the CPU oracle's bit for bit (tests/test_gpu_math.py), not only through
  * trajectories.  fn: 0 sincos(a) -> o0, o1 | 1 atan2(a, b) | 2 acos(a) | 3 sincosd(a) -> o0, o1 | 4 atan2d(a, b) | 5 pymod(a, b) |

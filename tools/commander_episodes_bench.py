@@ -9,8 +9,10 @@ batch; with it only those lines are written, APPENDED to --out.
 --accumulate measures only what train_batch_size costs a collect: complete_episodes overwriting its batch against complete_episodes
 appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_timing.py: medians of 20 after 3 warm-up, the spread
 rule); its lines are APPENDED to --out.
+--window measures only what window_metrics=True costs a truncate_episodes collect (tools/episode_metrics_timing.py: the same rule, and
+hh_window_metrics's five launches alone); its lines are APPENDED to --out.
     python tools/commander_episodes_bench.py [--arenas 8192] [--steps 16] [--horizon 500] [--warmup 8] [--collects 10] [--rounds 3]
-        [--logits] [--metrics] [--accumulate] [--out profiles/commander_episodes.log]"""
+        [--logits] [--metrics] [--accumulate] [--window] [--out profiles/commander_episodes.log]"""
 import argparse
 import math
 import os
@@ -26,7 +28,7 @@ from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weigh
 from hhmarl_2d_amd.pilots import VariantNetPilot  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
 from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
-from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
+from episode_metrics_timing import metrics_lines, window_lines  # noqa: E402  (tools/, next to this file)
 
 ROW_IN = 3 * 34 * 4 + 3 + 3 * 4 * 3 + 3          # obs, actions, logp / vf / reward, valid of one arena row
 ROW_OUT = ROW_IN + 3 * 4 * 2 + 1 + 3 * 4          # + adv / target, done, arena / episode / t
@@ -38,7 +40,7 @@ def make(N, T, H, mode, train_batch_size=None):
     net = CommanderNet(0, 3 * N).set_weights(random_weights(6))
     rec, met = mode.endswith("+logits"), mode.endswith("+metrics")
     return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode.split("+")[0], metrics=met, train_batch_size=train_batch_size,
-                            record_logits=rec)
+                            record_logits=rec, window_metrics=mode.endswith("+window_metrics"))
 
 
 def ms_per_collect(ro, n):
@@ -77,8 +79,17 @@ def main():
     ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends only its lines to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_episodes.log"))
     ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
+    ap.add_argument("--window", action="store_true", help="only: what window_metrics=True costs a truncate_episodes collect; appends its lines to --out")
     a = ap.parse_args()
     N, T, H = a.arenas, a.steps, a.horizon
+    if a.window:
+        wlines = [f"# tools/commander_episodes_bench.py --window on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per "
+                  f"collect, VariantNetPilot, horizon {H}"]
+        wlines += window_lines(make(N, T, H, "truncate_episodes"), make(N, T, H, "truncate_episodes+window_metrics"))
+        print("\n".join(wlines), flush=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(wlines) + "\n")
+        return
     if a.accumulate:
         alines = [f"# tools/commander_episodes_bench.py --accumulate on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per "
                   f"collect, VariantNetPilot, horizon {H}"]

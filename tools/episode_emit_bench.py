@@ -12,8 +12,10 @@ overhead, and the time of the three metrics launches alone on the last batch; th
 --accumulate measures only what train_batch_size costs a collect: complete_episodes overwriting its batch against complete_episodes
 appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_timing.py: medians of 20 after 3 warm-up, the spread
 rule); its lines are appended to --out.
+--window measures only what window_metrics=True costs a truncate_episodes collect (tools/episode_metrics_timing.py: the same rule, and
+hh_window_metrics's five launches alone); its lines are appended to --out.
     python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]
-        [--metrics [--out profiles/episode_emit.log]] | --accumulate [--arenas 16384] [--ticks 64] [--out ...]"""
+        [--metrics [--out profiles/episode_emit.log]] | --accumulate | --window [--arenas 16384] [--ticks 64] [--out ...]"""
 import argparse
 import os
 import statistics
@@ -26,12 +28,14 @@ from hhmarl_2d_amd import pilots  # noqa: E402
 from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
 from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
-from episode_metrics_timing import metrics_lines  # noqa: E402  (tools/, next to this file)
+from episode_metrics_timing import metrics_lines, window_lines  # noqa: E402  (tools/, next to this file)
 
 
 def make(N, T, mode, train_batch_size=None):
     w = World(make_config(n_arenas=N, level=3, seed=1, auto_reset=True), device=0)
     bank = pilots.PolicyBank.trainable_init(w.device, seed=0, max_rows=2 * N)
+    if mode.endswith("+window_metrics"):
+        return PPORollout(w, bank, T, batch_mode=mode[:-len("+window_metrics")], window_metrics=True)
     if train_batch_size is not None:
         return PPORollout(w, bank, T, batch_mode=mode, train_batch_size=train_batch_size)
     if mode.endswith("+metrics"):
@@ -75,8 +79,16 @@ def main():
     ap.add_argument("--metrics", action="store_true", help="also time complete_episodes with metrics=True; appends its lines to --out")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "episode_emit.log"))
     ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
+    ap.add_argument("--window", action="store_true", help="only: what window_metrics=True costs a truncate_episodes collect; appends its lines to --out")
     a = ap.parse_args()
     N, T = a.arenas, a.ticks
+    if a.window:
+        lines = [f"# tools/episode_emit_bench.py --window on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, level 3 fight"]
+        lines += window_lines(make(N, T, "truncate_episodes"), make(N, T, "truncate_episodes+window_metrics"))
+        print("\n".join(lines))
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.accumulate:
         lines = [f"# tools/episode_emit_bench.py --accumulate on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, level 3 fight"]
         lines += accumulate_lines(make(N, T, "complete_episodes"), make(N, T, "complete_episodes", train_batch_size=4 * N * T))
