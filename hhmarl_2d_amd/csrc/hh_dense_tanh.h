@@ -34,7 +34,17 @@
  * products of a single row (d_W of one row) have nothing to hide behind.
  * The forward scales for the same reason (x per row, W per row n from a small launch in front, hh_k_dense_tanh_wscale_rows): split as
  * they are, the network's weights (|W| ~ 0.03) keep 19 bits, and the learners' gradients then miss the project's 4 x float32 rule
- * (measured: 5.2 x on Fight2).  Any |x|, |W| that float32 holds as normal numbers is in the domain.
+ * (measured: 5.2 x on Fight2).
+ * What that guarantees (derivation: tests/dense_tanh_ref.py, "The extended bound").  A scale follows the LARGEST of the elements that
+ * share it (a row for the forward and d_x, a column of a 64-row tile for d_W), so a staged element a is off by at most
+ * max(2^-22 |a|, 2^-39 amax).  Where the elements that share a scale lie within 2^17 of each other the error bound of a product is the
+ * componentwise one, (4 * 2^-22 + (n + 2) * 2^-24) |A| |B|; otherwise 2^-38 (amax_i sum_k |b_kj| + bmax_j sum_k |a_ik|) comes on top
+ * of it: relative to the row's or tile column's maximum, not to the element.  A dense sum hides that term behind its larger elements;
+ * a W that picks the one small column of x does not.
+ * Limits.  A maximum below 2^-111 meets the clamp of hdt_sf and keeps fewer bits.  The epilogues multiply acc * un before the other
+ * operand's inverse scale, and acc is up to 2^30 n, so a row of x (forward) or of d_pre (d_x), or a tile column of d_pre (d_W), with
+ * a maximum above about 2^100 gives inf even where the product with a tiny W or x is representable.  No input of the learners comes
+ * near either.
  */
 #ifndef HH_DENSE_TANH_H
 #define HH_DENSE_TANH_H

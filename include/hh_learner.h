@@ -199,9 +199,14 @@ int hh_input_stage_backward(int64_t n_rows, const float *src, int64_t src_ld, in
  *     d_pre_i = d_y_i (1 - y_i^2);  d_x_i = d_pre_i W  [n_rows_i, K] contiguous;  d_w = sum_i d_pre_i^T x_i;  d_b = sum_i column sums of d_pre_i
  * Arithmetic: every product except d_b's sum is v_mfma_f32_16x16x32_f16 on an fp16 (hi, lo) split of both operands (hi hi + lo hi + hi lo,
  * float32 accumulators).  Every operand is scaled by powers of two before the split (forward: x per row, w per row n; d_x: d_pre per
- * row, w per column k; d_w: d_pre and x per row tile and column) and the scale is undone on the float32 result, so values of any
- * magnitude a float32 holds as a normal number keep their 22 bits — d_y of order 1e-12 as well as weights of order 0.03.  Against float64, componentwise, with n the length of the sum:
+ * row, w per column k; d_w: d_pre and x per row tile and column) and the scale is undone on the float32 result (both exact: a power-of-two
+ * change of a row or column that has a scale of its own moves the matching outputs by that power of two, bit for bit), so d_y of order 1e-12 keeps
+ * its 22 bits as well as weights of order 0.03.  Against float64, with n the length of the sum, where the elements that share a scale lie within 2^17 of each other, componentwise:
  *     |C - C64| <= (4 * 2^-22 + (n + 2) * 2^-24) (|A| |B|)      (tests/dense_tanh_ref.py)
+ * and otherwise with 2^-38 (amax_i sum_k |b_kj| + bmax_j sum_k |a_ik|) on top: a scale follows the largest element, amax, of its row
+ * (tile column for d_w), an element below 2^-17 amax is staged to 2^-39 amax, not to 2^-22 of itself (derivation: tests/dense_tanh_ref.py,
+ * "The extended bound").  A row or tile column with a maximum below 2^-111 keeps fewer bits; a row of x or of d_pre (for d_w: a tile column of d_pre) with one above
+ * about 2^100 gives inf (the epilogues undo that scale first, on a sum of up to 2^30 n), even where the product with a tiny other operand is representable.
  * Everything is ordered on `stream`; no allocation, no host synchronisation, HIP-graph capturable.  The forward is two launches (the row scales of w into
  * `scratch`; the layer), the backward four: the column scales of w; d_x; per-workgroup partial sums of d_w and d_b over the row tiles (HH_DENSE_ROW_TILE rows; the tiles of block 0, then
  * those of block 1, walked grid-stride by min(HH_DENSE_MAX_PARTS, tiles) workgroups per 128 x 128 block of d_w) into `scratch`; the slots
