@@ -146,25 +146,58 @@ def save(path, **objects):
     return os.path.getsize(path)
 
 
+def _read(who, path):
+    """the document at `path`: format, version and object table checked -> (doc, {name: type name})"""
+    doc = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+    if not isinstance(doc, dict) or doc.get("format") != FORMAT:
+        raise ValueError(f"{who}: {path} is not a {FORMAT} file")
+    if doc.get("version") != FORMAT_VERSION:
+        raise ValueError(f"{who}: {path} has format version {doc.get('version')!r}, this library reads {FORMAT_VERSION}")
+    saved = doc.get("objects")
+    if not isinstance(saved, dict) or not isinstance(doc.get("state"), dict) or set(doc["state"]) != set(saved):
+        raise ValueError(f"{who}: {path} has no consistent object table")
+    return doc, saved
+
+
+def _load(who, path, objects, whole):
+    """load (whole: the names given are the file's) and load_subset (they are among the file's)"""
+    _check_objects(who, objects)
+    doc, saved = _read(who, path)
+    if whole and set(saved) != set(objects):
+        raise ValueError(f"{who}: the file holds {sorted(saved)}, the objects given are {sorted(objects)}")
+    absent = sorted(set(objects) - set(saved))
+    if absent:
+        raise ValueError(f"{who}: the file holds {sorted(saved)}, not {absent}")
+    for name, obj in objects.items():
+        if saved[name] != _type_name(obj):
+            raise ValueError(f"{who}: `{name}` was saved as a {saved[name]}, the object given is a {_type_name(obj)}")
+    plans = [load_plan(obj, doc["state"][name]) for name, obj in objects.items()]
+    for commit in plans:
+        commit()
+
+
 def load(path, **objects):
     """The checkpoint at `path` into the objects given by keyword (built from the constructor arguments of the saved run).  Refused with
     ValueError, before any object is touched: another format or version, names that are not exactly the file's, an object of another
     type than was saved under its name, and whatever an object's own validation refuses (`_load_plan`).  Then every object is loaded in
     place, in the order given."""
-    _check_objects("checkpoint.load", objects)
-    doc = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
-    if not isinstance(doc, dict) or doc.get("format") != FORMAT:
-        raise ValueError(f"checkpoint.load: {path} is not a {FORMAT} file")
-    if doc.get("version") != FORMAT_VERSION:
-        raise ValueError(f"checkpoint.load: {path} has format version {doc.get('version')!r}, this library reads {FORMAT_VERSION}")
-    saved = doc.get("objects")
-    if not isinstance(saved, dict) or not isinstance(doc.get("state"), dict) or set(doc["state"]) != set(saved):
-        raise ValueError(f"checkpoint.load: {path} has no consistent object table")
-    if set(saved) != set(objects):
-        raise ValueError(f"checkpoint.load: the file holds {sorted(saved)}, the objects given are {sorted(objects)}")
-    for name, obj in objects.items():
-        if saved[name] != _type_name(obj):
-            raise ValueError(f"checkpoint.load: `{name}` was saved as a {saved[name]}, the object given is a {_type_name(obj)}")
-    plans = [load_plan(obj, doc["state"][name]) for name, obj in objects.items()]
-    for commit in plans:
-        commit()
+    _load("checkpoint.load", path, objects, True)
+
+
+def load_subset(path, **objects):
+    """`load` with one rule relaxed: the names given must all be IN the file, they need not be all of it.  What a resume must not do — a
+    run continued with half of its state is no longer the run that was saved, which is why `load` refuses it — is what the curriculum
+    does at every level change (the reference's `restore` of the previous level's checkpoint, config.py:65-80, train_hetero.py:253-257):
+    the learner goes on, with its weights, Adam state, KL coefficients and update count, in a world of the next level that no saved
+    world, bank or rollout fits:
+
+        checkpoint.load_subset(prev, learner=learner);  learner.publish(bank);  ro.start()
+
+    Everything else is `load`'s: format and version, the type per name, every object's own validation before the first is touched,
+    copies in place.  The objects of the file that are not named are not read."""
+    _load("checkpoint.load_subset", path, objects, False)
+
+
+def contents(path):
+    """{name: type name} of the objects a checkpoint file holds (the file is read whole; format and version checked as `load` does)"""
+    return dict(_read("checkpoint.contents", path)[1])

@@ -297,3 +297,11 @@ class CommanderLearner:
     def publish(self, net):
         """the new weights into the sampler's CommanderNet on the current stream (refresh_weights): captured collects replay with them"""
         net.refresh_weights(self.module.state_dict())
+
+    def export_commander(self, path):
+        """the module's current weights under commander.state_keys() as one file of policy_files' plain format ("hhmarl_2d_amd.commander":
+        float32 CPU tensors, read with torch.load(weights_only=True)) — what `evaluation.Evaluator(commander=path)` takes.  Written
+        atomically; synchronises (the weights are read back to the host).  -> the path"""
+        from ..policy_files import save_commander
+        torch.cuda.synchronize(self.device)
+        return save_commander(path, self.module.state_dict())

@@ -359,3 +359,44 @@ class PPOLearner:
     def publish(self, bank):
         """the new weights into the sampler's bank on the current stream (PolicyBank.refresh_trainable): captured collects replay with them"""
         bank.refresh_trainable(self.modules)
+
+    # ---- the curriculum's policy files (hhmarl_2d_amd/policy_files.py)
+    def export_policies(self, policy_dir, level, agent_mode=None):
+        """The two modules' current weights as `L{level}_AC1_{mode}.pt` and `L{level}_AC2_{mode}.pt` in policy_dir (created where it is
+        missing), in policy_files' plain format: what train_hetero.py:101-105 writes through policy_export.py, and what the next
+        levels, HighLevelEnv and the evaluators pick up by name (PolicyBank.from_reference_dir).  The reference exports from level 3 on;
+        any level 1..5 is taken here.  agent_mode defaults to the mode of the learner's kinds; one that contradicts them is refused.
+        Both files carry the one tied shared_layer.  Synchronises (the weights are read back to the host).  -> the two paths"""
+        import os
+        from .. import policy_files as PF
+        mode = PF.mode_of_kinds(self.kinds)
+        if agent_mode is not None and agent_mode != mode:
+            raise ValueError(f"export_policies: this learner trains the {mode} policies (kinds {self.kinds}), not agent_mode={agent_mode!r}")
+        names = [PF.policy_file_name(level, ac, mode) for ac in (1, 2)]
+        os.makedirs(policy_dir, exist_ok=True)
+        torch.cuda.synchronize(self.device)
+        return [PF.save_policy(os.path.join(policy_dir, name), kind, m.state_dict(), level=level, agent_mode=mode)
+                for name, kind, m in zip(names, self.kinds, self.modules)]
+
+    @classmethod
+    def from_policy_files(cls, device, policy_dir, level, agent_mode, **kw):
+        """The learner whose modules hold the weights of `L{level}_AC{1,2}_{agent_mode}.pt` in policy_dir (files of policy_files' plain
+        format: export_policies).  The weights only: Adam state, kl_coeff and the update count start fresh (a run is continued with all
+        of them through checkpoint.load_subset).  The two files of one export hold the same shared_layer; files whose shared layers
+        differ in any bit are refused with ValueError, not silently tied to the first.  kw: the constructor's options."""
+        import os
+        from .. import policy_files as PF
+        PF.policy_file_name(level, 1, agent_mode)      # level and agent_mode refused here, before a file is looked for
+        kinds = PF.MODE_KINDS[agent_mode]
+        sds = []
+        for ac, want in zip((1, 2), kinds):
+            path = os.path.join(policy_dir, PF.policy_file_name(level, ac, agent_mode))
+            kind, sd = PF.load_policy(path)
+            if kind != want:
+                raise ValueError(f"from_policy_files: {path} holds a {PN.KIND_NAMES[kind]} network, the {agent_mode} policy of aircraft type {ac} is {PN.KIND_NAMES[want]}")
+            sds.append(sd)
+        for k in cls._SHARED:
+            if not torch.equal(sds[0][k].view(torch.int32), sds[1][k].view(torch.int32)):
+                raise ValueError(f"from_policy_files: `{k}` differs between the two files of {policy_dir}: the two policies of a trainer "
+                                 "hold ONE shared layer (files of two different exports?)")
+        return cls(kinds, sds, device, **kw)

@@ -3,7 +3,9 @@
 models/ac_models_hetero.py) in the fused HIP kernel of csrc/hh_policy_kernel.h (C ABI include/hh_policy.h) and writes
 int8 actions for every unit of every arena in one launch sequence; `NetPilot` / `OpponentNets` plug it into
 HighLevelEnv / LowLevelEnv levels 4-5.  The reference torch.load()s `policies/L*_AC*_{fight,escape}.pt`, which are not
-shipped (.gitignore:5): a deployment loads its own files with `PolicyBank.from_modules`; benchmarks and tests use
+shipped (.gitignore:5): a deployment loads its own files with `PolicyBank.from_modules`, or by name with
+`PolicyBank.from_reference_dir` (the reference's pickled modules, or the plain files PPOLearner.export_policies writes:
+hhmarl_2d_amd/policy_files.py); benchmarks and tests use
 deterministic synthetic weights of the same shapes (`PolicyBank.random_init`).
 
 A pilot is `callable(pilot_obs f32 [N,A,30], pilot_mode u8 [N,A]) -> int8 actions [N,A,4]`
@@ -287,7 +289,11 @@ class PolicyBank:
     @classmethod
     def from_reference_dir(cls, device, policy_dir, env, args, max_rows=1 << 20, load=None):
         """The reference's `_get_policies` (envs/env_base.py:312-347): which exported policies an environment flies, by file name
-        in `policy_dir` (the reference keeps them in <repo>/policies; torch.load needs the reference's model classes importable).
+        in `policy_dir` (the reference keeps them in <repo>/policies).  A file is either this project's plain export
+        (policy_files.save_policy, PPOLearner.export_policies: read with torch.load(weights_only=True), nothing else needed) or the
+        reference's own, a pickled model object (torch.load(weights_only=False): needs the reference's model classes importable); a
+        directory may mix both.  load: a caller's own `path -> loaded object` in place of that default; whatever it returns goes
+        through policy_files.from_policy_object.
         env = "LowLevel" | "HighLevel".  Selector bytes as the world kernels emit them (policy type | aircraft type << 2, + 16 (k - 3)
         for the policy set k of a level-5 arena):
           LowLevel level 4 (fight):   L3_AC{1,2}_fight                                              -> 5, 9
@@ -299,8 +305,9 @@ class PolicyBank:
         LowLevel escape mode below level 5 loads nothing in the reference (env_base.py:328-330) and its _policy_actions would fail
         on the empty dict: refused here with a clear error."""
         import os
+        from .policy_files import from_policy_object, load_policy_file
         if load is None:
-            load = lambda path: torch.load(path, weights_only=False)
+            load = load_policy_file
         f = lambda name: load(os.path.join(policy_dir, name))
         plan = []   # (selector byte, file)
         if env == "LowLevel":
@@ -330,7 +337,7 @@ class PolicyBank:
         lut = {}
         loaded = locals().get("loaded", {})
         for slot, (byte, name) in enumerate(plan):
-            kind, sd = PN.from_torch_module(loaded[name] if name in loaded else f(name))
+            kind, sd = from_policy_object(loaded[name] if name in loaded else f(name))
             b.set_net(slot, kind, sd)
             lut[byte] = slot
         b.set_lut(lut)
