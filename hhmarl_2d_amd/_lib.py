@@ -144,7 +144,8 @@ LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_cate
                    "hh_input_stage_backward", "hh_dense_tanh_scratch_bytes", "hh_dense_tanh_forward", "hh_dense_tanh_backward",
                    "hh_adam_step", "hh_minibatch_stage", "hh_train_commit", "hh_gru_seq_tile",
                    "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped", "hh_minibatch_stage_gather",
-                   "hh_heads_loss_scratch_bytes", "hh_heads_loss_geometry", "hh_heads_loss", "hh_window_cut", "hh_window_gather"]  # include/hh_learner.h
+                   "hh_heads_loss_scratch_bytes", "hh_heads_loss_geometry", "hh_heads_loss", "hh_window_cut", "hh_window_gather",
+                   "hh_grad_pack", "hh_grad_combine"]  # include/hh_learner.h
 GRU_TILES = (16, 8, 4)  # the compiled instances of hh_k_gru_seq_fwd / _bwd (HH_GRU_TILE forces one; hh_gru_seq_tile tells which a call uses)
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
@@ -201,6 +202,14 @@ class HHWindowCol(C.Structure):
     """hh_window_col (include/hh_learner.h): one column of hh_window_gather; field order is ABI"""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("step_bytes", C.c_int64), ("offset", C.c_int64), ("width", C.c_int64),
                 ("per_seq", C.c_int32), ("reserved0", C.c_int32)]
+
+
+GRAD_MAX_SHARDS = 64  # HH_GRAD_MAX_SHARDS (include/hh_learner.h)
+
+
+class HHGradTensor(C.Structure):
+    """hh_grad_tensor (include/hh_learner.h): one gradient of hh_grad_pack / hh_grad_combine and its place in the bucket; field order is ABI"""
+    _fields_ = [("g", C.c_void_p), ("n", C.c_int64), ("off", C.c_int64)]
 
 
 _lib = None
@@ -316,6 +325,8 @@ def lib():
         L.hh_heads_loss.argtypes = [C.c_int64] + [vp] * 13 + [C.POINTER(HHPpoLossParams)] + [vp] * 10 + [C.c_int64, vp]
         L.hh_window_cut.argtypes = [C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.hh_window_gather.argtypes = [C.c_int32, C.POINTER(HHWindowCol), C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.hh_grad_pack.argtypes = [C.c_int32, C.POINTER(HHGradTensor), vp, C.c_int64, vp]
+        L.hh_grad_combine.argtypes = [C.c_int32, C.POINTER(HHGradTensor), vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), vp]
         for obj in ("world", "policy", "commander"):   # the snapshot triplets (hh_abi.h, hh_policy.h, hh_commander.h): handle, [host] buffer, bytes, stream
             getattr(L, f"hh_{obj}_snapshot_bytes").argtypes = [vp, C.POINTER(C.c_int64)]
             getattr(L, f"hh_{obj}_snapshot").argtypes = [vp, vp, C.c_int64, vp]

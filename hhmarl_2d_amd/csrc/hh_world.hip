@@ -912,6 +912,9 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 /* ---- gradient clipping by global norm inside that chain: the norm of a module's gradients, the Adam step scaled from device memory (C ABI in include/hh_learner.h) ---- */
 #include "hh_grad_clip.h"
 
+/* ---- a data-parallel step that equals one process over its shards: gradients into a flat bucket, W buckets back in shard order (C ABI in include/hh_learner.h) ---- */
+#include "hh_grad_shards.h"
+
 /* ---- tanh, the output heads, the PPO loss and their backward as one row pass behind shared_layer (C ABI in include/hh_learner.h) ---- */
 #include "hh_heads_loss.h"
 

@@ -18,6 +18,9 @@ minibatch staged by a device schedule (`minibatch_stage`: hh_minibatch_stage), f
 Both learners also train from the rollouts' default batch_mode="truncate_episodes" (`update_window`): the fixed [T, N] window is cut into
 sequences (`window_cut`: hh_window_cut) and its columns gathered into the padded form (`window_gather`: hh_window_gather); from there on
 it is `update`.
+And (`PPOLearner(group=LocalShards(K) | ShardGroup())`, eager steps): the update data-parallel over W shards with the bytes of one
+process over the W shards — the gradients packed (`grad_pack`: hh_grad_pack), all-gathered and added in shard order (`grad_combine`:
+hh_grad_combine); `shards` holds the groups, the step alignment and the moments over all shards.
 
 The reference's learner does not compute what its sampler computes, and this module keeps the difference:
   * Fight1 / Fight2 are RLlib `RecurrentNetwork`s with a dummy state.  The sampler sees sequences of length 1 (attention =
@@ -47,7 +50,8 @@ from .ops import (ATTENTION_MODES, COMMANDER_STAGE_LAYERS, GRU_H, INPUT_MODES, T
                   _DenseTanh, _gru_io, _gru_scratch_bytes, _GruSeq, _InputStage, _ResidualNormalize, _stage_layout, _trunk_mode, chunk_attention,
                   chunk_attention_torch, commander_stage_tables, dense_tanh, dense_tanh_torch, gru_cell_torch, gru_seq_backward, gru_seq_forward,
                   gru_seq_tile, gru_sequence, gru_sequence_pair, gru_sequence_torch, input_stage, input_stage_torch, residual_normalize,
-                  residual_normalize_torch, stage_groups, stage_layers, stage_tables)
+                  residual_normalize_torch, stage_groups, stage_layers, stage_tables, grad_combine, grad_combine_torch, grad_layout, grad_pack,
+                  grad_pack_torch)
 from .nets import _FC, CommanderTrainable, TrainableNet, _GRUWeights, tie
 from .batch import (_cut_args, _gather_args, chunk_mask, cut_chunks, kl_coeff_update, minibatch_order, minibatch_partition, minibatch_schedule,
                     pad_chunks, sequence_order, sequence_schedule, shuffled_schedule, standardize, standardize_masked, update_schedule, window_cut,
@@ -55,6 +59,7 @@ from .batch import (_cut_args, _gather_args, chunk_mask, cut_chunks, kl_coeff_up
 from .step import (ADAM_BETAS, ADAM_EPS, OPTIMIZER_MODES, STEP_MODES, DeviceAdam, _adam_desc, _grad_clip, _heads_keyword, _is_clip, _learner_options,
                    _optimizer_mode, _PolicySGD, _shuffle_flag, _stage_desc, _step_mode, _StepBook, adam_step, adam_step_torch, grad_norm,
                    grad_norm_scratch, grad_norm_torch, minibatch_stage, minibatch_stage_gather, minibatch_stage_gather_torch, minibatch_stage_torch,
-                   train_commit)
+                   train_commit, _shard_group)
+from .shards import LocalShards, ShardGroup, combine_stats, combined_mean, combined_std, ordered_sum, standardize_shards, step_weights
 from .ppo_learner import PPOLearner
 from .commander_learner import COMMANDER_STAGE_COLS, CommanderLearner

@@ -71,7 +71,11 @@ class CommanderLearner:
         buffer (grown to twice the need).  Slot 0 of a staged minibatch is a real sequence, so seq_len[0] >= 1 holds as before.  What
         shuffling does to learning curves has not been measured here.
         heads (keyword only, taken by _heads_keyword in front of this signature): PPOLearner's argument ("torch", the default: nothing changes; "fused", with fused=True and trunk="torch": the
-        step's forward stops at CommanderTrainable.pre_heads and the tail is one hh_heads_loss with n_comp = 1)."""
+        step's forward stops at CommanderTrainable.pre_heads and the tail is one hh_heads_loss with n_comp = 1).
+        group (keyword only, taken like heads): PPOLearner's argument; only None is taken for now (the driver's sharded run is shared, the commander's batch code over
+        shards is not written), anything else is a ValueError."""
+        if self._group_arg is not None:
+            raise ValueError("CommanderLearner takes group=None for now: sharded updates are PPOLearner's (learner/shards.py)")
         self.optimizer_mode = _learner_options(
             self, "CommanderLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
             dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),

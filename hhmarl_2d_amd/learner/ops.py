@@ -473,3 +473,98 @@ def gru_sequence_torch(gi, h0, w_hh, b_hh, seq_len):
         h = torch.where(on, hn, h)
         ys.append(torch.where(on, hn, torch.zeros_like(hn)))
     return torch.stack(ys, dim=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------ gradients of W shards
+def grad_layout(tensors):
+    """where a list of gradients lies in its bucket: tensors (or their element counts) in list order, each starting at the next multiple
+    of 4 elements -> (ns, offs, bucket_elems), bucket_elems a multiple of 4"""
+    ns = [int(t.numel()) if isinstance(t, torch.Tensor) else int(t) for t in tensors]
+    offs, at = [], 0
+    for n in ns:
+        if n < 0:
+            raise ValueError("grad_layout: an element count is >= 0")
+        offs.append(at)
+        at += (n + 3) // 4 * 4
+    return ns, offs, at
+
+
+def _grad_desc(who, grads, layout, dev):
+    ns, offs, _ = layout
+    if not (len(grads) == len(ns) == len(offs)):
+        raise ValueError(f"{who}: one layout entry per gradient ({len(grads)} gradients, {len(ns)} entries)")
+    desc = (L.HHGradTensor * max(len(grads), 1))()
+    for i, (g, n, off) in enumerate(zip(grads, ns, offs)):
+        if g is not None and not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == dev and g.numel() == n):
+            raise ValueError(f"{who}: a gradient is None or a contiguous float32 CUDA tensor of its layout entry's {n} elements on the bucket's device "
+                             f"(the torch-op form is {who}_torch)")
+        desc[i].g, desc[i].n, desc[i].off = (None if g is None else g.data_ptr()), n, off
+    return desc
+
+
+def grad_pack(grads, bucket, layout=None):
+    """A module's gradients into one flat bucket, the block an all-gather moves (hh_grad_pack, include/hh_learner.h): grads is a list of
+    contiguous float32 CUDA tensors or None (a parameter without .grad), layout grad_layout's triple for them (default: grad_layout(grads),
+    then without None), bucket a contiguous float32 [bucket_elems] CUDA tensor, 16-byte aligned.  Gradient i goes to
+    bucket[offs[i] : offs[i] + ns[i]] byte for byte; the range of a None and all padding are written as +0.0.  -> bucket.
+    ceil(n / 64) launches, no host synchronisation, HIP-graph capturable; a missing library or GPU is an error."""
+    _need_gpu("grad_pack")
+    grads = list(grads)
+    layout = grad_layout(grads) if layout is None else layout
+    if not (isinstance(bucket, torch.Tensor) and bucket.is_cuda and bucket.dtype == torch.float32 and bucket.is_contiguous() and bucket.dim() == 1
+            and bucket.numel() == layout[2]):
+        raise ValueError(f"grad_pack: bucket is a contiguous float32 [{layout[2]}] CUDA tensor (the torch-op form is grad_pack_torch)")
+    desc = _grad_desc("grad_pack", grads, layout, bucket.device)
+    L.check(L.lib().hh_grad_pack(len(grads), desc, _p(bucket), bucket.numel(), _stream(bucket.device)))
+    return bucket
+
+
+def grad_pack_torch(grads, layout=None, device=None):
+    """grad_pack with torch ops, any device -> a new bucket float32 [bucket_elems]: zeros, then every gradient that is not None copied in"""
+    grads = list(grads)
+    ns, offs, E = grad_layout(grads) if layout is None else layout
+    if device is None:
+        device = next((g.device for g in grads if g is not None), "cpu")
+    bucket = torch.zeros((E,), dtype=torch.float32, device=device)
+    for g, n, off in zip(grads, ns, offs):
+        if g is not None:
+            bucket[off:off + n] = g.detach().reshape(-1)
+    return bucket
+
+
+def _shard_weights(who, weight, W):
+    w = [float(x) for x in weight]
+    if len(w) != W or not 1 <= W <= L.GRAD_MAX_SHARDS:
+        raise ValueError(f"{who}: one weight per shard, 1 .. {L.GRAD_MAX_SHARDS} shards (got {len(w)} weights for {W} buckets)")
+    return w
+
+
+def grad_combine(grads, buckets, weight, layout=None):
+    """The gathered buckets of W shards back into the gradients, added in shard order (hh_grad_combine, include/hh_learner.h): buckets a
+    contiguous float32 [W, bucket_elems] CUDA tensor, weight W host floats (float64), grads the tensors to write — contiguous float32 CUDA
+    tensors, or None for a parameter that receives nothing — and layout their grad_layout (default: grad_layout(grads)).  Per element
+        acc = float64(b[0]) * weight[0];  acc = acc + float64(b[r]) * weight[r]  for r = 1 .. W-1;  g = float32(acc)
+    with every product and sum rounded on its own: the same bytes on every rank and for every W that presents the same shards; W = 1 with
+    weight 1.0 returns the bucket's bytes.  In place on grads.  ceil(n / 64) launches, no host synchronisation, HIP-graph capturable."""
+    _need_gpu("grad_combine")
+    grads = list(grads)
+    layout = grad_layout(grads) if layout is None else layout
+    if not (isinstance(buckets, torch.Tensor) and buckets.is_cuda and buckets.dtype == torch.float32 and buckets.is_contiguous() and buckets.dim() == 2
+            and buckets.shape[1] == layout[2]):
+        raise ValueError(f"grad_combine: buckets is a contiguous float32 [W, {layout[2]}] CUDA tensor (the torch-op form is grad_combine_torch)")
+    W = buckets.shape[0]
+    w = (C.c_double * max(W, 1))(*_shard_weights("grad_combine", weight, W))
+    desc = _grad_desc("grad_combine", grads, layout, buckets.device)
+    L.check(L.lib().hh_grad_combine(len(grads), desc, _p(buckets), buckets.shape[1], W, w, _stream(buckets.device)))
+
+
+def grad_combine_torch(buckets, weight, layout):
+    """grad_combine with torch ops, any device (the A/B partner): float64 products and sums in shard order, rounded to float32 once
+    -> per layout entry a new flat float32 tensor [ns[i]]"""
+    ns, offs, E = layout
+    w = _shard_weights("grad_combine_torch", weight, buckets.shape[0])
+    acc = buckets[0].double() * w[0]
+    for r in range(1, len(w)):
+        acc = acc + buckets[r].double() * w[r]
+    flat = acc.float()
+    return [flat[off:off + n].clone() for n, off in zip(ns, offs)]

@@ -13,7 +13,8 @@ from .loss import OLD_LD, _loss_kw, heads_loss, n_comp_of, ppo_loss, ppo_loss_to
 from .nets import TrainableNet, tie
 from .ops import _trunk_mode
 from .. import checkpoint as ck
-from .step import _heads_keyword, _learner_options, _learner_saved_options, _module_plan, _PolicySGD
+from .shards import standardize_shards
+from .step import _heads_keyword, _learner_options, _learner_saved_options, _module_plan, _PolicySGD, _shard_group
 
 # ------------------------------------------------------------------------------------------------------------------ the learner
 class PPOLearner:
@@ -80,11 +81,20 @@ class PPOLearner:
         heads (keyword only, taken by _heads_keyword in front of this signature): "torch" (the default): nothing changes.  "fused" (needs fused=True and trunk="torch"): the modules are built
         with heads="fused", every minibatch step's forward stops at shared_layer's pre-activations (TrainableNet.pre_heads) and tanh, the
         two heads, the loss and their backward run as one hh_heads_loss (heads_loss, unscaled: the step calls total.backward()), in all
-        three step modes, with grad_clip and shuffle_sequences as before."""
+        three step modes, with grad_clip and shuffle_sequences as before.
+        group (keyword only, taken like heads): None (the default: one process, nothing changes) or a learner/shards.py group, eager step modes only.  The update is then
+        data-parallel over group.W shards and writes the bytes ONE process over the W shards writes (_PolicySGD.run_sharded): every shard
+        cuts its own batch into minibatches of max(1, sgd_minibatch_size // W) rows, the shards' gradients are packed (hh_grad_pack),
+        gathered and added in shard order (hh_grad_combine) before the unchanged clip, Adam step and commit, and the advantages are
+        standardised over all shards' rows (standardize_shards).  ShardGroup(): this process is one of W torch.distributed ranks; `update`
+        and `update_window` are collective and take what they take today.  LocalShards(K): the in-process twin; they take sequences of K
+        batches or rollouts, and one bank or K.  The dicts gain rows_local; steps and rows count all shards.  What W ranks gain on real
+        hardware is unmeasured."""
         self.optimizer = _learner_options(
             self, "PPOLearner", device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused,
             dict(clip_param=clip_param, kl_target=kl_target, vf_clip_param=vf_clip_param, vf_loss_coeff=vf_loss_coeff, entropy_coeff=entropy_coeff),
             dict(num_sgd_iter=num_sgd_iter, sgd_minibatch_size=sgd_minibatch_size, max_seq_len=max_seq_len, seed=seed), self._heads_arg, trunk)
+        self.group = _shard_group(self._group_arg, self.step)
         self.kinds = tuple(int(k) for k in kinds)
         assert len(self.kinds) == 2 and PN.HAS_ATT[self.kinds[0]] == PN.HAS_ATT[self.kinds[1]]
         self.attention, self.inputs, self.trunk = attention, inputs, _trunk_mode(trunk)
@@ -163,14 +173,15 @@ class PPOLearner:
             raise ValueError("the batch has no logits column (PPORollout(record_logits=True)): a bank and n_arenas are needed to recompute them")
         return self.old_logits(rows["obs"], bank, n_arenas)
 
-    def policy_batch(self, rows, old_logits, agent):
+    def policy_batch(self, rows, old_logits, agent, adv=None):
         """the training batch of policy `agent` (0 | 1) from the emitted rows: dict of [S, L, ...] chunks (fight) or [R, ...] rows (escape)
-        and, for chunks, seq_len [S] and mask [S, L]"""
+        and, for chunks, seq_len [S] and mask [S, L].  adv: the agent's advantages f32 [R] already standardised (over all shards of a
+        group); default: standardised here over this batch"""
         kind = self.kinds[agent]
         b = {"obs": rows["obs"][:, agent, :PN.OBS_DIM[kind]].contiguous(),
              "critic": central_critic_rows(rows["obs"], rows["actions"], agent + 1),
              "actions": rows["actions"][:, agent].contiguous(), "old_logp": rows["logp"][:, agent].contiguous(),
-             "adv": standardize(rows["adv"][:, agent]), "target": rows["target"][:, agent].contiguous(),
+             "adv": standardize(rows["adv"][:, agent]) if adv is None else adv, "target": rows["target"][:, agent].contiguous(),
              "old_logits": old_logits[:, agent].contiguous()}
         if not self.recurrent:
             return b
@@ -236,6 +247,8 @@ class PPOLearner:
         `bank` is read only when the batch has no `logits` column (batch_old_logits).  With grad_clip also grad_gnorm.
         An EpisodeBatch built with train_batch_size hands over its accumulated batch (RLlib's train_batch_size: update once
         `episodes.ready()`, e.g. after `PPORollout.collect_batch()`); nothing else changes here."""
+        if self.group is not None:
+            return self._update_sharded(episodes, bank, window=False)
         rows = episodes.rows()
         if rows["obs"].shape[0] == 0:
             return [d.empty() for d in self._sgd]
@@ -275,20 +288,21 @@ class PPOLearner:
         adv_rows = rollout.adv.transpose(0, 1).reshape(N * T, 2)      # [R, 2], r = n T + t: what the episode path's rows["adv"] would hold
         return T, N, tables, logits.contiguous(), adv_rows
 
-    def window_batch(self, rollout, bank, agent, shared=None):
+    def window_batch(self, rollout, bank, agent, shared=None, adv=None):
         """the training batch of policy `agent` (0 | 1) from a PPORollout's [T, N] window, in policy_batch's format and — fed the same
         rows as episodes (the window's fragments, arena-major) — with policy_batch's values: fight kinds [S, L, ...] chunks with seq_len
         and mask (a chunk ends at a done row, at max_seq_len rows or at the window's end: window_cut), escape kinds [R, ...] with R = T N
         rows, arena-major (r = n T + t: the cut with max_seq_len = 1, the length-1 axis dropped).  One hh_window_gather launch of seven
         columns reads the rollout's buffers as they lie.  The trailing fragment of an arena carries RLlib's truncation bootstrap from
         vf[T] in adv and target (hh_gae_rllib).  `bank` is read only when the rollout recorded no logits.  The advantages are standardised
-        over the agent's T N values (standardize).  shared: _window_shared's tuple (update_window builds it once for both policies)."""
+        over the agent's T N values (standardize).  shared: _window_shared's tuple (update_window builds it once for both policies).
+        adv: the agent's advantages f32 [N T], arena-major, already standardised (over all shards of a group) in place of that."""
         T, N, tables, logits, adv_rows = self._window_shared(rollout, bank) if shared is None else shared
         kind = self.kinds[agent]
         Lm = self.max_seq_len if self.recurrent else 1
         D, Dk = rollout.obs.shape[3], PN.OBS_DIM[kind]
         critic = central_critic_rows(rollout.obs[:T], rollout.actions, agent + 1).contiguous()
-        adv = standardize(adv_rows[:, agent]).reshape(N, T).t().contiguous()          # back to [T, N]: where the gather reads a row (t, n)
+        adv = (standardize(adv_rows[:, agent]) if adv is None else adv).reshape(N, T).t().contiguous()          # back to [T, N]: where the gather reads a row (t, n)
         names = ("obs", "critic", "actions", "old_logp", "adv", "target", "old_logits")
         got = window_gather([(rollout.obs, (Dk,), agent * D * 4, False), (critic, (critic.shape[2],), 0, False),
                              (rollout.actions, (4,), agent * 4, False), (rollout.logp, (), agent * 4, False), (adv, (), 0, False),
@@ -311,6 +325,8 @@ class PPOLearner:
         The batches are window_batch's; from there on it is `update`: the same _columns and driver, so fused, attention, inputs, trunk,
         heads, optimizer, step="graph", grad_clip and shuffle_sequences act as they do there, and the row count T N is the same in every
         update.  The rollout's buffers are only read."""
+        if self.group is not None:
+            return self._update_sharded(rollout, bank, window=True)
         with torch.no_grad():
             shared = self._window_shared(rollout, bank)
             batches = [self.window_batch(rollout, bank, a, shared) for a in range(2)]
@@ -318,11 +334,54 @@ class PPOLearner:
         self.updates += 1
         return out
 
+    # ---- one update over the shards of a group (learner/shards.py)
+    def _per_shard(self, x, what):
+        """what this process's shards train on, one entry per group.local: a ShardGroup rank holds one shard and takes `x` as it is; a
+        LocalShards(K) learner takes a sequence of K"""
+        K = len(self.group.local)
+        if not getattr(self.group, "in_process", False):
+            return [x]
+        if not isinstance(x, (list, tuple)) or len(x) != K:
+            raise ValueError(f"a LocalShards({K}) learner takes a sequence of {K} {what}, one per shard")
+        return list(x)
+
+    def _update_sharded(self, sources, bank, window):
+        """`update` (window False: EpisodeBatches) or `update_window` (True: PPORollouts) with a group: the batches are today's, except
+        that every policy's advantages are standardised over all shards' rows, then the drivers' run_sharded.  Collective.  A shard
+        without rows takes part with empty steps; when no shard has a row the result is the empty update's and nothing is counted."""
+        group = self.group
+        srcs = self._per_shard(sources, "rollouts" if window else "EpisodeBatches")
+        banks = list(bank) if isinstance(bank, (list, tuple)) else [bank] * len(srcs)
+        if len(banks) != len(srcs):
+            raise ValueError(f"one bank or one per shard ({len(srcs)}), got {len(banks)}")
+        with torch.no_grad():
+            pre, advs = [], []
+            for src, bk in zip(srcs, banks):
+                if window:
+                    pre.append(self._window_shared(src, bk))
+                    advs.append(pre[-1][4])
+                else:
+                    rows = src.rows()
+                    pre.append((rows, self.batch_old_logits(rows, bk, src.N)) if rows["obs"].shape[0] else None)
+                    advs.append(rows["adv"])
+            batches = []
+            for a in range(2):
+                std, n_all = standardize_shards([x[:, a] for x in advs], group)
+                if n_all == 0:
+                    return [dict(d.empty(), rows_local=0) for d in self._sgd]
+                batches.append([None if p is None else
+                                (self.window_batch(src, bk, a, p, adv=x) if window else self.policy_batch(p[0], p[1], a, adv=x))
+                                for src, bk, p, x in zip(srcs, banks, pre, std)])
+        out = [d.run_sharded(group, [(None, []) if b is None else self._columns(b) for b in bs]) for d, bs in zip(self._sgd, batches)]
+        self.updates += 1
+        return out
+
     # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
     _SHARED = ("shared_layer._model.0.weight", "shared_layer._model.0.bias")
 
     def _options(self):
-        return _learner_saved_options(self, self.optimizer, kinds=self.kinds, attention=self.attention, inputs=self.inputs, trunk=self.trunk)
+        sharded = {} if self.group is None else dict(shards=self.group.W)      # a learner without a group saves what it always saved
+        return _learner_saved_options(self, self.optimizer, kinds=self.kinds, attention=self.attention, inputs=self.inputs, trunk=self.trunk, **sharded)
 
     def state_dict(self):
         """the two modules (the tied shared layer once, with the first), `updates` — it seeds minibatch_order and sequence_order —, per

@@ -10,6 +10,7 @@ import torch
 
 from .. import _lib as L
 from .. import checkpoint as ck
+from . import ops as _ops
 from ._ffi import _need_gpu, _p, _stream
 from .batch import kl_coeff_update, update_schedule
 from .loss import _heads_mode
@@ -419,6 +420,7 @@ class _PolicySGD:
 
     def __init__(self, cfg, module, lr, kl_coeff, device_adam, forward, loss, stage_groups, policy, noun):
         self.cfg, self.module, self.kl_coeff, self.gnorms = cfg, module, float(kl_coeff), []
+        self._buckets = None    # run_sharded: the shards' gradient buckets f32 [W, bucket_elems], kept between updates
         self.forward, self.loss, self.stage_groups, self.policy, self.noun = forward, loss, stage_groups, int(policy), noun
         if device_adam:
             self.optimizer, self.book = DeviceAdam(module.parameters(), lr=lr, max_norm=cfg.grad_clip), _StepBook(cfg.device, gnorm=cfg.grad_clip is not None)
@@ -611,6 +613,94 @@ class _PolicySGD:
             self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], cfg.kl_target)
         return self.result(m, n, rows)
 
+    # ---- one update over W shards (learner/shards.py)
+    def run_sharded(self, group, shards):
+        """`run` as one of group.W data-parallel shards' — or, with LocalShards, as all of them one after another — so that W ranks write
+        the bytes one process over the W shards writes.  shards: per entry of group.local (cols, seq_len) as `run` takes them, (None, [])
+        for a shard without rows.  Collective, eager modes only.
+          * every shard cuts its own batch with update_schedule at max(1, sgd_minibatch_size // W) rows (RLlib's per-device split) under
+            the learner's unchanged keys; the schedules' unpadded-row columns are gathered once per update (shards.step_weights): global
+            step i is shard r's i-th row or empty for r, max_r len steps, weight[i, r] = n_r[i] / sum_r n_r[i] in host float64;
+          * per step every local shard runs forward, loss and backward as minibatch_step does (an empty one runs nothing) and its
+            gradients, over the module's parameter list — the list grad_clip takes, the tied shared layer once — go into its bucket
+            (grad_pack; zeros for an empty shard); the buckets are gathered; grad_combine writes the weighted sum, added in shard order,
+            into every parameter's .grad (zeros where no shard reached a parameter);
+          * from there the step is minibatch_step's: clip_grad_norm_ or DeviceAdam's norm, opt.step(), train_commit (the device table
+            then holds this process's first shard's rows; the result is computed from all shards').  The combined gradient is the same
+            bytes on every rank, so weights, m, v, t and the norms stay identical without a broadcast;
+          * the steps' statistics rows are gathered at the end of the update and combined as sum_r weight_r stat_r in shard order, slot 5
+            = the step's rows over all shards (shards.combine_stats), so every rank moves kl_coeff alike.
+        -> the update's dict with steps and rows over all shards and rows_local, this process's rows.  One shard with weight 1.0 is `run`
+        bit for bit."""
+        from .shards import combine_stats, step_weights
+        cfg, opt, book, clip, dev = self.cfg, self.optimizer, self.book, self.cfg.grad_clip, self.cfg.device
+        size = max(1, cfg.sgd_minibatch_size // group.W)
+        plans = []
+        for cols, seq_len in shards:
+            if cols is None or len(seq_len) == 0:
+                plans.append((None, None, np.zeros((0, 4), dtype=np.int32), None))
+                continue
+            order, sched, _ = update_schedule(seq_len, size, cfg.num_sgd_iter, cfg.seed, cfg.updates, self.policy, cfg.shuffle_sequences)
+            n_valid = torch.from_numpy(np.ascontiguousarray(sched[:, 2])).to(dev)
+            if order is not None:
+                order = torch.from_numpy(order).to(dev).long()
+            plans.append((cols, order, sched, n_valid))
+        rows_local = int(sum(int(np.sum(seq_len)) for _, seq_len in shards))
+        per_shard = group.gather_ragged([p[2][:, 2] for p in plans])
+        n, n_glob, weight = step_weights(per_shard)
+        steps = len(n_glob)
+        if steps == 0:
+            return dict(self.empty(), rows_local=rows_local)
+        rows = int(sum(int(c.sum()) for c in per_shard)) // cfg.num_sgd_iter      # every pass visits every row once
+        params = list(self.module.parameters())
+        layout = _ops.grad_layout(params)
+        if self._buckets is None or tuple(self._buckets.shape) != (group.W, layout[2]):
+            self._buckets = torch.zeros((group.W, layout[2]), dtype=torch.float32, device=dev)
+        buckets, none = self._buckets, [None] * len(params)
+        zero6 = torch.zeros((len(L.PPO_STATS),), dtype=torch.float64, device=dev)
+        self.gnorms = []
+        if book is not None:
+            book.begin(steps, opt)
+        kept = [[] for _ in plans]
+        for i in range(steps):
+            targets = None
+            for j, r in enumerate(group.local):
+                cols, order, sched, n_valid = plans[j]
+                grads, stats = none, zero6
+                if i < len(sched):
+                    c0, c1 = int(sched[i, 0]), int(sched[i, 1])
+                    if order is None:
+                        mb = {k: v[c0:c1] for k, v in cols.items()}
+                    else:
+                        idx = order[c0:c1]
+                        mb = {k: v.index_select(0, idx) for k, v in cols.items()}
+                    mb["n_valid"] = n_valid[i:i + 1]
+                    logits, vf = self.forward(mb)
+                    total, stats = self.loss(logits, vf, mb, self.kl_term())
+                    opt.zero_grad(set_to_none=True)
+                    total.backward()
+                    grads = [p.grad for p in params]
+                    targets = grads if targets is None else targets
+                kept[j].append(stats)
+                _ops.grad_pack(grads, group.pack_target(buckets, r), layout)
+            group.gather_buckets(buckets)
+            # the sum goes into gradient tensors that are already packed (a local shard's own), or into new ones where there is none
+            for k, p in enumerate(params):
+                g = None if targets is None else targets[k]
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format) if g is None else g
+            _ops.grad_combine([p.grad for p in params], buckets, weight[i], layout)
+            if clip is not None and book is None:       # DeviceAdam: inside opt.step()
+                self.gnorms.append(torch.nn.utils.clip_grad_norm_(self.module.parameters(), clip))
+            opt.step()
+            if book is not None:
+                train_commit(kept[0][-1], book.table, book.cursor, opt.t)
+        local = torch.stack([torch.stack(k) for k in kept]).cpu().numpy().reshape(len(kept), steps * len(L.PPO_STATS))
+        table = combine_stats(group.gather_host(local).reshape(group.W, steps, len(L.PPO_STATS)), weight, n_glob)
+        m = torch.from_numpy(table).to(dev).mean(dim=0).tolist()        # the reduction `run` makes, on the same device
+        if cfg.use_kl:
+            self.kl_coeff = kl_coeff_update(self.kl_coeff, m[3], cfg.kl_target)
+        return dict(self.result(m, steps, rows), rows_local=rows_local)
+
 
 def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_sequences, kl_coeff, fused, floats, ints, heads="torch", trunk="torch"):
     """what both learners' constructors take the same way, set on `learner`: the modes, grad_clip, the flag and `heads` validated in this
@@ -633,6 +723,18 @@ def _learner_options(learner, who, device, optimizer, step, grad_clip, shuffle_s
     return mode
 
 
+def _shard_group(group, step):
+    """a learner's `group`: None (the default: one process, nothing changes) or a learner/shards.py group — LocalShards(K) | ShardGroup —,
+    eager step modes only"""
+    if group is None:
+        return None
+    if not all(hasattr(group, k) for k in ("W", "local", "gather_host", "gather_ragged", "pack_target", "gather_buckets")):
+        raise ValueError(f"group is None, a LocalShards or a ShardGroup (learner/shards.py), got {group!r}")
+    if step == "graph":
+        raise ValueError('group needs step="eager": the shards\' gather between backward and Adam is not captured into the step graph')
+    return group
+
+
 LEARNER_OPTIONS = ("seed", "num_sgd_iter", "sgd_minibatch_size", "max_seq_len", "shuffle_sequences", "grad_clip", "step", "fused", "heads", "use_kl",
                    "clip_param", "kl_target", "vf_clip_param", "vf_loss_coeff", "entropy_coeff")
 
@@ -652,9 +754,9 @@ def _heads_keyword(init):
     """a learner's __init__ with one more argument, `heads`, that can only be given by keyword: it is taken off before `init` runs and
     kept as `self._heads_arg`, which `init` hands to _learner_options for validation in its place.  The constructors' own signatures stay
     as they are — grad_clip their last parameter, so no positional caller moves — and functools.wraps keeps them what introspection
-    and help() show; the docstrings describe `heads`."""
+    and help() show; the docstrings describe `heads`.  `group` (learner/shards.py) is taken the same way and kept as `self._group_arg`."""
     @functools.wraps(init)
-    def __init__(self, *args, heads="torch", **kw):
-        self._heads_arg = heads
+    def __init__(self, *args, heads="torch", group=None, **kw):
+        self._heads_arg, self._group_arg = heads, group
         init(self, *args, **kw)
     return __init__

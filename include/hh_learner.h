@@ -411,6 +411,41 @@ typedef struct hh_window_col {   /* field order is ABI; host struct of device po
 int hh_window_gather(int32_t n_cols, const hh_window_col *cols, int64_t S, int32_t max_seq_len, int32_t T_src, int32_t N,
                      const int32_t *seq_t0, const int32_t *seq_arena, const int32_t *seq_len, void *stream);
 
+/* ---- a data-parallel minibatch step whose bytes do not depend on the number of ranks: pack, (all-gather), combine ----
+ *
+ * W shards each run forward, loss and backward on their own minibatch; the step's gradient is the weighted sum of the shards' gradients
+ * (weight_r = the shard's unpadded rows / the step's rows over all shards).  A ring or tree all-reduce adds in an order that depends on W
+ * and on the rank; here every rank receives all W gradients (one all-gather of a flat bucket) and adds them itself in SHARD ORDER, so a
+ * W-rank step writes the bytes that one process holding the W shards writes.  Both launches are ordered on `stream`: no atomics, no
+ * scratch, no allocation, no host synchronisation, HIP-graph capturable; descriptors by value, HH_ADAM_MAX_TENSORS per launch. */
+#define HH_GRAD_MAX_SHARDS 64    /* the weights travel by value: 64 x 8 bytes beside the descriptors */
+
+typedef struct hh_grad_tensor {  /* field order is ABI; host struct of a device pointer */
+    float *g;                    /* the gradient: f32 [n], 4-byte aligned (float4 accesses where it is 16-byte aligned).  NULL: a parameter without one */
+    int64_t n;
+    int64_t off;                 /* its first element in the bucket: a multiple of 4 */
+} hh_grad_tensor;
+
+/* bucket[t[i].off .. + t[i].n) = t[i].g, byte for byte, for every tensor of t[n_tensors] (host array, off ascending from t[0].off = 0, the
+ * ranges disjoint); every other element of bucket[0 .. bucket_elems) — the padding behind a tensor up to the next one's off, behind the
+ * last one up to bucket_elems, and the whole range of a tensor with g == NULL — is written as +0.0f, on every call.  [dev] bucket f32
+ * [bucket_elems], 16-byte aligned, bucket_elems a multiple of 4.  HH_E_ARG, with nothing enqueued: n_tensors < 1, a null t or bucket, a
+ * bucket that is not 16-byte aligned, bucket_elems negative or no multiple of 4, t[0].off != 0, an off that is no multiple of 4 or not
+ * ascending, a range that leaves the bucket or reaches into the next tensor's, n < 0, a gradient that is not 4-byte aligned. */
+int hh_grad_pack(int32_t n_tensors, const hh_grad_tensor *t, float *bucket, int64_t bucket_elems, void *stream);
+
+/* For every tensor with g != NULL and every element i < n, from [dev] buckets f32 [n_shards, bucket_elems] (16-byte aligned) and the HOST
+ * array weight f64 [n_shards] (copied into the launch; 1 <= n_shards <= HH_GRAD_MAX_SHARDS), with b[r] = buckets[r, off + i]:
+ *     acc = (double)b[0] * weight[0];   for r = 1 .. n_shards-1:  acc = acc + (double)b[r] * weight[r];   g[i] = (float)acc
+ * every product and every sum rounded on its own (never fused), the additions in shard order, one rounding to float32 at the end.
+ * Starting from shard 0's product, not from 0.0, makes n_shards = 1 with weight 1.0 the exact identity (-0.0 and denormals included).
+ * Non-finite inputs give what IEEE arithmetic gives (inf x 0.0 is NaN).  A tensor with g == NULL or n == 0 is skipped; an empty list
+ * succeeds without a launch.  g may not overlap the buckets.  HH_E_ARG, with nothing enqueued: a negative count, a null t, buckets or
+ * weight, n_shards outside 1 .. HH_GRAD_MAX_SHARDS, the bucket refusals of hh_grad_pack, an off that is negative or no multiple of 4, a
+ * range that leaves the bucket, n < 0, a gradient that is not 4-byte aligned. */
+int hh_grad_combine(int32_t n_tensors, const hh_grad_tensor *t, const float *buckets, int64_t bucket_elems, int32_t n_shards,
+                    const double *weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

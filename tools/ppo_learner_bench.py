@@ -62,6 +62,10 @@
           episodes, fight and escape, in the same run: (a) the batch build — window_cut and hh_window_gather against their torch twins (the
           gather as bytes/s of what it reads and writes), the torch parts (critic rows, standardisation), window_batch against policy_batch
           on the episode batch of the last collect; (b) one whole update each; (c) the graph captures over three windows with kl_coeff = 0
+--shards: PPOLearner(group=LocalShards(1)) (learner/shards.py) as a COST next to group=None in the same run: (a) hh_grad_pack and
+          hh_grad_combine alone on a Fight1 module's tensors and on one 64 Mi-element tensor, as bytes/s of their algorithmic bytes (pack:
+          4 B in, 4 B out per element; combine: 4 W B in, 4 B out); (b) the Fight1 eager minibatch step through the driver at 256 and
+          65536 rows, run against run_sharded.  The same spread rule.  What W ranks gain on real hardware is unmeasured
 The network GEMMs are PyTorch / rocBLAS in both modes; only the loss differs.
     python tools/ppo_learner_bench.py [--arenas 16384] [--T 64] [--iters 20] [--out profiles/ppo_learner.log]"""
 import argparse
@@ -105,6 +109,7 @@ def main():
     ap.add_argument("--shuffle", action="store_true", help="only the shuffle_sequences section; its lines are appended to --out")
     ap.add_argument("--heads", action="store_true", help="only the fused-tail section; its lines are appended to --out")
     ap.add_argument("--window", action="store_true", help="only the window-batch section (update_window); its lines are appended to --out")
+    ap.add_argument("--shards", action="store_true", help="only the sharded-update section (group=LocalShards(1)); its lines are appended to --out")
     ap.add_argument("--heads-mode", choices=("torch", "fused"), default="torch", help="--step-launches: the learner's heads option")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
@@ -974,6 +979,67 @@ def main():
     if a.window:
         lines.clear()
         window_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def shards_section():
+        """PPOLearner(group=LocalShards(1)) as a COST next to group=None, and hh_grad_pack / hh_grad_combine alone"""
+        med = statistics.median
+
+        def verdict(t_base, t_new):
+            spread = max(max(t_base) - min(t_base), max(t_new) - min(t_new))
+            d = med(t_new) - med(t_base)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+            return f"this / group=None = {med(t_new) / med(t_base):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --shards on {torch.cuda.get_device_name(0)}: PPOLearner(group=LocalShards(1)) against group=None, all in this "
+            f"run; {a.iters} timed iterations after {a.warmup} warm-up, device events (a later run, appended).  What W ranks gain on real hardware "
+            f"is unmeasured: this is the cost one rank pays")
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, num_sgd_iter=1, sgd_minibatch_size=1 << 30, **kw)
+        base, one = make(), make(group=LR.LocalShards(1))
+        # (a) the two kernels alone
+        params = [p.detach() for p in base.modules[0].parameters()]
+        for label, ps in ((f"a Fight1 module's {len(params)} tensors", params), ("one tensor of 64 Mi elements", [torch.zeros((1 << 26,), device=dev)])):
+            gs = [torch.randn_like(p) for p in ps]
+            lay = LR.grad_layout(gs)
+            n = sum(lay[0])
+            bucket = torch.zeros((lay[2],), dtype=torch.float32, device=dev)
+            t = events(lambda: LR.grad_pack(gs, bucket, lay))
+            say(f"    hh_grad_pack alone, {label} ({n} elements): {q(t)} = {8 * n / med(t) / 1e6:.1f} GB/s of {8 * n / 1e6:.2f} MB algorithmic bytes "
+                f"({100 * 8 * n / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+            for W in (1, 2, 8) if n < (1 << 26) else (1, 2):
+                buckets = bucket.repeat(W, 1).contiguous()
+                wt = [1.0 / W] * W
+                t = events(lambda: LR.grad_combine(gs, buckets, wt, lay))
+                nb = 4 * n * (W + 1)
+                say(f"    hh_grad_combine alone, {label}, W = {W}: {q(t)} = {nb / med(t) / 1e6:.1f} GB/s of {nb / 1e6:.2f} MB algorithmic bytes "
+                    f"({100 * nb / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+                del buckets
+            del gs, bucket
+        # (b) one eager minibatch step of the driver: run against run_sharded on one minibatch
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        with torch.no_grad():
+            b = base.policy_batch(rows, base.old_logits(rows["obs"], bank, ro.episodes.N), 0)
+        seq_len = b["seq_len"].cpu().numpy()
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+            t_n = events(lambda: base._sgd[0].run(*base._columns(sub)))
+            t_s = events(lambda: one._sgd[0].run_sharded(one.group, [one._columns(sub)]))
+            say(f"one eager minibatch step through the driver (Fight1, schedule + forward + loss + backward + Adam + the statistics read back), "
+                f"{int(seq_len[s0:s1].sum())} unpadded rows in {s1 - s0} chunks of 20: group=None {q(t_n)}; LocalShards(1) (+ pack, combine, the "
+                f"statistics through the host) {q(t_s)} [{verdict(t_n, t_s)}]")
+
+    if a.shards:
+        lines.clear()
+        shards_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
