@@ -111,6 +111,17 @@ class HHWindowMetricsBufs(C.Structure):
                                         "counts", "summary", "totals", "scratch")] + [("scratch_bytes", C.c_int64)]
 
 
+class HHEpisodeOutcomeBufs(C.Structure):
+    """hh_episode_outcome_bufs (include/hh_abi.h): sizes, then device pointers; field order is ABI"""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("n_agents", C.c_int32), ("reserved0", C.c_int32), ("ep_cap", C.c_int64)] + [
+        (name, C.c_void_p) for name in ("done", "outcome", "n_episodes", "ep_arena", "ep_len", "ep_return", "ep_outcome", "summary", "flags",
+                                        "scratch")] + [("scratch_bytes", C.c_int64)]
+
+
+OUTCOME_WIN, OUTCOME_LOSE, OUTCOME_DRAW, OUTCOME_NONE = 1, -1, 0, 2  # HH_OUTCOME_*: hh_episode_stats' codes
+# slot names of hh_episode_outcomes' summary f64 [HH_EO_SUMMARY], in slot order
+EO_SUMMARY = ("episodes", "agents_win", "opps_win", "draw", "reward_mean_win", "reward_mean_lose", "reward_mean_draw",
+              "len_mean_win", "len_mean_lose", "len_mean_draw", "other_codes", "reserved")
 EP_METRICS_MAX_AGENTS = 5  # HH_EP_METRICS_MAX_AGENTS
 # hh_episodes_emit_append's accumulator i32 [HH_EP_ACC], in slot order (slot 7 is reserved and stays 0)
 EP_ACC = ("rows", "episodes", "overflow", "sequences", "complete", "collects", "batches", "reserved")
@@ -131,6 +142,7 @@ EXPORTS = ["hh_world_create", "hh_world_destroy", "hh_last_error", "hh_obs_dim",
            "hh_hl_begin_variants", "hh_hl_act_tick", "hh_policy_act_binned_live", "hh_episodes_emit", "hh_policy_refresh", "hh_policy_copy_packed", "hh_episodes_emit_aux",
            "hh_episodes_metrics_scratch_bytes", "hh_episodes_metrics", "hh_episodes_emit_append",
            "hh_window_metrics_scratch_bytes", "hh_window_metrics",
+           "hh_outcome_tap", "hh_episode_outcomes_scratch_bytes", "hh_episode_outcomes",
            "hh_world_snapshot_bytes", "hh_world_snapshot", "hh_world_restore", "hh_policy_snapshot_bytes", "hh_policy_snapshot", "hh_policy_restore"]
 COMMANDER_EXPORTS = ["hh_commander_create", "hh_commander_destroy", "hh_commander_set_weights", "hh_commander_sample",
                      "hh_commander_kernel_name", "hh_commander_episodes_emit", "hh_commander_refresh_weights",
@@ -265,6 +277,9 @@ def lib():
         L.hh_episodes_metrics.argtypes = [C.POINTER(HHEpisodeMetricsBufs), vp]
         L.hh_window_metrics_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
         L.hh_window_metrics.argtypes = [C.POINTER(HHWindowMetricsBufs), vp]
+        L.hh_outcome_tap.argtypes = [vp, vp, vp, vp]
+        L.hh_episode_outcomes_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        L.hh_episode_outcomes.argtypes = [C.POINTER(HHEpisodeOutcomeBufs), vp]
         L.hh_math_eval.argtypes =[C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_policy_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
         L.hh_policy_destroy.argtypes = [vp]

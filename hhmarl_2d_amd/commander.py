@@ -10,7 +10,8 @@ import torch
 
 from . import _lib as L
 from . import policy_nets as PN
-from .rollout import EpisodeBatch, central_critic_rows_hl, collect_until_ready, rollout_load_plan, rollout_state_dict, window_metrics_keyword
+from .rollout import (EpisodeBatch, central_critic_rows_hl, collect_until_ready, outcomes_keyword, rollout_load_plan, rollout_outcome_names,
+                      rollout_state_dict, window_metrics_keyword)
 
 OBS, HIDDEN, N_ACTIONS, N_AGENTS = 34, 200, 3, 3
 
@@ -388,8 +389,15 @@ class CommanderRollout:
     window_metrics = True (keyword-only; batch_mode = "truncate_episodes" only): the same result line for a run that trains from the
     windows — `window_metrics`, a `rollout.WindowMetrics` with the per-agent entries keyed 1..3, carries every arena's running return and
     length across collects and reports the episodes that finish inside each window: five more launches in the collect's graph right
-    behind the GAE.  With the default False it is None and nothing changes."""
+    behind the GAE.  With the default False it is None and nothing changes.
 
+    outcomes = True (keyword-only; needs metrics = True with batch_mode = "complete_episodes", or window_metrics = True): `outcome` i8
+    [T, N], overwritten by every collect — row [t, n] is the outcome of the episode whose done row it is (1 agents win, -1 opponents win,
+    0 draw: `World.episode_stats()`' codes) and 2 elsewhere, tapped right behind every commander step (`World.outcome_tap`: T more
+    launches) — and `episodes` / `window_metrics` own `ep_outcome` and the outcome keys of `metrics()` (two more launches; see
+    rollout.EpisodeBatch).  With the default False `outcome` is None and nothing changes."""
+
+    @outcomes_keyword
     @window_metrics_keyword(CommanderEpisodeBatch.AGENT_KEYS)
     def __init__(self, world, commander, pilot, T, gamma=0.99, lam=1.0, use_graph=True, batch_mode="truncate_episodes", max_seq_len=20,
                  carry_cap=None, metrics=False, train_batch_size=None, record_logits=False):
@@ -440,6 +448,7 @@ class CommanderRollout:
                                                   aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
                                                   train_batch_size=train_batch_size)
         self.window_metrics = None          # window_metrics_keyword puts a rollout.WindowMetrics here
+        self.outcome = None                 # outcomes_keyword puts the tapped window here
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -471,6 +480,8 @@ class CommanderRollout:
                             logp=self.logp[t], vf=self.vf[t], logits=self.logits[t] if self.record_logits else None)
             macro_step(w, self.actions[t], self.pilot, out=(self.obs[t + 1], self.reward[t], self.valid[t], self.done[t]),
                        pilot_buf=self._pbuf, early_exit=False)
+            if self.outcome is not None:
+                w.outcome_tap(self.done[t], self.outcome[t])
         # the bootstrap value of every arena's unfinished tail; its state_out goes to scratch (the carried state does not advance), arenas
         # that just finished are evaluated from zero state (their value is cut by the recursion and never read)
         self.net.sample(self.obs[T], self.state_in[T], self._h_scratch, fresh=self.done[T - 1], greedy=True, actions=self._tmp_act,
@@ -532,11 +543,12 @@ class CommanderRollout:
 
     # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
     def _window_names(self):
-        return ("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target", "state_in", "_fresh") + (("logits",) if self.record_logits else ())
+        return (("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target", "state_in", "_fresh")
+                + (("logits",) if self.record_logits else ()) + rollout_outcome_names(self)[0])
 
     def _options(self):
-        return {"T": self.T, "N": self.w.N, "gamma": self.gamma, "lam": self.lam, "batch_mode": self.batch_mode, "max_seq_len": self.max_seq_len,
-                "record_logits": self.record_logits}
+        return dict({"T": self.T, "N": self.w.N, "gamma": self.gamma, "lam": self.lam, "batch_mode": self.batch_mode,
+                     "max_seq_len": self.max_seq_len, "record_logits": self.record_logits}, **rollout_outcome_names(self)[1])
 
     def state_dict(self):
         """the window buffers of the last collect with the GRU states (state_in[T] and obs[T] / vf[T] are the hand-over of the next one),

@@ -924,5 +924,8 @@ extern "C" int hh_hl_commands(hh_world *w, int8_t *out /* [host] [N, A] */) {
 /* ---- RLlib's episode metrics for fixed-window rollouts: a per-arena carry across windows (C ABI in include/hh_abi.h: hh_window_metrics) ---- */
 #include "hh_window_metrics.h"
 
+/* ---- win / lose / draw per training episode: the tap behind a tick, the episode tables' outcomes and their summary (C ABI in include/hh_abi.h: hh_outcome_tap, hh_episode_outcomes) ---- */
+#include "hh_outcomes.h"
+
 /* ---- opaque, complete snapshots of a world, a policy bank and a commander net: copies only (C ABI in include/hh_abi.h, hh_policy.h, hh_commander.h) ---- */
 #include "hh_snapshot.h"

@@ -125,6 +125,66 @@ def metrics_dict(s, totals, agent_keys):
     return out
 
 
+OUTCOME_CLASSES = ("win", "lose", "draw")   # hh_episode_outcomes' classes in slot order: codes 1, -1, 0
+
+
+def outcome_metrics(s):
+    """hh_episode_outcomes' summary (list of len(_lib.EO_SUMMARY) floats) under the names of evaluation.LOWLEVEL_STAT_KEYS /
+    LowLevelEvaluator.metrics: what `metrics()` gains with outcomes=True"""
+    n, counts = int(s[0]), [int(c) for c in s[1:4]]
+    return {"agents_win": counts[0], "opps_win": counts[1], "draw": counts[2],
+            "outcome_pct": {k: (c / n) * 100 if n else float("nan") for k, c in zip(OUTCOME_CLASSES, counts)},
+            "episode_reward_mean_by_outcome": dict(zip(OUTCOME_CLASSES, s[4:7])),
+            "episode_len_mean_by_outcome": dict(zip(OUTCOME_CLASSES, s[7:10]))}
+
+
+class EpisodeOutcomes:
+    """Win / lose / draw of an episode table (hh_episode_outcomes, include/hh_abi.h: two launches right behind the table's own, no
+    host synchronisation): what `EpisodeBatch` and `WindowMetrics` own when their rollout was built with outcomes=True.
+    `ep_outcome` i8 [ep_cap] (1 agents win, -1 opponents win, 0 draw: entry e is the outcome of the table's episode e; the call writes
+    the window's segment only, the table's last), `summary` f64 [len(_lib.EO_SUMMARY)] over every entry of the table so far, `flags` i32
+    [2] (the table did not hold this window's episodes; the window's done rows)."""
+
+    def __init__(self, done, outcome, n_episodes, ep_arena, ep_len, ep_return):
+        """done u8 / outcome i8 [T, N]: the rollout's window; n_episodes: a 0-d i32 view of the table's device count; ep_arena / ep_len
+        i32 [E], ep_return f64 [E, n_agents]: the table"""
+        T, N = done.shape
+        E, nA = ep_return.shape
+        dev = done.device
+        if tuple(outcome.shape) != (T, N) or outcome.dtype != torch.int8 or not outcome.is_contiguous():
+            raise ValueError(f"outcomes: outcome must be a contiguous int8 tensor of shape {(T, N)}")
+        nbytes = C.c_int64(0)
+        L.check(L.lib().hh_episode_outcomes_scratch_bytes(T, N, E, C.byref(nbytes)))
+        self.ep_outcome = torch.full((E,), L.OUTCOME_NONE, dtype=torch.int8, device=dev)
+        self.summary = torch.zeros((len(L.EO_SUMMARY),), dtype=torch.float64, device=dev)
+        self.flags = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self._scratch = torch.zeros((nbytes.value // 8,), dtype=torch.float64, device=dev)
+        self._keep = (done, outcome, n_episodes, ep_arena, ep_len, ep_return)   # the struct holds raw pointers: keep the tensors alive
+        self._bufs = L.HHEpisodeOutcomeBufs(
+            T=T, N=N, n_agents=nA, reserved0=0, ep_cap=E, done=done.data_ptr(), outcome=outcome.data_ptr(), n_episodes=n_episodes.data_ptr(),
+            ep_arena=ep_arena.data_ptr(), ep_len=ep_len.data_ptr(), ep_return=ep_return.data_ptr(), ep_outcome=self.ep_outcome.data_ptr(),
+            summary=self.summary.data_ptr(), flags=self.flags.data_ptr(), scratch=self._scratch.data_ptr(), scratch_bytes=nbytes.value)
+        self.reset()
+
+    def reset(self):
+        """the summary of an empty table (0 episodes, counts 0, nan means) and clear flags, until the next collect"""
+        self.summary.zero_()
+        self.summary[4:10] = float("nan")
+        self.flags.zero_()
+
+    def enqueue(self, stream):
+        L.check(L.lib().hh_episode_outcomes(C.byref(self._bufs), stream))
+
+    def whole(self):
+        """the small tensors a state_dict saves whole (ep_outcome is saved with the table, cut to its count)"""
+        return {"outcome_summary": self.summary, "outcome_flags": self.flags}
+
+    @staticmethod
+    def failed(summary, flags):
+        """host copies -> did the table not hold a window's episodes, or does an entry carry no outcome?"""
+        return bool(flags[0]) or summary[L.EO_SUMMARY.index("other_codes")] != 0
+
+
 class EpisodeBatch:
     """The whole-episode batch of a `PPORollout(..., batch_mode="complete_episodes")` (train_hetero.py:212): after every collect, the rows
     of every episode that ENDED in it, from its reset row to its done row, in one flat batch — the episode's earlier rows come from a
@@ -172,7 +232,15 @@ class EpisodeBatch:
     Capacity: a batch was below B before its last collect, so R = B - 1 + N (H - 1 + T) rows and E = B - 1 + N T episodes (both must
     stay below 2^31); the carry is unchanged.  For two agents 8 D + 47 bytes per row and 12 per episode (with the logits 256 more per
     row): B = 4 collects' worth of rows at N = 16384, T = 64, fight D = 26 (B = 4194304) is 1.07 GB of rows and 50 MB of episode table
-    more than without.  With the default None everything is what it was: the same entry point, allocations and graph."""
+    more than without.  With the default None everything is what it was: the same entry point, allocations and graph.
+
+    outcomes (the rollouts' keyword-only outcomes=True, with metrics=True; `attach_outcomes`): the batch also owns an `EpisodeOutcomes`
+    over its episode table — `ep_outcome` i8 [E], entry e the outcome of episode e (1 agents win, -1 opponents win, 0 draw), in `rows()`
+    and `metrics_device()` — filled by hh_episode_outcomes right behind the metrics (two more launches), and `metrics()` gains
+    agents_win / opps_win / draw (ints: evaluation.LOWLEVEL_STAT_KEYS' names), outcome_pct = {win, lose, draw} ((count / episodes) *
+    100 as LowLevelEvaluator.metrics computes it; nan with 0 episodes), episode_reward_mean_by_outcome and episode_len_mean_by_outcome
+    (dicts over win / lose / draw; nan for a class without an episode) — over the batch so far, as the other keys.  The caller adds the
+    counts across iterations and ranks.  Without it, nothing is allocated and every key set is what it was."""
 
     COLUMNS = ("obs", "actions", "logp", "vf", "reward", "valid", "adv", "target", "done", "arena", "episode", "t")
     TABLES = ("ep_start", "ep_len", "ep_arena")
@@ -283,6 +351,16 @@ class EpisodeBatch:
                 target=self.target.data_ptr(), ep_start=self.ep_start.data_ptr(), ep_len=self.ep_len.data_ptr(), counts=self._size.data_ptr(),
                 ep_return=self.ep_return.data_ptr(), summary=self._summary.data_ptr(), totals=self._m_totals.data_ptr(),
                 scratch=self._m_scratch.data_ptr(), scratch_bytes=nbytes.value)
+        self._outcomes = None                    # attach_outcomes puts an EpisodeOutcomes here
+
+    def attach_outcomes(self, outcome):
+        """outcome i8 [T, N]: the rollout's tapped window (World.outcome_tap behind every tick).  From now on every emission also fills
+        `ep_outcome` and the outcomes' summary (see the class); needs metrics=True (the summary reads ep_return)."""
+        if self._metrics is None:
+            raise ValueError(f"{type(self).__name__}: outcomes need metrics=True (their summary reads the episodes' returns)")
+        self._outcomes = EpisodeOutcomes(self._collect["done"], outcome, self.n_episodes, self.ep_arena, self.ep_len, self.ep_return)
+        self.ep_outcome = self._outcomes.ep_outcome
+        self._m_host = None
 
     def _capacities(self):
         """(R, E) of this batch; a subclass checks its own capacities here as well"""
@@ -307,7 +385,8 @@ class EpisodeBatch:
 
     def _parts(self):
         """(names, index in the counts of the length they are cut to) for rows()"""
-        return ((self.COLUMNS + ((self.aux_name,) if self.aux_name else ()), 0), (self.TABLES + (("ep_return",) if self._metrics else ()), 1))
+        return ((self.COLUMNS + ((self.aux_name,) if self.aux_name else ()), 0),
+                (self.TABLES + (("ep_return",) if self._metrics else ()) + (("ep_outcome",) if self._outcomes else ()), 1))
 
     def reset(self):
         """no episode spans a reset: the carry and the per-arena episode counters start again (the overflow flag stays); with metrics, the
@@ -318,6 +397,8 @@ class EpisodeBatch:
             self._totals.zero_()
             self._summary.fill_(float("nan"))    # no collect since the reset: what a collect without a finished episode leaves
             self._summary[:2] = 0.0
+        if self._outcomes is not None:
+            self._outcomes.reset()
         self.carried.zero_()
         self._finished.zero_()
         self._counts[:2].zero_()
@@ -351,6 +432,8 @@ class EpisodeBatch:
         if self._metrics is not None:
             self._summary.fill_(float("nan"))    # an empty batch: what a collect without a finished episode leaves
             self._summary[:2] = 0.0
+        if self._outcomes is not None:
+            self._outcomes.reset()
 
     def emit(self, stream):
         aux = None if self._aux is None else C.byref(self._aux)
@@ -363,6 +446,8 @@ class EpisodeBatch:
             L.check(getattr(L.lib(), self._EMIT + "_aux")(C.byref(self._bufs), aux, stream))
         if self._metrics is not None:
             self.enqueue_metrics(stream)
+        if self._outcomes is not None:
+            self._outcomes.enqueue(stream)
 
     def enqueue_metrics(self, stream):
         """hh_episodes_metrics over the batch as it stands, on `stream` (what emit() does right behind the emitter; a second call adds the
@@ -382,7 +467,10 @@ class EpisodeBatch:
         n_agents] (the first n_episodes entries are valid).  Overwritten by the next collect."""
         if self._metrics is None:
             raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
-        return {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return}
+        out = {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return}
+        if self._outcomes is not None:   # ep_outcome [E] like ep_return; outcome_summary: _lib.EO_SUMMARY's slots; outcome_flags i32 [2]
+            out.update(ep_outcome=self.ep_outcome, **self._outcomes.whole())
+        return out
 
     def metrics(self):
         """-> the last collect's metrics (with train_batch_size: the accumulated batch's so far) under RLlib's result names (see the class
@@ -391,19 +479,25 @@ class EpisodeBatch:
         Keys: episode_reward_mean / _min / _max, episode_len_mean, episodes_this_iter, policy_reward_mean / _min / _max, vf_explained_var,
         episodes_total, timesteps_total (RLlib's), and from the same summary episode_len_min / _max and timesteps_this_iter (the batch's
         rows).  The per-agent entries (policy_reward_*, vf_explained_var) are dicts keyed by AGENT_KEYS.  After reset() / start() and
-        before the next collect: 0 episodes, nan, totals 0."""
+        before the next collect: 0 episodes, nan, totals 0.  With outcomes: also outcome_metrics' keys (see the class); a table that did not
+        hold a window's episodes, or an entry without an outcome, raises the overflow error."""
         if self._metrics is None:
             raise RuntimeError(f"{type(self).__name__}: built without metrics=True")
-        src = (self._summary, self._totals, self._counts) + (() if self._acc is None else (self._acc,))
+        eo = () if self._outcomes is None else (self._outcomes.summary, self._outcomes.flags)
+        src = eo + (self._summary, self._totals, self._counts) + (() if self._acc is None else (self._acc,))
         if self._m_host is None:
             self._m_host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in src)
         for h, d in zip(self._m_host, src):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream(self._device).synchronize()
-        s, totals, *flags = (h.tolist() for h in self._m_host)
-        if any(f[2] for f in flags):
+        host = [h.tolist() for h in self._m_host]
+        s, totals, *flags = host[len(eo):]
+        if any(f[2] for f in flags) or (eo and EpisodeOutcomes.failed(*host[:2])):
             raise self._overflow()
-        return metrics_dict(s, totals, self.AGENT_KEYS)
+        out = metrics_dict(s, totals, self.AGENT_KEYS)
+        if eo:
+            out.update(outcome_metrics(host[0]))
+        return out
 
     def rows(self):
         """synchronises; -> dict of views cut to the last collect (with train_batch_size: to the accumulated batch so far): the columns
@@ -422,9 +516,12 @@ class EpisodeBatch:
     # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
     def _options(self):
         """what a saved batch must share with the one it is loaded into"""
-        return {"N": self.N, "T": self.T, "carry_cap": self.carry_cap, "n_agents": self.n_agents, "D": self.D, "aux_name": self.aux_name,
-                "train_batch_size": self.train_batch_size, "metrics": self._metrics is not None, "row_cap": int(self._bufs.row_cap),
-                "ep_cap": int(self._bufs.ep_cap), "gamma": float(self._bufs.gamma), "lam": float(self._bufs.lam)}
+        o = {"N": self.N, "T": self.T, "carry_cap": self.carry_cap, "n_agents": self.n_agents, "D": self.D, "aux_name": self.aux_name,
+             "train_batch_size": self.train_batch_size, "metrics": self._metrics is not None, "row_cap": int(self._bufs.row_cap),
+             "ep_cap": int(self._bufs.ep_cap), "gamma": float(self._bufs.gamma), "lam": float(self._bufs.lam)}
+        if self._outcomes is not None:
+            o["outcomes"] = True
+        return o
 
     def _whole(self):
         """the small tensors saved whole: per-arena counts, the emitter's counts, the accumulator, the metrics' summary and totals"""
@@ -435,6 +532,8 @@ class EpisodeBatch:
             t.update(summary=self._summary, totals=self._totals)
             if self._m_totals is not self._totals:
                 t["m_totals"] = self._m_totals
+        if self._outcomes is not None:
+            t.update(self._outcomes.whole())
         return t
 
     def _carry_lead(self, k, m):
@@ -499,7 +598,12 @@ class WindowMetrics:
     The two differences from RLlib of EpisodeBatch's metrics hold here too (the means are over the episodes finished in THIS window, no
     smoothing over the last 100; `vf_explained_var` is the sampler's VF_PREDS against the value targets), and `vf_explained_var` is
     taken over the window's T N rows, whose targets bootstrap at the window's end.  A window without a finished episode reports
-    episodes_this_iter = 0 and nan for the episode entries, but its timesteps and vf_explained_var as always."""
+    episodes_this_iter = 0 and nan for the episode entries, but its timesteps and vf_explained_var as always.
+
+    outcomes (the rollouts' keyword-only outcomes=True; `attach_outcomes`): also an `EpisodeOutcomes` over the table — `ep_outcome` i8
+    [T N], entry e the outcome of the window's episode e (1 agents win, -1 opponents win, 0 draw), in `episodes()` and
+    `metrics_device()`; two more launches right behind hh_window_metrics; `metrics()` gains the keys EpisodeBatch.metrics() gains
+    (outcome_metrics), over the episodes finished in this window.  Without it, nothing is allocated and every key set is what it was."""
 
     TABLES = ("ep_return", "ep_len", "ep_arena", "ep_end")
 
@@ -537,7 +641,16 @@ class WindowMetrics:
             run_len=self.run_len.data_ptr(), ep_return=self.ep_return.data_ptr(), ep_len=self.ep_len.data_ptr(),
             ep_arena=self.ep_arena.data_ptr(), ep_end=self.ep_end.data_ptr(), counts=self.counts.data_ptr(),
             summary=self._summary.data_ptr(), totals=self._totals.data_ptr(), scratch=self._scratch.data_ptr(), scratch_bytes=nbytes.value)
+        self._outcomes = None                    # attach_outcomes puts an EpisodeOutcomes here
         self.reset()
+
+    def attach_outcomes(self, outcome):
+        """outcome i8 [T, N]: the rollout's tapped window (World.outcome_tap behind every tick).  From now on every call also fills
+        `ep_outcome` and the outcomes' summary (see the class)."""
+        self._outcomes = EpisodeOutcomes(self._collect["done"], outcome, self.n_episodes, self.ep_arena, self.ep_len, self.ep_return)
+        self.ep_outcome = self._outcomes.ep_outcome
+        self.TABLES = type(self).TABLES + ("ep_outcome",)
+        self._host = None
 
     def reset(self):
         """no episode spans a reset: the carry and the running totals start again, and the summary is that of a window without a
@@ -548,44 +661,60 @@ class WindowMetrics:
         self.counts.zero_()
         self._summary.fill_(float("nan"))
         self._summary[:2] = 0.0
+        if self._outcomes is not None:
+            self._outcomes.reset()
 
     def enqueue(self, stream):
         """hh_window_metrics over the window as it stands, on `stream` (what the rollout's collect does right behind the GAE).  Every
-        call advances the carry and the totals by one window."""
+        call advances the carry and the totals by one window.  With outcomes, hh_episode_outcomes follows it."""
         L.check(L.lib().hh_window_metrics(C.byref(self._bufs), stream))
+        if self._outcomes is not None:
+            self._outcomes.enqueue(stream)
 
     def metrics_device(self):
         """the device tensors of the last collect's metrics, without synchronising: `summary` (slots: _lib.EP_METRICS_SLOT), `totals`,
         the table `ep_return` / `ep_len` / `ep_arena` / `ep_end` (the first counts[0] entries are valid) and `counts`.  Overwritten by
         the next collect."""
-        return {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return, "ep_len": self.ep_len,
-                "ep_arena": self.ep_arena, "ep_end": self.ep_end, "counts": self.counts}
+        out = {"summary": self._summary, "totals": self._totals, "ep_return": self.ep_return, "ep_len": self.ep_len,
+               "ep_arena": self.ep_arena, "ep_end": self.ep_end, "counts": self.counts}
+        if self._outcomes is not None:   # ep_outcome [T N] like the table; outcome_summary: _lib.EO_SUMMARY's slots; outcome_flags i32 [2]
+            out.update(ep_outcome=self.ep_outcome, **self._outcomes.whole())
+        return out
 
     def metrics(self):
         """-> the last window's metrics under RLlib's result names, the keys and types of `EpisodeBatch.metrics()` (per-agent entries are
         dicts keyed by AGENT_KEYS); copies the summary and the totals to the host: one synchronisation of the current stream.  After
-        reset() / start() and before the next collect: 0 episodes, 0 timesteps, nan, totals 0."""
-        src = (self._summary, self._totals)
+        reset() / start() and before the next collect: 0 episodes, 0 timesteps, nan, totals 0.  With outcomes: also outcome_metrics' keys
+        (see the class); RuntimeError if the outcomes did not match the table or an entry carries none."""
+        src = (self._summary, self._totals) + (() if self._outcomes is None else (self._outcomes.summary, self._outcomes.flags))
         if self._host is None:
             self._host = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in src)
         for h, d in zip(self._host, src):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream(self._device).synchronize()
-        s, totals = (h.tolist() for h in self._host)
-        return metrics_dict(s, totals, self.AGENT_KEYS)
+        s, totals, *eo = (h.tolist() for h in self._host)
+        out = metrics_dict(s, totals, self.AGENT_KEYS)
+        if eo:
+            if EpisodeOutcomes.failed(*eo):
+                raise RuntimeError("WindowMetrics: the window's outcomes do not match its episode table (an entry of another arena, or a "
+                                   "done row without an outcome): the outcome metrics since that collect are incomplete")
+            out.update(outcome_metrics(eo[0]))
+        return out
 
     def episodes(self):
-        """synchronises; -> dict of views cut to the episodes that finished in the last window: ep_return, ep_len, ep_arena, ep_end"""
+        """synchronises; -> dict of views cut to the episodes that finished in the last window: ep_return, ep_len, ep_arena, ep_end
+        (with outcomes: ep_outcome too)"""
         torch.cuda.synchronize(self._device)
         n = int(self.counts[0])
         return {k: getattr(self, k)[:n] for k in self.TABLES}
 
     # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
     def _options(self):
-        return {"T": self.T, "N": self.N, "n_agents": self.n_agents}
+        return dict({"T": self.T, "N": self.N, "n_agents": self.n_agents}, **({} if self._outcomes is None else {"outcomes": True}))
 
     def _whole(self):
-        return {"run_return": self.run_return, "run_len": self.run_len, "counts": self.counts, "summary": self._summary, "totals": self._totals}
+        return dict({"run_return": self.run_return, "run_len": self.run_len, "counts": self.counts, "summary": self._summary, "totals": self._totals},
+                    **({} if self._outcomes is None else self._outcomes.whole()))
 
     def state_dict(self):
         """the carry, the counts, the summary and the totals whole, the table cut to the count.  Scratch is not saved.  Synchronises the
@@ -643,6 +772,45 @@ def window_metrics_keyword(agent_keys):
             self.window_metrics = WindowMetrics({k: getattr(self, k) for k in ("reward", "vf", "target", "done")}, agent_keys) if on else None
         return __init__
     return wrap
+
+
+def check_outcomes(outcomes, batch_mode, metrics, window_metrics):
+    """outcomes as both rollouts' constructors take it -> bool, or ValueError"""
+    if not isinstance(outcomes, bool):
+        raise ValueError(f"outcomes: False or True, got {outcomes!r}")
+    if outcomes and not ((metrics and batch_mode == "complete_episodes") or window_metrics):
+        raise ValueError("outcomes=True needs a consumer of the episode table: metrics=True with batch_mode='complete_episodes', or "
+                         "window_metrics=True")
+    return outcomes
+
+
+def outcomes_keyword(init):
+    """Decorator of both rollouts' `__init__`, around window_metrics_keyword's: adds the keyword-only `outcomes=False` the same way (the
+    positional signature, and `inspect.signature` through `__wrapped__`, stay as they were; `window_metrics` is declared again and
+    handed on, so that the outermost signature still shows it).  Validated (check_outcomes) before the
+    constructor runs, so before the world is touched.  With True, `self.outcome` is the tapped window — i8 [T, N], row [t, n] the outcome
+    of the episode whose done row it is (1 agents win, -1 opponents win, 0 draw) and 2 elsewhere, written by World.outcome_tap right
+    behind every tick of `_run` — and the rollout's episode batch / WindowMetrics owns the table's outcomes (`attach_outcomes`).  With the
+    default it is None: no allocation, no launch, the same graph."""
+    sig = inspect.signature(init)                    # the constructor's own parameters (through __wrapped__)
+
+    @functools.wraps(init)
+    def __init__(self, *args, window_metrics=False, outcomes=False, **kw):   # window_metrics: handed on as it came
+        a = sig.bind(self, *args, **kw)              # TypeError for arguments the constructor does not take, as from the constructor
+        a.apply_defaults()
+        on = check_outcomes(outcomes, a.arguments["batch_mode"], a.arguments["metrics"], window_metrics)
+        init(self, *args, window_metrics=window_metrics, **kw)
+        if on:
+            self.outcome = torch.full(tuple(self.done.shape), L.OUTCOME_NONE, dtype=torch.int8, device=self.done.device)
+            for consumer in (self.episodes, self.window_metrics):
+                if consumer is not None:
+                    consumer.attach_outcomes(self.outcome)
+    return __init__
+
+
+def rollout_outcome_names(ro):
+    """what `outcomes=True` adds to a rollout's saved window buffers and options"""
+    return (("outcome",), {"outcomes": True}) if ro.outcome is not None else ((), {})
 
 
 def rollout_state_dict(ro, names, options):
@@ -738,8 +906,17 @@ class PPORollout:
     that trains from the windows — `window_metrics`, a `WindowMetrics`, carries every arena's running return and length on the device
     across collects and reports the episodes that finish inside each window (`window_metrics.metrics()`: the keys of
     `episodes.metrics()`): five more launches in the collect's graph right behind the GAE.  With the default False it is None, nothing
-    is allocated and the launches, the graph, the buffers and `state_dict()` are what they were."""
+    is allocated and the launches, the graph, the buffers and `state_dict()` are what they were.
 
+    outcomes = True (keyword-only; needs metrics = True with batch_mode = "complete_episodes", or window_metrics = True): win, lose and
+    draw of every training episode.  `outcome` i8 [T, N] is one more window buffer, overwritten by every collect: row [t, n] is the outcome
+    of the episode whose done row it is — 1 agents win, -1 opponents win, 0 draw, `World.episode_stats()`' codes — and 2 elsewhere, tapped
+    right behind every tick (`World.outcome_tap`: T more launches in the collect's graph).  `episodes` / `window_metrics` then own
+    `ep_outcome`, one entry per episode of their table, and their `metrics()` gains agents_win / opps_win / draw, outcome_pct and the
+    mean reward and length per outcome (two more launches; see EpisodeBatch).  `state_dict()` holds all of it.  With the default False
+    `outcome` is None, nothing is allocated and the launches, the graph, `metrics()` and `state_dict()` are what they were."""
+
+    @outcomes_keyword
     @window_metrics_keyword(EpisodeBatch.AGENT_KEYS)
     def __init__(self, world, bank, T, gamma=0.99, lam=0.95, use_graph=True, opponents=None, semantics="rllib", batch_mode="truncate_episodes",
                  metrics=False, train_batch_size=None, record_logits=False):
@@ -801,6 +978,7 @@ class PPORollout:
                                          self.gamma, self.lam, aux=("logits", self.logits) if self.record_logits else None, metrics=bool(metrics),
                                          train_batch_size=train_batch_size)
         self.window_metrics = None          # window_metrics_keyword puts a WindowMetrics here
+        self.outcome = None                 # outcomes_keyword puts the tapped window here
         self.use_graph = use_graph
         self._graph = None
         self._started = False
@@ -829,6 +1007,8 @@ class PPORollout:
                 self.w.step_finish(self.opponents(self._opp_obs, None).contiguous(), out=out)
             else:
                 self.w.step(self.actions[t], out=out)
+            if self.outcome is not None:
+                self.w.outcome_tap(self.done[t], self.outcome[t])
         # value of the observation after the last tick: the bootstrap of every arena's unfinished tail (an arena that just finished starts a
         # new episode there: both recursions cut at done and never read it)
         self.bank.sample(self.obs[T], None, greedy=True, actions=self._tmp_act, logp=self._tmp_logp, vf=self.vf[T])
@@ -869,11 +1049,12 @@ class PPORollout:
 
     # ---- checkpointing (hhmarl_2d_amd/checkpoint.py)
     def _window_names(self):
-        return ("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target") + (("logits",) if self.record_logits else ())
+        return (("obs", "actions", "logp", "vf", "reward", "valid", "done", "adv", "target") + (("logits",) if self.record_logits else ())
+                + rollout_outcome_names(self)[0])
 
     def _options(self):
-        return {"T": self.T, "N": self.w.N, "D": self.w.D, "gamma": self.gamma, "lam": self.lam, "semantics": self.semantics,
-                "batch_mode": self.batch_mode, "record_logits": self.record_logits, "split": self.split}
+        return dict({"T": self.T, "N": self.w.N, "D": self.w.D, "gamma": self.gamma, "lam": self.lam, "semantics": self.semantics,
+                     "batch_mode": self.batch_mode, "record_logits": self.record_logits, "split": self.split}, **rollout_outcome_names(self)[1])
 
     def state_dict(self):
         """the window buffers of the last collect (obs[T] / vf[T] are the hand-over rows of the next one), `collects`, `_started` and the

@@ -219,6 +219,16 @@ class World:
         L.check(L.lib().hh_episode_stats(self.h, _p(ret), _p(ln), _p(oc), self._stream()))
         return ret, ln, oc
 
+    def outcome_tap(self, done_row, out_row):
+        """right behind a tick: out_row[n] = episode_stats()' outcome of arena n where done_row[n] is set (1 agents win, -1 opponents win,
+        0 draw), 2 elsewhere.  done_row u8 [N] (the tick's done output), out_row i8 [N], both on the world's device.  One launch on the
+        current stream (hh_outcome_tap): it only reads the world, so it may follow every tick of a captured graph."""
+        for t, dt, name in ((done_row, torch.uint8, "done_row"), (out_row, torch.int8, "out_row")):
+            if t.dtype != dt or tuple(t.shape) != (self.N,) or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"outcome_tap: {name} must be a contiguous {dt} tensor of shape ({self.N},) on {self.device}")
+        L.check(L.lib().hh_outcome_tap(self.h, _p(done_row), _p(out_row), self._stream()))
+        return out_row
+
     def episode_stats_packed(self, out=None):
         """f32 [N, 3] (return, length, outcome) of the last finished episode per arena, one launch"""
         if out is None:

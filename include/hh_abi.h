@@ -468,6 +468,58 @@ typedef struct hh_window_metrics_bufs {   /* field order is ABI; host struct of 
 int hh_window_metrics_scratch_bytes(int32_t T, int32_t N, int32_t n_agents, int64_t *bytes);
 int hh_window_metrics(const hh_window_metrics_bufs *m, void *stream);
 
+/* Win / lose / draw of every training episode.  The step kernels write an arena's outcome (hh_episode_stats' codes) when it finishes an
+ * episode, and under auto-reset its next finished episode overwrites the value.  hh_outcome_tap, enqueued right behind a tick, keeps it:
+ *   out_row[n] = done_row[n] != 0 ? last_outcome[n] : HH_OUTCOME_NONE          for all N arenas of the world
+ * done_row [dev] u8 [N] is the tick's done output, out_row [dev] i8 [N].  One small launch on `stream`; it only reads the world, makes
+ * no allocation and no synchronisation (graph-capturable).  HH_E_ARG (hh_last_error() starts with "hh_outcome_tap: ") for a NULL
+ * argument. */
+#define HH_OUTCOME_WIN 1       /* agents win */
+#define HH_OUTCOME_LOSE (-1)   /* opponents win */
+#define HH_OUTCOME_DRAW 0
+#define HH_OUTCOME_NONE 2      /* no episode finished (hh_episode_stats: none finished yet) */
+int hh_outcome_tap(hh_world *w, const uint8_t *done_row, int8_t *out_row, void *stream);
+
+/* The outcomes of an episode table and their summary, behind hh_episodes_emit* / hh_commander_episodes_emit* (+ hh_episodes_metrics) or
+ * hh_window_metrics.  Both tables list the episodes that ended in a window arena-major, then in time, so the j-th done row of arena n is
+ * the window's entry e0 + offset(n) + j: offset is the exclusive scan of the arenas' done counts, m their total, and e0 = e1 - m with e1
+ * the table's device count (the window's segment is the table's last one — also in a batch that accumulates under
+ * hh_episodes_emit_append).  Two launches on `stream` (count, then one workgroup: scan, check, write, summary), no host synchronisation,
+ * no allocation (graph-capturable), no atomics; nothing but the outputs below is written.
+ *   ep_outcome       i8 [ep_cap]: entry e0 + offset(n) + j = outcome[t, n] at arena n's j-th done row t.  Only [e0, e1) is written:
+ *                    earlier segments keep their bytes.
+ *   summary          f64 [HH_EO_SUMMARY] over the entries [0, e1): [0] episodes (e1); [1..3] episodes won / lost / drawn (codes 1 / -1 /
+ *                    0); [4..6] the mean episode reward per class, an episode's reward being the sum of its agents' ep_return in agent
+ *                    order (hh_episodes_metrics' convention); [7..9] the mean ep_len per class; [10] entries with any other code;
+ *                    [11] 0.  A class without an episode has count 0 and NaN means.
+ *   flags            i32 [2]: [0] != 0 when e1 < m or some ep_arena[e0 + offset(n) + j] != n — the table does not hold this window's
+ *                    episodes (after an emitter overflow, say) — and then NOTHING is written to ep_outcome; [1] = m.
+ * e1 is read on the device from n_episodes[0] and clamped to 0 .. ep_cap.
+ * Determinism: float64; the order of the entries comes from the scan; the summary adds tiles of 1024 entries in index order, inside a
+ * tile one entry per lane, a butterfly over each wave's 64 lanes and the 16 waves in index order — the same inputs give the same bytes
+ * on every run.
+ * HH_E_ARG, nothing enqueued (hh_last_error() starts with the function's name): b = NULL, a NULL pointer, T < 1, N < 1, T N above
+ * 2^31 - 1024, ep_cap outside 1 .. 2^31 - 1024, n_agents outside 1 .. HH_EP_METRICS_MAX_AGENTS, reserved0 != 0, n_episodes / ep_arena /
+ * ep_len / flags not 4-byte aligned, ep_return / summary / scratch not 8-byte aligned, scratch_bytes below
+ * hh_episode_outcomes_scratch_bytes(T, N, ep_cap). */
+#define HH_EO_SUMMARY 12
+typedef struct hh_episode_outcome_bufs {   /* field order is ABI; host struct of device pointers */
+    int32_t T, N, n_agents, reserved0;     /* n_agents 1 .. HH_EP_METRICS_MAX_AGENTS; reserved0 must be 0 */
+    int64_t ep_cap;                        /* entries of the episode table */
+    const uint8_t *done;                   /* [dev] u8 [T, N]  the window */
+    const int8_t *outcome;                 /* [dev] i8 [T, N]  hh_outcome_tap's rows */
+    const int32_t *n_episodes;             /* [dev] i32 [1]: e1, the table's count (the emitter's counts[1] / acc[1], hh_window_metrics' counts[0]) */
+    const int32_t *ep_arena;               /* [dev] i32 [ep_cap] */
+    const int32_t *ep_len;                 /* [dev] i32 [ep_cap] */
+    const double *ep_return;               /* [dev] f64 [ep_cap, n_agents] */
+    int8_t *ep_outcome;                    /* [dev] i8 [ep_cap] out */
+    double *summary;                       /* [dev] f64 [HH_EO_SUMMARY] out */
+    int32_t *flags;                        /* [dev] i32 [2] out */
+    void *scratch; int64_t scratch_bytes;  /* [dev] >= hh_episode_outcomes_scratch_bytes(...), 8-byte aligned */
+} hh_episode_outcome_bufs;
+int hh_episode_outcomes_scratch_bytes(int32_t T, int32_t N, int64_t ep_cap, int64_t *bytes);
+int hh_episode_outcomes(const hh_episode_outcome_bufs *b, void *stream);
+
 /* Test probe: the shared math of include/hh_math.h / hh_geodesic.h evaluated ON THE DEVICE over arrays of operands, so that a
  * -m gpu test can compare the kernels' arithmetic with the CPU oracle's bit for bit (tests/test_gpu_math.py), not only through
  * trajectories.  fn: 0 sincos(a) -> o0, o1 | 1 atan2(a, b) | 2 acos(a) | 3 sincosd(a) -> o0, o1 | 4 atan2d(a, b) | 5 pymod(a, b) |

@@ -11,8 +11,11 @@ appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_tim
 rule); its lines are APPENDED to --out.
 --window measures only what window_metrics=True costs a truncate_episodes collect (tools/episode_metrics_timing.py: the same rule, and
 hh_window_metrics's five launches alone); its lines are APPENDED to --out.
+--outcomes measures only what outcomes=True costs a collect (T taps and hh_episode_outcomes' two launches), in the same run against its
+own twin without the option (complete_episodes with metrics=True; tools/episode_metrics_timing.py: the same rule); its lines are
+APPENDED to --out.
     python tools/commander_episodes_bench.py [--arenas 8192] [--steps 16] [--horizon 500] [--warmup 8] [--collects 10] [--rounds 3]
-        [--logits] [--metrics] [--accumulate] [--window] [--out profiles/commander_episodes.log]"""
+        [--logits] [--metrics] [--accumulate] [--window] [--outcomes] [--out profiles/commander_episodes.log]"""
 import argparse
 import math
 import os
@@ -28,19 +31,19 @@ from hhmarl_2d_amd.commander import CommanderNet, CommanderRollout, random_weigh
 from hhmarl_2d_amd.pilots import VariantNetPilot  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
 from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
-from episode_metrics_timing import metrics_lines, window_lines  # noqa: E402  (tools/, next to this file)
+from episode_metrics_timing import metrics_lines, outcome_lines, window_lines  # noqa: E402  (tools/, next to this file)
 
 ROW_IN = 3 * 34 * 4 + 3 + 3 * 4 * 3 + 3          # obs, actions, logp / vf / reward, valid of one arena row
 ROW_OUT = ROW_IN + 3 * 4 * 2 + 1 + 3 * 4          # + adv / target, done, arena / episode / t
 STATE = 3 * 2 * 200 * 4                          # the GRU states of one arena row
 
 
-def make(N, T, H, mode, train_batch_size=None):
+def make(N, T, H, mode, train_batch_size=None, outcomes=False):
     w = World(make_config(n_arenas=N, env_kind=L.ENV_HIGHLEVEL, n_agents=3, n_opps=3, seed=1, auto_reset=True, horizon=H), device=0)
     net = CommanderNet(0, 3 * N).set_weights(random_weights(6))
     rec, met = mode.endswith("+logits"), mode.endswith("+metrics")
     return CommanderRollout(w, net, VariantNetPilot(w, seed=8), T, batch_mode=mode.split("+")[0], metrics=met, train_batch_size=train_batch_size,
-                            record_logits=rec, window_metrics=mode.endswith("+window_metrics"))
+                            record_logits=rec, window_metrics=mode.endswith("+window_metrics"), outcomes=outcomes)
 
 
 def ms_per_collect(ro, n):
@@ -80,8 +83,18 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "commander_episodes.log"))
     ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
     ap.add_argument("--window", action="store_true", help="only: what window_metrics=True costs a truncate_episodes collect; appends its lines to --out")
+    ap.add_argument("--outcomes", action="store_true", help="only: what outcomes=True costs a collect; appends its lines to --out")
     a = ap.parse_args()
     N, T, H = a.arenas, a.steps, a.horizon
+    if a.outcomes:
+        olines = [f"# tools/commander_episodes_bench.py --outcomes on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per "
+                  f"collect, VariantNetPilot, horizon {H}"]
+        mode = "complete_episodes+metrics"
+        olines += outcome_lines(make(N, T, H, mode), make(N, T, H, mode, outcomes=True), mode)
+        print("\n".join(olines), flush=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(olines) + "\n")
+        return
     if a.window:
         wlines = [f"# tools/commander_episodes_bench.py --window on {torch.cuda.get_device_name(0)}: {N} arenas x {T} commander steps per "
                   f"collect, VariantNetPilot, horizon {H}"]

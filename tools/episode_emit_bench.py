@@ -14,8 +14,11 @@ appending to it with B = 4 collects' worth of rows (tools/episode_accumulate_tim
 rule); its lines are appended to --out.
 --window measures only what window_metrics=True costs a truncate_episodes collect (tools/episode_metrics_timing.py: the same rule, and
 hh_window_metrics's five launches alone); its lines are appended to --out.
+--outcomes measures only what outcomes=True costs a collect (T taps and hh_episode_outcomes' two launches), in the same run against its
+own twin without the option, for both consumers: complete_episodes with metrics=True, and truncate_episodes with window_metrics=True
+(tools/episode_metrics_timing.py: the same rule); its lines are appended to --out.
     python tools/episode_emit_bench.py [--arenas 16384] [--ticks 64] [--warmup 20] [--collects 30] [--rounds 3] [--logits]
-        [--metrics [--out profiles/episode_emit.log]] | --accumulate | --window [--arenas 16384] [--ticks 64] [--out ...]"""
+        [--metrics [--out profiles/episode_emit.log]] | --accumulate | --window | --outcomes [--arenas 16384] [--ticks 64] [--out ...]"""
 import argparse
 import os
 import statistics
@@ -28,12 +31,15 @@ from hhmarl_2d_amd import pilots  # noqa: E402
 from hhmarl_2d_amd.rollout import PPORollout  # noqa: E402
 from hhmarl_2d_amd.world import World, make_config  # noqa: E402
 from episode_accumulate_timing import accumulate_lines  # noqa: E402  (tools/, next to this file)
-from episode_metrics_timing import metrics_lines, window_lines  # noqa: E402  (tools/, next to this file)
+from episode_metrics_timing import metrics_lines, outcome_lines, window_lines  # noqa: E402  (tools/, next to this file)
 
 
-def make(N, T, mode, train_batch_size=None):
+def make(N, T, mode, train_batch_size=None, outcomes=False):
     w = World(make_config(n_arenas=N, level=3, seed=1, auto_reset=True), device=0)
     bank = pilots.PolicyBank.trainable_init(w.device, seed=0, max_rows=2 * N)
+    if outcomes:
+        kw = dict(window_metrics=True) if mode.endswith("+window_metrics") else dict(metrics=True)
+        return PPORollout(w, bank, T, batch_mode=mode.split("+")[0], outcomes=True, **kw)
     if mode.endswith("+window_metrics"):
         return PPORollout(w, bank, T, batch_mode=mode[:-len("+window_metrics")], window_metrics=True)
     if train_batch_size is not None:
@@ -80,8 +86,17 @@ def main():
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "episode_emit.log"))
     ap.add_argument("--accumulate", action="store_true", help="only: what train_batch_size = 4 N T costs a collect; appends its lines to --out")
     ap.add_argument("--window", action="store_true", help="only: what window_metrics=True costs a truncate_episodes collect; appends its lines to --out")
+    ap.add_argument("--outcomes", action="store_true", help="only: what outcomes=True costs a collect, for both consumers; appends its lines to --out")
     a = ap.parse_args()
     N, T = a.arenas, a.ticks
+    if a.outcomes:
+        lines = [f"# tools/episode_emit_bench.py --outcomes on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, level 3 fight"]
+        for mode in ("complete_episodes+metrics", "truncate_episodes+window_metrics"):
+            lines += outcome_lines(make(N, T, mode), make(N, T, mode, outcomes=True), mode)
+        print("\n".join(lines))
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if a.window:
         lines = [f"# tools/episode_emit_bench.py --window on {torch.cuda.get_device_name(0)}: {N} arenas x {T} ticks per collect, level 3 fight"]
         lines += window_lines(make(N, T, "truncate_episodes"), make(N, T, "truncate_episodes+window_metrics"))

@@ -4,7 +4,9 @@ launches alone, and the lines both tools report about an `EpisodeBatch(metrics=T
 configuration and seed in one process, one with the option and one without, timed alternately collect by collect with device events:
 medians of 20 timed collects after 3 warm-up, and a difference counts only where the medians differ by more than the larger of the two
 runs' (max - min) spreads; then hh_window_metrics's five launches alone.  Reported as a cost against the collect without the option,
-not gated."""
+not gated.
+--outcomes (both tools): what outcomes=True costs a collect — T taps (hh_outcome_tap) and hh_episode_outcomes' two launches — by the
+same rule, the rollout with the option against its own twin without it; then the two table launches and one tap alone."""
 import ctypes as C
 import statistics
 
@@ -101,3 +103,54 @@ def window_lines(plain, on):
             f"last collect: episode_reward_mean {m['episode_reward_mean']:.4f} min {m['episode_reward_min']:.4f} max {m['episode_reward_max']:.4f} "
             f"episode_len_mean {m['episode_len_mean']:.2f} vf_explained_var {m['vf_explained_var']} episodes_total {m['episodes_total']} "
             f"timesteps_total {m['timesteps_total']}"]
+
+
+def _consumer(ro):
+    return ro.episodes if ro.episodes is not None else ro.window_metrics
+
+
+def _alone_us(call, n=200):
+    """an idempotent enqueue, eagerly, back to back on the idle stream -> us per call (launch gaps included)"""
+    for _ in range(10):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / n
+
+
+def outcome_lines(plain, on, what):
+    """plain / on: two rollouts of one configuration and seed, on with outcomes=True; what: the configuration's name -> the lines for the
+    log.  hh_episode_outcomes rewrites the same segment from the same window and a tap the same row: both are timed alone as they stand."""
+    for _ in range(WARMUP):
+        plain.collect()
+        on.collect()
+    torch.cuda.synchronize()
+    t_plain, t_on, eps = [], [], []
+    c = _consumer(on)
+    for _ in range(TIMED):                          # alternate: drift of the box hits both
+        t_plain.append(_ms(plain))
+        t_on.append(_ms(on))
+        eps.append(int(c.metrics_device()["outcome_flags"][1]))
+    m = c.metrics()
+    st = C.c_void_p(torch.cuda.current_stream(on.done.device).cuda_stream)
+    table_us = _alone_us(lambda: c._outcomes.enqueue(st))
+    tap_us = _alone_us(lambda: on.w.outcome_tap(on.done[0], on.outcome[0]))
+    med = statistics.median
+    d = med(t_on) - med(t_plain)
+    spread = max(max(t_plain) - min(t_plain), max(t_on) - min(t_on))
+    word = "no difference beyond the spread" if abs(d) <= spread else ("cost" if d > 0 else "gain")
+    paired = med([a - p for a, p in zip(t_on, t_plain)])
+    T = on.done.shape[0]
+    return [f"{what}: ms per collect, medians of {TIMED} after {WARMUP}: without {med(t_plain):.3f} (min {min(t_plain):.3f}, max {max(t_plain):.3f}) | "
+            f"outcomes=True {med(t_on):.3f} (min {min(t_on):.3f}, max {max(t_on):.3f})",
+            f"{what}: outcomes overhead ({T} taps + two table launches): medians {d * 1e3:+.1f} us apart = {100 * d / med(t_plain):+.3f} % of a collect, "
+            f"larger spread {spread * 1e3:.1f} us: {word} (median of the {TIMED} paired differences {paired * 1e3:+.1f} us)",
+            f"{what}: alone (eager, back to back, launch gaps included): hh_episode_outcomes {table_us:.1f} us per call on a table of "
+            f"{m['episodes_this_iter']} episodes, hh_outcome_tap {tap_us:.1f} us per call; episodes ended per timed window min {min(eps)} max {max(eps)}",
+            f"{what}: last collect: agents_win {m['agents_win']} opps_win {m['opps_win']} draw {m['draw']} outcome_pct {m['outcome_pct']} "
+            f"episode_reward_mean_by_outcome {m['episode_reward_mean_by_outcome']} episode_len_mean_by_outcome {m['episode_len_mean_by_outcome']}"]
