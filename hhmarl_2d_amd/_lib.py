@@ -157,9 +157,11 @@ LEARNER_EXPORTS = ["hh_ppo_loss_scratch_bytes", "hh_ppo_loss", "hh_ppo_loss_cate
                    "hh_adam_step", "hh_minibatch_stage", "hh_train_commit", "hh_gru_seq_tile",
                    "hh_grad_norm_scratch_bytes", "hh_grad_norm", "hh_adam_step_clipped", "hh_minibatch_stage_gather",
                    "hh_heads_loss_scratch_bytes", "hh_heads_loss_geometry", "hh_heads_loss", "hh_window_cut", "hh_window_gather",
-                   "hh_grad_pack", "hh_grad_combine"]  # include/hh_learner.h
+                   "hh_grad_pack", "hh_grad_combine", "hh_attn_block_tile", "hh_attn_block_save_bytes", "hh_attn_block_scratch_bytes",
+                   "hh_attn_block_forward", "hh_attn_block_backward"]  # include/hh_learner.h
 GRU_TILES = (16, 8, 4)  # the compiled instances of hh_k_gru_seq_fwd / _bwd (HH_GRU_TILE forces one; hh_gru_seq_tile tells which a call uses)
 ATTN_HEADS, ATTN_MAX_LEN, ATTN_WIDTHS = 2, 32, (100, 150)  # HH_ATTN_HEADS, HH_ATTN_MAX_LEN and the compiled widths of hh_chunk_attn_* / hh_residual_normalize_*
+ATTN_BLOCK_ROWS, ATTN_BLOCK_MAX_WG = 32, 128  # HH_ATTN_BLOCK_ROWS, HH_ATTN_BLOCK_MAX_WG: rows of a tile and the backward's workgroup cap of hh_attn_block_*
 PPO_STATS = ("total_loss", "mean_policy_loss", "mean_vf_loss", "mean_kl", "mean_entropy", "n_valid")  # hh_ppo_loss's stats f64 [HH_PPO_STATS]
 
 
@@ -322,6 +324,11 @@ def lib():
         L.hh_chunk_attn_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
         L.hh_residual_normalize_forward.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
         L.hh_residual_normalize_backward.argtypes = [C.c_int64, C.c_int32, vp, vp, vp, vp, vp]
+        L.hh_attn_block_tile.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.hh_attn_block_save_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_attn_block_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.hh_attn_block_forward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
+        L.hh_attn_block_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
         L.hh_input_stage_scratch_bytes.argtypes = [C.c_int32, C.POINTER(HHInputGroup), C.c_int64, C.POINTER(C.c_int64)]
         L.hh_input_stage_forward.argtypes = [C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HHInputGroup), vp]
         L.hh_input_stage_backward.argtypes = [C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HHInputGroup), vp, C.c_int64, vp]

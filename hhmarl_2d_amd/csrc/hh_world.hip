@@ -840,6 +840,9 @@ extern "C" int hh_gae_rllib(int32_t T, int32_t N, int32_t n_agents, const float 
 /* ---- the fight networks' chunk attention core and normalize(x + att), forward and backward (C ABI in include/hh_learner.h) ---- */
 #include "hh_chunk_attn.h"
 
+/* ---- a whole attention block, projections included, as one launch forward and two backward (C ABI in include/hh_learner.h) ---- */
+#include "hh_attn_block.h"
+
 /* ---- the networks' input layers in front of shared_layer as one grouped stage, forward and backward (C ABI in include/hh_learner.h) ---- */
 #include "hh_input_stage.h"
 

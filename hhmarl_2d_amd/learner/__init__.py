@@ -5,6 +5,8 @@ ac2_policy and hands the new weights back to the sampler's `PolicyBank` — coll
 batch never leaving it.  The network GEMMs stay in PyTorch / rocBLAS; the loss and its gradient are one HIP pass.  Opt-in
 (`attention="fused"`): what the fight networks' two attention blocks do between and after their projections runs in HIP too
 (`chunk_attention`: hh_chunk_attn_*, `residual_normalize`: hh_residual_normalize_*); the default path is nn.MultiheadAttention.
+And (`attention="block"`): each whole block, both projections included, as ONE launch forward and two backward (`attention_block`:
+hh_attn_block_*).
 Opt-in as well (`inputs="fused"`, all five networks): the layers in front of shared_layer as one grouped launch per side
 (`input_stage`: hh_input_stage_*); the default path slices, concatenates and runs them one by one.
 And (`trunk="fused"`, all five networks): shared_layer with its bias and tanh over the actor's and the critic's rows as ONE call
@@ -47,7 +49,8 @@ from ._ffi import _fused_input, _need_gpu, _p, _stream
 from .loss import (CMD_LD, HEADS_MODES, OLD_LD, _head_params, _heads_mode, _HeadsLoss, _PPOLoss, heads_loss, heads_loss_torch, n_comp_of, ppo_loss,
                    ppo_loss_categorical, ppo_loss_categorical_torch, ppo_loss_torch)
 from .ops import (ATTENTION_MODES, COMMANDER_STAGE_LAYERS, GRU_H, INPUT_MODES, TRUNK_MODES, _check_gru, _ChunkAttn, _dense_args, _dense_rows,
-                  _DenseTanh, _gru_io, _gru_scratch_bytes, _GruSeq, _InputStage, _ResidualNormalize, _stage_layout, _trunk_mode, chunk_attention,
+                  _DenseTanh, _gru_io, _gru_scratch_bytes, _GruSeq, _InputStage, _ResidualNormalize, _stage_layout, _trunk_mode, _AttnBlock,
+                  attention_block, attention_block_tile, attention_block_torch, chunk_attention,
                   chunk_attention_torch, commander_stage_tables, dense_tanh, dense_tanh_torch, gru_cell_torch, gru_seq_backward, gru_seq_forward,
                   gru_seq_tile, gru_sequence, gru_sequence_pair, gru_sequence_torch, input_stage, input_stage_torch, residual_normalize,
                   residual_normalize_torch, stage_groups, stage_layers, stage_tables, grad_combine, grad_combine_torch, grad_layout, grad_pack,

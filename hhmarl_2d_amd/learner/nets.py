@@ -6,8 +6,8 @@ import torch.nn.functional as F
 
 from .. import policy_nets as PN
 from .loss import _heads_mode
-from .ops import (ATTENTION_MODES, COMMANDER_STAGE_LAYERS, GRU_H, INPUT_MODES, _trunk_mode, chunk_attention, commander_stage_tables, dense_tanh,
-                  gru_sequence_pair, gru_sequence_torch, input_stage, residual_normalize, stage_groups, stage_layers, stage_tables)
+from .ops import (ATTENTION_MODES, COMMANDER_STAGE_LAYERS, GRU_H, INPUT_MODES, _trunk_mode, attention_block, chunk_attention, commander_stage_tables,
+                  dense_tanh, gru_sequence_pair, gru_sequence_torch, input_stage, residual_normalize, stage_groups, stage_layers, stage_tables)
 
 # ------------------------------------------------------------------------------------------------------------------ the networks
 class _FC(nn.Module):
@@ -36,7 +36,8 @@ class TrainableNet(nn.Module):
 
     attention = "torch" (the default) runs att_act / att_val through nn.MultiheadAttention and F.normalize.  "fused" (fight kinds only,
     float32 on the GPU) keeps the two projections as GEMMs and runs what lies between and after them through chunk_attention and
-    residual_normalize; the nn.MultiheadAttention objects stay the parameter holders, so state_dict() is the same either way.
+    residual_normalize; "block" (the same conditions) runs each whole block, projections included, as ONE attention_block.  The
+    nn.MultiheadAttention objects stay the parameter holders, so state_dict() is the same in all three.
 
     inputs = "torch" (the default) slices, concatenates and runs inp1..inp3 and v1..v3 / inp1_val one by one.  "fused" (any kind, float32
     on the GPU) runs each side's layers as ONE input_stage that reads obs_own / critic_row as they are and writes the concatenated
@@ -62,8 +63,8 @@ class TrainableNet(nn.Module):
         self.inputs = inputs
         if attention not in ATTENTION_MODES:
             raise ValueError(f"attention is one of {ATTENTION_MODES}, got {attention!r}")
-        if attention == "fused" and not PN.HAS_ATT[self.kind]:
-            raise ValueError(f'attention="fused": {PN.KIND_NAMES[self.kind]} has no attention')
+        if attention != "torch" and not PN.HAS_ATT[self.kind]:
+            raise ValueError(f'attention="{attention}": {PN.KIND_NAMES[self.kind]} has no attention')
         self.attention = attention
         for i, (c0, c1, w) in enumerate(PN.INPUTS[kind]):
             setattr(self, f"inp{i + 1}", _FC(c1 - c0, w))
@@ -84,6 +85,11 @@ class TrainableNet(nn.Module):
         qkv = F.linear(h, att.in_proj_weight, att.in_proj_bias)
         out = F.linear(chunk_attention(qkv), att.out_proj.weight, att.out_proj.bias)
         return residual_normalize(h, out)
+
+    @staticmethod
+    def _attend_block(att, h):
+        """normalize(h + att(h, h, h)) as one attention_block: one launch forward, two backward, the projections inside"""
+        return attention_block(h, att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias)
 
     @staticmethod
     def _attend_torch(att, h):
@@ -115,7 +121,7 @@ class TrainableNet(nn.Module):
             else:
                 y = [torch.tanh(self.inp1_val(v3))]
         if PN.HAS_ATT[kind]:
-            attend = self._attend_fused if self.attention == "fused" else self._attend_torch
+            attend = {"fused": self._attend_fused, "block": self._attend_block, "torch": self._attend_torch}[self.attention]
             h[-1], y[-1] = attend(self.att_act, h[-1]), attend(self.att_val, y[-1])
         h, y = (t[0] if len(t) == 1 else torch.cat(t, dim=-1) for t in (h, y))
         return h, y, flat

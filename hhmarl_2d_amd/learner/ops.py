@@ -10,7 +10,7 @@ from .. import policy_nets as PN
 from ._ffi import _fused_input, _need_gpu, _p, _stream
 
 # ------------------------------------------------------------------------------------------------------------------ the chunk attention
-ATTENTION_MODES = ("torch", "fused")
+ATTENTION_MODES = ("torch", "fused", "block")
 
 
 class _ChunkAttn(torch.autograd.Function):
@@ -92,6 +92,76 @@ def chunk_attention_torch(qkv):
 def residual_normalize_torch(x, a):
     """residual_normalize with torch ops, any dtype and device"""
     return F.normalize(x + a, dim=-1)
+
+
+def attention_block_tile(n_seq, seq_len, embed):
+    """(sequences per workgroup tile, workgroups of the backward's first launch) of an attention_block call (hh_attn_block_tile)"""
+    spt, nwg = C.c_int32(), C.c_int32()
+    L.check(L.lib().hh_attn_block_tile(int(n_seq), int(seq_len), int(embed), C.byref(spt), C.byref(nwg)))
+    return spt.value, nwg.value
+
+
+def _attn_block_bytes(fn, S, Lm, E):
+    nbytes = C.c_int64()
+    L.check(fn(S, Lm, E, C.byref(nbytes)))
+    return nbytes.value
+
+
+class _AttnBlock(torch.autograd.Function):
+    """forward: hh_attn_block_forward, keeping qkv, ctx and the norms in `save`; backward: hh_attn_block_backward.  save and scratch are
+    torch allocations: inside a captured step they come from the graph's pool"""
+
+    @staticmethod
+    def forward(ctx, x, in_w, in_b, out_w, out_b):
+        S, Lm, E = x.shape
+        w = [t.detach().contiguous() for t in (in_w, in_b, out_w, out_b)]
+        y = torch.empty_like(x)
+        lib = L.lib()
+        nbytes = _attn_block_bytes(lib.hh_attn_block_save_bytes, S, Lm, E)
+        save = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+        L.check(lib.hh_attn_block_forward(S, Lm, E, _p(x), _p(w[0]), _p(w[1]), _p(w[2]), _p(w[3]), _p(y), _p(save), nbytes, _stream(x.device)))
+        ctx.save_for_backward(x, w[0], w[2], y, save)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_y):
+        x, w_in, w_out, y, save = ctx.saved_tensors
+        S, Lm, E = x.shape
+        dev = x.device
+        new = torch.zeros if S == 0 else torch.empty        # n_seq == 0 launches nothing: the gradients of an empty call are zeros
+        d_x = torch.empty_like(x)
+        d_w_in, d_b_in = new((3 * E, E), dtype=torch.float32, device=dev), new((3 * E,), dtype=torch.float32, device=dev)
+        d_w_out, d_b_out = new((E, E), dtype=torch.float32, device=dev), new((E,), dtype=torch.float32, device=dev)
+        lib = L.lib()
+        nbytes = _attn_block_bytes(lib.hh_attn_block_scratch_bytes, S, Lm, E)
+        scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        L.check(lib.hh_attn_block_backward(S, Lm, E, _p(x), _p(w_in), _p(w_out), _p(y), _p(save), save.numel() * 4, _p(d_y.contiguous()), _p(d_x),
+                                           _p(d_w_in), _p(d_b_in), _p(d_w_out), _p(d_b_out), _p(scratch), nbytes, _stream(dev)))
+        return d_x, d_w_in, d_b_in, d_w_out, d_b_out
+
+
+def attention_block(x, in_w, in_b, out_w, out_b):
+    """F.normalize(x + nn.MultiheadAttention(E, 2, batch_first=True)(x, x, x)[0], dim=-1) as ONE launch forward and two backward
+    (hh_attn_block_forward / hh_attn_block_backward, include/hh_learner.h): x f32 [S, L, E], contiguous, CUDA, E = 100 | 150,
+    1 <= L <= 32; in_w [3E, E], in_b [3E], out_w [E, E], out_b [E] the module's in_proj_weight, in_proj_bias, out_proj.weight and
+    out_proj.bias -> f32 [S, L, E].  No mask: a zero-padded row is a key like any other.  Differentiable with respect to all five (first
+    order); the same inputs give the same bytes.  No host synchronisation; a missing library or GPU is an error."""
+    _need_gpu("attention_block")
+    _fused_input("attention_block", x, "x")
+    if x.dim() != 3 or x.shape[2] not in L.ATTN_WIDTHS or not 1 <= x.shape[1] <= L.ATTN_MAX_LEN:
+        raise ValueError(f"attention_block: x is [S, L, E] with E in {L.ATTN_WIDTHS} and 1 <= L <= {L.ATTN_MAX_LEN}, got {tuple(x.shape)}")
+    E = x.shape[2]
+    for what, t, shape in (("in_w", in_w, (3 * E, E)), ("in_b", in_b, (3 * E,)), ("out_w", out_w, (E, E)), ("out_b", out_b, (E,))):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.device == x.device and tuple(t.shape) == shape):
+            raise ValueError(f"attention_block: {what} is a float32 CUDA tensor {shape} on x's device (the torch-op form is attention_block_torch)")
+    return _AttnBlock.apply(x, in_w, in_b, out_w, out_b)
+
+
+def attention_block_torch(x, in_w, in_b, out_w, out_b):
+    """attention_block with torch ops, any dtype and device (the A/B partner): the two projections around chunk_attention_torch, then
+    residual_normalize_torch"""
+    return residual_normalize_torch(x, F.linear(chunk_attention_torch(F.linear(x, in_w, in_b)), out_w, out_b))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the input stage

@@ -56,7 +56,8 @@ class PPOLearner:
                  optimizer="torch", step="eager", shuffle_sequences=False, grad_clip=None):
         """kinds: (kind of ac1_policy, kind of ac2_policy); state_dicts: per policy the actor and value-branch tensors in one dict (numpy or
         torch), keyed like the reference's state_dict().  The shared layer is tied to the first policy's.  attention: TrainableNet's
-        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*).
+        argument, handed to both modules ("fused": the fight networks' chunk attention through hh_chunk_attn_* / hh_residual_normalize_*;
+        "block": each whole attention block, projections included, through hh_attn_block_*).
         inputs: TrainableNet's argument as well ("fused": everything in front of shared_layer through hh_input_stage_*).
         trunk: TrainableNet's argument too ("fused": shared_layer, bias and tanh of both sides through hh_dense_tanh_*).
         optimizer: "torch" (the default) steps with torch.optim.Adam; "fused" keeps each policy's m, v and step count on the device

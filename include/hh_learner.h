@@ -2,8 +2,8 @@
  * hh_learner.h — C ABI of the learner side of train_hetero.py's and train_hier.py's PPO (part of libhh_world.so): the fused PPO loss,
  * forward and backward, for the TorchMultiCategorical action distribution of the 2-vs-2 policies and for the commander's Categorical,
  * the commander's GRUs over whole sequences, forward and backward (hh_gru_seq_*), and the fight networks' chunk attention without its
- * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*), the networks' input layers as one grouped stage (hh_input_stage_*), and the
- * layer they share on the matrix cores (hh_dense_tanh_*, at the end of this file).
+ * GEMMs (hh_chunk_attn_*, hh_residual_normalize_*) and as one whole block with its projections (hh_attn_block_*), the networks' input
+ * layers as one grouped stage (hh_input_stage_*), and the layer they share on the matrix cores (hh_dense_tanh_*).
  *
  * What RLlib 2.4's PPOTorchPolicy.loss (ray/rllib/algorithms/ppo/ppo_torch_policy.py) computes from the learner's logits and value
  * predictions, per row that the mask keeps (n = number of such rows):
@@ -150,6 +150,43 @@ int hh_chunk_attn_backward(int64_t n_seq, int32_t len, int32_t embed, const floa
 int hh_residual_normalize_forward (int64_t n_rows, int32_t width, const float *x, const float *a, float *y, float *norm, void *stream);
 /* d_s (= d_x = d_a) = (d_y - y (y . d_y)) / norm where norm >= 1e-12, d_y / 1e-12 elsewhere (autograd of clamp_min and of norm at 0) */
 int hh_residual_normalize_backward(int64_t n_rows, int32_t width, const float *y, const float *norm, const float *d_y, float *d_s, void *stream);
+
+/* ---- one whole attention block of a fight network as one launch forward and two backward (learner.attention_block) ----
+ *
+ *     qkv = x W_in^T + b_in                      [n_seq, len, 3 embed]
+ *     ctx = per sequence and head softmax(Q K^T / sqrt(d)) V, heads concatenated      (d = embed / 2, HH_ATTN_HEADS heads, no mask)
+ *     a   = ctx W_out^T + b_out
+ *     s   = x + a;   y = s / max(|s|_2, 1e-12)   per row
+ * what the in-projection GEMM, hh_chunk_attn_forward, the out-projection GEMM and hh_residual_normalize_forward compute one after the
+ * other, with their conventions: zero-padded rows are keys like any other, expf with the row maximum subtracted, and backward autograd's
+ * clamp branch d_s = d_y / 1e-12 where the norm is below 1e-12.  With len == 1 (the networks' 2-D form) ctx is the v columns bit for bit.
+ *   x, y, d_y, d_x  f32 [n_seq, len, embed];  w_in [3 embed, embed], b_in [3 embed] (nn.MultiheadAttention's in_proj_weight / _bias:
+ *                   rows q | k | v);  w_out [embed, embed], b_out [embed] (out_proj);  d_w_in .. d_b_out in their shapes
+ * embed is 100 or 150 (compile-time instances), 1 <= len <= HH_ATTN_MAX_LEN, 0 <= n_seq <= 2^24; anything else, a null or not 16-byte
+ * aligned pointer, an output that overlaps another tensor of the call, or a save / scratch smaller than the queries below say is
+ * HH_E_ARG and launches nothing.  n_seq == 0 succeeds without a launch and writes nothing.  Everything is float32 (the five
+ * products on the float32-input MFMA, the rest fmaf chains; every sum in an order that the shapes alone decide) and ordered on `stream`; no allocation, no host synchronisation, no atomics, HIP-graph capturable; the same inputs
+ * give the same bytes on every run, and a row's y and d_x do not depend on which other sequences the call holds.
+ * Tiles: a workgroup owns HH_ATTN_BLOCK_ROWS / len whole sequences (at most HH_ATTN_BLOCK_ROWS rows).  The forward is one launch of one
+ * workgroup per tile.  It keeps in `save`, per row, qkv, ctx and |s|_2: (4 embed + 1) * 4 = 1604 | 2404 bytes, each of the three parts
+ * rounded up to 16 bytes over the whole call (hh_attn_block_save_bytes); the probabilities are recomputed.  The backward is two launches.
+ * The first walks the tiles grid-stride with min(tiles, HH_ATTN_BLOCK_MAX_WG) workgroups (tile t goes to workgroup t mod that number);
+ * each writes its tiles' rows of d_x — the complete input gradient: d_s + d_qkv W_in — and keeps its partial d_w_in | d_b_in | d_w_out |
+ * d_b_out, (4 embed^2 + 4 embed) floats, in `scratch`, summed over its tiles in tile order (within a tile in row order).  The second adds
+ * every element's partials in workgroup order in float64 and rounds once.  Every output is overwritten.  `scratch` stops growing at
+ * HH_ATTN_BLOCK_MAX_WG tiles: at most 20.7 | 46.4 MB. */
+#define HH_ATTN_BLOCK_ROWS   32    /* rows of a workgroup's tile */
+#define HH_ATTN_BLOCK_MAX_WG 128   /* the cap on the backward's workgroups, and so on the partial sums per weight element */
+/* the sequences per tile and the workgroups of the backward's first launch for such a call (either pointer may be NULL).  Host only. */
+int hh_attn_block_tile(int64_t n_seq, int32_t len, int32_t embed, int32_t *seq_per_tile, int32_t *n_workgroups);
+int hh_attn_block_save_bytes(int64_t n_seq, int32_t len, int32_t embed, int64_t *bytes);
+int hh_attn_block_scratch_bytes(int64_t n_seq, int32_t len, int32_t embed, int64_t *bytes);
+int hh_attn_block_forward(int64_t n_seq, int32_t len, int32_t embed, const float *x, const float *w_in, const float *b_in,
+                          const float *w_out, const float *b_out, float *y, void *save, int64_t save_bytes, void *stream);
+/* x, w_in, w_out, y and save as the forward took and left them (the biases are not needed) */
+int hh_attn_block_backward(int64_t n_seq, int32_t len, int32_t embed, const float *x, const float *w_in, const float *w_out,
+                           const float *y, const void *save, int64_t save_bytes, const float *d_y, float *d_x, float *d_w_in,
+                           float *d_b_in, float *d_w_out, float *d_b_out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ---- the input stage: what every trainable network does in front of shared_layer (inp1..inp4, v1..v4, inp1_val) ----
  *

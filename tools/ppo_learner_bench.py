@@ -58,6 +58,13 @@
           out; plus the head weights in and their gradients out); (b) the Fight1 and the Esc1 minibatch step at 256 and 65536 rows, eager
           + torch Adam and the graph step, one step per timing and 50 replays back to back; (c) one whole graph update at
           --step-minibatch.  The same rule for gain / loss.  --step-launches with --heads-mode fused counts the launches of that path
+  block   --attention-block runs this section alone and appends its lines to --out: TrainableNet(attention="block") (hh_attn_block_*: a whole
+          attention block, projections included, as one launch forward and two backward) against attention="fused" in the same run:
+          (a) one block, forward + backward, E = 100 and 150 at 14 and 3560 chunks of 20; (b) the two calls alone as bytes/s of their
+          algorithmic bytes (forward: x in, y, qkv, ctx and the norm out, 24 E + 4 per row; backward: x, y, d_y, qkv, ctx and the norm in,
+          d_x out, 32 E + 4 per row; the weights once each way); (c) the Fight1 graph step with inputs="fused", heads="fused" at 256 and
+          65536 rows, one replay per timing and 50 back to back at 256.  The same rule for gain / loss.  --step-launches graph with
+          --attention-mode block (and --heads-mode fused) counts the launches of that step under rocprofv3
 --window: PPOLearner.update_window on a PPORollout's fixed [T, N] window (batch_mode = "truncate_episodes") next to update on whole
           episodes, fight and escape, in the same run: (a) the batch build — window_cut and hh_window_gather against their torch twins (the
           gather as bytes/s of what it reads and writes), the torch parts (critic rows, standardisation), window_batch against policy_batch
@@ -110,7 +117,9 @@ def main():
     ap.add_argument("--heads", action="store_true", help="only the fused-tail section; its lines are appended to --out")
     ap.add_argument("--window", action="store_true", help="only the window-batch section (update_window); its lines are appended to --out")
     ap.add_argument("--shards", action="store_true", help="only the sharded-update section (group=LocalShards(1)); its lines are appended to --out")
+    ap.add_argument("--attention-block", action="store_true", help="only the attention-block section (attention=\"block\" against \"fused\"); its lines are appended to --out")
     ap.add_argument("--heads-mode", choices=("torch", "fused"), default="torch", help="--step-launches: the learner's heads option")
+    ap.add_argument("--attention-mode", choices=("fused", "block"), default="fused", help="--step-launches: the learner's attention option")
     ap.add_argument("--step-minibatch", type=int, default=256, help="--step: sgd_minibatch_size of the whole update")
     ap.add_argument("--step-launches", choices=("eager", "graph"), help="only --step-count minibatch steps of this kind (for a kernel count under rocprofv3)")
     ap.add_argument("--step-count", type=int, default=16)
@@ -433,7 +442,7 @@ def main():
             word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
             return f"eager+torch / this = {med(t_base) / med(t_new):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
 
-        FUSED = dict(attention="fused", inputs="fused", trunk="torch", heads=a.heads_mode if a.step_launches else "torch")
+        FUSED = dict(attention=a.attention_mode if a.step_launches else "fused", inputs="fused", trunk="torch", heads=a.heads_mode if a.step_launches else "torch")
         make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, **FUSED, **kw)
         w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
         bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
@@ -875,6 +884,115 @@ def main():
     if a.heads:
         lines.clear()
         heads_section()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+
+    def attention_block_section():
+        """attention="block" against attention="fused": one block, the two kernel calls alone, the Fight1 graph step"""
+        import ctypes as C
+        from hhmarl_2d_amd import _lib as L
+        med = statistics.median
+        K = 50
+
+        def verdict(t_fused, t_block):
+            spread = max(max(t_fused) - min(t_fused), max(t_block) - min(t_block))
+            d = med(t_fused) - med(t_block)
+            word = "no difference beyond the spread" if abs(d) <= spread else ("gain" if d > 0 else "loss")
+            return f"fused / block = {med(t_fused) / med(t_block):.2f}x, medians {d:+.3f} ms apart, larger spread {spread:.3f} ms: {word}"
+
+        say(f"# tools/ppo_learner_bench.py --attention-block on {torch.cuda.get_device_name(0)}: TrainableNet(attention=\"block\") (hh_attn_block_*: one launch "
+            f"forward, two backward per block) against attention=\"fused\" (GEMMs + hh_chunk_attn_* + hh_residual_normalize_*), both in this run; {a.iters} timed "
+            f"iterations after {a.warmup} warm-up, device events (a later run, appended):")
+        # (a) one block, forward + backward
+        for E in (100, 150):
+            att = nn.MultiheadAttention(E, 2, batch_first=True).to(dev)
+            for S in (14, 3560):
+                g = torch.Generator().manual_seed(E + S)
+                h = torch.tanh(torch.randn((S, 20, E), generator=g)).to(dev).requires_grad_(True)
+                dy = torch.randn((S, 20, E), generator=g).to(dev)
+
+                def block(attend):
+                    h.grad = None
+                    att.zero_grad(set_to_none=True)
+                    attend(att, h).backward(dy)
+                t_f, t_b = events(lambda: block(LR.TrainableNet._attend_fused)), events(lambda: block(LR.TrainableNet._attend_block))
+                say(f"attention block (in-projection, core, out-projection, normalize(x + att); forward + backward, eager launches), E = {E}, {S} chunks of 20: "
+                    f"fused {q(t_f)}; block {q(t_b)}; {verdict(t_f, t_b)}")
+        # (b) the two calls alone
+        lib = L.lib()
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        for E in (100, 150):
+            for S in (14, 3560):
+                R = S * 20
+                r = lambda *shape: torch.randn(shape, device=dev)
+                x, d_y, w_in, b_in, w_out, b_out = r(S, 20, E), r(S, 20, E), 0.1 * r(3 * E, E), 0.1 * r(3 * E), 0.1 * r(E, E), 0.1 * r(E)
+                y, d_x = torch.empty_like(x), torch.empty_like(x)
+                outs = [torch.empty_like(t) for t in (w_in, b_in, w_out, b_out)]
+                nb_save, nb_scr = C.c_int64(), C.c_int64()
+                L.check(lib.hh_attn_block_save_bytes(S, 20, E, C.byref(nb_save)))
+                L.check(lib.hh_attn_block_scratch_bytes(S, 20, E, C.byref(nb_scr)))
+                save, scratch = torch.empty((nb_save.value // 4,), device=dev), torch.empty((nb_scr.value // 4,), device=dev)
+                spt, nwg = LR.attention_block_tile(S, 20, E)
+                wbytes = (4 * E * E + 4 * E) * 4
+                runs = (("hh_attn_block_forward (one launch)", R * (24 * E + 4) + wbytes,
+                         lambda: L.check(lib.hh_attn_block_forward(S, 20, E, p(x), p(w_in), p(b_in), p(w_out), p(b_out), p(y), p(save), nb_save.value, st))),
+                        ("hh_attn_block_backward (two launches)", R * (32 * E + 4) + 2 * wbytes,
+                         lambda: L.check(lib.hh_attn_block_backward(S, 20, E, p(x), p(w_in), p(w_out), p(y), p(save), nb_save.value, p(d_y), p(d_x),
+                                                                    *[p(o) for o in outs], p(scratch), nb_scr.value, st))))
+                for name, nbytes, fn in runs:
+                    t = events(fn)
+                    say(f"    {name} alone, E = {E}, {S} chunks of 20 ({R} rows; {spt} sequence(s) per tile, {nwg} backward workgroups, {nb_scr.value / 1e6:.2f} MB of "
+                        f"scratch): {q(t)} = {nbytes / med(t) / 1e6:.1f} GB/s of {nbytes / 1e6:.2f} MB algorithmic bytes "
+                        f"({100 * nbytes / med(t) / 1e6 / 6290:.1f} % of the 6.29 TB/s a float4 copy reaches)")
+                del save, scratch
+
+        def burst(fn):
+            out = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / K)
+            return " ".join(f"{d:.3f}" for d in out)
+
+        # (c) the Fight1 graph step with inputs = fused, heads = fused
+        make = lambda **kw: LR.PPOLearner.trainable_init(dev, mode="fight", seed=1, inputs="fused", heads="fused", **kw)
+        w = World(make_config(n_arenas=a.arenas, level=3, seed=7, auto_reset=True, horizon=a.horizon), device=0)
+        bank = PolicyBank.trainable_init(dev, mode="fight", seed=1, max_rows=2 * a.arenas)
+        ro = PPORollout(w, bank, a.T, batch_mode="complete_episodes")
+        for _ in range(max(2, (a.horizon + a.T - 1) // a.T)):
+            ro.collect()
+        rows = ro.episodes.rows()
+        base = make(attention="fused")
+        with torch.no_grad():
+            old = base.old_logits(rows["obs"], bank, ro.episodes.N)
+            b = base.policy_batch(rows, old, 0)
+        cols, seq_len = base._columns(b)
+        for size in (256, 65536):
+            s0, s1 = LR.minibatch_partition(seq_len, size)[0]
+            sub = {k: v[s0:s1].contiguous() for k, v in b.items()}
+            n_rows = int(seq_len[s0:s1].sum())
+            n_total = 2 * (a.iters + a.warmup) + 4 * K + 8
+            graphs = {m: make(attention=m, optimizer="fused", step="graph", num_sgd_iter=n_total, sgd_minibatch_size=1 << 30) for m in ("fused", "block")}
+            for lr in graphs.values():
+                lr.graph_prepare(0, sub)
+            t_g = {m: events(lambda lr=lr: lr.graph_replay(0, 1)) for m, lr in graphs.items()}
+            say(f"graph step (Fight1, inputs = fused, heads = fused; stage + forward + loss + backward + Adam + commit), {n_rows} unpadded rows in {s1 - s0} chunks "
+                f"of 20: attention = fused {q(t_g['fused'])}; attention = block {q(t_g['block'])} [{verdict(t_g['fused'], t_g['block'])}]")
+            if size == 256:
+                say(f"    {K} graph replays back to back, ms per step, three runs: attention = fused {burst(lambda: graphs['fused'].graph_replay(0, K))} | "
+                    f"attention = block {burst(lambda: graphs['block'].graph_replay(0, K))}")
+            del graphs
+
+    if a.attention_block:
+        lines.clear()
+        attention_block_section()
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
