@@ -381,6 +381,14 @@ __device__ __forceinline__ bool d_maybe_within_km(double lat1, double lon1, doub
     bool lowlat = hh_fabs(lat1) < 25.0 && hh_fabs(lat2) < 25.0;
     return near || !lowlat;
 }
+/* the cannon cone's planar stage where it is ANDed with d_maybe_within_km(..., HH_AC_CANNON_KM): hh_envelope.h's sibling without the separation clauses
+ * that prefilter implies (HH_ABL_CONE_DOMAIN: the tuning build with the clauses kept).  Used by the register-exchange HighLevelEnv tick (hh_kernels_oct.h);
+ * the 2-vs-2 tick keeps the original: there the sibling's own A/B stayed inside the run-to-run spread (profiles/r09_quad_x_to_y.md) */
+#ifdef HH_ABL_CONE_DOMAIN
+#define HH_CANNON_CONE_OUTSIDE_NEAR hh_cannon_cone_planar_outside
+#else
+#define HH_CANNON_CONE_OUTSIDE_NEAR hh_cannon_cone_planar_outside_near
+#endif
 
 /* cmano_simulator.py:65-72 position update: short-step RK4 Direct (hh_geodesic.h) with the general
  * Karney Direct as an out-of-line fallback outside its domain (same selection as hh_geo_move) */

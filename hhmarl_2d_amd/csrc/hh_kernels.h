@@ -38,7 +38,7 @@
 /* phase timers for tuning builds only (-DHH_PROFILE_PHASES): s_memtime deltas per phase, summed per wave
  * into hh_prof_cycles[]; compiled out of the product */
 #ifdef HH_PROFILE_PHASES
-__device__ unsigned long long hh_prof_cycles[24]; /* 0..11 phases, 12..15 queue statistics, 16..19 output wave (wait X, table, wait Y, rows), 20 / 21 barrier X / Y waits of the simulation wave */
+__device__ unsigned long long hh_prof_cycles[24]; /* 0..11 phases, 12..15 queue statistics, 16..19 output wave (wait X, table, wait Y, rows), 20 / 21 barrier X / Y waits of the simulation wave, 22 drains whose first round needed no geometry */
 #define HH_PROF_DECL unsigned long long prof_t0_ = __builtin_readcyclecounter(), prof_acc_[14] = {0}
 #define HH_PROF(k) do { unsigned long long t_ = __builtin_readcyclecounter(); prof_acc_[k] += t_ - prof_t0_; prof_t0_ = t_; } while (0)
 #define HH_PROF_ARGS , unsigned long long &prof_t0_, unsigned long long *prof_acc_
@@ -411,13 +411,36 @@ __device__ __forceinline__ void drain_envelope_queue_t(SH &sh, int tid, int coun
         /* filtered exact predicate: decide from the mid-latitude estimate when it is farther from every
          * threshold than its proven error bound; otherwise redo the test with the Karney solution */
         const int t = (sh.flags[src] >> 1) & 3;
+#ifndef HH_ABL_DRAW_LAST
+        /* Draw first.  A cannon entry's Bernoulli draw (ac1.py:112-113) is keyed by tick, shooter and target — no sequence state — so it can be
+         * taken in front of the geometry: on a miss (0.85 / 0.70 of the draws) the entry's bit is 0 whatever the cone says, and the lane leaves the
+         * pass.  Three drains in four hold cannon entries only, and in most of those every draw misses: the loop's exec-mask region below is then
+         * branched over as a whole.  Where some lane does need geometry the others ride along masked. */
+        int hit_bit = 0;
+        if (kind == 1) {
+            const int id_src = GS == 8 ? (ss < 4 ? ss + 1 : opp_id0 + (ss - 4)) : ss + 1;
+            const int id_tgt = GS == 8 ? (j < 4 ? j + 1 : opp_id0 + (j - 4)) : j + 1;
+            const double u = hh_rng_u01(sh.g_tkey[src / GS], (uint32_t)id_src, HH_SITE_CANNON, (uint32_t)id_tgt);
+            hit_bit = u < HH_AC_HIT_PROB(t) ? (2 << j) : 0;
+        }
+        const bool geometry = kind != 1 || hit_bit != 0;
+#ifdef HH_PROFILE_PHASES
+        if (__ballot(geometry) == 0ULL && q == tid && tid == 0) atomicAdd(&hh_prof_cycles[22], 1ULL); /* a round of the pass that needed no geometry */
+#endif
+        if (!geometry) continue;
+#endif
         const double hdg_src = kind == 0 ? sh.hdg[src] : sh.u.t.hdg1[src];
         const double sep = hh_max(hh_fabs(la2 - la1), hh_fabs(lo2 - lo1));
         const bool dom = hh_fabs(la1) <= HH_GEO_EST_MAX_LAT && hh_fabs(la2) <= HH_GEO_EST_MAX_LAT &&
                          hh_fabs(lo1) < 170.0 && hh_fabs(lo2) < 170.0;
         int verdict = -1; /* -1 undecided, 0 outside the envelope, 1 inside */
         if (dom && sep <= (kind == 0 ? HH_GEO_EST_LONG_DEG : HH_GEO_EST_SHORT_DEG)) {
-            double s_m, az;
+            double s_m, az = 0.0;
+#ifndef HH_ABL_DRAW_LAST
+            /* a fuse entry asks for the range only: the bearing (an atan2) is evaluated where a lane holds a launch entry or a cannon entry that hit */
+            if (kind >= 2) hh_geo_inverse_estimate_range(la1, lo1, la2, lo2, &s_m);
+            else
+#endif
             hh_geo_inverse_estimate(la1, lo1, la2, lo2, &s_m, &az);
             if (kind == 0) {
                 double delta = hh_fabs(d_signed_heading_diff(d_normalize_angle(hdg_src + HH_MISSILE_HALF_DEG), az));
@@ -446,12 +469,17 @@ __device__ __forceinline__ void drain_envelope_queue_t(SH &sh, int tid, int coun
         int bit = 0;
         if (verdict) {
             if (kind == 0) bit = 1;
-            else if (kind == 1) { /* ac1.py:112-113 Bernoulli hit, drawn only when in the cone */
+#ifndef HH_ABL_DRAW_LAST
+            else if (kind == 1) bit = hit_bit; /* ac1.py:112-113 Bernoulli hit: the keyed draw taken above */
+#else
+            else if (kind == 1) { /* the tuning build of the order before: drawn only when in the cone */
                 const int id_src = GS == 8 ? (ss < 4 ? ss + 1 : opp_id0 + (ss - 4)) : ss + 1;
                 const int id_tgt = GS == 8 ? (j < 4 ? j + 1 : opp_id0 + (j - 4)) : j + 1;
                 double u = hh_rng_u01(sh.g_tkey[src / GS], (uint32_t)id_src, HH_SITE_CANNON, (uint32_t)id_tgt);
                 if (u < HH_AC_HIT_PROB(t)) bit = 2 << j;
-            } else bit = kind == 2 ? (1 << HH_RES_FUSE_BIT(GS)) : (1 << (HH_RES_FUSE_BIT(GS) + 1));
+            }
+#endif
+            else bit = kind == 2 ? (1 << HH_RES_FUSE_BIT(GS)) : (1 << (HH_RES_FUSE_BIT(GS) + 1));
         }
         if (bit) atomicOr(&sh.res[src], bit);
     }

@@ -567,7 +567,7 @@ __device__ __forceinline__ void tick_oct(const DevCfg &c, OctShared &sh, int tid
             const double tl = lower ? lat1[r] : tb.lat[r];
             const double to = lower ? lon1[r] : tb.lon[r];
             push[r] = (int)fired & (int)snap_j & ((int)(c.friendly_kill != 0) | (int)enemy) & (int)d_maybe_within_km(lat_old, lon_old, tl, to, HH_AC_CANNON_KM(t)) &
-                      (int)!hh_cannon_cone_planar_outside(lat_old, lon_old, tl, to, pn.uc, pn.us, t);
+                      (int)!HH_CANNON_CONE_OUTSIDE_NEAR(lat_old, lon_old, tl, to, pn.uc, pn.us, t); /* the range prefilter implies the sibling's precondition */
             pjs[r] = pj;
             any_push |= push[r];
         }

@@ -62,4 +62,20 @@ HH_HD int hh_cannon_cone_planar_outside(double lat1, double lon1, double lat2, d
     return ok & ((dot <= 0.0) | (dot * dot < (cw * cw) * (d2 * h2))); /* straight-line: no region for the GPU's exec mask to skip */
 }
 
+/* The same test without the |dx|, |dy| <= HH_GEO_EST_SHORT_DEG clauses of its domain.  PRECONDITION: the result is used only ANDed (as "not outside")
+ * with the range prefilter "|dlat|, |dlon| <= R / 100 deg, or some |lat| >= 25 deg" for R <= 4.5 km (the kernels' d_maybe_within_km with a cannon range).
+ * Then the push bit is the same: below 25 deg the range prefilter bounds both separations by R / 100 <= 0.045 < 0.06, so where it passes the dropped
+ * clauses hold, and where it fails the bit is 0 whatever this answers; at or above 25 deg the |lat| <= 10 clause fails in both forms (answer 0, "not
+ * decided").  tests/test_drain_paths.py compares the two forms bit by bit. */
+HH_HD int hh_cannon_cone_planar_outside_near(double lat1, double lon1, double lat2, double lon2, double he, double hn, int ac_type) {
+    const double dx = lon2 - lon1, dy = lat2 - lat1;
+    const int dom = (hh_fabs(lat1) <= HH_GEO_EST_MAX_LAT) & (hh_fabs(lat2) <= HH_GEO_EST_MAX_LAT) & (hh_fabs(lon1) < 170.0) & (hh_fabs(lon2) < 170.0);
+    const double d2 = dx * dx + dy * dy;
+    const int ok = dom & !(d2 < 1e-10);
+    const double dot = he * dx + hn * dy;
+    const double h2 = he * he + hn * hn;
+    const double cw = ac_type == 1 ? HH_COS_5P3_DEG : HH_COS_3P8_DEG;
+    return ok & ((dot <= 0.0) | (dot * dot < (cw * cw) * (d2 * h2)));
+}
+
 #endif /* HH_ENVELOPE_H */

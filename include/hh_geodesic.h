@@ -334,6 +334,20 @@ HH_HD void hh_geo_inverse_estimate(double lat1, double lon1, double lat2, double
     if (a >= 360.0) a -= 360.0;
     *azi1 = a; /* [0, 360) */
 }
+/* The range of hh_geo_inverse_estimate alone: the same expressions for s12 in the same order (bit-identical: the library is built
+ * without contraction), without the atan2 and the convergence term.  For the envelope tests that ask for no bearing (the rocket fuse). */
+HH_HD void hh_geo_inverse_estimate_range(double lat1, double lon1, double lat2, double lon2, double *s12) {
+    double pm = (0.5 * (lat1 + lat2)) * HH_DEG2RAD;
+    double dp = (lat2 - lat1) * HH_DEG2RAD, dl = (lon2 - lon1) * HH_DEG2RAD;
+    double sm, cm;
+    hh_sincos(pm, &sm, &cm);
+    double W2 = 1.0 - HH_GEO_E2 * sm * sm;
+    double W = hh_sqrt(W2);
+    double N = HH_GEO_A / W;
+    double M = N * (1.0 - HH_GEO_E2) / W2;
+    double x = N * cm * dl, y = M * dp;
+    *s12 = hh_sqrt(x * x + y * y);
+}
 
 /* ------------------------------------------------------------------ Inverse */
 HH_HD void hh_geo_lengths(double eps, double sig12, double ssig1, double csig1, double dn1, double ssig2,

@@ -29,6 +29,8 @@ for k, nm in enumerate(names):
 print(f"{'total':36s} {tot / (waves * 4 * T):9.0f} cycles/wave-tick")
 wt = waves * 4 * T
 print(f"queue: non-empty on {buf[12] / wt:.3f} of wave-ticks; entries per wave-tick: launch {buf[13] / wt:.3f}, cannon {buf[14] / wt:.3f}, rocket fuse {buf[15] / wt:.3f}")
+if buf[12]:   # the draw-first drain (hh_kernels.h: drain_envelope_queue_t): how often the pass left before any geometry
+    print(f"drain: {buf[22] / buf[12]:.3f} of the non-empty drains needed no geometry (cannon entries only, every draw a miss)")
 if buf[16] or buf[17]:   # two-wave preset instances: the output wave builds the pair table (hh_kernels_quad.h: OWT)
     on = ["wait at barrier X", "pair table", "wait at barrier Y", "observation rows + stores"]
     for k, nm in enumerate(on):
